@@ -31,6 +31,10 @@ Tracking does not shard inside a frame: N GPUs = N indepe
 data-path collective ("scaling": "weak").  What does shard is the ring-key database: with N > 1 the line also carries
 config.ringkey_sharded -- the DB split `ordinal mod N`, local scans, cross-shard merge by RCCL all-reduce(min) through the
 C ABI (dsm_ringdb_merge_topk), checked against the unsharded answer.
+
+A plain run measures the headline figure alone: set-up, W warm-up steps, the K timed steps, `--dump-outputs DIR` (the arrays the
+timed path returned in its last step), the line.  Everything else above -- CPU baseline, extra legs, the instrumented advances
+behind the per-kernel roofline, the sharded ring-key leg, the side file -- runs with `--full`.
 """
 import argparse
 import json
@@ -45,6 +49,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+DETAIL_OUT = "bench_out/bench_detail.json"  # --full's side file (relative to the repository root)
 
 # Scene seeds (offsets from 0x5EED0000) on which the REFERENCE ALGORITHM itself (CPU oracle) converges from the identity
 # guess on every bench configuration -- selected by tools/select_scenes.py.  Offsets 3, 5 (S2), 7 (S1) and 15 (S2) drive
@@ -131,7 +136,7 @@ def _parse():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-second-leg", action="store_true", help="skip the short reference-faithful five-level (S1) leg reported in config.reference_five_level")
     ap.add_argument("--second-leg-steps", type=int, default=10, help="timed steps of the fixed-schedule and five-level legs (streamed: ramp-up and drain are inside, so a handful of steps understates the rate)")
-    ap.add_argument("--quick", action="store_true", help="the headline leg alone: --no-cpu --no-fixed-leg --no-second-leg --no-plane-leg --no-upload-leg --no-replay-leg --no-ringkey-leg (A/B runs, profiles)")
+    ap.add_argument("--quick", action="store_true", help="with --full: the headline leg alone, with its instrumented advances: --no-cpu --no-fixed-leg --no-second-leg --no-plane-leg --no-upload-leg --no-replay-leg --no-ringkey-leg (A/B runs, profiles)")
     ap.add_argument("--upload-stream-ticks", type=int, default=0, help="ticks per advance of the streamed hand-over leg (0: the library's own choice)")
     ap.add_argument("--no-upload-leg", action="store_true", help="skip the PCIe-inclusive leg of the default line (config.with_upload)")
     ap.add_argument("--no-plane-leg", action="store_true", help="skip the short leg on SURVEY.md 8d's literal scene family (config.plane_family)")
@@ -153,12 +158,24 @@ def _parse():
     ap.add_argument("--ringkey-leg-seconds", type=float, default=120.0, help="N > 1: deadline of the sharded ring-key leg; a rank that misses it reports an error in config.ringkey_sharded and the line is printed regardless")
     ap.add_argument("--rk-n", type=int, default=1_000_000)
     ap.add_argument("--rk-q", type=int, default=1024)
-    ap.add_argument("--detail-out", default="gpurun_out/bench_detail.json",
+    ap.add_argument("--detail-out", default=None,
                     help="side file (relative to the repository root unless absolute) that receives the FULL result object -- every leg, table and note; the ONE "
-                         "stdout line is its compact form (< 4 KB: contract keys, roofline and cpu_baseline as numbers, one summary per leg)")
+                         "stdout line is its compact form (< 4 KB: contract keys, roofline and cpu_baseline as numbers, one summary per leg).  Default: "
+                         f"{DETAIL_OUT} with --full, none without")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline, the extra legs (fixed schedule, five-level S1, plane family, hand-over, "
+                         "replay, ring-key, loop chain; with N > 1 the sharded ring-key leg) and the instrumented advances after the timed region "
+                         "(per-kernel roofline, steady state).  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its LAST step (per frame: pose, affine, last residuals, flow, good; "
+                         "per keyframe: scale and its error) as DIR/<name>.npy, float32 / float64 -- the inputs are seeded, so two builds compare output for output")
     a = ap.parse_args()
-    if a.quick:
+    if a.quick or not a.full:
         a.no_cpu = a.no_fixed_leg = a.no_second_leg = a.no_plane_leg = a.no_upload_leg = a.no_replay_leg = a.no_ringkey_leg = True
+    if a.detail_out is None and a.full:
+        a.detail_out = DETAIL_OUT
+    if a.dump_outputs and (a.replay or a.ringkey or a.membw):
+        ap.error("--dump-outputs writes the tracking benchmark's outputs: not with --replay / --ringkey / --membw")
     return a
 
 
@@ -279,11 +296,58 @@ def frame_seeds(args):
     return tuple(range(18)) if args.textures == "all" else SCENE_SEEDS
 
 
+_RENDER = {}  # build_frames' work list and output arrays, inherited by its forked workers
+
+
+def _device_open():
+    """whether this process may hold a GPU: the product library is loaded or torch has initialised its HIP runtime"""
+    lib, torch = sys.modules.get("direct_stereo_slam_amd._lib"), sys.modules.get("torch")
+    return (lib is not None and lib._lib is not None) or (torch is not None and torch.cuda.is_initialized())
+
+
+def _render_frame(j):
+    """frame j of build_frames into the shared arrays; j < n_tex also renders texture j's keyframe and right image"""
+    from direct_stereo_slam_amd import synth as S
+
+    r = _RENDER
+    K, w, h, T, seeds, n_tex, Scene = r["K"], r["w"], r["h"], r["T"], r["seeds"], r["n_tex"], r["Scene"]
+    u8 = (lambda im: np.clip(np.rint(im), 0, 255).astype(np.float32)) if r["u8"] else (lambda im: im)
+    k = j % n_tex
+    scene = Scene(seed=0x5EED0000 + seeds[k])
+    if j < n_tex:  # the first cycle: exactly round 2's frames (one generator per texture: keyframe, motion, new image, right image)
+        rng = np.random.default_rng(0x5EED0000 + seeds[k])
+        r["ref"][k] = u8(scene.render(K, w, h, noise=2.0, rng=rng))
+        R, t = S.random_motion(rng)
+        r["new"][j] = u8(scene.render(K, w, h, R, t, a=0.02, b=3.0, noise=2.0, rng=rng))
+        r["right"][k] = u8(scene.render(K, w, h, T[:3, :3], T[:3, 3], noise=2.0, rng=rng))
+    else:
+        rng = np.random.default_rng(0x5EED0000 + 0x100000 * (j // n_tex) + seeds[k])
+        R, t = S.random_motion(rng)
+        r["new"][j] = u8(scene.render(K, w, h, R, t, a=0.02, b=3.0, noise=2.0, rng=rng))
+    r["R"][j], r["t"][j] = R, t
+
+
+def _render_worker(counter, n):
+    while True:
+        with counter.get_lock():
+            j = counter.value
+            counter.value += 1
+        if j >= n:
+            return
+        _render_frame(j)
+
+
 def build_frames(args, w, h, K, T):
     """The distinct synthetic frames of the workload.  Frame f = texture f mod n_tex seen under its OWN ground-truth motion
     and image noise (seeded by f), with its own initial guess; the keyframe image, the template and the right image belong
     to the texture and are shared by its frames.  Returns (textures, frames): textures[k] = (scene, ref, right),
-    frames[f] = (k, new image, gt pose, guess pose)."""
+    frames[f] = (k, new image, gt pose, guess pose).  Every frame is drawn from its own seeded generators, so the images do
+    not depend on who renders them: up to 16 forked processes writing into shared memory while this process has no device
+    open (rendering is numpy-bound: threads serialise on the interpreter and on page faults) -- the headline's frames, which
+    bench_tracking renders before it opens the device -- and up to 16 threads of this process once it has one (the --full
+    legs' frames: rendering never forks a process that runs the HIP runtime)."""
+    import mmap
+    import multiprocessing as mp
     from concurrent.futures import ThreadPoolExecutor
 
     from direct_stereo_slam_amd import synth as S
@@ -295,27 +359,37 @@ def build_frames(args, w, h, K, T):
     Scene = S.ReliefScene if args.scene_family == "relief" else S.PlaneScene
     if key in _FRAMES:  # (the fixed-schedule leg runs on the frames of the headline leg)
         return _FRAMES[key]
-    u8 = (lambda im: np.clip(np.rint(im), 0, 255).astype(np.float32)) if args.u8 else (lambda im: im)
-    textures, first = [], []
-    for k in range(n_tex):
-        seed = 0x5EED0000 + seeds[k]
-        scene = Scene(seed=seed)
-        rng = np.random.default_rng(seed)
-        ref = scene.render(K, w, h, noise=2.0, rng=rng)
-        R, t = S.random_motion(rng)
-        new = scene.render(K, w, h, R, t, a=0.02, b=3.0, noise=2.0, rng=rng)
-        right = scene.render(K, w, h, T[:3, :3], T[:3, 3], noise=2.0, rng=rng)
-        textures.append((scene, u8(ref), u8(right)))
-        first.append((u8(new), R, t))
+
+    def shared(shape, dtype):
+        return np.frombuffer(mmap.mmap(-1, int(np.prod(shape)) * np.dtype(dtype).itemsize), dtype).reshape(shape)
+
+    _RENDER.clear()
+    _RENDER.update(K=K, w=w, h=h, T=T, seeds=seeds, n_tex=n_tex, Scene=Scene, u8=bool(args.u8),
+                   ref=shared((n_tex, h, w), np.float32), right=shared((n_tex, h, w), np.float32), new=shared((n_frames, h, w), np.float32),
+                   R=shared((n_frames, 3, 3), np.float64), t=shared((n_frames, 3), np.float64))
+    workers = min(16, os.cpu_count() or 4, n_frames)
+    if workers <= 1:
+        for j in range(n_frames):
+            _render_frame(j)
+    elif _device_open():
+        with ThreadPoolExecutor(max_workers=workers) as ex:
+            list(ex.map(_render_frame, range(n_frames)))
+    else:
+        ctxm = mp.get_context("fork")
+        counter = ctxm.Value("l", 0)
+        procs = [ctxm.Process(target=_render_worker, args=(counter, n_frames), daemon=True) for _ in range(workers)]
+        for p in procs:
+            p.start()
+        for p in procs:
+            p.join()
+        if any(p.exitcode != 0 for p in procs):
+            raise RuntimeError(f"build_frames: a rendering process failed (exit codes {[p.exitcode for p in procs]})")
+    r = dict(_RENDER)
+    _RENDER.clear()
+    textures = [(Scene(seed=0x5EED0000 + seeds[k]), r["ref"][k], r["right"][k]) for k in range(n_tex)]
 
     def make(f):
-        k = f % n_tex
-        if f < n_tex:  # the first cycle: exactly round 2's frames (same seeds, same draws)
-            new, R, t = first[f]
-        else:
-            rng = np.random.default_rng(0x5EED0000 + 0x100000 * (f // n_tex) + seeds[k])
-            R, t = S.random_motion(rng)
-            new = u8(textures[k][0].render(K, w, h, R, t, a=0.02, b=3.0, noise=2.0, rng=rng))
+        R, t, new = r["R"][f], r["t"][f], r["new"][f]
         gt = S.pose_from_Rt(R, t)
         if args.init == "identity":
             guess = np.array(S.IDENTITY_POSE, np.float64)
@@ -325,10 +399,9 @@ def build_frames(args, w, h, K, T):
             e = np.random.default_rng(0xACCE1000 + f)
             Re, te = S.random_motion(e, sigma_t=np.array((0.05, 0.05, 0.2)) * args.init_err, sigma_r=0.005 * args.init_err)
             guess = S.pose_from_Rt(Re @ R, Re @ t + te)
-        return (k, new, gt, guess)
+        return (f % n_tex, new, gt, guess)
 
-    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as ex:
-        frames = list(ex.map(make, range(n_frames)))
+    frames = [make(f) for f in range(n_frames)]
     _FRAMES.clear()  # one configuration's images at a time
     _FRAMES[key] = (textures, frames)
     return textures, frames
@@ -364,20 +437,32 @@ def build_workload(args, ctx, config):
     textures, frames = build_frames(args, w, h, K, T)
     trackers, gts, guesses, host, images = [], [], [], [], []
     tpl_cache = {}
+    if args.template == "dense":
+        # one dense template per texture, made up front: the keyframe's pyramid built on the device (makeImages) by a scratch tracker and
+        # read back for the template colours, the inverse depths ray-cast on host threads side by side
+        from concurrent.futures import ThreadPoolExecutor
+
+        used = sorted({frames[(b + _FRAME_OFFSET) % len(frames)][0] for b in range(args.batch)})
+        scratch = TrackerAndScaler(ctx, w, h, nl, T, K, params)
+        scratch.makeK(*K)
+        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4, len(used))) as ex:
+            futs = {}
+            for k in used:
+                scratch.upload_image(0, textures[k][1], 1.0)
+                futs[k] = ex.submit(S.dense_template, textures[k][0], K, w, h, nl, [scratch.get_frame(0, l) for l in range(nl)])
+            tpl_cache = {k: f.result() for k, f in futs.items()}
+        scratch.close()
     for b in range(args.batch):
         k, new, gt, guess = frames[(b + _FRAME_OFFSET) % len(frames)]
         scene, ref, right = textures[k]
         trk = TrackerAndScaler(ctx, w, h, nl, T, K, params)
         trk.makeK(*K)
-        if args.template == "dense" and k in tpl_cache:
+        if args.template == "dense":
             tpl = tpl_cache[k]
         else:
             trk.upload_image(0, ref, 1.0)  # device makeImages of the keyframe, read back for the template colours
             ref_p = [trk.get_frame(0, l) for l in range(nl)]
-            if args.template == "dense":
-                tpl = tpl_cache[k] = S.dense_template(scene, K, w, h, nl, ref_p)
-            else:
-                tpl = S.sparse_template(scene, K, w, h, nl, ref_p, n0=10000, seed=b)
+            tpl = S.sparse_template(scene, K, w, h, nl, ref_p, n0=10000, seed=b)
         trk.setCoarseTrackingRef(b, (0.0, 0.0), 1.0, *tpl)
         trk.upload_image(0, new, 1.0)
         trk.upload_image(1, right, 1.0)
@@ -439,7 +524,9 @@ def one_step(ctx, wl, kf_idx, with_upload=False):
         good, poses, affs, last, flow, err, sc = ctx.track_and_scale_batch(wl["trackers"], poses0, np.zeros((B, 2)), wl["nl"] - 1, kf, np.ones(len(kf)))
         st_track, st_scale = ctx.stats(), ctx.stats2()
         st_scale.total_ms = 0.0  # (one call: its time is the tracking segment's total)
-    return good, poses, err, sc, st_track, st_scale
+    # (everything the calls returned, for --dump-outputs)
+    outputs = dict(track_pose=poses, track_aff=affs, track_last_residuals=last, track_flow=flow, track_good=good, scale=sc, scale_err=err)
+    return good, poses, err, sc, st_track, st_scale, outputs
 
 
 class StreamRunner:
@@ -520,6 +607,17 @@ class StreamRunner:
         sc = np.array([self.out[t].scale for t in ts], np.float32)
         self.last_evals = np.array([list(self.out[t].evals) for t in tk], np.int64)  # per frame and level
         return good, poses, err, sc
+
+    def outputs_of(self, tag):
+        """what dsm_stream_results handed back for the step `tag`, as arrays (--dump-outputs); scheduling fields (ticket, passes) left out"""
+        tr, sr = [self.out[t] for t in self.owner[tag][0]], [self.out[t] for t in self.owner[tag][1]]
+        return {"track_pose": np.array([list(r.pose) for r in tr], np.float64).reshape(-1, 7),
+                "track_aff": np.array([list(r.aff) for r in tr], np.float64).reshape(-1, 2),
+                "track_last_residuals": np.array([list(r.last_residuals) for r in tr], np.float64).reshape(-1, 6),
+                "track_flow": np.array([list(r.flow) for r in tr], np.float64).reshape(-1, 3),
+                "track_good": np.array([r.good for r in tr], np.float32), "track_status": np.array([r.status for r in tr], np.float32),
+                "track_evals": np.array([list(r.evals) for r in tr], np.float64).reshape(-1, 6),
+                "scale": np.array([r.scale for r in sr], np.float32), "scale_err": np.array([r.err for r in sr], np.float32)}
 
     def close(self):
         self.st.close()
@@ -676,6 +774,13 @@ def measure_stream(args, ctx, wl, steps, warmup, world):
     timed_passes = run.passes - p0
     good, poses, err, sc = run.results_of(("t", steps - 1))
     last_evals = run.last_evals
+    outputs = run.outputs_of(("t", steps - 1))
+    if not args.full:  # a plain run: what the timed region counted itself, no further advances
+        run.close()
+        stream = {"engine": "ticks" if args.stream_engine == 1 else "passes", "track_slots": B, "scale_slots": max(1, len(kf_idx)),
+                  "advances_in_timed_region": int(timed_passes), "host_share_of_timed_region": 1.0 - float(timed["ms"]) * 1e-3 / dt}
+        return plain_result(args, wl, dt, steps, world, good, poses, int(timed["bytes"] + timed["bytes_scale"]), timed["evals"], outputs,
+                            evals=last_evals, stream=stream)
     sched = run.st.schedule(0)
     # roofline of the dominant kernel: steady-state passes (the pool refilled every pass) with HIP events around every eval dispatch
     for i in range(10):
@@ -771,7 +876,29 @@ def measure_stream(args, ctx, wl, steps, warmup, world):
               "fixed_schedule": int(wl["params"].fixed_schedule), "work_queue": int(wl["params"].work_queue),
               "frames_with_translation_error_above_1cm": int((terr_all > 0.01).sum()), "all_tracked": bool(good.all())}
     return dict(dt=dt, value=world * frames / dt, ms_per_step=1e3 * dt / steps, good=good, poses=poses, roofline=roofline, detail=detail, n0=n0,
-                evals=last_evals)
+                evals=last_evals, outputs=outputs)
+
+
+def plain_result(args, wl, dt, steps, world, good, poses, timed_bytes, timed_evals, outputs, evals=None, **extra):
+    """measure()'s result in a plain run (no --full): the headline figure and what the timed region itself counted --
+    algorithmic bytes and evaluations of all its steps, the poses of its last step; no instrumented runs"""
+    B = len(wl["trackers"])
+    frames = B * steps
+    whole = timed_bytes / dt / 1e9
+    terr = np.abs(poses[:, 4:] - wl["gts"][:, 4:]).max(1)
+    detail = {"frames_in_flight_per_gpu": B, "streams": args.streams, **extra,
+              "evals_per_frame_by_level": [float(timed_evals[l]) / frames for l in range(wl["nl"])],
+              "algorithmic_MB_per_frame": timed_bytes / frames / 1e6, "whole_step_GBps": whole,
+              "max_abs_translation_error_m": float(terr.max()), "distinct_frames": int(wl["distinct_frames"]), "textures": int(wl["textures"]),
+              "initial_guess": args.init if args.init == "identity" else f"constant-motion (error sigma {args.init_err} x motion sigma)",
+              "texture_list": args.textures, "scene_family": args.scene_family,
+              "fixed_schedule": int(wl["params"].fixed_schedule), "work_queue": int(wl["params"].work_queue),
+              "frames_with_translation_error_above_1cm": int((terr > 0.01).sum()), "all_tracked": bool(good.all())}
+    roofline = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac_whole_step": whole / HBM_PEAK_GBS,
+                "note": "all algorithmic bytes of the timed region / its wall time; the dominant kernel's figures need --full"}
+    n0 = len(wl["trackers"][0].get_template(0)[0])
+    return dict(dt=dt, value=world * frames / dt, ms_per_step=1e3 * dt / steps, good=good, poses=poses, roofline=roofline, detail=detail, n0=n0,
+                evals=evals, outputs=outputs)
 
 
 def kernel_source_sha():
@@ -837,6 +964,10 @@ def measure(args, ctx, wl, steps, warmup, world, with_upload=False):
     if trace is not None:
         sys.stderr.write(f"per-step ms: {trace}\n")
     good, poses = out[0], out[1]
+    if not args.full:  # a plain run: every step is the same work, so the timed region's bytes and evaluations are the last step's x steps
+        stt, sts = out[4], out[5]
+        return plain_result(args, wl, dt, steps, world, good, poses, (stt.algorithmic_bytes + sts.algorithmic_bytes) * steps,
+                            np.array(list(stt.evals), np.int64) * steps, out[6])
 
     # roofline of the dominant kernel (level-0 pose eval): one extra step, same stream configuration, with one pair
     # of HIP events around every eval-kernel dispatch ON THE STREAM IT IS LAUNCHED ON.  The stream groups' level-0
@@ -908,7 +1039,7 @@ def measure(args, ctx, wl, steps, warmup, world, with_upload=False):
               "fixed_schedule": int(wl["params"].fixed_schedule), "work_queue": int(wl["params"].work_queue),
               "frames_with_translation_error_above_1cm": int((terr_all > 0.01).sum()), "all_tracked": bool(good.all())}
     return dict(dt=dt, value=world * B * steps / dt, ms_per_step=1e3 * dt / steps, good=good, poses=poses, roofline=roofline,
-                detail=detail, n0=n0)
+                detail=detail, n0=n0, outputs=out[6])
 
 
 def workload_label(args, wl, n0):
@@ -1447,9 +1578,10 @@ def compact_line(res, detail_path):
     if isinstance(st, dict):
         cfg["form"] = "dsm_stream_* " + str(st.get("engine")) + " engine"
         tpa = st.get("ticks_per_advance")
-        cfg["stream"] = {**_pick(st, ("track_slots", "scale_slots", "advances_in_timed_region", "host_share_of_timed_region"), 3),
-                         "ticks_per_advance": tpa if not isinstance(tpa, str) else "auto",
-                         "steady_state_frames_per_s": _r((st.get("steady_state") or {}).get("frames_per_s"), 4)}
+        cfg["stream"] = _pick(st, ("track_slots", "scale_slots", "advances_in_timed_region", "host_share_of_timed_region"), 3)
+        if "steady_state" in st:  # (--full: measured after the timed region)
+            cfg["stream"].update(ticks_per_advance=tpa if not isinstance(tpa, str) else "auto",
+                                 steady_state_frames_per_s=_r((st.get("steady_state") or {}).get("frames_per_s"), 4))
     else:
         cfg["form"] = "one synchronous dsm_track_and_scale_batch call per step"
     legs = {}
@@ -1513,8 +1645,11 @@ def compact_line(res, detail_path):
                     "avg_launch_us", "kernel_busy_us_per_launch", "launches", "dispatches", "stream_groups", "evals_by_level", "bytes_per_eval_by_level",
                     "evals", "residual_only_evals"), 4)
     ro["traffic"] = _r(rf.get("traffic"), 5)
-    ro["kernel"] = str(rf.get("kernel", "")).split(" (")[0]
-    ro["traffic_source"] = str(rf.get("traffic_source", "")).split(":")[0][:100]
+    if "kernel" in rf:  # (a plain run measures no kernel of its own: roofline.note says so)
+        ro["kernel"] = str(rf.get("kernel", "")).split(" (")[0]
+        ro["traffic_source"] = str(rf.get("traffic_source", "")).split(":")[0][:100]
+    else:
+        ro["note"] = str(rf.get("note", ""))[:120]
     out["roofline"] = ro
     if cb is None:
         out["cpu_baseline"] = None
@@ -1561,7 +1696,7 @@ def write_detail(res, path):
     return path
 
 
-def line_guard(res, detail_path="gpurun_out/bench_detail.json"):
+def line_guard(res, detail_path=DETAIL_OUT):
     """The sharded ring-key leg is this bench's first contact with several RCCL ranks on a box; a process that dies inside a
     native library (SIGSEGV, abort) prints nothing.  Before the leg, rank 0 parks its finished bench line with a forked
     helper that touches neither the GPU nor torch: it waits on a pipe and, if rank 0 goes away without calling the returned
@@ -1623,14 +1758,36 @@ def run_with_deadline(fn, seconds, device):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+def dump_outputs(outputs, path, limit=64 << 20):
+    """--dump-outputs: DIR/<name>.npy for every array the timed path returned in its last step, float32 / float64.  Above `limit`
+    bytes in all, a seeded sample of the rows is written instead, its row numbers as DIR/<name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: np.asarray(v) if np.asarray(v).dtype in (np.float32, np.float64) else np.asarray(v).astype(np.float64) for k, v in outputs.items()}
+    budget = limit - 2 * 128 * len(arrs)  # (two .npy headers of at most 128 bytes per array)
+    frac = 1.0
+    if sum(a.nbytes for a in arrs.values()) > budget:  # a sampled array's row numbers (8 bytes a row) are part of the budget
+        frac = budget / sum(a.nbytes + 8 * len(a) for a in arrs.values())
+    for name, a in arrs.items():
+        if frac < 1.0 and len(a) > 1:
+            rows = np.sort(np.random.default_rng(len(a)).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def bench_tracking(args):
+    from direct_stereo_slam_amd import synth as S
     from direct_stereo_slam_amd.tracker import Context
 
+    w, h, _, K = config_geometry(args.config)
+    build_frames(args, w, h, K, S.KITTI_T_STEREO)  # (before the device is opened: the rendering processes are forked)
     rank, local, world = dist_setup(args)
     ctx = Context(local)
     ctx.set_streams(args.streams)
     wl = build_workload(args, ctx, args.config)
     m = measure(args, ctx, wl, args.steps, args.warmup, world, args.with_upload)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(m["outputs"], args.dump_outputs)
     res = {
         "metric": baseline_metric(),
         "value": m["value"],
@@ -1754,7 +1911,8 @@ def bench_tracking(args):
         if guard is not None:
             guard()
     if rank == 0:
-        write_detail(res, args.detail_out)
+        if args.detail_out:
+            write_detail(res, args.detail_out)
         sys.stderr.flush()
         print(compact_line(res, args.detail_out), flush=True)
     if stuck:

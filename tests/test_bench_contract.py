@@ -30,6 +30,75 @@ def test_metric_is_baseline_jsons_and_defaults_are_the_contracts(monkeypatch):
     assert (a.gpus, a.steps, a.warmup) == (4, 7, 3)
 
 
+def test_a_plain_run_is_the_headline_alone_and_full_restores_the_rest(monkeypatch):
+    """without --full: no CPU baseline, no extra leg, no side file; --full runs them all (--quick keeps its meaning under it)"""
+    m = _bench()
+    legs = ("no_cpu", "no_fixed_leg", "no_second_leg", "no_plane_leg", "no_upload_leg", "no_replay_leg", "no_ringkey_leg")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = m.parse()
+    assert not a.full and all(getattr(a, k) for k in legs) and a.detail_out is None and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = m.parse()
+    assert a.full and not any(getattr(a, k) for k in legs) and a.detail_out == m.DETAIL_OUT
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--quick"])
+    a = m.parse()
+    assert a.full and all(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", "out_dir"])
+    assert m.parse().dump_outputs == "out_dir"
+
+
+def test_dump_outputs_writes_float_arrays_within_the_size_bound(tmp_path):
+    import numpy as np
+
+    m = _bench()
+    outs = {"track_pose": np.arange(70, dtype=np.float64).reshape(10, 7), "track_good": np.ones(10, bool), "scale": np.ones(2, np.float32)}
+    m.dump_outputs(outs, str(tmp_path / "a"))
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == set(outs) and all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["track_pose"], outs["track_pose"]) and got["track_good"].dtype == np.float64 and got["scale"].dtype == np.float32
+    # above the bound: the same seeded sample of rows every time, with the row numbers beside it
+    big = {"track_pose": np.arange(7000, dtype=np.float64).reshape(1000, 7)}
+    for d in ("b", "c"):
+        m.dump_outputs(big, str(tmp_path / d), limit=8 * 7 * 100)
+    rows = np.load(tmp_path / "b" / "track_pose_rows.npy").astype(int)
+    sample = np.load(tmp_path / "b" / "track_pose.npy")
+    assert sample.nbytes <= 8 * 7 * 100 and np.array_equal(sample, big["track_pose"][rows])
+    assert np.array_equal(sample, np.load(tmp_path / "c" / "track_pose.npy"))
+    # the bound holds for everything written, the row numbers and the .npy headers included
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 8 * 7 * 100
+
+
+def test_frames_rendered_on_threads_equal_the_forked_ones(monkeypatch):
+    """build_frames forks its rendering processes only while no device is open in the process; once one is, it renders on
+    threads and never forks -- the same images either way"""
+    import multiprocessing
+
+    import numpy as np
+
+    m = _bench()
+    from direct_stereo_slam_amd import synth as S
+
+    w, h, K = 312, 96, (179.7, 179.7, 152.6, 47.3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--batch", "24", "--u8"])
+    a = m.parse()
+    monkeypatch.setattr(m, "_device_open", lambda: False)
+    tex_f, fr_f = m.build_frames(a, w, h, K, S.KITTI_T_STEREO)
+    m._FRAMES.clear()
+
+    def no_fork(*args, **kw):
+        raise AssertionError("build_frames forked with a device open")
+
+    monkeypatch.setattr(m, "_device_open", lambda: True)
+    monkeypatch.setattr(multiprocessing, "get_context", no_fork)
+    tex_t, fr_t = m.build_frames(a, w, h, K, S.KITTI_T_STEREO)
+    m._FRAMES.clear()
+    assert len(fr_t) == len(fr_f) == 24
+    for (_, r1, q1), (_, r2, q2) in zip(tex_f, tex_t):
+        assert np.array_equal(r1, r2) and np.array_equal(q1, q2)
+    for f1, f2 in zip(fr_f, fr_t):
+        assert f1[0] == f2[0] and all(np.array_equal(x, y) for x, y in zip(f1[1:], f2[1:]))
+
+
 def test_gpus_flag_is_honoured_or_fails_loudly():
     """`--gpus N` without a launcher spawns N ranks itself; a mismatching launcher or too few devices is an error, never a
     silent 1-GPU run labelled otherwise"""
@@ -103,7 +172,7 @@ def test_compact_line_of_the_largest_stored_result_fits_the_drivers_tail():
 @pytest.mark.gpu
 def test_bench_line_carries_every_key_of_the_contract(tmp_path):
     detail = str(tmp_path / "detail.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "8", "--scenes", "2", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "8", "--scenes", "2", "--steps", "2",
                           "--warmup", "1", "--cpu-seconds", "0", "--second-leg-steps", "1", "--detail-out", detail], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     last = out.stdout.strip().splitlines()[-1]
@@ -146,6 +215,37 @@ def test_bench_line_carries_every_key_of_the_contract(tmp_path):
     assert "same fixed schedule" in fx["cpu_baseline"]["sample"]
     ac = c["all_cores"]
     assert ac["cores"] >= 2 and ac["value"] > 0 and ac["cpu_model"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_same_outputs_every_time(tmp_path):
+    """a plain run: the contract keys, exactly --steps timed steps, and --dump-outputs: the last timed step's arrays, equal from run to run"""
+    import ast
+
+    import numpy as np
+
+    dumps = []
+    env = dict(os.environ, DSM_BENCH_TRACE_STEPS="1")  # the steps the run itself took, one host time each, on stderr
+    for i, form in enumerate((["--stream", "1"], ["--stream", "1"], ["--stream", "0"])):
+        d = str(tmp_path / f"out{i}")
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "8", "--scenes", "3", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", d, *form], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+        line = _line(out)
+        # streamed: warm-up and timed steps (1 + 3) and no step after them; batch form: the timed steps alone
+        trace = [l for l in out.stderr.splitlines() if l.startswith("per-step")]
+        assert len(trace) == 1 and len(ast.literal_eval(trace[0].split(": ", 1)[1])) == (1 + 3 if form[1] == "1" else 3), trace
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["value"] > 0 and abs(line["value"] - 8 * 3 / (line["ms_per_step"] * 3e-3)) < 1e-3 * line["value"]
+        assert line["cpu_baseline"] is None and "legs" not in line["config"] and line["config"]["detail"] is None
+        assert line["config"]["all_tracked"] is True and 0 < line["roofline"]["frac_whole_step"] < 1
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    for got in dumps:
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert got["track_pose"].shape == (8, 7) and got["scale"].shape == (2,) and (got["track_good"] == 1).all()
+    assert set(dumps[0]) == set(dumps[1]) and all(np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True) for k in dumps[0])
+    # the batch form returns the same bits as the streamed form (dsm_stream_*: "bit-identical to the batch calls")
+    for k in dumps[2]:
+        assert np.array_equal(dumps[2][k], dumps[0][k], equal_nan=True), k
 
 
 @pytest.mark.gpu

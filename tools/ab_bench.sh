@@ -13,7 +13,7 @@ for rep in 1 2; do
   for l in "${libs[@]}"; do
     cp "$l" "$LIB"
     printf "%s: " "$(basename "$l")"
-    python "$R/bench.py" --no-cpu "$@" | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print(round(d['value']), 'frames/s', round(r['achieved']), 'GB/s', [x['GBps'] for x in d['config'].get('pose_eval_kernels_by_level', [])])"
+    python "$R/bench.py" --full --no-cpu "$@" | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print(round(d['value']), 'frames/s', round(r['achieved']), 'GB/s', [x['GBps'] for x in d['config'].get('pose_eval_kernels_by_level', [])])"
   done
 done
 cp /tmp/lib_restore.so "$LIB"

@@ -7,7 +7,7 @@ timeout 1200 python -m pytest tests/test_stream.py -x -q -m gpu 2>&1 | tail -25 
 tail -3 gpurun_out/chain_tests.log
 run() { # label -- bench args
   local label=$1; shift; shift
-  timeout 400 python $R/bench.py --quick "$@" 2>/dev/null | python -c "
+  timeout 400 python $R/bench.py --full --quick "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$label', round(d['value']), 'frac', round(r['frac'],3), 'whole', round(r['frac_whole_step'],3), 'avg_launch_us', round(r['avg_launch_us'],1), 'steady', round(d['config']['stream']['steady_state_frames_per_s']), 'ticks/adv', d['config']['stream'].get('ticks_per_advance'))"

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 cd $R; mkdir -p gpurun_out
 run() { # label -- bench args
   local label=$1; shift; shift
-  timeout 400 python $R/bench.py --quick "$@" 2>/dev/null | python -c "
+  timeout 400 python $R/bench.py --full --quick "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$label', round(d['value']), 'frac', round(r['frac'],3), 'whole', round(r['frac_whole_step'],3), 'avg_launch_us', round(r['avg_launch_us'],1), 'steady', round(d['config']['stream']['steady_state_frames_per_s']))"

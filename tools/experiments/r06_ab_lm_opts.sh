@@ -3,9 +3,10 @@
 # reservation (tick_lm_kernel) -- against the tree of the round's last profile set; then the sparse template with the default chains
 R=${GRAFT_REPO_ROOT:-$PWD}
 cd $R; mkdir -p gpurun_out
+mkdir -p "$R/bench_out"  # (stderr of the last bench run: bench_out/ab_err.log)
 run() { # label tree -- bench args
   local label=$1 tree=$2; shift; shift; shift
-  (cd $tree && timeout ${TMO:-150} python bench.py --quick "$@" 2>gpurun_out/_err.log) | python -c "
+  (cd $tree && timeout ${TMO:-150} python bench.py --full --quick "$@" 2>"$R/bench_out/ab_err.log") | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; st=d['config'].get('stream') or {}

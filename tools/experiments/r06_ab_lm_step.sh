@@ -8,7 +8,7 @@ timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -15 > gpurun_out/lm
 tail -3 gpurun_out/lm_step_tests.log
 run() { # label tree -- bench args
   local label=$1 tree=$2; shift; shift; shift
-  (cd $tree && timeout 400 python bench.py --quick "$@" 2>/dev/null) | python -c "
+  (cd $tree && timeout 400 python bench.py --full --quick "$@" 2>/dev/null) | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; st=d['config'].get('stream') or {}
 print('$label', round(d['value'],1), 'ms/step', round(d['ms_per_step'],4), 'frac', round(r['frac'],3), 'whole', round(r['frac_whole_step'],3), 'avg_launch_us', round(r['avg_launch_us'],1), 'steady', st.get('steady_state_frames_per_s'))"

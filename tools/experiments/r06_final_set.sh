@@ -9,9 +9,10 @@ timeout 200 python __graft_entry__.py smoke > gpurun_out/final/smoke.log 2>&1; t
 timeout 600 bash tools/profile_pmc_r06.sh r06b > gpurun_out/final/pmc.log 2>&1; tail -2 gpurun_out/final/pmc.log
 cp gpurun_out/r06b_profiles/r06b_pmc_traffic.json profiles/ 2>/dev/null
 cd $R
-timeout 500 python bench.py --detail-out gpurun_out/final/bench_default_detail.json > gpurun_out/final/bench_default_line.json 2> gpurun_out/final/bench_default.err
+mkdir -p bench_out/final  # (the line, the detail and the log of the default bench)
+timeout 500 python bench.py --full --detail-out bench_out/final/bench_default_detail.json > bench_out/final/bench_default_line.json 2> bench_out/final/bench_default.err
 python -c "
-import json; d=json.loads(open('gpurun_out/final/bench_default_line.json').read().strip().splitlines()[-1]); r=d['roofline']
+import json; d=json.loads(open('bench_out/final/bench_default_line.json').read().strip().splitlines()[-1]); r=d['roofline']
 print('default', d['value'], 'frac', r['frac'], 'whole', r.get('frac_whole_step'), 'traffic', r.get('traffic'), 'cpu', d.get('cpu_baseline',{}).get('value'))
 rp=d['config']['legs']['replay']; print('replay', rp)"
 for cfg in S2 S1; do

@@ -10,7 +10,7 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("DSM_HOTPATH_LIB", os.path.join(ROOT, "scratch", "lib_stamps", "libdsm_hotpath.so"))
 import bench  # noqa: E402
 
-sys.argv = ["bench.py", "--quick"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--quick"] + sys.argv[1:]
 a = bench.parse()
 bench.bench_tracking(a)
 L = C.CDLL(os.environ["DSM_HOTPATH_LIB"])

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}
 for B in 8 12 16 24 32 64 256; do
   printf "B=%d: " $B
-  python $R/bench.py --evals-only --batch $B --kf-every 100000 --no-cpu --no-second-leg --steps 30 --streams 1 "$@" | python -c "
+  python $R/bench.py --full --evals-only --batch $B --kf-every 100000 --no-cpu --no-second-leg --steps 30 --streams 1 "$@" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), 'frames/s', [x['GBps'] for x in d['config']['pose_eval_kernels_by_level']], 'whole', round(d['config']['whole_step_GBps']))"

@@ -9,8 +9,8 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 Q="--quick"
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python $R/bench.py $Q --steps 2 --warmup 1 --detail-out $OUT/pmc_fetch.log.detail.json > $OUT/pmc_fetch.log 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python $R/bench.py $Q --steps 2 --warmup 1 --detail-out $OUT/pmc_write.log.detail.json > $OUT/pmc_write.log 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python $R/bench.py --full $Q --steps 2 --warmup 1 --detail-out $OUT/pmc_fetch.log.detail.json > $OUT/pmc_fetch.log 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python $R/bench.py --full $Q --steps 2 --warmup 1 --detail-out $OUT/pmc_write.log.detail.json > $OUT/pmc_write.log 2>&1
 python $R/tools/summarize_profiles_r06.py $OUT $TAG $R/gpurun_out/${TAG}_profiles pmc > $OUT/summary_pmc.log 2>&1
 tail -3 $OUT/summary_pmc.log
 rm -rf $OUT/pmc_fetch $OUT/pmc_write

@@ -12,19 +12,19 @@ cd /tmp && export TMPDIR=/tmp
 Q="--quick"
 b() { # name, args...: one bench run, log + detail
   local name=$1; shift
-  timeout 900 python $R/bench.py "$@" --detail-out $OUT/$name.log.detail.json > $OUT/$name.log 2>$OUT/$name.err
+  timeout 900 python $R/bench.py --full "$@" --detail-out $OUT/$name.log.detail.json > $OUT/$name.log 2>$OUT/$name.err
 }
 # 1. HBM traffic counters of the tick engine's evaluation kernel, one pass each (never combined with other trace domains) -- FIRST:
 #    the summary is stamped with the kernel-source hash and the default line below then quotes it
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python $R/bench.py $Q --steps 2 --warmup 1 --detail-out $OUT/pmc_fetch.log.detail.json > $OUT/pmc_fetch.log 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python $R/bench.py $Q --steps 2 --warmup 1 --detail-out $OUT/pmc_write.log.detail.json > $OUT/pmc_write.log 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python $R/bench.py --full $Q --steps 2 --warmup 1 --detail-out $OUT/pmc_fetch.log.detail.json > $OUT/pmc_fetch.log 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python $R/bench.py --full $Q --steps 2 --warmup 1 --detail-out $OUT/pmc_write.log.detail.json > $OUT/pmc_write.log 2>&1
 # 2. per-kernel statistics of the default command (without the CPU / second legs: they only add host time and other kernels)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $R/bench.py $Q --detail-out $OUT/trace.log.detail.json > $OUT/trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $R/bench.py --full $Q --detail-out $OUT/trace.log.detail.json > $OUT/trace.log 2>&1
 python $R/tools/tick_timeline.py $(find $OUT/trace -name "*kernel_trace.csv" | head -1) 2 1200 > $OUT/tick_timeline.txt 2>&1
 python $R/tools/summarize_profiles_r06.py $OUT $TAG $R/gpurun_out/${TAG}_profiles pmc > $OUT/summary_pmc.log 2>&1
 mkdir -p $R/profiles && cp $R/gpurun_out/${TAG}_profiles/${TAG}_pmc_traffic.json $R/profiles/ 2>/dev/null
 # 3. the default bench line (CPU legs, five-level, fixed-schedule, plane-family and PCIe-inclusive legs, replay, ring-key and loop-chain legs): the line itself and its detail
-timeout 1500 python $R/bench.py --detail-out $OUT/bench_default.log.detail.json > $OUT/bench_default.log 2>$OUT/bench_default.err
+timeout 1500 python $R/bench.py --full --detail-out $OUT/bench_default.log.detail.json > $OUT/bench_default.log 2>$OUT/bench_default.err
 cp $OUT/bench_default.log $R/gpurun_out/${TAG}_profiles/${TAG}_bench_default_line.json
 # 4. the other forms and workloads
 b bench_batch_form $Q --stream 0

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for T in 0 1; do
   OUT=$R/gpurun_out/r04_sq_tile$T
   mkdir -p $OUT
-  CMD="python $R/bench.py --no-cpu --no-second-leg --no-fixed-leg --no-ringkey-leg --no-replay-leg --evals-only --kf-every 100000 --streams 1 --stream 0 --steps 2 --warmup 1 --tile $T"
+  CMD="python $R/bench.py --full --no-cpu --no-second-leg --no-fixed-leg --no-ringkey-leg --no-replay-leg --evals-only --kf-every 100000 --streams 1 --stream 0 --steps 2 --warmup 1 --tile $T"
   timeout 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_INSTS_LDS --kernel-trace --output-format csv -d $OUT/p1 -- $CMD > $OUT/p1.log 2>&1
   timeout 400 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAIT_ANY --kernel-trace --output-format csv -d $OUT/p2 -- $CMD > $OUT/p2.log 2>&1
   timeout 400 rocprofv3 --pmc SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_WAVES --kernel-trace --output-format csv -d $OUT/p3 -- $CMD > $OUT/p3.log 2>&1
