@@ -82,6 +82,21 @@ class StreamResult(C.Structure):
     ]
 
 
+class StreamHypResult(C.Structure):
+    _fields_ = [
+        ("ticket", C.c_uint64),
+        ("have_one_good", C.c_int),
+        ("tries_used", C.c_int),
+        ("tries_run", C.c_int),
+        ("advances", C.c_int),
+        ("pose", C.c_double * 7),
+        ("aff", C.c_double * 2),
+        ("flow", C.c_double * 3),
+        ("achieved_res", C.c_double * MAX_LEVELS),
+        ("evals", C.c_int64 * MAX_LEVELS),
+    ]
+
+
 class RefJob(C.Structure):
     _fields_ = [
         ("t", C.c_void_p), ("frame_owner", C.c_void_p), ("slot", C.c_int), ("ref_frame_id", C.c_int),
@@ -130,6 +145,12 @@ SYMBOLS = {
     "dsm_stream_set_rounds": (C.c_int, [_vp, C.c_int, c_int_p]),
     "dsm_stream_get_stats": (C.c_int, [_vp, C.POINTER(Stats), C.POINTER(Stats)]),
     "dsm_stream_get_schedule": (C.c_int, [_vp, C.c_int, c_int_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "dsm_stream_submit_hypotheses": (C.c_int, [_vp, _vp, C.c_int, c_double_p, c_double_p, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_uint64)]),
+    "dsm_stream_hypotheses_results": (C.c_int, [_vp, C.c_int, C.POINTER(StreamHypResult), c_int_p]),
+    "dsm_stream_hypotheses_counts": (C.c_int, [_vp, c_int_p, c_int_p]),
+    "dsm_stream_set_hypothesis_window": (C.c_int, [_vp, C.c_int]),
+    "dsm_hypotheses_resolve": (C.c_int, [C.c_int, c_double_p, c_double_p, C.c_int, C.c_double, C.c_double, C.c_int, c_int_p, c_double_p, c_double_p,
+                                         c_double_p, c_double_p, C.POINTER(StreamHypResult), c_int_p]),
     "dsm_context_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "dsm_context_destroy": (C.c_int, [_vp]),
     "dsm_context_sync": (C.c_int, [_vp]),

@@ -1,9 +1,12 @@
 // host_capi.cpp -- the pieces of the path that SURVEY.md section 8a keeps on the host by design:
-// search_sc (<= 3 candidates per query, src/loop_closure/loop_detection/search_place.h:59-84).
+// search_sc (<= 3 candidates per query, src/loop_closure/loop_detection/search_place.h:59-84) and the replay of the hypothesis
+// loop of FrontEnd::trackNewCoarse (dsm_hypotheses_resolve).
 // Plain C++; no device code.
 #include "../../include/dsm_hotpath.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
+#include <cstring>
 
 extern "C" {
 
@@ -53,6 +56,56 @@ int dsm_search_sc(const int *sig_idx, const double *sig_val, int n_sig, int n_ca
       *res_diff = cur;
     }
   }
+  return DSM_OK;
+}
+
+// The hypothesis loop of FrontEnd::trackNewCoarse (FrontEnd.cpp:194-256) replayed from tries run without abort (the stream's hypothesis
+// groups, stream_capi.hip; the same replay as dsm_host::trackHypotheses and tracker.track_hypotheses)
+int dsm_hypotheses_resolve(int n_tries, const double *tries, const double aff_last[2], int coarsest_lvl, double last_coarse_rmse0,
+                           double retrack_threshold, int k, const int *good, const double *pose, const double *aff,
+                           const double *last_residuals, const double *flow, dsm_stream_hyp_result *out, int *decided_out) {
+  if (n_tries < 1 || k < 0 || k > n_tries || !tries || !aff_last || !out || !decided_out || coarsest_lvl < 0 || coarsest_lvl >= DSM_MAX_LEVELS ||
+      (k > 0 && (!good || !pose || !aff || !last_residuals || !flow)))
+    return DSM_ERR_INVALID;
+  dsm_stream_hyp_result R;
+  memset(&R, 0, sizeof R);
+  for (double &a : R.achieved_res) a = NAN; // Vec5::Constant(NAN) (:197)
+  bool have = false, done = false;
+  double fl[3] = {100, 100, 100};
+  int used = 0;
+  for (int i = 0; i < k && !done; i++) {
+    used++;
+    double cur[DSM_MAX_LEVELS];
+    memcpy(cur, last_residuals + (size_t)DSM_MAX_LEVELS * i, sizeof cur);
+    bool g = good[i] != 0;
+    for (int l = coarsest_lvl; l >= 0; l--) // the abort the sequential run takes at the first level 1.5x worse than achievedRes (:598)
+      if (cur[l] > 1.5 * R.achieved_res[l]) {
+        for (int j = 0; j < l; j++) cur[j] = NAN;
+        g = false;
+        break;
+      }
+    if (g && std::isfinite((float)cur[0]) && !(cur[0] >= R.achieved_res[0])) { // a new winner (:225-233); an aborted try never gets here
+      memcpy(fl, flow + 3 * (size_t)i, sizeof fl);
+      memcpy(R.aff, aff + 2 * (size_t)i, sizeof R.aff);
+      memcpy(R.pose, pose + 7 * (size_t)i, sizeof R.pose);
+      have = true;
+    }
+    if (have) // take over achievedRes (:236-243): the reference's Vec5
+      for (int l = 0; l < 5; l++)
+        if (!std::isfinite((float)R.achieved_res[l]) || R.achieved_res[l] > cur[l]) R.achieved_res[l] = cur[l];
+    done = have && R.achieved_res[0] < last_coarse_rmse0 * retrack_threshold; // :245-247
+  }
+  if (!have) { // :249-256
+    memcpy(R.pose, tries, sizeof R.pose);
+    memcpy(R.aff, aff_last, sizeof R.aff);
+    fl[0] = fl[1] = fl[2] = 0;
+  }
+  memcpy(R.flow, fl, sizeof R.flow);
+  R.have_one_good = have ? 1 : 0;
+  R.tries_used = used;
+  R.tries_run = k;
+  *out = R;
+  *decided_out = done || k == n_tries;
   return DSM_OK;
 }
 

@@ -21,6 +21,10 @@
 // candidate for this; measured with the tail amortised over 2048 frames it runs at 42.7 k frames/s against 48.5 k for the
 // launch form (profiles/r04_queue_form_b2048.json, r04_launch_form_b2048.json): its per-item cost is there in steady
 // state too, so the streaming form is built on the launches.
+//
+// Hypothesis groups (dsm_stream_submit_hypotheses): FrontEnd::trackNewCoarse's list of tries as one submission.  Its tries are ordinary
+// track problems without abort thresholds; their results go to the group (route_result) instead of `done`, and the loop is replayed on
+// the host by dsm_hypotheses_resolve (host_capi.cpp).  Host bookkeeping only: no launch or copy changes, with or without groups.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -79,6 +83,24 @@ int invalid(const char *msg) {
 }
 
 constexpr size_t kHistCap = 4096; // retired problems whose round counts the schedule looks at
+
+// A hypothesis group (dsm_stream_submit_hypotheses): the tries of FrontEnd::trackNewCoarse's loop as track problems without abort, their
+// outputs kept by try, the loop replayed by dsm_hypotheses_resolve over the tries that are back in order.  Host bookkeeping only.
+struct HypGroup {
+  dsm_tracker *trk = nullptr;
+  int n = 0, coarsest = 0;
+  double aff_last[2] = {0, 0}, rmse0 = 0, thr = 0;
+  std::vector<double> tries, pose, aff, last, flow; // n x 7 / n x 7 / n x 2 / n x DSM_MAX_LEVELS / n x 3
+  std::vector<int> good;
+  std::vector<char> back; // try i's result is back
+  int prefix = 0;         // tries 0 .. prefix-1 are back
+  int next = 1;           // the next try to queue (try 0 is queued at submission)
+  int in_flight = 0;      // queued (waiting on the host or handed to the device) and not back
+  int run = 0;            // tries whose results came back
+  bool decided = false;
+  long long born = 0;     // the stream's advance count at submission
+  dsm_stream_hyp_result res{};
+};
 
 } // namespace
 
@@ -159,6 +181,11 @@ struct dsm_stream {
   };
   std::unordered_map<uint64_t, Origin> origin;
   long long advances = 0, total_ticks = 0;
+  // ---- hypothesis groups ----
+  std::unordered_map<uint64_t, HypGroup> groups;                // group ticket -> group, until its result is handed back
+  std::unordered_map<uint64_t, std::pair<uint64_t, int>> member; // a group try's internal ticket -> (group ticket, try)
+  std::deque<dsm_stream_hyp_result> hyp_done;
+  int hyp_window = 0; // tries of a group waiting or resident at once after try 0; 0 = all
 };
 
 // the tick engine's resources (tick_setup); safe on a partially set-up stream, leaves every pointer null
@@ -320,31 +347,154 @@ static int submit_common(dsm_stream *s, int mode, int n, dsm_tracker *const *ts,
   return DSM_OK;
 }
 
+} // extern "C"
+
+// one trackNewestCoarse problem into the host's waiting queue (min_res: DSM_MAX_LEVELS thresholds, NULL = no abort); returns its ticket
+static uint64_t enqueue_track(dsm_stream *s, dsm_tracker *t, const double *pose0, const double *aff0, int coarsest_lvl, const double *min_res) {
+  Waiting wq;
+  wq.ticket = s->next_ticket++;
+  wq.trk = t;
+  StartInfo &I = wq.start;
+  memset(&I, 0, sizeof I);
+  memcpy(I.pose, pose0, sizeof I.pose);
+  memcpy(I.aff, aff0, sizeof I.aff);
+  for (int l = 0; l < DSM_MAX_LEVELS; l++) I.min_res[l] = min_res ? min_res[l] : std::numeric_limits<double>::quiet_NaN();
+  I.scale = 1.0f;
+  I.coarsest = coarsest_lvl;
+  dsm_stream::Origin og;
+  og.trk = t, og.admitted_at = -1;
+  memcpy(og.pose0, I.pose, sizeof og.pose0);
+  memcpy(og.aff0, I.aff, sizeof og.aff0);
+  s->origin[wq.ticket] = og;
+  s->waiting[0].push_back(wq);
+  return wq.ticket;
+}
+
+// ---- hypothesis groups ----
+static void group_queue_try(dsm_stream *s, uint64_t gt, HypGroup &g, int i) {
+  const uint64_t tk = enqueue_track(s, g.trk, &g.tries[7 * (size_t)i], g.aff_last, g.coarsest, nullptr); // no abort: replayed by the resolver
+  s->member[tk] = std::make_pair(gt, i);
+  g.in_flight++;
+}
+
+// the group's tries that still wait on the host leave the queue (those on the device run to their end)
+static void group_drop_waiting(dsm_stream *s, uint64_t gt, HypGroup &g) {
+  std::deque<Waiting> &wq = s->waiting[0];
+  auto keep_end = std::remove_if(wq.begin(), wq.end(), [&](const Waiting &w) {
+    auto it = s->member.find(w.ticket);
+    if (it == s->member.end() || it->second.first != gt) return false;
+    s->member.erase(it);
+    s->origin.erase(w.ticket);
+    g.in_flight--;
+    return true;
+  });
+  wq.erase(keep_end, wq.end());
+}
+
+// a retired track problem: a group try's result goes to its group, every other result to dsm_stream_results
+static void route_result(dsm_stream *s, const dsm_stream_result &r) {
+  auto mit = s->member.empty() ? s->member.end() : s->member.find(r.ticket);
+  if (mit == s->member.end()) {
+    s->done.push_back(r);
+    return;
+  }
+  const uint64_t gt = mit->second.first;
+  const int i = mit->second.second;
+  s->member.erase(mit);
+  HypGroup &g = s->groups.at(gt);
+  g.in_flight--, g.run++;
+  for (int l = 0; l < DSM_MAX_LEVELS; l++) g.res.evals[l] += r.evals[l];
+  if (!g.decided) {
+    g.good[i] = r.good;
+    memcpy(&g.pose[7 * (size_t)i], r.pose, sizeof r.pose);
+    memcpy(&g.aff[2 * (size_t)i], r.aff, sizeof r.aff);
+    memcpy(&g.last[DSM_MAX_LEVELS * (size_t)i], r.last_residuals, sizeof r.last_residuals);
+    memcpy(&g.flow[3 * (size_t)i], r.flow, sizeof r.flow);
+    g.back[i] = 1;
+    const int before = g.prefix;
+    while (g.prefix < g.n && g.back[g.prefix]) g.prefix++;
+    if (g.prefix > before) {
+      int64_t evals[DSM_MAX_LEVELS];
+      memcpy(evals, g.res.evals, sizeof evals);
+      int decided = 0;
+      dsm_hypotheses_resolve(g.n, g.tries.data(), g.aff_last, g.coarsest, g.rmse0, g.thr, g.prefix, g.good.data(), g.pose.data(), g.aff.data(),
+                             g.last.data(), g.flow.data(), &g.res, &decided);
+      memcpy(g.res.evals, evals, sizeof evals);
+      g.decided = decided != 0;
+    }
+    if (g.decided)
+      group_drop_waiting(s, gt, g);
+    else { // try 0 did not settle the frame: keep `window` of the following tries queued, in try order
+      const int w = s->hyp_window > 0 ? s->hyp_window : g.n;
+      while (g.next < g.n && g.in_flight < w) group_queue_try(s, gt, g, g.next++);
+    }
+  }
+  if (g.decided && g.in_flight == 0) { // nothing of the group is on the device any more: its result is handed back
+    g.res.ticket = gt;
+    g.res.tries_run = g.run;
+    g.res.advances = (int)(s->passes - g.born);
+    s->hyp_done.push_back(g.res);
+    s->groups.erase(gt);
+  }
+}
+
+extern "C" {
+
 int dsm_stream_submit_track(dsm_stream *s, int n, dsm_tracker *const *ts, const double *pose0, const double *aff0, int coarsest_lvl,
                             const double *min_res_for_abort, uint64_t *tickets_out) {
   if (n && (!pose0 || !aff0)) return invalid("dsm_stream_submit_track: null pose/aff");
   int rc = submit_common(s, 0, n, ts, coarsest_lvl, tickets_out);
   if (rc) return rc;
   for (int i = 0; i < n; i++) {
-    Waiting wq;
-    wq.ticket = s->next_ticket++;
-    wq.trk = ts[i];
-    StartInfo &I = wq.start;
-    memset(&I, 0, sizeof I);
-    memcpy(I.pose, pose0 + 7 * i, sizeof I.pose);
-    memcpy(I.aff, aff0 + 2 * i, sizeof I.aff);
-    for (int l = 0; l < DSM_MAX_LEVELS; l++)
-      I.min_res[l] = min_res_for_abort ? min_res_for_abort[DSM_MAX_LEVELS * i + l] : std::numeric_limits<double>::quiet_NaN();
-    I.scale = 1.0f;
-    I.coarsest = coarsest_lvl;
-    if (tickets_out) tickets_out[i] = wq.ticket;
-    dsm_stream::Origin og;
-    og.trk = ts[i], og.admitted_at = -1;
-    memcpy(og.pose0, I.pose, sizeof og.pose0);
-    memcpy(og.aff0, I.aff, sizeof og.aff0);
-    s->origin[wq.ticket] = og;
-    s->waiting[0].push_back(wq);
+    const uint64_t tk = enqueue_track(s, ts[i], pose0 + 7 * i, aff0 + 2 * i, coarsest_lvl, min_res_for_abort ? min_res_for_abort + DSM_MAX_LEVELS * i : nullptr);
+    if (tickets_out) tickets_out[i] = tk;
   }
+  return DSM_OK;
+}
+
+int dsm_stream_submit_hypotheses(dsm_stream *s, dsm_tracker *tracker, int n_tries, const double *tries, const double aff_last[2], int coarsest_lvl,
+                                 double last_coarse_rmse0, double retrack_threshold, uint64_t *ticket_out) {
+  if (!s || !tracker || n_tries < 1 || !tries || !aff_last || !ticket_out)
+    return invalid("dsm_stream_submit_hypotheses: null stream / tracker / tries / aff_last / ticket_out, or n_tries < 1");
+  if (s->cap[0] == 0) return invalid("dsm_stream_submit_hypotheses: the stream has no track slots");
+  int rc = submit_common(s, 0, 1, &tracker, coarsest_lvl, nullptr);
+  if (rc) return rc;
+  const uint64_t gt = s->next_ticket++;
+  HypGroup &g = s->groups[gt];
+  g.trk = tracker, g.n = n_tries, g.coarsest = coarsest_lvl;
+  g.aff_last[0] = aff_last[0], g.aff_last[1] = aff_last[1];
+  g.rmse0 = last_coarse_rmse0, g.thr = retrack_threshold;
+  g.tries.assign(tries, tries + 7 * (size_t)n_tries);
+  g.pose.assign(7 * (size_t)n_tries, 0.0), g.aff.assign(2 * (size_t)n_tries, 0.0);
+  g.last.assign(DSM_MAX_LEVELS * (size_t)n_tries, 0.0), g.flow.assign(3 * (size_t)n_tries, 0.0);
+  g.good.assign(n_tries, 0), g.back.assign(n_tries, 0);
+  g.born = s->passes;
+  group_queue_try(s, gt, g, 0); // try 0 (the constant-motion guess): nothing achieved yet, so no abort threshold either
+  *ticket_out = gt;
+  return DSM_OK;
+}
+
+int dsm_stream_hypotheses_results(dsm_stream *s, int max_results, dsm_stream_hyp_result *out, int *n_out) {
+  if (!s || max_results < 0 || (max_results && !out) || !n_out) return invalid("dsm_stream_hypotheses_results: bad argument");
+  int k = 0;
+  while (k < max_results && !s->hyp_done.empty()) {
+    out[k++] = s->hyp_done.front();
+    s->hyp_done.pop_front();
+  }
+  *n_out = k;
+  return DSM_OK;
+}
+
+int dsm_stream_hypotheses_counts(dsm_stream *s, int *pending_out, int *ready_out) {
+  if (!s) return invalid("null stream");
+  if (pending_out) *pending_out = (int)s->groups.size();
+  if (ready_out) *ready_out = (int)s->hyp_done.size();
+  return DSM_OK;
+}
+
+int dsm_stream_set_hypothesis_window(dsm_stream *s, int window) {
+  if (!s || window < 0) return invalid("dsm_stream_set_hypothesis_window: window >= 1, or 0 for all of a group's tries");
+  s->hyp_window = window;
   return DSM_OK;
 }
 
@@ -648,8 +798,8 @@ int dsm_stream_advance(dsm_stream *s) {
     }
     memcpy(r.last_residuals, S.last_residuals, sizeof r.last_residuals);
     for (int l = 0; l < DSM_MAX_LEVELS; l++) r.evals[l] = S.evals[l];
-    s->done.push_back(r);
     s->origin.erase(sl.ticket);
+    route_result(s, r);
     s->retired[mode]++;
     for (int l = 0; l < nlevels; l++) {
       std::vector<int> &hv = s->hist[mode][l];
@@ -828,9 +978,9 @@ static int tick_collect(dsm_stream *s, long long k) {
         const long long nl = og.trk->desc.lv[l].n, img = 12ll * (og.trk->w >> l) * (og.trk->h >> l);
         if (l < s->nlevels) st.algorithmic_bytes += R.evals[l] * (16ll * nl + (48ll * nl < img ? 48ll * nl : img));
       }
-      s->done.push_back(r);
       s->retired[mode]++;
-      s->origin.erase(it);
+      s->origin.erase(it); // (before route_result: a group's next tries are added to `origin`)
+      route_result(s, r);
     }
     if (new_ret > 0 && mode == (s->cap[0] > 0 ? 0 : 1)) { // (a tick = one LM round of every resident problem)
       const double mean = (double)life_sum / (double)new_ret;
@@ -1042,7 +1192,7 @@ int dsm_stream_drain(dsm_stream *s) {
     if (rc) return rc;
     int resident = 0, waiting = 0;
     dsm_stream_counts(s, &resident, &waiting, nullptr);
-    if (resident == 0 && waiting == 0) {
+    if (resident == 0 && waiting == 0 && s->groups.empty()) { // (a group's next tries are queued when the try before them is read back)
       if (lm_spin_expired() != 0) { // (a wave hand-shake inside an LM step gave up waiting: results cannot be trusted -- never seen; the waits are bounded so that a defect shows here, not as a hung device)
         set_error("internal: a bounded wait inside an LM step expired");
         return DSM_ERR_STATE;

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/dsm_hotpath.h"
@@ -222,6 +223,17 @@ inline void uploadImages(dsm_context *ctx, const std::vector<TrackerAndScaler *>
   for (size_t i = 0; i < n; i++) trackers[i]->noteResident(slots[i], unique_ids[i]);
 }
 
+// Outputs of the hypothesis loop of FrontEnd::trackNewCoarse (FrontEnd.cpp:194-256): trackHypotheses below, Stream::submitHypotheses
+struct HypothesesResult {
+  bool haveOneGood = false;
+  SE3 lastF_2_fh;
+  AffLight aff_g2l;
+  double flowVecs[3] = {0, 0, 0};
+  double achievedRes[5];
+  int triesUsed = 0;
+  int triesRun = 0; // Stream::hypothesesResults: tries the stream ran (>= triesUsed)
+};
+
 // ---- streaming form of many sequences (dsm_stream_*): continuous admission ------------------------------
 // Many TrackerAndScaler instances (one per sequence / hypothesis) share the GPU: each submits its trackNewestCoarse /
 // optimizeScale problem and polls for the result; the stream keeps `track_slots` + `scale_slots` problems resident, advances
@@ -258,6 +270,47 @@ public:
     check(dsm_stream_submit_scale(s_, 1, &t, &scale, coarsestLvl, &ticket), "dsm_stream_submit_scale");
     return ticket;
   }
+  // the whole hypothesis loop of FrontEnd::trackNewCoarse (FrontEnd.cpp:194-256) as ONE group: same result as trackHypotheses, without
+  // holding up the stream's other problems (try 0 is an ordinary problem; the other tries follow only when it does not settle the frame).
+  // The frame must be resident in the tracker's NEW_LEFT slot until the group's result is back.  Returns the group's ticket.
+  uint64_t submitHypotheses(TrackerAndScaler &tracker, const std::vector<SE3> &lastF_2_fh_tries, const AffLight &aff_last_2_l, int coarsestLvl,
+                            double last_coarse_rmse0, double reTrackThreshold = 1.5) {
+    std::vector<double> tries(7 * lastF_2_fh_tries.size());
+    for (size_t i = 0; i < lastF_2_fh_tries.size(); i++) {
+      for (int k = 0; k < 4; k++) tries[7 * i + k] = lastF_2_fh_tries[i].q[k];
+      for (int k = 0; k < 3; k++) tries[7 * i + 4 + k] = lastF_2_fh_tries[i].t[k];
+    }
+    const double aff[2] = {aff_last_2_l.a, aff_last_2_l.b};
+    uint64_t ticket = 0;
+    check(dsm_stream_submit_hypotheses(s_, tracker.handle(), (int)lastF_2_fh_tries.size(), tries.data(), aff, coarsestLvl, last_coarse_rmse0,
+                                       reTrackThreshold, &ticket),
+          "dsm_stream_submit_hypotheses");
+    return ticket;
+  }
+  // appends the groups resolved so far as (ticket, result)
+  void hypothesesResults(std::vector<std::pair<uint64_t, HypothesesResult>> &out) {
+    int ready = 0;
+    check(dsm_stream_hypotheses_counts(s_, nullptr, &ready), "dsm_stream_hypotheses_counts");
+    if (ready <= 0) return;
+    std::vector<dsm_stream_hyp_result> raw((size_t)ready);
+    int n = 0;
+    check(dsm_stream_hypotheses_results(s_, ready, raw.data(), &n), "dsm_stream_hypotheses_results");
+    for (int i = 0; i < n; i++) {
+      const dsm_stream_hyp_result &r = raw[i];
+      HypothesesResult H;
+      H.haveOneGood = r.have_one_good != 0;
+      for (int k = 0; k < 4; k++) H.lastF_2_fh.q[k] = r.pose[k];
+      for (int k = 0; k < 3; k++) H.lastF_2_fh.t[k] = r.pose[4 + k];
+      H.aff_g2l = AffLight(r.aff[0], r.aff[1]);
+      for (int k = 0; k < 3; k++) H.flowVecs[k] = r.flow[k];
+      for (int l = 0; l < 5; l++) H.achievedRes[l] = r.achieved_res[l];
+      H.triesUsed = r.tries_used;
+      H.triesRun = r.tries_run;
+      out.emplace_back(r.ticket, H);
+    }
+  }
+  // tries of one group waiting or resident at once after try 0 (0: all; 1: one by one).  Scheduling only.
+  void setHypothesisWindow(int w) { check(dsm_stream_set_hypothesis_window(s_, w), "dsm_stream_set_hypothesis_window"); }
   void advance() { check(dsm_stream_advance(s_), "dsm_stream_advance"); }
   // LM rounds a problem whose pending evaluation is one chunk may run inside one tick (dsm_stream_set_chain; 0 off, -1 the default)
   void setChain(int max_rounds) { check(dsm_stream_set_chain(s_, max_rounds), "dsm_stream_set_chain"); }
@@ -283,15 +336,8 @@ private:
 // ---- "next" row N4: the hypothesis loop of FrontEnd::trackNewCoarse (FrontEnd.cpp:194-256) -----------
 // Same results as the reference's sequential loop; try 0 runs alone, the remaining tries as ONE batched
 // launch sequence without abort, and the abort / take-over logic (TrackerAndScaler.cpp:598,
-// FrontEnd.cpp:225-247) is replayed on the host from their per-level residuals.
-struct HypothesesResult {
-  bool haveOneGood = false;
-  SE3 lastF_2_fh;
-  AffLight aff_g2l;
-  double flowVecs[3] = {0, 0, 0};
-  double achievedRes[5];
-  int triesUsed = 0;
-};
+// FrontEnd.cpp:225-247) is replayed on the host from their per-level residuals.  (A caller that drives a
+// Stream for many sequences submits the list as one group instead: Stream::submitHypotheses.)
 
 inline HypothesesResult trackHypotheses(dsm_context *ctx, TrackerAndScaler &tracker, const FrameView &fh,
                                         const std::vector<SE3> &lastF_2_fh_tries, const AffLight &aff_last_2_l,

@@ -292,6 +292,38 @@ class Stream:
         check(self.L.dsm_stream_results(self.h, max_results, buf, C.byref(n)))
         return [buf[i] for i in range(n.value)]
 
+    def submit_hypotheses(self, trk, tries, aff_last_2_l, coarsestLvl, last_coarse_rmse0, reTrackThreshold=1.5):
+        """the hypothesis loop of FrontEnd::trackNewCoarse (as track_hypotheses) as ONE group of the stream: the frame must be resident in
+        trk's NEW_LEFT slot until the group's result is back.  Returns the group's ticket."""
+        tries = np.ascontiguousarray(tries, np.float64).reshape(-1, 7)
+        aff = np.ascontiguousarray(aff_last_2_l, np.float64).reshape(2)
+        tk = C.c_uint64()
+        check(self.L.dsm_stream_submit_hypotheses(self.h, trk.h, len(tries), _dp(tries), _dp(aff), int(coarsestLvl), float(last_coarse_rmse0),
+                                                  float(reTrackThreshold), C.byref(tk)))
+        return tk.value
+
+    def hypotheses_results(self, raw=False):
+        """resolved groups in resolution order: [(ticket, (haveOneGood, lastF_2_fh, aff_g2l, flowVecs, achievedRes, tries_used, tries_run))]
+        -- track_hypotheses' tuple plus the tries the stream ran; raw=True: the _lib.StreamHypResult structures"""
+        n_ready = self.hypotheses_counts()[1]
+        if n_ready <= 0:
+            return []
+        buf = (_lib.StreamHypResult * n_ready)()
+        n = C.c_int()
+        check(self.L.dsm_stream_hypotheses_results(self.h, n_ready, buf, C.byref(n)))
+        out = [buf[i] for i in range(n.value)]
+        return out if raw else [(r.ticket, hyp_result_tuple(r)) for r in out]
+
+    def hypotheses_counts(self):
+        """(groups pending, group results ready)"""
+        a, b = C.c_int(), C.c_int()
+        check(self.L.dsm_stream_hypotheses_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def set_hypothesis_window(self, w):
+        """the most tries of one group waiting or resident at once after try 0; None / 0 = all of them.  Scheduling only."""
+        check(self.L.dsm_stream_set_hypothesis_window(self.h, int(w or 0)))
+
     def set_quantile(self, q, lvl=-1):
         """q: one value (level lvl, or every level when lvl < 0) or a list from level 0"""
         if np.ndim(q) == 0:
@@ -571,3 +603,26 @@ def track_hypotheses(ctx, trk, tries, aff_last_2_l, coarsestLvl, last_coarse_rms
 
 
 IDENTITY_POSE7 = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
+
+
+def hyp_result_tuple(r):
+    """a dsm_stream_hyp_result in track_hypotheses' tuple shape, plus tries_run"""
+    return (bool(r.have_one_good), np.array(r.pose), np.array(r.aff), np.array(r.flow), np.array(r.achieved_res), int(r.tries_used),
+            int(r.tries_run))
+
+
+def hypotheses_resolve(tries, aff_last_2_l, coarsestLvl, last_coarse_rmse0, goods, poses, affs, last_residuals, flows, reTrackThreshold=1.5):
+    """dsm_hypotheses_resolve (host code): the loop of FrontEnd.cpp:194-256 replayed from the outputs of the first k = len(goods) tries run
+    without abort.  Returns (decided, track_hypotheses' tuple plus tries_run)."""
+    tries = np.ascontiguousarray(tries, np.float64).reshape(-1, 7)
+    aff = np.ascontiguousarray(aff_last_2_l, np.float64).reshape(2)
+    k = len(goods)
+    g = np.ascontiguousarray(goods, np.int32).reshape(k)
+    P = np.ascontiguousarray(poses, np.float64).reshape(k, 7)
+    A = np.ascontiguousarray(affs, np.float64).reshape(k, 2)
+    R = np.ascontiguousarray(last_residuals, np.float64).reshape(k, MAX_LEVELS)
+    F = np.ascontiguousarray(flows, np.float64).reshape(k, 3)
+    out, dec = _lib.StreamHypResult(), C.c_int()
+    check(_lib.load().dsm_hypotheses_resolve(len(tries), _dp(tries), _dp(aff), int(coarsestLvl), float(last_coarse_rmse0), float(reTrackThreshold), k,
+                                             g.ctypes.data_as(c_int_p), _dp(P), _dp(A), _dp(R), _dp(F), C.byref(out), C.byref(dec)))
+    return bool(dec.value), hyp_result_tuple(out)

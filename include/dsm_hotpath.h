@@ -442,6 +442,55 @@ int dsm_stream_get_stats(dsm_stream *s, dsm_stats *track_out, dsm_stats *scale_o
 /* the schedule in force and the stream's counters: passes run, problems retired (of `mode`), slot-passes spent carrying */
 int dsm_stream_get_schedule(dsm_stream *s, int mode, int *rounds_out, long long *passes_out, long long *retired_out, long long *carried_out);
 
+/* ---- hypothesis groups: the loop of FrontEnd::trackNewCoarse (FrontEnd.cpp:194-256) as ONE stream submission ----------------
+ * The reference tracks a new frame from a list of pose guesses (constant motion first, then 82-108 others, FrontEnd.cpp:132-192): try i
+ * runs trackNewestCoarse with minResForAbort = the best residuals of tries 0..i-1 (aborting at :598 when a level is 1.5x worse), a good
+ * try with a lower level-0 residual takes over (:225-243), and the loop stops at the first take-over below last_coarse_rmse0 *
+ * retrack_threshold (:245-247).  A level's LM result does not depend on minResForAbort, so the loop is reproduced exactly from tries
+ * run WITHOUT abort: dsm_hypotheses_resolve replays the aborts and the take-over / stop rules from their outputs, in try order.
+ * A group is scheduling only -- its result equals dsm_host::trackHypotheses (try 0 alone, then the rest as one dsm_track_batch):
+ *   try 0 enters the stream as an ordinary track problem without abort thresholds (its ticket is internal: it never appears in
+ *   dsm_stream_results); when it is read back and does not settle the frame, tries 1.. are queued in try order, at most `window` of them
+ *   waiting or resident at once (dsm_stream_set_hypothesis_window); every retirement feeds the resolver as far as the tries retired IN
+ *   ORDER reach, and refills the window.  Once the loop is decided, tries still waiting on the host are dropped, tries already on the
+ *   device run to their end and are discarded, and the group's result is handed back when none of its tries is on the device any more.
+ * The frame must be resident in the tracker's DSM_SLOT_NEW_LEFT slot (as for dsm_stream_submit_track) and stay untouched, like the
+ * tracker's template, until the group's result is back.  Group tries count as track problems in dsm_stream_counts; dsm_stream_drain
+ * returns when every group is resolved.  Both engines.  The group is expanded when try 0 is read back on the host: with pipelined
+ * advances a frame that needs retries costs one or two advances more than one that does not. */
+typedef struct dsm_stream_hyp_result {
+  uint64_t ticket;                    /* from dsm_stream_submit_hypotheses */
+  int have_one_good;                  /* haveOneGood (FrontEnd.cpp:227-233) */
+  int tries_used;                     /* tries the reference's sequential loop runs (tryIterations, :208) */
+  int tries_run;                      /* tries the stream ran (>= tries_used; = tries_used with window 1) */
+  int advances;                       /* advances issued while the group was pending */
+  double pose[7];                     /* lastF_2_fh (tries[0] when no try was good, :249-256) */
+  double aff[2];                      /* aff_g2l (aff_last when no try was good) */
+  double flow[3];                     /* flowVecs (0 when no try was good) */
+  double achieved_res[DSM_MAX_LEVELS];/* achievedRes -- what the caller keeps as last_coarse_rmse_ (:258); [5] stays NaN (a Vec5) */
+  int64_t evals[DSM_MAX_LEVELS];      /* evaluations per level, summed over the tries run */
+} dsm_stream_hyp_result;
+/* tries: n_tries x 7 (pose layout of dsm_stream_submit_track), aff_last[2]: the affine guess of every try; coarsest_lvl as there;
+ * last_coarse_rmse0 = last_coarse_rmse_[0], retrack_threshold = setting_reTrackThreshold (1.5).  DSM_ERR_INVALID for n_tries < 1,
+ * a NULL pointer or a stream without track slots. */
+int dsm_stream_submit_hypotheses(dsm_stream *s, dsm_tracker *tracker, int n_tries, const double *tries, const double aff_last[2],
+                                 int coarsest_lvl, double last_coarse_rmse0, double retrack_threshold, uint64_t *ticket_out);
+/* resolved groups in resolution order (at most max_results) */
+int dsm_stream_hypotheses_results(dsm_stream *s, int max_results, dsm_stream_hyp_result *out, int *n_out);
+/* groups not resolved yet / resolved and not yet returned (either pointer may be NULL) */
+int dsm_stream_hypotheses_counts(dsm_stream *s, int *pending_out, int *ready_out);
+/* the most tries of one group waiting or resident at once after try 0: 0 (default) = all of them (the work of dsm_host::trackHypotheses'
+ * batch), 1 = one by one as the reference runs them.  Scheduling only: a group's result does not depend on it.  Applies from the next refill. */
+int dsm_stream_set_hypothesis_window(dsm_stream *s, int window);
+/* HOST function (no device call): the loop of FrontEnd.cpp:194-256 replayed from the outputs of tries 0 .. k-1 run WITHOUT abort, in try
+ * order -- good[k], pose[k x 7], aff[k x 2] (as dsm_track_batch leaves pose_io / aff_io), last_residuals[k x DSM_MAX_LEVELS], flow[k x 3].
+ * Try i's abort (TrackerAndScaler.cpp:598) is replayed from its residuals against the achievedRes of tries 0 .. i-1.  *decided_out = 1
+ * when the loop ends within these k tries; out then holds its result (ticket, tries_run = k, advances and evals zero).  Otherwise out
+ * holds the loop's state after k tries, tries_used = k. */
+int dsm_hypotheses_resolve(int n_tries, const double *tries, const double aff_last[2], int coarsest_lvl, double last_coarse_rmse0,
+                           double retrack_threshold, int k, const int *good, const double *pose, const double *aff,
+                           const double *last_residuals, const double *flow, dsm_stream_hyp_result *out, int *decided_out);
+
 /* Batched forms: n independent trackers of one context advance in lock-step launches
  * (SURVEY.md section 7 "throughput mode").  Arrays are n x 7 / n x 2 / n x DSM_MAX_LEVELS / n x 3. */
 int dsm_track_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, double *pose_io, double *aff_io,

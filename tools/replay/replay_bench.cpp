@@ -735,7 +735,8 @@ static RunResult run(B &be, const Pack &P) {
 // Every sequence is the driver above reduced to the tracker's calls -- hand-over, trackNewCoarse, makeKeyFrame, optimizeScale, tracker
 // swap (the loop descriptors stay with the one-sequence run) -- and has ONE problem in flight: its frame's first hypothesis (the
 // constant-motion guess; a frame it does not settle goes through the whole list synchronously, as trackHypotheses does) or its
-// keyframe's scale guesses.  All sequences submit into one stream; an advance moves every resident problem.  Results equal the
+// keyframe's scale guesses.  With DSM_REPLAY_HYPOTHESES=stream a frame's whole hypothesis list is ONE group of the stream instead
+// (Stream::submitHypotheses): a frame that needs retries no longer holds up the other sequences.  All sequences submit into one stream; an advance moves every resident problem.  Results equal the
 // one-sequence run's bit for bit (the stream is scheduling only), which main() checks.
 struct ConcurrentResult {
   int sequences = 0, advances = 0, fallbacks = 0, lost = 0;
@@ -745,6 +746,12 @@ struct ConcurrentResult {
   std::vector<std::vector<float>> scales;
   std::map<std::string, double> host_ms; // host wall time inside each kind of call, summed over the run
 };
+
+// DSM_REPLAY_HYPOTHESES=stream: the concurrent leg submits every frame's hypothesis list as one stream group
+static bool replay_hypotheses_in_stream() {
+  const char *e = getenv("DSM_REPLAY_HYPOTHESES");
+  return e && strcmp(e, "stream") == 0;
+}
 
 static ConcurrentResult run_concurrent(const Pack &P, int S, bool pipelined) {
   struct Seq {
@@ -806,6 +813,7 @@ static ConcurrentResult run_concurrent(const Pack &P, int S, bool pipelined) {
     if (const char *e = getenv("DSM_REPLAY_CHAIN")) stream.setChain(atoi(e)); // (experiments: the library's default otherwise)
     if (const char *e = getenv("DSM_REPLAY_TICKS")) dsm_host::check(dsm_stream_set_engine(stream.handle(), 1, atoi(e)), "dsm_stream_set_engine");
     std::map<uint64_t, std::pair<int, int>> owner; // ticket -> (sequence, index of the scale guess or -1 for the frame's tracking)
+    const bool hyp_groups = replay_hypotheses_in_stream();
     int n_done = 0;
     auto left_id = [&](int s, int i) { return (long long)s * 100000000LL + i; };
     auto frame_done = [&](Seq &q) {
@@ -909,12 +917,22 @@ static ConcurrentResult run_concurrent(const Pack &P, int S, bool pipelined) {
             continue;
           }
           q.tries = hypothesis_list(q.est, q.T_kf);
-          owner[stream.submitTrack(*q.cur, q.tries[0], q.aff_last, P.nl - 1, nullptr)] = {s, -1};
+          if (hyp_groups)
+            owner[stream.submitHypotheses(*q.cur, q.tries, q.aff_last, P.nl - 1, q.last_rmse0)] = {s, -1};
+          else
+            owner[stream.submitTrack(*q.cur, q.tries[0], q.aff_last, P.nl - 1, nullptr)] = {s, -1};
           q.state = Seq::TRACKING;
         }
         make_keyframes();
         if (!again) return;
       }
+    };
+    auto settle = [&](int s, Seq &q, const SE3 &pose, const AffLight &aff, double res0, bool have) {
+      R.lost += !have;
+      q.last_rmse0 = res0;
+      q.est_now = se3_mul(pose, q.T_kf);
+      q.aff_now = aff;
+      finish_track(s, q);
     };
     auto on_track = [&](int s, Seq &q, const dsm_stream_result &r) {
       // the first try of trackHypotheses (FrontEnd.cpp:204-247): nothing achieved yet, so no abort threshold
@@ -936,11 +954,11 @@ static ConcurrentResult run_concurrent(const Pack &P, int S, bool pipelined) {
         pose = H.lastF_2_fh, aff = H.aff_g2l, res0 = H.achievedRes[0], have = H.haveOneGood;
         R.fallbacks++;
       }
-      R.lost += !have;
-      q.last_rmse0 = res0;
-      q.est_now = se3_mul(pose, q.T_kf);
-      q.aff_now = aff;
-      finish_track(s, q);
+      settle(s, q, pose, aff, res0, have);
+    };
+    auto on_hypotheses = [&](int s, Seq &q, const dsm_host::HypothesesResult &H) { // the whole list came back as one group
+      R.fallbacks += H.triesUsed > 1;
+      settle(s, q, H.lastF_2_fh, H.aff_g2l, H.achievedRes[0], H.haveOneGood);
     };
     auto on_scale = [&](Seq &q, int g, const dsm_stream_result &r) {
       q.scale_val[g] = r.scale, q.scale_err[g] = r.err;
@@ -963,6 +981,7 @@ static ConcurrentResult run_concurrent(const Pack &P, int S, bool pipelined) {
       finish_kf(q);
     };
     std::vector<dsm_stream_result> res;
+    std::vector<std::pair<uint64_t, dsm_host::HypothesesResult>> hres;
     const auto t_all = Clock::now();
     for (int iter = 0; n_done < S; iter++) {
       if (iter > 100 * P.n_frames * 8) throw std::runtime_error("concurrent replay: no progress");
@@ -981,6 +1000,17 @@ static ConcurrentResult run_concurrent(const Pack &P, int S, bool pipelined) {
           on_track(s, seqs[s], r);
         else
           on_scale(seqs[s], g, r);
+      }
+      if (hyp_groups) {
+        hres.clear();
+        timed("stream.hypothesesResults", [&] { stream.hypothesesResults(hres); });
+        for (const auto &h : hres) {
+          const auto it = owner.find(h.first);
+          if (it == owner.end()) throw std::runtime_error("concurrent replay: unknown group ticket");
+          const int s = it->second.first;
+          owner.erase(it);
+          on_hypotheses(s, seqs[s], h.second);
+        }
       }
       make_keyframes(); // (the frames of this advance's results that became keyframes)
       submit_scales();
@@ -1301,6 +1331,7 @@ int main(int argc, char **argv) {
            cc.sequences, replay_concurrent_geometry(), cc.sequences, conc_pipelined ? "true" : "false", cc.frames, cc.wall_ms, 1e3 * (double)cc.frames / cc.wall_ms,
            cc.wall_ms * cc.sequences / (double)cc.frames, cc.latency_ms_sum / (double)cc.frames, cc.latency_ms_max, cc.advances, cc.fallbacks, cc.lost, ate_max, dmax,
            scales_equal ? "true" : "false");
+    if (replay_hypotheses_in_stream()) printf(", \"hypothesis_lists_as_stream_groups\": true");
     printf(", \"host_ms_per_advance_by_call\": {");
     bool first = true;
     for (const auto &kv : cc.host_ms) printf("%s\"%s\": %.4f", first ? "" : ", ", kv.first.c_str(), kv.second / std::max(1, cc.advances)), first = false;
