@@ -1190,83 +1190,137 @@ void collect_eval_timing(dsm_context *ctx, const std::vector<int> &ev_lvl, int n
 } // namespace dsm
 extern "C" {
 
-// runs the device LM state machine for a batch (mode 0 = trackNewestCoarse, 1 = optimizeScale, 2 = loop-closure pose).
-// n2 > 0: problems [n, n + n2) form a COMPANION segment in mode2 (dsm_track_and_scale_batch: the keyframes' scale
-// optimisations next to the frames' tracking).  The two segments are independent problems; the companion's launches go to a
-// stream of their own, so its latency-bound chains of small launches run under the main segment's kernels instead of after
-// them.  Launch-per-step form only.  Statistics of the companion: ctx->stats2.
-static int run_lm_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mode, int coarsest, int n2 = 0, int mode2 = 1) {
-  const int nlevels = ts[0]->nlevels;
-  if (coarsest < 0 || coarsest >= nlevels) return invalid("coarsest level out of range"); // :457 / :856
-  const dsm_params &P = ts[0]->params;
-  const int N = n + n2;
-  memset(&ctx->stats, 0, sizeof ctx->stats);
-  memset(&ctx->stats2, 0, sizeof ctx->stats2);
-  DSM_HIP(hipEventRecord(ctx->ev_total[0], ctx->stream));
-  DSM_HIP(hipMemcpyAsync(ctx->d_start, ctx->h_start, sizeof(StartInfo) * N, hipMemcpyHostToDevice, ctx->stream));
-  launch_lm(ctx->stream, mode, LM_OP_START, coarsest, n, ctx->d_tracker_ptrs, ctx->d_states, ctx->d_partials,
-            ctx->partial_stride, ctx->d_start, nullptr, ctx->d_status);
-  if (n2 > 0)
-    launch_lm(ctx->stream, mode2, LM_OP_START, coarsest, n2, ctx->d_tracker_ptrs + n, ctx->d_states + n,
-              ctx->d_partials + (size_t)n * ctx->partial_stride, ctx->partial_stride, ctx->d_start + n, nullptr, ctx->d_status + 2 * n);
-  // Work-queue form: one launch of persistent workgroups for the whole call (queue_kernel).  Scheduling only:
-  // results are bit-identical to the launch-per-step form below.
-  // Default rule (measured): the queue form wins while the batch is large enough to fill the
-  // persistent workgroups and small enough that its per-item cost (a few microseconds per chunk) does not add up --
-  // up to about 24 k finest-level chunks per call (about 200 dense KITTI frames; thousands of sparse ones).
+// fork: the extra streams (and the companion's) start after everything enqueued on the main stream so far
+static int fork_from_main(dsm_context *ctx, int ng, bool companion) {
+  if (ng > 1 || companion) {
+    DSM_HIP(hipEventRecord(ctx->fork_event, ctx->stream));
+    for (int g = 1; g < ng; g++) DSM_HIP(hipStreamWaitEvent(ctx->extra_streams[g - 1], ctx->fork_event, 0));
+    if (companion) DSM_HIP(hipStreamWaitEvent(ctx->companion_stream, ctx->fork_event, 0));
+  }
+  return DSM_OK;
+}
+
+// Work-queue form: one launch of persistent workgroups for the whole call (queue_kernel).  Scheduling only:
+// results are bit-identical to the launch-per-step form (run_passes).
+// Default rule (measured): the queue form wins while the batch is large enough to fill the
+// persistent workgroups and small enough that its per-item cost (a few microseconds per chunk) does not add up --
+// up to about 24 k finest-level chunks per call (about 200 dense KITTI frames; thousands of sparse ones).
+static bool queue_wanted(const dsm_params &P, int n, int n2, dsm_tracker *const *ts) {
   bool use_queue = P.work_queue >= 2 && n2 == 0;
   if (P.work_queue == 1 && n >= 32 && n2 == 0) {
     long long chunks0 = 0;
     for (int i = 0; i < n; i++) chunks0 += level_chunks(ts[i]->desc, 0);
     use_queue = chunks0 <= 24576; // (256 dense S2 frames = 29.7 k chunks: 4 % slower than the launch form; 192: faster)
   }
-  if (use_queue) {
-    int max_items = 1;
-    for (int L = 0; L <= coarsest; L++)
-      for (int i = 0; i < n; i++) {
-        const int c = level_chunks(ts[i]->desc, L);
-        if (c > max_items) max_items = c;
-      }
-    if (max_items >= (1 << kQueueChunkBits) || n >= (1 << (32 - kQueueChunkBits))) return invalid("work queue: batch or level too large");
-    size_t qcap = 1024; // outstanding items <= problems x chunks of one evaluation: a problem has one evaluation in flight
-    while (qcap < (size_t)n * max_items) qcap <<= 1;
-    if (qcap > ctx->qcap) {
-      if (ctx->d_qitems) DSM_HIP(hipFree(ctx->d_qitems));
-      ctx->d_qitems = nullptr;
-      ctx->qcap = 0;
-      DSM_HIP(hipMalloc(&ctx->d_qitems, qcap * sizeof(unsigned long long)));
-      ctx->qcap = qcap;
+  return use_queue;
+}
+static int run_queue(dsm_context *ctx, dsm_tracker *const *ts, int n, int mode, int coarsest) {
+  int max_items = 1;
+  for (int L = 0; L <= coarsest; L++)
+    for (int i = 0; i < n; i++) {
+      const int c = level_chunks(ts[i]->desc, L);
+      if (c > max_items) max_items = c;
     }
-    if (!ctx->d_queue) DSM_HIP(hipMalloc(&ctx->d_queue, sizeof(WorkQueue)));
-    if (!ctx->h_queue) DSM_HIP(hipHostMalloc(&ctx->h_queue, sizeof(WorkQueue), hipHostMallocDefault));
-    DSM_HIP(hipMemsetAsync(ctx->d_queue, 0, sizeof(WorkQueue), ctx->stream));
-    DSM_HIP(hipMemsetAsync(ctx->d_qitems, 0, ctx->qcap * sizeof(unsigned long long), ctx->stream)); // stale publication tags
-    if (ctx->queue_blocks[mode] == 0) {
-      hipDeviceProp_t prop;
-      DSM_HIP(hipGetDeviceProperties(&prop, ctx->device));
-      const int per_cu = queue_kernel_blocks_per_cu(mode);
-      if (per_cu < 1) return invalid("work queue: kernel does not fit the device");
-      ctx->queue_blocks[mode] = per_cu * prop.multiProcessorCount; // all workgroups must be co-resident
-    }
-    hipEvent_t qa = ctx->timing ? get_event(ctx, 0) : nullptr, qb = ctx->timing ? get_event(ctx, 1) : nullptr;
-    if (qa) DSM_HIP(hipEventRecord(qa, ctx->stream));
-    launch_queue(ctx->stream, mode, ctx->queue_blocks[mode], n, ctx->d_tracker_ptrs, ctx->d_states, ctx->d_partials,
-                 ctx->partial_stride, ctx->d_tickets, ctx->d_queue, ctx->d_qitems, (unsigned)(ctx->qcap - 1));
-    if (qb) DSM_HIP(hipEventRecord(qb, ctx->stream));
-    DSM_HIP(hipGetLastError());
-    DSM_HIP(hipMemcpyAsync(ctx->h_queue, ctx->d_queue, sizeof(WorkQueue), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->stats.queue_blocks = ctx->queue_blocks[mode];
+  if (max_items >= (1 << kQueueChunkBits) || n >= (1 << (32 - kQueueChunkBits))) return invalid("work queue: batch or level too large");
+  size_t qcap = 1024; // outstanding items <= problems x chunks of one evaluation: a problem has one evaluation in flight
+  while (qcap < (size_t)n * max_items) qcap <<= 1;
+  if (qcap > ctx->qcap) {
+    if (ctx->d_qitems) DSM_HIP(hipFree(ctx->d_qitems));
+    ctx->d_qitems = nullptr;
+    ctx->qcap = 0;
+    DSM_HIP(hipMalloc(&ctx->d_qitems, qcap * sizeof(unsigned long long)));
+    ctx->qcap = qcap;
   }
+  if (!ctx->d_queue) DSM_HIP(hipMalloc(&ctx->d_queue, sizeof(WorkQueue)));
+  if (!ctx->h_queue) DSM_HIP(hipHostMalloc(&ctx->h_queue, sizeof(WorkQueue), hipHostMallocDefault));
+  DSM_HIP(hipMemsetAsync(ctx->d_queue, 0, sizeof(WorkQueue), ctx->stream));
+  DSM_HIP(hipMemsetAsync(ctx->d_qitems, 0, ctx->qcap * sizeof(unsigned long long), ctx->stream)); // stale publication tags
+  if (ctx->queue_blocks[mode] == 0) {
+    hipDeviceProp_t prop;
+    DSM_HIP(hipGetDeviceProperties(&prop, ctx->device));
+    const int per_cu = queue_kernel_blocks_per_cu(mode);
+    if (per_cu < 1) return invalid("work queue: kernel does not fit the device");
+    ctx->queue_blocks[mode] = per_cu * prop.multiProcessorCount; // all workgroups must be co-resident
+  }
+  hipEvent_t qa = ctx->timing ? get_event(ctx, 0) : nullptr, qb = ctx->timing ? get_event(ctx, 1) : nullptr;
+  if (qa) DSM_HIP(hipEventRecord(qa, ctx->stream));
+  launch_queue(ctx->stream, mode, ctx->queue_blocks[mode], n, ctx->d_tracker_ptrs, ctx->d_states, ctx->d_partials,
+               ctx->partial_stride, ctx->d_tickets, ctx->d_queue, ctx->d_qitems, (unsigned)(ctx->qcap - 1));
+  if (qb) DSM_HIP(hipEventRecord(qb, ctx->stream));
+  DSM_HIP(hipGetLastError());
+  DSM_HIP(hipMemcpyAsync(ctx->h_queue, ctx->d_queue, sizeof(WorkQueue), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->stats.queue_blocks = ctx->queue_blocks[mode];
+  return DSM_OK;
+}
+// after the call's read-back: the queue kernel's verdict and statistics
+static int queue_outcome(dsm_context *ctx) {
+  if (ctx->h_queue->error) {
+    // leave the arrival counters clean for the next call
+    DSM_HIP(hipMemsetAsync(ctx->d_tickets, 0, sizeof(int) * ctx->cap_prob, ctx->stream));
+    DSM_HIP(hipStreamSynchronize(ctx->stream));
+    set_error("internal: work-queue kernel gave up waiting (bounded wait expired)");
+    return DSM_ERR_STATE;
+  }
+  ctx->stats.queue_items = ctx->h_queue->tail;
+  if (ctx->timing && ctx->ev_pool.size() >= 2) {
+    float qm = 0;
+    if (hipEventElapsedTime(&qm, ctx->ev_pool[0], ctx->ev_pool[1]) == hipSuccess) ctx->stats.queue_kernel_ms = qm;
+  }
+  return DSM_OK;
+}
+
+// Small levels as a CHAIN (chain_kernel, dsm_params.persistent_coarse < 0): every problem whose evaluation at the coarsest level is one
+// chunk runs its LM loop in one launch, down to its first level of several chunks.  One launch per stream group and one for the
+// companion segment.  top / top2 (in: the coarsest level, -1 for no companion): the first level of each segment that the
+// launch-per-step schedule has to run.
+static int run_chain_prefix(dsm_context *ctx, dsm_tracker *const *ts, int n, int n2, int mode, int mode2, int coarsest, int ng, int &top,
+                            int &top2) {
+  const int N = n + n2;
+  auto one_chunk = [&](int i, int L) { return level_chunks(ts[i]->desc, L) <= 1; };
+  bool any = false;
+  for (int i = 0; i < N && !any; i++) any = one_chunk(i, coarsest);
+  if (!any) return DSM_OK;
+  {
+    const int rc = fork_from_main(ctx, ng, top2 >= 0);
+    if (rc) return rc;
+  }
+  for (int g = 0; g < ng; g++) {
+    const int g0 = (int)((long long)n * g / ng), g1 = (int)((long long)n * (g + 1) / ng);
+    if (g1 <= g0) continue;
+    launch_chain(g == 0 ? ctx->stream : ctx->extra_streams[g - 1], mode, g1 - g0, ctx->d_tracker_ptrs + g0, ctx->d_states + g0, ctx->d_status + 2 * g0);
+  }
+  if (n2 > 0) launch_chain(ctx->companion_stream, mode2, n2, ctx->d_tracker_ptrs + n, ctx->d_states + n, ctx->d_status + 2 * n);
+  ctx->stats.coarse_launches = 1;
+  auto first_launch_level = [&](int i0, int i1) { // (the launch-per-step schedule starts at the first level some problem cannot chain through)
+    int t = -1;
+    for (int i = i0; i < i1; i++)
+      for (int L = coarsest; L > t; L--)
+        if (!one_chunk(i, L)) {
+          t = L;
+          break;
+        }
+    return t;
+  };
+  top = first_launch_level(0, n);
+  if (n2 > 0) top2 = first_launch_level(n, N);
+  return DSM_OK;
+}
+
+// Launch-per-step form.  The LM loop is sequential per problem and its length is data dependent
+// (TrackerAndScaler.cpp:477,505,588,601); polling the device after every few launches costs a
+// host round trip each time.  Instead every level gets a speculative number of (eval, lm) launch
+// pairs -- the largest count any problem needed in recent calls plus slack -- and the state is
+// read back ONCE per pass.  Problems that finish a level early idle through the remaining
+// launches (their workgroups exit on the first instruction); problems that need more simply stay
+// at their level and are continued by the next pass.  Results do not depend on the schedule.
+// top / top2: the first level of the main / companion segment (-1: nothing to run); ev_lvl: the level of each timed eval dispatch.
+static int run_passes(dsm_context *ctx, dsm_tracker *const *ts, int n, int n2, int mode, int mode2, int ng, int top, int top2,
+                      std::vector<int> &ev_lvl) {
+  const int nlevels = ts[0]->nlevels;
+  const dsm_params &P = ts[0]->params;
+  const int N = n + n2;
   size_t ev_used = 0;
-  std::vector<int> ev_lvl;
   int rc_build = DSM_OK;
-  // Launch schedule.  The LM loop is sequential per problem and its length is data dependent
-  // (TrackerAndScaler.cpp:477,505,588,601); polling the device after every few launches costs a
-  // host round trip each time.  Instead every level gets a speculative number of (eval, lm) launch
-  // pairs -- the largest count any problem needed in recent calls plus slack -- and the state is
-  // read back ONCE per pass.  Problems that finish a level early idle through the remaining
-  // launches (their workgroups exit on the first instruction); problems that need more simply stay
-  // at their level and are continued by the next pass.  Results do not depend on the schedule.
   int worst[DSM_MAX_LEVELS], grid_x[DSM_MAX_LEVELS], level_pts[DSM_MAX_LEVELS];
   bool spec[DSM_MAX_LEVELS];
   for (int L = 0; L < nlevels; L++) {
@@ -1296,100 +1350,8 @@ static int run_lm_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mod
       spec[L] = P.fixed_schedule <= 0 && (P.speculate >= 2 || (P.speculate == 1 && max_n <= 8192 && launch_points <= 1000000ll));
     }
   }
-  // the learnt "rounds most problems need" belong to calls of this size and form: another batch-size bucket (powers of four)
-  // or form must not inherit them (a batch of hundreds following a single-frame call would switch to compact launches after
-  // one round, covering almost every problem)
-  {
-    int bucket = 0;
-    for (int v = N; v >= 4; v >>= 2) bucket++;
-    const int key = bucket * 4 + (use_queue ? 2 : 0) + (P.persistent_coarse != 0 ? 1 : 0);
-    if (key != ctx->sched_bulk_key) {
-      for (int m = 0; m < 3; m++)
-        for (int l = 0; l < DSM_MAX_LEVELS; l++) ctx->sched_bulk[m][l] = 1 << 30;
-      ctx->sched_bulk_key = key;
-    }
-  }
-  int *sched = ctx->sched[mode], *sched2 = ctx->sched[mode2];
+  const int *sched = ctx->sched[mode], *sched2 = ctx->sched[mode2];
   const int *bulk = ctx->sched_bulk[mode], *bulk2 = ctx->sched_bulk[mode2];
-  int ng = ctx->n_streams < 1 ? 1 : ctx->n_streams;
-  if (ng > n) ng = n;
-  {
-    const int rc = ensure_streams(ctx, ng, n2 > 0);
-    if (rc) return rc;
-  }
-  int top = coarsest, top2 = n2 > 0 ? coarsest : -1;
-  if (!use_queue && P.persistent_coarse < 0) {
-    // Small levels as a CHAIN (chain_kernel): every problem whose evaluation at the coarsest level is one chunk runs its LM loop in one
-    // launch, down to its first level of several chunks.  One launch per stream group and one for the companion segment.
-    auto one_chunk = [&](int i, int L) { return level_chunks(ts[i]->desc, L) <= 1; };
-    bool any = false;
-    for (int i = 0; i < N && !any; i++) any = one_chunk(i, coarsest);
-    if (any) {
-      if (ng > 1 || top2 >= 0) {
-        DSM_HIP(hipEventRecord(ctx->fork_event, ctx->stream));
-        for (int g = 1; g < ng; g++) DSM_HIP(hipStreamWaitEvent(ctx->extra_streams[g - 1], ctx->fork_event, 0));
-        if (top2 >= 0) DSM_HIP(hipStreamWaitEvent(ctx->companion_stream, ctx->fork_event, 0));
-      }
-      for (int g = 0; g < ng; g++) {
-        const int g0 = (int)((long long)n * g / ng), g1 = (int)((long long)n * (g + 1) / ng);
-        if (g1 <= g0) continue;
-        launch_chain(g == 0 ? ctx->stream : ctx->extra_streams[g - 1], mode, g1 - g0, ctx->d_tracker_ptrs + g0, ctx->d_states + g0, ctx->d_status + 2 * g0);
-      }
-      if (n2 > 0) launch_chain(ctx->companion_stream, mode2, n2, ctx->d_tracker_ptrs + n, ctx->d_states + n, ctx->d_status + 2 * n);
-      ctx->stats.coarse_launches = 1;
-      auto first_launch_level = [&](int i0, int i1) { // (the launch-per-step schedule starts at the first level some problem cannot chain through)
-        int t = -1;
-        for (int i = i0; i < i1; i++)
-          for (int L = coarsest; L > t; L--)
-            if (!one_chunk(i, L)) {
-              t = L;
-              break;
-            }
-        return t;
-      };
-      top = first_launch_level(0, n);
-      if (n2 > 0) top2 = first_launch_level(n, N);
-    }
-  }
-  if (!use_queue && P.persistent_coarse > 0) {
-    // Small levels: the whole LM loop in one launch per problem on LDS-resident data (coarse_kernel), one launch per stream
-    // group and one for the companion segment.  A problem is handed back (still RUNNING) at the first level whose target
-    // plane does not fit the kernel's LDS arena.
-    const int max_px = P.persistent_coarse;
-    bool any = false;
-    for (int i = 0; i < N && !any; i++) any = coarse_level_fits(ts[i]->w >> coarsest, ts[i]->h >> coarsest, ts[i]->desc.lv[coarsest].n, ts[i]->desc.p.geometry, max_px);
-    if (any) {
-      if (ng > 1 || top2 >= 0) {
-        DSM_HIP(hipEventRecord(ctx->fork_event, ctx->stream));
-        for (int g = 1; g < ng; g++) DSM_HIP(hipStreamWaitEvent(ctx->extra_streams[g - 1], ctx->fork_event, 0));
-        if (top2 >= 0) DSM_HIP(hipStreamWaitEvent(ctx->companion_stream, ctx->fork_event, 0));
-      }
-      const bool cspec = P.speculate >= 1 && P.fixed_schedule <= 0;
-      for (int g = 0; g < ng; g++) {
-        const int g0 = (int)((long long)n * g / ng), g1 = (int)((long long)n * (g + 1) / ng);
-        if (g1 <= g0) continue;
-        launch_coarse(g == 0 ? ctx->stream : ctx->extra_streams[g - 1], mode, g1 - g0, ctx->d_tracker_ptrs + g0, ctx->d_states + g0,
-                      ctx->d_status + 2 * g0, max_px, cspec);
-      }
-      if (n2 > 0)
-        launch_coarse(ctx->companion_stream, mode2, n2, ctx->d_tracker_ptrs + n, ctx->d_states + n, ctx->d_status + 2 * n, max_px, cspec);
-      ctx->stats.coarse_launches = 1;
-      // The launch-per-step schedule starts at the first level some problem cannot run there.  No join: each stream's next
-      // launches are ordered behind its own coarse launch (the pass loop's fork adds the main stream's only).
-      auto first_launch_level = [&](int i0, int i1) {
-        int t = -1;
-        for (int i = i0; i < i1; i++)
-          for (int L = coarsest; L > t; L--)
-            if (!coarse_level_fits(ts[i]->w >> L, ts[i]->h >> L, ts[i]->desc.lv[L].n, ts[i]->desc.p.geometry, max_px)) {
-              t = L;
-              break;
-            }
-        return t;
-      };
-      top = first_launch_level(0, n);
-      if (n2 > 0) top2 = first_launch_level(n, N);
-    }
-  }
   // Segments of the launch schedule: the stream groups of the main batch (the batch is split into `ng` contiguous groups,
   // each with its own HIP stream: a group's lm_kernel -- one small workgroup per problem -- and its small-level eval kernels
   // leave most of the chip idle; another group's kernels fill it) and the companion segment.  Per-problem results do not
@@ -1451,11 +1413,10 @@ static int run_lm_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mod
     if (r > 0) DSM_HIP(hipMemcpyAsync(ctx->d_rowmap + sg.i0, ctx->h_rowmap + sg.i0, sizeof(int) * r, hipMemcpyHostToDevice, sg.st));
     return DSM_OK;
   };
-  for (int pass = 0; !use_queue; pass++) {
-    if (ng > 1 || top2 >= 0) { // fork: the extra streams start after everything enqueued on the main stream so far
-      DSM_HIP(hipEventRecord(ctx->fork_event, ctx->stream));
-      for (int g = 1; g < ng; g++) DSM_HIP(hipStreamWaitEvent(ctx->extra_streams[g - 1], ctx->fork_event, 0));
-      if (top2 >= 0) DSM_HIP(hipStreamWaitEvent(ctx->companion_stream, ctx->fork_event, 0));
+  for (int pass = 0;; pass++) {
+    {
+      const int rc = fork_from_main(ctx, ng, top2 >= 0);
+      if (rc) return rc;
     }
     // Later passes only continue what the previous one left unfinished: compact launches over the problems still running
     // (a launch over all problems of a batch costs ~1.6 ns per idle workgroup: 100 us for a level-0 grid of 512 problems).
@@ -1560,29 +1521,16 @@ static int run_lm_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mod
       return DSM_ERR_STATE;
     }
   }
-  DSM_HIP(hipMemcpyAsync(ctx->h_states, ctx->d_states, sizeof(LMState) * N, hipMemcpyDeviceToHost, ctx->stream));
-  DSM_HIP(hipEventRecord(ctx->ev_total[1], ctx->stream));
-  DSM_HIP(hipStreamSynchronize(ctx->stream));
-  if (use_queue) {
-    if (ctx->h_queue->error) {
-      // leave the arrival counters clean for the next call
-      DSM_HIP(hipMemsetAsync(ctx->d_tickets, 0, sizeof(int) * ctx->cap_prob, ctx->stream));
-      DSM_HIP(hipStreamSynchronize(ctx->stream));
-      set_error("internal: work-queue kernel gave up waiting (bounded wait expired)");
-      return DSM_ERR_STATE;
-    }
-    ctx->stats.queue_items = ctx->h_queue->tail;
-    if (ctx->timing && ctx->ev_pool.size() >= 2) {
-      float qm = 0;
-      if (hipEventElapsedTime(&qm, ctx->ev_pool[0], ctx->ev_pool[1]) == hipSuccess) ctx->stats.queue_kernel_ms = qm;
-    }
-  }
-  float ms = 0;
-  DSM_HIP(hipEventElapsedTime(&ms, ctx->ev_total[0], ctx->ev_total[1]));
-  ctx->stats.total_ms = ms;
-  if (ctx->timing) collect_eval_timing(ctx, ev_lvl, nlevels, ctx->stats);
+  return DSM_OK;
+}
+
+// after the call's read-back: every problem must have terminated; the statistics of the call (ctx->stats, the companion's ctx->stats2)
+// and the schedule the next call starts from
+static int account_and_learn(dsm_context *ctx, dsm_tracker *const *ts, int n, int n2, int mode, int mode2) {
+  const int nlevels = ts[0]->nlevels;
+  const int N = n + n2;
+  int *sched = ctx->sched[mode], *sched2 = ctx->sched[mode2];
   int need[DSM_MAX_LEVELS] = {0}, need2[DSM_MAX_LEVELS] = {0};
-  ctx->stats2.total_ms = ms;
   for (int i = 0; i < N; i++) {
     const LMState &S = ctx->h_states[i];
     if (S.status == ST_RUNNING) {
@@ -1626,6 +1574,71 @@ static int run_lm_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mod
     }
   }
   return DSM_OK;
+}
+
+// runs the device LM state machine for a batch (mode 0 = trackNewestCoarse, 1 = optimizeScale, 2 = loop-closure pose).
+// n2 > 0: problems [n, n + n2) form a COMPANION segment in mode2 (dsm_track_and_scale_batch: the keyframes' scale
+// optimisations next to the frames' tracking).  The two segments are independent problems; the companion's launches go to a
+// stream of their own, so its latency-bound chains of small launches run under the main segment's kernels instead of after
+// them.  Launch-per-step form only.  Statistics of the companion: ctx->stats2.
+static int run_lm_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mode, int coarsest, int n2 = 0, int mode2 = 1) {
+  const int nlevels = ts[0]->nlevels;
+  if (coarsest < 0 || coarsest >= nlevels) return invalid("coarsest level out of range"); // :457 / :856
+  const dsm_params &P = ts[0]->params;
+  const int N = n + n2;
+  memset(&ctx->stats, 0, sizeof ctx->stats);
+  memset(&ctx->stats2, 0, sizeof ctx->stats2);
+  DSM_HIP(hipEventRecord(ctx->ev_total[0], ctx->stream));
+  DSM_HIP(hipMemcpyAsync(ctx->d_start, ctx->h_start, sizeof(StartInfo) * N, hipMemcpyHostToDevice, ctx->stream));
+  launch_lm(ctx->stream, mode, LM_OP_START, coarsest, n, ctx->d_tracker_ptrs, ctx->d_states, ctx->d_partials,
+            ctx->partial_stride, ctx->d_start, nullptr, ctx->d_status);
+  if (n2 > 0)
+    launch_lm(ctx->stream, mode2, LM_OP_START, coarsest, n2, ctx->d_tracker_ptrs + n, ctx->d_states + n,
+              ctx->d_partials + (size_t)n * ctx->partial_stride, ctx->partial_stride, ctx->d_start + n, nullptr, ctx->d_status + 2 * n);
+  const bool use_queue = queue_wanted(P, n, n2, ts);
+  if (use_queue) {
+    const int rc = run_queue(ctx, ts, n, mode, coarsest);
+    if (rc) return rc;
+  }
+  // the learnt "rounds most problems need" belong to calls of this size and form: another batch-size bucket (powers of four)
+  // or form must not inherit them (a batch of hundreds following a single-frame call would switch to compact launches after
+  // one round, covering almost every problem)
+  {
+    int bucket = 0;
+    for (int v = N; v >= 4; v >>= 2) bucket++;
+    const int key = bucket * 4 + (use_queue ? 2 : 0) + (P.persistent_coarse < 0 ? 1 : 0);
+    if (key != ctx->sched_bulk_key) {
+      for (int m = 0; m < 3; m++)
+        for (int l = 0; l < DSM_MAX_LEVELS; l++) ctx->sched_bulk[m][l] = 1 << 30;
+      ctx->sched_bulk_key = key;
+    }
+  }
+  int ng = ctx->n_streams < 1 ? 1 : ctx->n_streams;
+  if (ng > n) ng = n;
+  {
+    const int rc = ensure_streams(ctx, ng, n2 > 0);
+    if (rc) return rc;
+  }
+  std::vector<int> ev_lvl;
+  if (!use_queue) {
+    int top = coarsest, top2 = n2 > 0 ? coarsest : -1;
+    int rc = P.persistent_coarse < 0 ? run_chain_prefix(ctx, ts, n, n2, mode, mode2, coarsest, ng, top, top2) : DSM_OK;
+    if (!rc) rc = run_passes(ctx, ts, n, n2, mode, mode2, ng, top, top2, ev_lvl);
+    if (rc) return rc;
+  }
+  DSM_HIP(hipMemcpyAsync(ctx->h_states, ctx->d_states, sizeof(LMState) * N, hipMemcpyDeviceToHost, ctx->stream));
+  DSM_HIP(hipEventRecord(ctx->ev_total[1], ctx->stream));
+  DSM_HIP(hipStreamSynchronize(ctx->stream));
+  if (use_queue) {
+    const int rc = queue_outcome(ctx);
+    if (rc) return rc;
+  }
+  float ms = 0;
+  DSM_HIP(hipEventElapsedTime(&ms, ctx->ev_total[0], ctx->ev_total[1]));
+  ctx->stats.total_ms = ms;
+  ctx->stats2.total_ms = ms;
+  if (ctx->timing) collect_eval_timing(ctx, ev_lvl, nlevels, ctx->stats);
+  return account_and_learn(ctx, ts, n, n2, mode, mode2);
 }
 
 int dsm_track_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, double *pose_io, double *aff_io,

@@ -162,13 +162,8 @@ void launch_tick_lm(hipStream_t s, int mode, int nslots, const TrackerDev **trac
 // bounded waits of the LM steps' wave hand-shakes that expired since the library was loaded (0 unless something is badly wrong)
 int lm_spin_expired();
 
-// persistent LM loop of the small levels on LDS-resident data (levels whose target plane has at most max_px pixels, capped
-// by the kernel's LDS arena): coarse_level_fits tells whether a level of w x h pixels and n template points qualifies
-void launch_coarse(hipStream_t s, int mode, int nprob, const TrackerDev *const *trackers, LMState *states,
-                   int *status_out, int max_px, bool spec);
-bool coarse_level_fits(int w, int h, int n, int geom, int max_px);
-// the same for the levels whose evaluation is ONE chunk, without LDS staging (chain_kernel: the tick engine's chain as a launch of its
-// own, one workgroup per problem, until the problem reaches a level of several chunks or terminates; no speculative candidates)
+// persistent LM loop of the levels whose evaluation is ONE chunk (chain_kernel: the tick engine's chain as a launch of its own, one
+// workgroup per problem, until the problem reaches a level of several chunks or terminates; no speculative candidates)
 void launch_chain(hipStream_t s, int mode, int nprob, const TrackerDev *const *trackers, LMState *states, int *status_out);
 
 // row A4 / N3: makeCoarseDepthL0 on the device (template_kernels.hip), batched over the keyframes of a call

@@ -72,7 +72,7 @@ enum { kOEQ = 1, kOGT = 2, kOGE = 3, kOLT = 4, kSLT = 40 };
 #define DSM_FCMP(a, b, pred) ((lmask)__builtin_amdgcn_fcmpf((a), (b), (pred)))
 __device__ __forceinline__ lmask lanes_finite(float x) { return DSM_FCMP(__builtin_fabsf(x), __builtin_inff(), kOLT); } // false for NaN
 // A lane mask is the same in every lane by construction; where the compiler cannot see that (a mask chosen under a condition it takes
-// for divergent, e.g. the thread group's chunk in coarse_kernel) this pins it to an SGPR pair -- no instruction where it already is one.
+// for divergent) this pins it to an SGPR pair -- no instruction where it already is one.
 __device__ __forceinline__ lmask mask_sgpr(lmask m) {
   return ((lmask)(unsigned)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)m);
 }
@@ -119,16 +119,8 @@ __device__ __forceinline__ TapBases tap_bases(const DSM_GLOBAL float *img, int w
   const long pitch = 4l * w;
   return TapBases{cb - pitch, cb - 4, cb + pitch - 4, cb + 2 * pitch};
 }
-// The same four row bases for a plane staged in LDS (coarse_kernel): byte addresses in the local address space; the taps
-// become ds_read instructions (unaligned rows: the compiler picks ds_read2_b32 / ds_read_b64 as alignment allows).
+// the local (LDS) address space: the chains' LDS copies of the state and the partial are addressed through it
 #define DSM_LDS __attribute__((address_space(3)))
-struct TapBasesL {
-  unsigned r0, r1, r2, r3;
-};
-__device__ __forceinline__ TapBasesL tap_bases_lds(unsigned img, int w) {
-  const unsigned pitch = 4u * (unsigned)w;
-  return TapBasesL{img - pitch, img - 4u, img + pitch - 4u, img + 2u * pitch};
-}
 // byte offset of the taps of position (x, y): texel (floor x, floor y), or the safe texel (2, 2) for lanes outside `ok` -- ONE
 // select, on the finished offset (an unusable lane's x / y may be anything, NaN included: its fractions and values are masked later)
 __device__ __forceinline__ unsigned tap_offset(float x, float y, int w, lmask ok, unsigned safe_off, float &dx, float &dy) {
@@ -138,29 +130,6 @@ __device__ __forceinline__ unsigned tap_offset(float x, float y, int w, lmask ok
   dy = __builtin_amdgcn_fractf(y);
   const unsigned off = 4u * ((unsigned)ix + (unsigned)iy * (unsigned)w);
   return sel_u(ok, safe_off, off);
-}
-template <bool L> struct TapSel { typedef TapBases type; };
-template <> struct TapSel<true> { typedef TapBasesL type; };
-template <bool GRAD = true>
-__device__ __forceinline__ void taps_load(const TapBasesL &B, float x, float y, int w, lmask ok, unsigned safe_off, Taps &T) {
-  const unsigned off = tap_offset(x, y, w, ok, safe_off, T.dx, T.dy);
-  if (GRAD) {
-    const fvec4u a = *(const DSM_LDS fvec4u *)(size_t)(B.r1 + off);
-    const fvec4u b = *(const DSM_LDS fvec4u *)(size_t)(B.r2 + off);
-    const fvec2u c = *(const DSM_LDS fvec2u *)(size_t)(B.r0 + off);
-    const fvec2u d = *(const DSM_LDS fvec2u *)(size_t)(B.r3 + off);
-    T.r1[0] = a.x, T.r1[1] = a.y, T.r1[2] = a.z, T.r1[3] = a.w;
-    T.r2[0] = b.x, T.r2[1] = b.y, T.r2[2] = b.z, T.r2[3] = b.w;
-    T.r0[0] = c.x, T.r0[1] = c.y;
-    T.r3[0] = d.x, T.r3[1] = d.y;
-  } else {
-    const fvec2u a = *(const DSM_LDS fvec2u *)(size_t)(B.r1 + off + 4u);
-    const fvec2u b = *(const DSM_LDS fvec2u *)(size_t)(B.r2 + off + 4u);
-    T.r1[0] = T.r1[3] = T.r2[0] = T.r2[3] = 0.f;
-    T.r1[1] = a.x, T.r1[2] = a.y;
-    T.r2[1] = b.x, T.r2[2] = b.y;
-    T.r0[0] = T.r0[1] = T.r3[0] = T.r3[1] = 0.f;
-  }
 }
 // GRAD = false (residual-only evaluations): the intensity needs columns x, x+1 of rows y, y+1 only -- two 8-byte loads.
 template <bool GRAD = true>
@@ -236,19 +205,35 @@ struct EvalConsts {
   float t[3];
   float aff0, aff1, b0, scale, cutoff, max_energy;
   int residual_only; // EvalIn::residual_only
-  unsigned lds_img, lds_pts; // coarse_kernel: LDS byte addresses of the staged intensity plane / template (else unused)
 };
-__device__ __forceinline__ void eval_consts_defaults(EvalConsts &c) { c.lds_img = c.lds_pts = 0; }
+// wave-uniform evaluation inputs: LDS -> SGPRs
+__device__ __forceinline__ void eval_consts_from_lds(const EvalIn &in, EvalConsts &c) {
+  auto rf = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+  const unsigned long long pp = (unsigned long long)in.pts, ip = (unsigned long long)in.img;
+  c.pts = (const float4 *)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(pp >> 32)) << 32) |
+                           (unsigned)__builtin_amdgcn_readfirstlane((int)pp));
+  c.img = (const float *)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(ip >> 32)) << 32) |
+                          (unsigned)__builtin_amdgcn_readfirstlane((int)ip));
+  c.n = __builtin_amdgcn_readfirstlane(in.n);
+  c.ppt = __builtin_amdgcn_readfirstlane(in.ppt);
+  c.w = __builtin_amdgcn_readfirstlane(in.w);
+  c.h = __builtin_amdgcn_readfirstlane(in.h);
+  c.fx = rf(in.fx), c.fy = rf(in.fy), c.cx = rf(in.cx), c.cy = rf(in.cy), c.huber = rf(in.huber);
+#pragma unroll
+  for (int i = 0; i < 9; i++) c.Ki[i] = rf(in.Ki[i]), c.M[i] = rf(in.M[i]);
+  c.t[0] = rf(in.t[0]), c.t[1] = rf(in.t[1]), c.t[2] = rf(in.t[2]);
+  c.aff0 = rf(in.aff0), c.aff1 = rf(in.aff1), c.b0 = rf(in.b0), c.scale = rf(in.scale);
+  c.cutoff = rf(in.cutoff), c.max_energy = rf(in.max_energy);
+  c.residual_only = __builtin_amdgcn_readfirstlane(in.residual_only);
+}
 
 // One chunk of one evaluation by 256 threads (tid = 0..255 inside the chunk's thread group):
 // the per-point loop, the flow-indicator pass and the fixed-order reduction into the chunk's 52-slot
-// partial `out` (global memory in eval_kernel, LDS in coarse_kernel).  `red` is this thread group's
+// partial `out` (global memory in eval_kernel, LDS in the chains).  `red` is this thread group's
 // [16][kNumSlots] LDS scratch.  Contains two workgroup barriers: every thread of the workgroup must
 // call it; thread groups without a chunk pass active = false.
 // RO = residual-only (EvalIn::residual_only): the residual side alone -- energy, counts, flow indicators; no gradients, no
 // Jacobian, no normal-equation sums (their partial slots are written as zeros), two tap loads per point instead of four.
-// LDSIMG / LDSPTS: the target plane / the template are read from their LDS copies (c.lds_img / c.lds_pts) -- same values,
-// same operations, hence the same results as from global memory.
 // arrive != nullptr (eval_kernel without the fused LM step): instead of a workgroup barrier between the row sums and the
 // final sum, every wave takes a ticket on an LDS counter after its rows are written and only the LAST one stays to add the 16
 // rows and store the partial -- the same additions in the same order by another wave; the other waves leave at once instead
@@ -263,7 +248,7 @@ __device__ __forceinline__ void eval_consts_defaults(EvalConsts &c) { c.lds_img 
 // (the 96-register kernels of five waves per SIMD), 1 the warp's twelve (the two-point loop at four waves per SIMD: 128 registers hold
 // these and no more), 2 the camera, gradient-scale and brightness constants as well (the one-point loop inside a kernel that is
 // allocated 128 registers anyway: tick_eval_kernel)
-template <int MODE, bool LVL0, bool RO, bool LDSIMG = false, bool LDSPTS = false, bool DEEP = LVL0, int VC = DEEP ? 1 : 0>
+template <int MODE, bool LVL0, bool RO, bool DEEP = LVL0, int VC = DEEP ? 1 : 0>
 __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, int tid, bool active, float (*red)[kNumSlots],
                                                 float *out, int *arrive = nullptr) {
   const int n = c.n;
@@ -286,12 +271,7 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
     const int wl = c.w, hl = c.h;
     const float wm3 = (float)(wl - 3), hm3 = (float)(hl - 3);
     const int pitch = wl; // floats per row of what the taps are fetched from
-    typename TapSel<LDSIMG>::type img;
-    if constexpr (LDSIMG)
-      img = tap_bases_lds(c.lds_img, pitch);
-    else
-      img = tap_bases((const DSM_GLOBAL float *)c.img, wl);
-    const TapBases img_g = tap_bases((const DSM_GLOBAL float *)c.img, wl); // the plane in HBM (the rare non-finite-gradient path re-fetches from it)
+    const TapBases img = tap_bases((const DSM_GLOBAL float *)c.img, wl);
     const DSM_GLOBAL fvec4 *pts = (const DSM_GLOBAL fvec4 *)c.pts;
     // scale mode: (scale * M) is formed once per evaluation, as `scale * rot_f1_f0_K0_i` is (:1061)
     const float sc = c.scale;
@@ -371,8 +351,8 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
       // makeImages' "non-finite gradient -> 0", the rare path: the taps are fetched again (so that the common path
       // does not keep twelve registers alive for it) and the replacement is applied tap by tap
       if (!RO && __builtin_expect((W.inb & ~(lanes_finite(g1) & lanes_finite(g2))) != 0ull, 0)) {
-        Taps Tx; // (always from the plane in HBM: the same values as a staged copy holds)
-        taps_load(img_g, fxl * W.u + cxl, fyl * W.v + cyl, wl, W.inb, safe_off, Tx);
+        Taps Tx;
+        taps_load(img, fxl * W.u + cxl, fyl * W.v + cyl, wl, W.inb, safe_off, Tx);
         taps_interp<true>(Tx, h0, g1, g2);
       }
       const float refColor = W.refColor;
@@ -512,21 +492,15 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
       // Template stream: entry (start + tid) of the list = one coalesced 16-byte load per lane from a wave-uniform base (SGPR pair)
       // plus this thread's constant byte offset -- no per-point index arithmetic.  Entries past the chunk (the loop prefetches up to
       // three trips ahead) or past the list are never used: their lanes are masked, and an entry past the list reads as zeros (the
-      // buffer descriptor checks the range); the LDS copy (coarse_kernel) is read with a clamped index instead.
+      // buffer descriptor checks the range).
       const unsigned voff = 16u * (unsigned)tid;
-      const unsigned lds_pts = c.lds_pts;
       const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)c.pts, 0, 16 * n, 0x00020000);
       auto load_pt = [=](int start) {
-        if constexpr (LDSPTS) {
-          const int idx = start + tid;
-          return *(const DSM_LDS fvec4 *)(size_t)(lds_pts + 16u * (unsigned)(idx < n ? idx : n - 1));
-        } else {
-          // streamed once: non-temporal (aux = 2), so the template does not evict target rows from the 32 KiB L1 (+2.5 %).
-          // buffer_load ... offen: descriptor and the trip's byte offset in SGPRs, this thread's constant offset in a VGPR -- no vector
-          // address arithmetic at all; an entry beyond the list reads as zeros (range-checked by the descriptor).
-          const uvec4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 16 * start, 2);
-          return fvec4{__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
-        }
+        // streamed once: non-temporal (aux = 2), so the template does not evict target rows from the 32 KiB L1 (+2.5 %).
+        // buffer_load ... offen: descriptor and the trip's byte offset in SGPRs, this thread's constant offset in a VGPR -- no vector
+        // address arithmetic at all; an entry beyond the list reads as zeros (range-checked by the descriptor).
+        const uvec4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 16 * start, 2);
+        return fvec4{__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
       };
       // lanes whose entry `start + tid` exists and whose trip belongs to the chunk: every lane except in the list's last chunk
       const bool tail = chunk_start + kThreads * P > n;
@@ -658,9 +632,9 @@ template <int MODE, bool LVL0, bool DEEP = LVL0, int VC = DEEP ? 1 : 0>
 __device__ __forceinline__ void eval_chunk(const EvalConsts &c, int chunk, int tid, bool active, float (*red)[kNumSlots],
                                            float *out, int *arrive = nullptr) {
   if (c.residual_only) // wave-uniform
-    eval_chunk_impl<MODE, LVL0, true, false, false, DEEP, VC>(c, chunk, tid, active, red, out, arrive);
+    eval_chunk_impl<MODE, LVL0, true, DEEP, VC>(c, chunk, tid, active, red, out, arrive);
   else
-    eval_chunk_impl<MODE, LVL0, false, false, false, DEEP, VC>(c, chunk, tid, active, red, out, arrive);
+    eval_chunk_impl<MODE, LVL0, false, DEEP, VC>(c, chunk, tid, active, red, out, arrive);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1198,7 +1172,7 @@ __device__ __forceinline__ void end_level(const TrackerDev &T, LMState &S) {
   begin_level(T, S, next);
 }
 
-// LDS workspace of the partial reduction / LM step (lm_kernel and coarse_kernel)
+// LDS workspace of the partial reduction / LM step (the LM kernels and the chains)
 struct RedBuf { // fixed-order reduction of one evaluation's chunk partials
   double psum[19][kNumSlots];
   long long pisum[19][4];
@@ -1219,7 +1193,7 @@ struct LmShared {
   LdltScratch ldlt; // wave 0's
   LmHelp help;      // wave 0's helper (wave 2)
   // The problem's LMState and its tracker descriptor are staged here for the duration of a step
-  // (lm_kernel) or of the whole small-level loop (coarse_kernel): the state machine then runs on LDS
+  // (lm_kernel) or of a whole chain (chain_kernel, the tick engine's chains): the state machine then runs on LDS
   // latencies instead of a chain of dependent global-memory round trips.
   __attribute__((aligned(16))) LMState st;
   __attribute__((aligned(16))) TrackerDev trk;
@@ -1260,7 +1234,7 @@ __device__ __forceinline__ void store16_coherent(void *p, const uint4 &v) {
 // ---- fixed-order reduction over the chunk partials (double / int64), first 247 threads of the
 // workgroup.  Thread (g, q) sums the slot quad q (one float4 = 4 of the 52 slots) over chunks
 // g, g+19, g+38, ...: every load is a 16-byte read and up to kRedBatch of them are in flight per
-// thread.  `P` may point to global memory (lm_kernel) or LDS (coarse_kernel): same order, same sums.
+// thread.  `P` may point to global memory (lm_kernel) or LDS (the chains): same order, same sums.
 // reduce_partials_groups2: TWO evaluations' partials -- the main and the speculative candidate's -- reduced side by side, each in
 // exactly the order above, their loads requested TOGETHER (two reductions one after the other were two memory round trips in front of
 // every LM step of the small levels; shader-clock stamps: profiles/r06_tick_stamps.json).  A speculative candidate exists on levels of at
@@ -1660,7 +1634,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(ROSEL 
   c.t[0] = in.t[0], c.t[1] = in.t[1], c.t[2] = in.t[2];
   c.aff0 = in.aff0, c.aff1 = in.aff1, c.b0 = in.b0, c.scale = in.scale, c.cutoff = in.cutoff, c.max_energy = in.max_energy;
   c.residual_only = in.residual_only;
-  eval_consts_defaults(c);
   asm volatile("" ::"s"(s_status), "s"(s_lvl), "s"(s_kind), "s"(s_spec_valid), "s"(c.pts), "s"(c.img), "s"(c.n), "s"(c.w), "s"(c.h),
                "s"(c.residual_only));
   if (FUSED) asm volatile("" ::"s"(trk_ptr), "s"(main_n), "s"(main_ppt));
@@ -1876,193 +1849,6 @@ __global__ __launch_bounds__(kLmThreads) void lm_kernel(int mode, int op, int lv
     }
     S.status = ST_IDLE;
   }
-}
-
-// ------------------------------------------------------------------------------------------
-// coarse_kernel: the whole LM loop of the small pyramid levels inside ONE launch, on LDS-resident data.
-// One 512-thread workgroup per problem.  On entering a level it copies the level's intensity plane (and the template, when
-// both fit) into LDS with coalesced 16-byte loads; every LM iteration of the level then evaluates its chunks (two at a
-// time, each by a 256-thread group running exactly the code of eval_kernel, taps by ds_read instead of global gathers),
-// reduces the chunk partials (same fixed order, partials in LDS) and steps the state machine -- state and tracker
-// descriptor staged in LDS for the whole loop -- until the problem reaches a level whose plane does not fit (left to the
-// launch-per-step path) or terminates.  With `spec` the speculative second candidate of dsm_params.speculate is evaluated
-// in the same round and its proposal staged by wave 1 beside wave 0's, as in lm_step_block.  Same arithmetic, same chunk
-// geometry, same summation order: bit-identical results to the launch-per-step path; what disappears is every launch
-// boundary, every state round trip through global memory and every gather miss of the levels that need the most LM
-// iterations and have the least work per iteration.
-// Two workgroups per CU (LDS: ~39 KB static + the arena; registers: four waves per SIMD).
-// ------------------------------------------------------------------------------------------
-#ifndef DSM_COARSE_THREADS
-#define DSM_COARSE_THREADS 512
-#endif
-#ifndef DSM_COARSE_WAVES
-#define DSM_COARSE_WAVES 4
-#endif
-constexpr int kCoarseThreads = DSM_COARSE_THREADS;
-constexpr int kCoarseGroups = kCoarseThreads / 256;
-constexpr int kCoarseMaxChunks = 20;      // chunks of one evaluation whose partials the kernel keeps in LDS
-constexpr int kCoarseArenaFloats = 9216;  // 36 KB: planes up to 120 x 67 (level 4 of 1920 x 1080), 156 x 48 (level 3 of 1248 x 384)
-
-// a level runs in coarse_kernel iff its target plane fits the arena and its chunk partials fit the LDS block (host and device)
-__host__ __device__ inline bool coarse_level_ok(int w, int h, int nchunks, int arena_floats) {
-  return ((w * h + 3) & ~3) <= arena_floats && nchunks <= kCoarseMaxChunks;
-}
-
-template <int MODE, bool LVL0>
-__device__ __forceinline__ void eval_chunk_lds(const EvalConsts &c, int chunk, int tid, bool active, float (*red)[kNumSlots], float *out) {
-  // (all branches are workgroup-uniform: every thread group of a round evaluates the same candidate)
-  if (LVL0) { // level 0 of a tiny image: flow indicators; the template stays in global memory
-    if (c.residual_only)
-      eval_chunk_impl<MODE, true, true, true, false>(c, chunk, tid, active, red, out);
-    else
-      eval_chunk_impl<MODE, true, false, true, false>(c, chunk, tid, active, red, out);
-  } else if (c.lds_pts) {
-    if (c.residual_only)
-      eval_chunk_impl<MODE, false, true, true, true>(c, chunk, tid, active, red, out);
-    else
-      eval_chunk_impl<MODE, false, false, true, true>(c, chunk, tid, active, red, out);
-  } else {
-    if (c.residual_only)
-      eval_chunk_impl<MODE, false, true, true, false>(c, chunk, tid, active, red, out);
-    else
-      eval_chunk_impl<MODE, false, false, true, false>(c, chunk, tid, active, red, out);
-  }
-}
-
-// wave-uniform evaluation inputs: LDS -> SGPRs
-__device__ __forceinline__ void eval_consts_from_lds(const EvalIn &in, EvalConsts &c) {
-  auto rf = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-  const unsigned long long pp = (unsigned long long)in.pts, ip = (unsigned long long)in.img;
-  c.pts = (const float4 *)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(pp >> 32)) << 32) |
-                           (unsigned)__builtin_amdgcn_readfirstlane((int)pp));
-  c.img = (const float *)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(ip >> 32)) << 32) |
-                          (unsigned)__builtin_amdgcn_readfirstlane((int)ip));
-  c.n = __builtin_amdgcn_readfirstlane(in.n);
-  c.ppt = __builtin_amdgcn_readfirstlane(in.ppt);
-  c.w = __builtin_amdgcn_readfirstlane(in.w);
-  c.h = __builtin_amdgcn_readfirstlane(in.h);
-  c.fx = rf(in.fx), c.fy = rf(in.fy), c.cx = rf(in.cx), c.cy = rf(in.cy), c.huber = rf(in.huber);
-#pragma unroll
-  for (int i = 0; i < 9; i++) c.Ki[i] = rf(in.Ki[i]), c.M[i] = rf(in.M[i]);
-  c.t[0] = rf(in.t[0]), c.t[1] = rf(in.t[1]), c.t[2] = rf(in.t[2]);
-  c.aff0 = rf(in.aff0), c.aff1 = rf(in.aff1), c.b0 = rf(in.b0), c.scale = rf(in.scale);
-  c.cutoff = rf(in.cutoff), c.max_energy = rf(in.max_energy);
-  c.residual_only = __builtin_amdgcn_readfirstlane(in.residual_only);
-  eval_consts_defaults(c);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(kCoarseThreads) __attribute__((amdgpu_waves_per_eu(DSM_COARSE_WAVES, DSM_COARSE_WAVES))) void coarse_kernel(
-    const TrackerDev *const *__restrict__ trackers, LMState *__restrict__ states, int *__restrict__ status_out, int arena_floats, int spec) {
-  extern __shared__ __attribute__((aligned(16))) float arena[];
-  const int prob = blockIdx.x;
-  const int tid = threadIdx.x;
-  LMState &S = states[prob];
-  __shared__ LmShared sh;
-  __shared__ LmSpecShared sps;
-  __shared__ float red[kCoarseGroups][16][kNumSlots];
-  __shared__ __attribute__((aligned(16))) float part[2][kCoarseMaxChunks][kPartialStride];
-  if (!(S.status == ST_RUNNING && S.is_scale == MODE)) return; // workgroup-uniform
-  stage_in(sh.st, &S, tid, kCoarseThreads);
-  stage_in(sh.trk, trackers[prob], tid, kCoarseThreads);
-  __syncthreads();
-  const unsigned arena_lds = (unsigned)(unsigned long long)(DSM_LDS float *)arena;
-  const int vb = tid >> 8, t256 = tid & 255;
-  bool stepped = false;
-  int staged_lvl = -1;
-  unsigned lds_pts = 0;
-  for (;;) {
-    const EvalIn &in = sh.st.in;
-    const int status = sh.st.status, lvl = __builtin_amdgcn_readfirstlane(sh.st.lvl);
-    EvalConsts c;
-    eval_consts_from_lds(in, c);
-    if (status != ST_RUNNING || !coarse_level_ok(c.w, c.h, chunks_of(c.n, c.ppt), arena_floats)) break; // workgroup-uniform
-    stepped = true;
-    if (lvl != staged_lvl) { // entering a level: its plane (and the template, when both fit) -> LDS
-      const int px4 = (c.w * c.h + 3) >> 2; // (planes carry four rows of slack: reading up to three floats past w*h is safe)
-      const uint4 *src = (const uint4 *)c.img;
-      uint4 *dst = (uint4 *)arena;
-      for (int i = tid; i < px4; i += kCoarseThreads) dst[i] = src[i];
-      lds_pts = 0;
-      if (4 * px4 + 4 * c.n <= arena_floats) {
-        const fvec4 *ps = (const fvec4 *)c.pts;
-        fvec4 *pd = (fvec4 *)(arena + 4 * px4);
-        for (int i = tid; i < c.n; i += kCoarseThreads) pd[i] = ps[i];
-        lds_pts = arena_lds + 16u * (unsigned)px4;
-      }
-      staged_lvl = lvl;
-      __syncthreads();
-    }
-    c.lds_img = arena_lds;
-    c.lds_pts = lds_pts;
-    const int nch = chunks_of(c.n, c.ppt);
-    const bool have_spec = spec && sh.st.spec_valid != 0; // workgroup-uniform
-    for (int cand = 0; cand < (have_spec ? 2 : 1); cand++) {
-      if (cand == 1) {
-        eval_consts_from_lds(sh.st.spec_in, c);
-        c.lds_img = arena_lds;
-        c.lds_pts = lds_pts;
-      }
-      for (int c0 = 0; c0 < nch; c0 += kCoarseGroups) {
-        const int chunk = c0 + vb;
-        const bool active = chunk < nch;
-        if (lvl == 0)
-          eval_chunk_lds<MODE, true>(c, chunk, t256, active, red[vb], part[cand][active ? chunk : 0]);
-        else
-          eval_chunk_lds<MODE, false>(c, chunk, t256, active, red[vb], part[cand][active ? chunk : 0]);
-        __syncthreads(); // red[] is reused by the next round
-      }
-    }
-    if (vb == 0) reduce_partials_groups(&part[0][0][0], nch, t256, sh.red);
-    if (spec && vb == (kCoarseGroups > 1 ? 1 : 0)) // (garbage where no speculative candidate was evaluated: never looked at then)
-      reduce_partials_groups(&part[1][0][0], nch, t256, sps.red);
-    if (tid == 0 && spec) sps.cmd = 0, sps.done = 0;
-    __syncthreads();
-    if (tid < 64) {
-      reduce_partials_final(tid, sh.red);
-      if (spec) reduce_partials_final(tid, sps.red);
-      lm_step_wave0(MODE, lvl, sh.trk, sh.st, sh, tid, spec ? &sps : nullptr);
-    } else if (spec && tid < 128) {
-      lm_spec_wave1(MODE, sh.trk, sh.st, sps, tid - 64);
-    }
-    __syncthreads(); // the state (status, level, next evaluation inputs) is read by all waves
-  }
-  if (stepped) stage_out(&S, sh.st, tid, kCoarseThreads);
-  if (tid == 0 && status_out) {
-    status_out[2 * prob] = sh.st.status;
-    status_out[2 * prob + 1] = sh.st.lvl;
-  }
-}
-
-void launch_coarse(hipStream_t s, int mode, int nprob, const TrackerDev *const *trackers, LMState *states,
-                   int *status_out, int max_px, bool spec) {
-  if (max_px > kCoarseArenaFloats) max_px = kCoarseArenaFloats;
-  {
-    // never ask for more LDS than the device gives a workgroup (gfx950: 160 KB; the kernel's static part is ~39 KB)
-    static int lds_limit = 0;
-    if (!lds_limit) {
-      int dev = 0, v = 0;
-      if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && v > 0)
-        lds_limit = v;
-      else
-        lds_limit = 64 * 1024;
-    }
-    const int room = (lds_limit - 40 * 1024) / (int)sizeof(float);
-    if (max_px > room) max_px = room > 0 ? room : 0;
-  }
-  const int arena_floats = (max_px + 3) & ~3;
-  dim3 grid(nprob), block(kCoarseThreads);
-  const size_t dyn = sizeof(float) * (size_t)arena_floats;
-  if (mode == 0)
-    hipLaunchKernelGGL((coarse_kernel<0>), grid, block, dyn, s, trackers, states, status_out, arena_floats, spec ? 1 : 0);
-  else if (mode == 1)
-    hipLaunchKernelGGL((coarse_kernel<1>), grid, block, dyn, s, trackers, states, status_out, arena_floats, spec ? 1 : 0);
-  else
-    hipLaunchKernelGGL((coarse_kernel<2>), grid, block, dyn, s, trackers, states, status_out, arena_floats, spec ? 1 : 0);
-}
-bool coarse_level_fits(int w, int h, int n, int geom, int max_px) {
-  if (max_px > kCoarseArenaFloats) max_px = kCoarseArenaFloats;
-  return coarse_level_ok(w, h, num_chunks(n, geom), (max_px + 3) & ~3);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2573,7 +2359,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     c.t[0] = in.t[0], c.t[1] = in.t[1], c.t[2] = in.t[2];
     c.aff0 = in.aff0, c.aff1 = in.aff1, c.b0 = in.b0, c.scale = in.scale, c.cutoff = in.cutoff, c.max_energy = in.max_energy;
     c.residual_only = in.residual_only;
-    eval_consts_defaults(c);
     float *const out = partials + (size_t)prob * partial_stride + (cand ? (partial_stride >> 1) : 0) + (size_t)chunk * kPartialStride;
     if (lvl == 0)
       eval_chunk<MODE, true>(c, chunk, threadIdx.x, true, red, out);

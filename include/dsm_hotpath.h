@@ -80,20 +80,15 @@ typedef struct dsm_params {
                                          host read-back per pass (plus, with compact_tail, one per level and stream group in the
                                          first pass); 0: enqueue the worst case (2*(7+max_iterations) launch
                                          pairs per level) and never poll.  Scheduling only -- results are identical. */
-  int persistent_coarse;              /* N > 0: pyramid levels whose target plane has at most min(N, 9216) pixels (156x48,
-                                         120x67, ...; and at most 20 chunks of template points) run their whole LM loop inside
-                                         ONE kernel launch per problem, on an LDS-resident copy of the plane (and of the
-                                         template when both fit), speculative candidates included; 0 (default): one
-                                         (evaluate, step) launch pair per LM evaluation at every level.  Scheduling only --
-                                         results are bit-identical.  Measured: neutral for hundreds of frames in
-                                         flight (a third of the launches), slower for one frame (the launch form spreads a
-                                         level's chunks over many CUs).
-                                         N < 0 (round 6): the CHAIN form for single calls -- every level whose evaluation is ONE chunk
+  int persistent_coarse;              /* N < 0: the CHAIN form for single calls -- every level whose evaluation is ONE chunk
                                          (chunk_geometry) runs its LM loop in one launch per problem (evaluate, reduce, step on an LDS
                                          copy of the state; global gathers, no speculative candidates), down to the first level of
                                          several chunks, where the launch-per-step schedule takes over: one frame in flight saves a
                                          launch per LM round of its coarse levels (with chunk_geometry 2: what the replay adaptors
-                                         set).  Scheduling only -- bit-identical under the same chunk table. */
+                                         set).  Scheduling only -- bit-identical under the same chunk table.
+                                         0 (default): one (evaluate, step) launch pair per LM evaluation at every level.
+                                         N > 0: accepted and run as 0 (it selected an LDS-resident small-level kernel, since
+                                         retired: DESIGN_HISTORY.md section 4.2). */
   int fuse_lm;                        /* at pyramid levels >= 1 the evaluation kernel's last-arriving workgroup of a
                                          problem can perform the LM step itself (one launch per evaluation instead of
                                          two): 0 never, 1 (default) for batches of at most 8 problems (where it shortens
@@ -162,7 +157,7 @@ typedef struct dsm_stats {
   int64_t eval_dispatches[DSM_MAX_LEVELS];     /* timed dispatches per level (launches x stream groups) */
   double total_ms;                      /* HIP-event time of the whole call */
   int64_t polls;                        /* host read-backs of the device LM state (passes) */
-  int64_t coarse_launches;              /* launches of the persistent small-level kernel */
+  int64_t coarse_launches;              /* 1 when the call ran its small levels in chain_kernel (persistent_coarse < 0), else 0 */
   int64_t queue_blocks;                 /* work-queue kernel: persistent workgroups launched (0: launch-per-step form) */
   int64_t queue_items;                  /* work-queue kernel: (problem, chunk) items processed */
   double queue_kernel_ms;               /* work-queue kernel: HIP-event duration of the launch (timing enabled) */

@@ -592,10 +592,9 @@ def test_stream_groups_do_not_change_results(ctx):
 
 
 @pytest.mark.parametrize("size,template", [("small", "dense"), ("medium", "dense"), ("medium", "sparse"), ("kitti", "dense")])
-def test_persistent_coarse_kernel_is_bit_identical(ctx, size, template):
-    """levels whose target plane has at most persistent_coarse pixels (capped by the kernel's LDS arena) run their whole LM
-    loop in one launch on LDS-resident data (coarse_kernel); same arithmetic, chunk geometry and summation order as the
-    launch-per-step path, so every output must be bit-identical and the evaluation counts equal."""
+def test_retired_persistent_coarse_value_changes_nothing(ctx, size, template):
+    """persistent_coarse > 0 selected a retired small-level form: the value is still accepted and runs the launch-per-step path,
+    so every output must be bit-identical to persistent_coarse = 0, the evaluation counts equal and no small-level kernel launched."""
     from direct_stereo_slam_amd.tracker import default_params
 
     sc = make_scene(size, seed=60, template=template, n0=12000)
@@ -611,7 +610,7 @@ def test_persistent_coarse_kernel_is_bit_identical(ctx, size, template):
         s = trk.optimizeScale(1.3, sc.nl - 1)
         evals.append(list(ctx.stats().evals))
         out.append((r, s))
-    assert coarse == [0, 1, 1, 1]
+    assert coarse == [0, 0, 0, 0]
     (r0, s0) = out[0]
     for k in range(1, 4):
         assert evals[2 * k] == evals[0] and evals[2 * k + 1] == evals[1]
@@ -826,7 +825,7 @@ def test_fixed_schedule_runs_one_plus_k_evaluations_per_level_like_the_oracle(ct
     assert list(ctx.stats().evals)[:sc.nl] == [4] * sc.nl
     assert abs(s_g - s_o) < 1e-4 * abs(s_o) and abs(err_g - err_o) < 1e-3 * err_o
     # ... whatever the scheduling form
-    for coarse, queue in ((9216, 0), (0, 2)):
+    for coarse, queue in ((-1, 0), (0, 2)):
         p2 = default_params()
         p2.fixed_schedule, p2.persistent_coarse, p2.work_queue = 3, coarse, queue
         r2 = hip_tracker(ctx, sc, p2).trackNewestCoarse(S.IDENTITY_POSE, [0, 0], sc.nl - 1)

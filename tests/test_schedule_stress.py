@@ -32,10 +32,10 @@ def test_every_schedule_gives_identical_results(ctx):
     try:
         ref = _run(ctx, scs, 0, 1, 0)
         for it in range(12):
-            for fuse, ns, coarse, queue, spec in ((2, 1, 0, 0, 0), (2, 2, 0, 0, 0), (1, 3, 0, 0, 0), (0, 2, 4096, 0, 0), (2, 2, 2048, 0, 0),
+            for fuse, ns, coarse, queue, spec in ((2, 1, 0, 0, 0), (2, 2, 0, 0, 0), (1, 3, 0, 0, 0), (0, 2, -1, 0, 0), (2, 2, -1, 0, 0),
                                                   (0, 1, 0, 2, 0), (1, 2, 0, 2, 0),
                                                   # speculative second candidate: two-kernel form, fused form, with the other switches
-                                                  (0, 1, 0, 0, 2), (2, 2, 0, 0, 2), (1, 3, 0, 0, 1), (0, 2, 4096, 0, 2), (1, 2, 0, 2, 2)):
+                                                  (0, 1, 0, 0, 2), (2, 2, 0, 0, 2), (1, 3, 0, 0, 1), (0, 2, -1, 0, 2), (1, 2, 0, 2, 2)):
                 got = _run(ctx, scs, fuse, ns, coarse, queue, spec)
                 for g, r in zip(got, ref):
                     for a, b in zip(g, r):
@@ -81,7 +81,7 @@ def test_last_evaluation_of_a_level_is_residual_only(ctx):
     err_o, s_o = orc.optimize_scale(1.0, sc.nl - 1)
     want_s = orc.eval_counts()[0][:sc.nl]
     ref = None
-    for fuse, queue, spec, coarse in ((0, 0, 0, 0), (2, 0, 2, 0), (0, 2, 0, 0), (0, 0, 1, 2048)):
+    for fuse, queue, spec, coarse in ((0, 0, 0, 0), (2, 0, 2, 0), (0, 2, 0, 0), (0, 0, 1, -1)):
         p = default_params()
         p.fuse_lm, p.work_queue, p.speculate, p.persistent_coarse = fuse, queue, spec, coarse
         trk = hip_tracker(ctx, sc, p)
