@@ -177,6 +177,10 @@ SYMBOLS = {
     "dsm_upload_images_enqueue": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), c_int_p, C.POINTER(_vp), c_float_p, C.c_int, C.c_size_t]),
     "dsm_upload_wait": (C.c_int, [_vp]),
     "dsm_frames_advance": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), c_int_p]),
+    "dsm_pinhole_undistort_map": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_float_p, c_int_p, c_float_p, c_float_p]),
+    "dsm_undistorter_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, C.POINTER(_vp)]),
+    "dsm_undistorter_destroy": (C.c_int, [_vp]),
+    "dsm_upload_images_undistorted": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp), c_int_p, C.POINTER(_vp), c_float_p, C.c_size_t, C.c_int]),
     "dsm_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),
     "dsm_host_free": (C.c_int, [_vp]),
     "dsm_tracker_get_frame": (C.c_int, [_vp, C.c_int, C.c_int, c_float_p]),

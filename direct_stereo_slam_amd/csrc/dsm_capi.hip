@@ -757,10 +757,29 @@ int dsm_tracker_upload_image(dsm_tracker *t, int slot, const float *image, float
 
 // Target buffers of a hand-over: the frame slot itself (0, 1) or its back buffers (DSM_SLOT_NEXT_*), which
 // dsm_frames_advance later swaps in.  Back buffers are allocated on first use.
-static int upload_target(dsm_tracker *t, int slot, float **raw, float **img) {
+// raw_bytes: what the staged image needs; more than the 4 w h bytes of a level-0 float image (raw camera bytes of a larger
+// camera, dsm_upload_images_undistorted) grows the staging buffer once
+static int upload_target(dsm_tracker *t, int slot, float **raw, float **img, size_t raw_bytes) {
   const size_t npx0 = (size_t)t->w * t->h;
   const int s = slot & 1;
   const bool back = slot >= 2;
+  if (raw_bytes > npx0 * sizeof(float)) {
+    float *&buf = back ? t->d_raw_back[s] : t->d_raw[s];
+    size_t &cap = back ? t->raw_back_bytes[s] : t->raw_bytes[s];
+    if (buf && cap < raw_bytes) {
+      // the pyramid kernels of an earlier hand-over may still read it
+      dsm_context *ctx = t->ctx;
+      DSM_HIP(hipStreamSynchronize(ctx->stream));
+      if (ctx->upload_stream) DSM_HIP(hipStreamSynchronize(ctx->upload_stream));
+      if (ctx->copy_stream) DSM_HIP(hipStreamSynchronize(ctx->copy_stream));
+      DSM_HIP(hipFree(buf));
+      buf = nullptr;
+    }
+    if (!buf) {
+      DSM_HIP(hipMalloc(&buf, raw_bytes));
+      cap = raw_bytes;
+    }
+  }
   if (back) {
     for (int l = 0; l < t->nlevels; l++)
       if (!t->d_img_back[s][l]) {
@@ -789,8 +808,11 @@ static void upload_mark(dsm_tracker *t, int slot, float exposure) {
 
 // async = false: copies and pyramids ordered on the context's stream, returns when the copies are through.
 // async = true: everything on the context's upload stream, returns at once; dsm_upload_wait waits for the copies.
+// und != null (dsm_upload_images_undistorted): the images are und's raw w_in x h_in camera bytes, staged as they are; level
+// 0 is their undistortion.
 static int upload_images_impl(dsm_context *ctx, int n, dsm_tracker *const *trackers, const int *slots, const void *const *images,
-                              const float *ab_exposures, int pixel_type, size_t row_pitch_bytes, bool async, bool nowait = false) {
+                              const float *ab_exposures, int pixel_type, size_t row_pitch_bytes, bool async, bool nowait = false,
+                              const dsm_undistorter *und = nullptr) {
   if (!ctx || n < 0 || (n > 0 && (!trackers || !slots || !images)))
     return invalid("dsm_upload_images: bad argument");
   if (pixel_type != DSM_PIXEL_F32 && pixel_type != DSM_PIXEL_U8) return invalid("dsm_upload_images: bad pixel type");
@@ -804,10 +826,14 @@ static int upload_images_impl(dsm_context *ctx, int n, dsm_tracker *const *track
     if (t->ctx != ctx) return invalid("dsm_upload_images: tracker of another context");
     if (t->w != t0->w || t->h != t0->h || t->nlevels != t0->nlevels)
       return invalid("dsm_upload_images: trackers of different geometry in one call");
+    if (und && (t->w != und->tab.w_out || t->h != und->tab.h_out))
+      return invalid("dsm_upload_images_undistorted: tracker size differs from the undistorter's output size");
     for (int j = 0; j < i; j++)
       if (trackers[j] == t && slots[j] == slots[i]) return invalid("dsm_upload_images: the same slot twice");
   }
-  const size_t row = (size_t)t0->w * px;
+  // the staged source image: und's camera bytes, else level-0 pixels of the trackers' size
+  const int src_w = und ? und->tab.w_in : t0->w, src_h = und ? und->tab.h_in : t0->h;
+  const size_t row = (size_t)src_w * px;
   if (row_pitch_bytes != 0 && row_pitch_bytes < row) return invalid("dsm_upload_images: row pitch smaller than a row");
   if (!ctx->copy_stream) DSM_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
   if (async && !ctx->upload_stream) {
@@ -834,14 +860,14 @@ static int upload_images_impl(dsm_context *ctx, int n, dsm_tracker *const *track
     if (rc) return rc;
     ctx->pyr_jobs_cap = n;
   }
-  const size_t npx0 = (size_t)t0->w * t0->h;
+  const size_t npx0 = (size_t)src_w * src_h;
   const size_t pitch = row_pitch_bytes ? row_pitch_bytes : row;
   // pinned caller buffers (dsm_host_alloc, hipHostMalloc, hipHostRegister) are read by the GPU directly
   bool all_pinned = true;
   uintptr_t align = (uintptr_t)row | (uintptr_t)pitch;
   for (int i = 0; i < n; i++) {
     float *raw = nullptr;
-    int rc = upload_target(trackers[i], slots[i], &raw, ctx->h_pyr_jobs[i].img);
+    int rc = upload_target(trackers[i], slots[i], &raw, ctx->h_pyr_jobs[i].img, npx0 * px);
     if (rc) return rc;
     ctx->h_pyr_jobs[i].raw = raw;
     ctx->h_pyr_jobs[i].src = nullptr;
@@ -870,10 +896,13 @@ static int upload_images_impl(dsm_context *ctx, int n, dsm_tracker *const *track
     DSM_HIP(hipMemcpyAsync(ctx->d_pyr_jobs, ctx->h_pyr_jobs, sizeof(dsm::PyrJob) * n, hipMemcpyHostToDevice, work));
     // asynchronous: few workgroups, so that the host reads (microseconds of latency each) do not sit in the memory
     // pipelines of the CUs the tracking kernels run on
-    launch_host_rows_copy(work, ctx->d_pyr_jobs, n, (int)row, t0->h, pitch, unit, async ? ctx->async_copy_blocks : 1 << 20);
+    launch_host_rows_copy(work, ctx->d_pyr_jobs, n, (int)row, src_h, pitch, unit, async ? ctx->async_copy_blocks : 1 << 20);
     DSM_HIP(hipGetLastError());
     DSM_HIP(hipEventRecord(async ? ctx->upload_copies_event : ctx->copy_event, work));
-    launch_pyramid_batched(work, t0->w, t0->h, t0->nlevels, ctx->d_pyr_jobs, n, u8);
+    if (und)
+      launch_undistort_pyramid_batched(work, und->tab, t0->nlevels, ctx->d_pyr_jobs, n);
+    else
+      launch_pyramid_batched(work, t0->w, t0->h, t0->nlevels, ctx->d_pyr_jobs, n, u8);
     DSM_HIP(hipGetLastError());
     if (!async && nowait)
       ctx->enqueue_pending = true; // (waited for by the next hand-over or dsm_upload_wait)
@@ -899,11 +928,14 @@ static int upload_images_impl(dsm_context *ctx, int n, dsm_tracker *const *track
         if (pitch == row)
           DSM_HIP(hipMemcpyAsync(dst, images[i], npx0 * px, hipMemcpyHostToDevice, ctx->copy_stream));
         else
-          DSM_HIP(hipMemcpy2DAsync(dst, row, images[i], pitch, row, (size_t)t0->h, hipMemcpyHostToDevice, ctx->copy_stream));
+          DSM_HIP(hipMemcpy2DAsync(dst, row, images[i], pitch, row, (size_t)src_h, hipMemcpyHostToDevice, ctx->copy_stream));
       }
       DSM_HIP(hipEventRecord(ctx->upload_events[g], ctx->copy_stream));
       DSM_HIP(hipStreamWaitEvent(work, ctx->upload_events[g], 0));
-      launch_pyramid_batched(work, t0->w, t0->h, t0->nlevels, ctx->d_pyr_jobs + i0, i1 - i0, u8);
+      if (und)
+        launch_undistort_pyramid_batched(work, und->tab, t0->nlevels, ctx->d_pyr_jobs + i0, i1 - i0);
+      else
+        launch_pyramid_batched(work, t0->w, t0->h, t0->nlevels, ctx->d_pyr_jobs + i0, i1 - i0, u8);
       DSM_HIP(hipGetLastError());
     }
     if (async)
@@ -934,6 +966,87 @@ int dsm_upload_images_enqueue(dsm_context *ctx, int n, dsm_tracker *const *track
   for (int i = 0; trackers && slots && i < n; i++)
     if (slots[i] > 1) return invalid("dsm_upload_images_enqueue: front buffers only (slots 0 / 1)");
   return upload_images_impl(ctx, n, trackers, slots, images, ab_exposures, pixel_type, row_pitch_bytes, false, true);
+}
+
+int dsm_undistorter_create(dsm_context *ctx, int w_in, int h_in, int w_out, int h_out, const float *remap_x, const float *remap_y,
+                           const float *G, const float *vignette_inv, dsm_undistorter **out) {
+  if (!ctx || !out) return invalid("dsm_undistorter_create: null argument");
+  *out = nullptr;
+  if (w_in < 2 || h_in < 2 || w_out < 1 || h_out < 1 || (long long)w_in * h_in >= (1ll << 31) || (long long)w_out * h_out >= (1ll << 31))
+    return invalid("dsm_undistorter_create: bad image size");
+  if (!remap_x != !remap_y) return invalid("dsm_undistorter_create: remap_x and remap_y are both given or both NULL");
+  const bool pass = !remap_x;
+  if (pass && (w_out != w_in || h_out != h_in)) return invalid("dsm_undistorter_create: passthrough requires the input size");
+  const size_t n_out = (size_t)w_out * h_out, n_in = (size_t)w_in * h_in;
+  std::vector<float2> remap;
+  if (!pass) {
+    // every entry outside (x < 0) or with its whole bilinear footprint inside: xi + 1 <= w_in - 1, yi + 1 <= h_in - 1
+    remap.resize(n_out);
+    const float wm1 = (float)(w_in - 1), hm1 = (float)(h_in - 1);
+    for (size_t i = 0; i < n_out; i++) {
+      const float x = remap_x[i], y = remap_y[i];
+      if (!(x < 0) && !(x >= 0 && x < wm1 && y >= 0 && y < hm1)) {
+        char msg[256];
+        snprintf(msg, sizeof msg,
+                 "dsm_undistorter_create: remap entry %zu (x = %d, y = %d) = (%.9g, %.9g): its 2x2 footprint leaves the %d x %d source",
+                 i, (int)(i % w_out), (int)(i / w_out), x, y, w_in, h_in);
+        return invalid(msg);
+      }
+      remap[i] = make_float2(x, y);
+    }
+  }
+  DSM_HIP(hipSetDevice(ctx->device));
+  dsm_undistorter *u = new dsm_undistorter();
+  u->ctx = ctx;
+  u->tab.w_in = w_in, u->tab.h_in = h_in, u->tab.w_out = w_out, u->tab.h_out = h_out;
+  float2 *d_remap = nullptr;
+  float *d_G = nullptr, *d_vig = nullptr;
+  hipError_t e = hipSuccess;
+  if (!pass && e == hipSuccess) e = hipMalloc(&d_remap, n_out * sizeof(float2));
+  if (!pass && e == hipSuccess) e = hipMemcpy(d_remap, remap.data(), n_out * sizeof(float2), hipMemcpyHostToDevice);
+  if (G && e == hipSuccess) e = hipMalloc(&d_G, 256 * sizeof(float));
+  if (G && e == hipSuccess) e = hipMemcpy(d_G, G, 256 * sizeof(float), hipMemcpyHostToDevice);
+  if (vignette_inv && e == hipSuccess) e = hipMalloc(&d_vig, n_in * sizeof(float));
+  if (vignette_inv && e == hipSuccess) e = hipMemcpy(d_vig, vignette_inv, n_in * sizeof(float), hipMemcpyHostToDevice);
+  u->tab.remap = d_remap, u->tab.G = d_G, u->tab.vig = d_vig;
+  if (e != hipSuccess) {
+    dsm_undistorter_destroy(u);
+    DSM_HIP(e);
+  }
+  *out = u;
+  return DSM_OK;
+}
+
+int dsm_undistorter_destroy(dsm_undistorter *u) {
+  if (!u) return DSM_OK;
+  dsm_context *ctx = u->ctx;
+  hipSetDevice(ctx->device);
+  // hand-overs still in flight read the tables
+  hipStreamSynchronize(ctx->stream);
+  if (ctx->upload_stream) hipStreamSynchronize(ctx->upload_stream);
+  hipFree(const_cast<float2 *>(u->tab.remap));
+  hipFree(const_cast<float *>(u->tab.G));
+  hipFree(const_cast<float *>(u->tab.vig));
+  delete u;
+  return DSM_OK;
+}
+
+int dsm_upload_images_undistorted(dsm_context *ctx, const dsm_undistorter *u, int n, dsm_tracker *const *trackers, const int *slots,
+                                  const void *const *images_u8, const float *ab_exposures, size_t row_pitch_bytes, int form) {
+  if (!u) return invalid("dsm_upload_images_undistorted: null undistorter");
+  if (u->ctx != ctx) return invalid("dsm_upload_images_undistorted: undistorter of another context");
+  switch (form) {
+  case DSM_UPLOAD_SYNC:
+    return upload_images_impl(ctx, n, trackers, slots, images_u8, ab_exposures, DSM_PIXEL_U8, row_pitch_bytes, false, false, u);
+  case DSM_UPLOAD_ASYNC:
+    return upload_images_impl(ctx, n, trackers, slots, images_u8, ab_exposures, DSM_PIXEL_U8, row_pitch_bytes, true, false, u);
+  case DSM_UPLOAD_ENQUEUE:
+    for (int i = 0; trackers && slots && i < n; i++)
+      if (slots[i] > 1) return invalid("dsm_upload_images_undistorted: the enqueue form takes front buffers only (slots 0 / 1)");
+    return upload_images_impl(ctx, n, trackers, slots, images_u8, ab_exposures, DSM_PIXEL_U8, row_pitch_bytes, false, true, u);
+  default:
+    return invalid("dsm_upload_images_undistorted: bad form");
+  }
 }
 
 int dsm_upload_wait(dsm_context *ctx) {
@@ -976,6 +1089,9 @@ int dsm_frames_advance(dsm_context *ctx, int n, dsm_tracker *const *trackers, co
     float *r = t->d_raw[s];
     t->d_raw[s] = t->d_raw_back[s];
     t->d_raw_back[s] = r;
+    const size_t rb = t->raw_bytes[s];
+    t->raw_bytes[s] = t->raw_back_bytes[s];
+    t->raw_back_bytes[s] = rb;
     t->desc.exposure[s] = t->back_exposure[s];
     t->have_frame[s] = true;
     t->have_back[s] = false;

@@ -108,11 +108,20 @@ struct dsm_tracker {
   // back buffers of the two frame slots (DSM_SLOT_NEXT_*), swapped in by dsm_frames_advance
   float *d_img_back[2][DSM_MAX_LEVELS] = {};
   float *d_raw_back[2] = {nullptr, nullptr};
+  // size of d_raw / d_raw_back once grown past the 4 w h bytes they are allocated with (raw camera images larger than
+  // that: dsm_upload_images_undistorted), 0 = not grown; swapped along with the buffers
+  size_t raw_bytes[2] = {0, 0}, raw_back_bytes[2] = {0, 0};
   bool have_back[2] = {false, false};
   float back_exposure[2] = {1.f, 1.f};
   bool have_k = false, have_ref = false, have_frame[2] = {false, false};
   int ref_frame_id = -1;
   bool desc_dirty = true;
+};
+
+// dsm_undistorter_create: the device copy of one camera's undistortion
+struct dsm_undistorter {
+  dsm_context *ctx = nullptr;
+  dsm::UndistortTables tab{}; // device pointers + sizes (dsm_kernels.hpp)
 };
 
 namespace dsm {

@@ -212,6 +212,16 @@ void launch_desc_scatter(hipStream_t s, int n, const TrackerDev *d_src, TrackerD
 // raw <- src for every job, rows of row_bytes at pitch `pitch` in src (tight in raw); unit: 16, 4 or 1 bytes per access
 void launch_host_rows_copy(hipStream_t s, const PyrJob *d_jobs, int njobs, int row_bytes, int rows, size_t pitch, int unit, int max_blocks);
 void launch_pyramid_batched(hipStream_t s, int w, int h, int nlevels, const PyrJob *d_jobs, int njobs, bool u8);
+// dsm_undistorter: remap = w_out * h_out (x, y) source coordinates (x < 0: outside; null: passthrough), G = 256 floats,
+// vig = w_in * h_in inverse vignette (each null when absent)
+struct UndistortTables {
+  int w_in, h_in, w_out, h_out;
+  const float2 *remap;
+  const float *G, *vig;
+};
+// the batched pyramids of dsm_upload_images_undistorted: level 0 (and 1) from the staged camera bytes of every job, the
+// other levels as launch_pyramid_batched builds them -- as many launches as that
+void launch_undistort_pyramid_batched(hipStream_t s, const UndistortTables &u, int nlevels, const PyrJob *d_jobs, int njobs);
 
 // queue probe of ensure_streams (diag_kernels.hip): a kernel resident for `ticks` of the wall clock, and an empty one
 void launch_queue_probe_wait(hipStream_t s, long long ticks);

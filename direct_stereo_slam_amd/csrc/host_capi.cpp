@@ -408,3 +408,154 @@ int dsm_make_coarse_depth_l0(int w0, int h0, int nl, int npts, const float *pu, 
 }
 
 } // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// UPSTREAM-DSO Undistort (src/util/Undistort.cpp): readFromFile's remap for the Pinhole model, makeOptimalK_crop and
+// UndistortPinhole::distortCoordinates.  Quirks U1-U7: DESIGN.md section 9.
+// ---------------------------------------------------------------------------------------------
+#include <string>
+
+namespace dsm {
+void set_error(const std::string &msg);
+}
+
+namespace {
+struct Pinhole {
+  float fx, fy, cx, cy; // input camera (distortCoordinates: float copies of parsOrg)
+  // distortCoordinates with output camera (ofx, ofy, ocx, ocy): ((x - ocx) / ofx) * fx + cx, in float
+  void distort(float ofx, float ofy, float ocx, float ocy, float x, float y, float &ox, float &oy) const {
+    const float ix = (x - ocx) / ofx, iy = (y - ocy) / ofy;
+    ox = fx * ix + cx;
+    oy = fy * iy + cy;
+  }
+};
+
+// makeOptimalK_crop in normalised coordinates (K = identity while searching); false after 500 iterations
+bool optimal_k_crop(const Pinhole &cam, int w_in, int h_in, int w, int h, float K[4]) {
+  float minX = 0, maxX = 0, minY = 0, maxY = 0;
+  // 1. stretch the centre lines as far as they stay inside the image (U2: 0 doubles as "not found yet")
+  for (int i = 0; i < 100000; i++) {
+    const float t = (i - 50000.0f) / 10000.0f;
+    float ox, oy;
+    cam.distort(1.f, 1.f, 0.f, 0.f, t, 0.f, ox, oy);
+    if (ox > 0 && ox < w_in - 1) {
+      if (minX == 0) minX = t;
+      maxX = t;
+    }
+  }
+  for (int i = 0; i < 100000; i++) {
+    const float t = (i - 50000.0f) / 10000.0f;
+    float ox, oy;
+    cam.distort(1.f, 1.f, 0.f, 0.f, 0.f, t, ox, oy);
+    if (oy > 0 && oy < h_in - 1) {
+      if (minY == 0) minY = t;
+      maxY = t;
+    }
+  }
+  // U3: float * double literal, rounded back to float
+  minX = (float)(minX * 1.01);
+  maxX = (float)(maxX * 1.01);
+  minY = (float)(minY * 1.01);
+  maxY = (float)(maxY * 1.01);
+  // 2. shrink the sides whose edge samples leave the image; both dimensions out: only the wider one
+  bool oobLeft = true, oobRight = true, oobTop = true, oobBottom = true;
+  int iteration = 0;
+  while (oobLeft || oobRight || oobTop || oobBottom) {
+    oobLeft = oobRight = oobTop = oobBottom = false;
+    for (int y = 0; y < h; y++) {
+      const float yy = minY + (maxY - minY) * (float)y / ((float)h - 1.0f);
+      float lx, ly, rx, ry;
+      cam.distort(1.f, 1.f, 0.f, 0.f, minX, yy, lx, ly);
+      cam.distort(1.f, 1.f, 0.f, 0.f, maxX, yy, rx, ry);
+      if (!(lx > 0 && lx < w_in - 1)) oobLeft = true;
+      if (!(rx > 0 && rx < w_in - 1)) oobRight = true;
+    }
+    for (int x = 0; x < w; x++) {
+      const float xx = minX + (maxX - minX) * (float)x / ((float)w - 1.0f);
+      float tx, ty, bx, by;
+      cam.distort(1.f, 1.f, 0.f, 0.f, xx, minY, tx, ty);
+      cam.distort(1.f, 1.f, 0.f, 0.f, xx, maxY, bx, by);
+      if (!(ty > 0 && ty < h_in - 1)) oobTop = true;
+      if (!(by > 0 && by < h_in - 1)) oobBottom = true;
+    }
+    if ((oobLeft || oobRight) && (oobTop || oobBottom)) {
+      if ((maxX - minX) > (maxY - minY))
+        oobBottom = oobTop = false;
+      else
+        oobLeft = oobRight = false;
+    }
+    if (oobLeft) minX = (float)(minX * 0.995);
+    if (oobRight) maxX = (float)(maxX * 0.995);
+    if (oobTop) minY = (float)(minY * 0.995);
+    if (oobBottom) maxY = (float)(maxY * 0.995);
+    if (++iteration > 500) return false; // U4: upstream prints and exit(1)s
+  }
+  K[0] = ((float)w - 1.0f) / (maxX - minX);
+  K[1] = ((float)h - 1.0f) / (maxY - minY);
+  K[2] = -minX * K[0];
+  K[3] = -minY * K[1];
+  return true;
+}
+} // namespace
+
+extern "C" {
+
+int dsm_pinhole_undistort_map(const double calib[4], int w_in, int h_in, int out_mode, const float out_calib[4], int w_out, int h_out,
+                              float K_out[4], int *passthrough, float *remap_x, float *remap_y) {
+  auto fail = [](const char *msg) {
+    dsm::set_error(msg);
+    return (int)DSM_ERR_INVALID;
+  };
+  if (!calib || !K_out || !passthrough) return fail("dsm_pinhole_undistort_map: null argument");
+  if (w_in < 2 || h_in < 2 || w_out < 2 || h_out < 2) return fail("dsm_pinhole_undistort_map: bad image size");
+  if (out_mode != DSM_UNDISTORT_CROP && out_mode != DSM_UNDISTORT_NONE && out_mode != DSM_UNDISTORT_EXPLICIT)
+    return fail("dsm_pinhole_undistort_map: bad output mode");
+  if (out_mode == DSM_UNDISTORT_EXPLICIT && !out_calib) return fail("dsm_pinhole_undistort_map: explicit output calibration missing");
+  // U1: relative calibration (parsOrg is double: the rescale runs in double, distortCoordinates takes float copies)
+  double p[4] = {calib[0], calib[1], calib[2], calib[3]};
+  if (p[2] < 1 && p[3] < 1) {
+    p[0] = p[0] * w_in;
+    p[1] = p[1] * h_in;
+    p[2] = p[2] * w_in - 0.5;
+    p[3] = p[3] * h_in - 0.5;
+  }
+  const Pinhole cam{(float)p[0], (float)p[1], (float)p[2], (float)p[3]};
+  *passthrough = 0;
+  if (out_mode == DSM_UNDISTORT_NONE) {
+    if (w_out != w_in || h_out != h_in) return fail("dsm_pinhole_undistort_map: output mode none requires the input size");
+    K_out[0] = cam.fx, K_out[1] = cam.fy, K_out[2] = cam.cx, K_out[3] = cam.cy;
+    *passthrough = 1;
+    return DSM_OK;
+  }
+  if (!remap_x || !remap_y) return fail("dsm_pinhole_undistort_map: remap tables missing");
+  float K[4];
+  if (out_mode == DSM_UNDISTORT_CROP) {
+    if (!optimal_k_crop(cam, w_in, h_in, w_out, h_out, K))
+      return fail("dsm_pinhole_undistort_map: makeOptimalK_crop did not converge in 500 iterations");
+  } else { // outputCalibration (float) relative to the output size; - 0.5 in double, read back as float: one rounding
+    K[0] = out_calib[0] * w_out;
+    K[1] = out_calib[1] * h_out;
+    K[2] = out_calib[2] * w_out - 0.5f;
+    K[3] = out_calib[3] * h_out - 0.5f;
+  }
+  for (int k = 0; k < 4; k++) K_out[k] = K[k];
+  const float wm1 = (float)(w_in - 1), hm1 = (float)(h_in - 1);
+  for (int y = 0; y < h_out; y++)
+    for (int x = 0; x < w_out; x++) {
+      float ix, iy;
+      cam.distort(K[0], K[1], K[2], K[3], (float)x, (float)y, ix, iy);
+      // U5: nudge exact borders inwards -- with upstream's slip: the iy == hOrg-1 branch assigns ix
+      if (ix == 0) ix = (float)0.001;
+      if (iy == 0) iy = (float)0.001;
+      if (ix == wm1) ix = (float)(w_in - 1.001);
+      if (iy == hm1) ix = (float)(h_in - 1.001);
+      // U6: strictly inside -- with upstream's slip: iy is compared against wOrg-1.  D1 (deviation): and the whole 2x2
+      // bilinear footprint inside the source, which the slip alone does not guarantee
+      const bool in = ix > 0 && iy > 0 && ix < wm1 && iy < wm1 && iy < hm1;
+      remap_x[x + y * w_out] = in ? ix : -1.f;
+      remap_y[x + y * w_out] = in ? iy : -1.f;
+    }
+  return DSM_OK;
+}
+
+} // extern "C"

@@ -2699,5 +2699,84 @@ void launch_pyramid_batched(hipStream_t s, int w, int h, int nlevels, const PyrJ
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// dsm_upload_images_undistorted: UPSTREAM-DSO Undistort::undistort<unsigned char>(img, 1, 0, 1.0f) (main.cpp:246-256) fused
+// with makeImages' level 0 -> 1.  blockIdx.y = image; every thread produces one 2x2 quad of level 0 and, from those four
+// values, its level-1 texel (0.25 ((a + b) + c) + d) as pyr_level_body forms it.  The 2x2 taps come from the staged camera
+// bytes (neighbouring outputs share them: L2 / MALL); the remap entries are read as 8-byte (x, y) pairs.  dsm_undistorter_create
+// checked every entry: x < 0, or the whole footprint inside the w_in x h_in source.
+// ------------------------------------------------------------------------------------------
+// PhotometricUndistorter::processFrame: G[byte] (setting_photometricCalibration >= 1) else factor * byte with factor 1;
+// then times vignetteMapInv (== 2)
+template <bool HAS_G, bool HAS_VIG>
+__device__ __forceinline__ float photometric(const unsigned char *__restrict__ raw, const float *__restrict__ Gs,
+                                             const float *__restrict__ vig, int i) {
+  float p = HAS_G ? Gs[raw[i]] : (float)raw[i];
+  if (HAS_VIG) p *= vig[i];
+  return p;
+}
+template <bool HAS_G, bool HAS_VIG, bool REMAP>
+__device__ __forceinline__ float undistort_px(const UndistortTables &u, const unsigned char *__restrict__ raw, const float *__restrict__ Gs,
+                                              int idx) {
+  if (!REMAP) return photometric<HAS_G, HAS_VIG>(raw, Gs, u.vig, idx); // passthrough: w_out == w_in
+  const float2 r = u.remap[idx];
+  if (r.x < 0) return 0.f;
+  const int xi = (int)r.x, yi = (int)r.y;
+  const float ax = r.x - xi, ay = r.y - yi, axy = ax * ay;
+  const int b = xi + yi * u.w_in;
+  const float s00 = photometric<HAS_G, HAS_VIG>(raw, Gs, u.vig, b), s10 = photometric<HAS_G, HAS_VIG>(raw, Gs, u.vig, b + 1);
+  const float s01 = photometric<HAS_G, HAS_VIG>(raw, Gs, u.vig, b + u.w_in), s11 = photometric<HAS_G, HAS_VIG>(raw, Gs, u.vig, b + 1 + u.w_in);
+  return axy * s11 + (ay - axy) * s01 + (ax - axy) * s10 + (1 - ax - ay + axy) * s00;
+}
+template <bool HAS_G, bool HAS_VIG, bool REMAP>
+__global__ __launch_bounds__(256) void undistort_pyr_kernel(UndistortTables u, int nlevels, const PyrJob *__restrict__ jobs) {
+  __shared__ float Gs[256];
+  if (HAS_G) {
+    Gs[threadIdx.x] = u.G[threadIdx.x]; // blockDim.x == 256
+    __syncthreads();
+  }
+  const PyrJob &j = jobs[blockIdx.y];
+  const unsigned char *raw = (const unsigned char *)j.raw;
+  float *out0 = j.img[0], *out1 = nlevels > 1 ? j.img[1] : nullptr;
+  const int w = u.w_out, h = u.h_out, wq = (w + 1) >> 1, hq = (h + 1) >> 1, wn = w >> 1, hn = h >> 1;
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < wq * hq; q += gridDim.x * blockDim.x) {
+    const int qx = q % wq, qy = q / wq, x = 2 * qx, y = 2 * qy, i = x + y * w;
+    const bool right = x + 1 < w, below = y + 1 < h;
+    const float a = undistort_px<HAS_G, HAS_VIG, REMAP>(u, raw, Gs, i);
+    const float b = right ? undistort_px<HAS_G, HAS_VIG, REMAP>(u, raw, Gs, i + 1) : 0.f;
+    const float c = below ? undistort_px<HAS_G, HAS_VIG, REMAP>(u, raw, Gs, i + w) : 0.f;
+    const float d = right && below ? undistort_px<HAS_G, HAS_VIG, REMAP>(u, raw, Gs, i + w + 1) : 0.f;
+    out0[i] = a;
+    if (right) out0[i + 1] = b;
+    if (below) out0[i + w] = c;
+    if (right && below) out0[i + w + 1] = d;
+    if (out1 && qx < wn && qy < hn) out1[qx + qy * wn] = 0.25f * (a + b + c + d);
+  }
+}
+template <bool HAS_G, bool HAS_VIG>
+static void launch_undistort_l0(hipStream_t s, const UndistortTables &u, int nlevels, const PyrJob *d_jobs, const dim3 &grid) {
+  if (u.remap)
+    hipLaunchKernelGGL((undistort_pyr_kernel<HAS_G, HAS_VIG, true>), grid, dim3(256), 0, s, u, nlevels, d_jobs);
+  else
+    hipLaunchKernelGGL((undistort_pyr_kernel<HAS_G, HAS_VIG, false>), grid, dim3(256), 0, s, u, nlevels, d_jobs);
+}
+void launch_undistort_pyramid_batched(hipStream_t s, const UndistortTables &u, int nlevels, const PyrJob *d_jobs, int njobs) {
+  const dim3 grid0(grid_for(((u.w_out + 1) >> 1) * ((u.h_out + 1) >> 1)), njobs);
+  if (u.G && u.vig)
+    launch_undistort_l0<true, true>(s, u, nlevels, d_jobs, grid0);
+  else if (u.G)
+    launch_undistort_l0<true, false>(s, u, nlevels, d_jobs, grid0);
+  else if (u.vig)
+    launch_undistort_l0<false, true>(s, u, nlevels, d_jobs, grid0);
+  else
+    launch_undistort_l0<false, false>(s, u, nlevels, d_jobs, grid0);
+  // levels >= 1: launch_pyramid_batched's launches l = 1 .. nlevels - 2
+  for (int l = 1; l + 1 < nlevels; l++) {
+    const int wl = u.w_out >> l, hl = u.h_out >> l;
+    const dim3 grid(grid_for((wl >> 1) * (hl >> 1)), njobs);
+    hipLaunchKernelGGL(pyr_level_batched_kernel<false>, grid, dim3(256), 0, s, l, nlevels, wl, hl, d_jobs);
+  }
+}
+
 } // namespace dsm
 

@@ -176,6 +176,37 @@ class Context:
         if asynchronous:
             self._pending_images = keep  # alive until upload_wait
 
+    def upload_images_undistorted(self, und, trackers, slots, images, exposures=None, form="sync"):
+        """dsm_upload_images_undistorted: hand over RAW uint8 camera images (und.original_size, all of one row pitch) per
+        (tracker, slot); level 0 is their undistortion (Undistort::undistort, main.cpp:246-256).  form: "sync" (as
+        upload_images), "async" (as upload_images(asynchronous=True): slots 2 / 3 + advance_frames, upload_wait) or
+        "enqueue" (stream-ordered, front slots only; the images must stay untouched until upload_wait)."""
+        forms = {"sync": 0, "async": 1, "enqueue": 2}
+        if form not in forms:
+            raise ValueError(f"upload_images_undistorted: form is one of {sorted(forms)}")
+        n = len(trackers)
+        if n == 0:
+            return
+        w_in, h_in = und.original_size
+        keep, pitch = [], None
+        for im in images:
+            if im.dtype != np.uint8 or im.shape != (h_in, w_in):
+                raise ValueError("upload_images_undistorted: uint8 images of the undistorter's input size")
+            if im.strides[1] != 1 or im.strides[0] < w_in:
+                im = np.ascontiguousarray(im)
+            if pitch is None:
+                pitch = im.strides[0]
+            elif im.strides[0] != pitch:
+                raise ValueError("upload_images_undistorted: images of one call share one row pitch")
+            keep.append(im)
+        hs = (C.c_void_p * n)(*[t.h for t in trackers])
+        ps = (C.c_void_p * n)(*[im.ctypes.data for im in keep])
+        sl = np.ascontiguousarray(slots, np.int32)
+        ex = np.ones(n, np.float32) if exposures is None else np.ascontiguousarray(exposures, np.float32)
+        check(self.L.dsm_upload_images_undistorted(self.h, und.h, n, hs, sl.ctypes.data_as(c_int_p), ps, _fp(ex), pitch, forms[form]))
+        if form != "sync":
+            self._pending_images = keep  # alive until upload_wait
+
     def upload_wait(self):
         check(self.L.dsm_upload_wait(self.h))
         self._pending_images = None
@@ -212,6 +243,104 @@ class Context:
         err = np.zeros(n, np.float32)
         check(self.L.dsm_optimize_scale_batch(self.h, n, hs, _fp(sc), coarsest, _fp(err)))
         return err, sc
+
+
+UNDISTORT_MODES = {"crop": 0, "none": 1, "explicit": 2}
+
+
+def read_camera_file(path):
+    """UPSTREAM-DSO's four-line camera file (cams/*/camera*.txt): `Pinhole fx fy cx cy 0` / `W H` / `crop | none |
+    fx fy cx cy 0` / `W' H'`.  Returns dict(calib=(fx, fy, cx, cy), size_in=(W, H), mode="crop"|"none"|"explicit",
+    out_calib=(4 floats) or None, size_out=(W', H')).  Other camera models are not built here (a caller's table covers
+    them: Undistorter(..., remap=...))."""
+    with open(path) as f:
+        lines = [ln.strip() for ln in f.read().splitlines()]
+    while lines and not lines[-1]:
+        lines.pop()
+    if len(lines) < 4:
+        raise ValueError(f"{path}: a camera file has four lines")
+    tok = lines[0].split()
+    if len(tok) < 5 or tok[0] != "Pinhole":
+        raise ValueError(f"{path}: line 1 is not `Pinhole fx fy cx cy 0`")
+    calib = tuple(float(v) for v in tok[1:5])
+    size_in = tuple(int(v) for v in lines[1].split()[:2])
+    third = lines[2].split()
+    if third == ["crop"]:
+        mode, out_calib = "crop", None
+    elif third == ["none"]:
+        mode, out_calib = "none", None
+    elif len(third) == 5:
+        mode, out_calib = "explicit", tuple(float(np.float32(v)) for v in third[:4])  # (read with %f upstream)
+    else:
+        raise ValueError(f"{path}: line 3 is `crop`, `none` or five numbers (`full` is not supported)")
+    size_out = tuple(int(v) for v in lines[3].split()[:2])
+    return dict(calib=calib, size_in=size_in, mode=mode, out_calib=out_calib, size_out=size_out)
+
+
+def pinhole_undistort_map(calib, size_in, mode="crop", size_out=None, out_calib=None):
+    """dsm_pinhole_undistort_map (host code): (K_out (fx, fy, cx, cy) float32[4], passthrough, remap_x, remap_y) with the
+    remap tables float32[h_out, w_out] (source coordinates, -1 = outside) or None for passthrough"""
+    L = _lib.load()
+    w_in, h_in = size_in
+    w_out, h_out = size_in if size_out is None else size_out
+    cal = np.ascontiguousarray(calib, np.float64)
+    oc = None if out_calib is None else np.ascontiguousarray(out_calib, np.float32)
+    K = np.zeros(4, np.float32)
+    pt = C.c_int()
+    rx = np.empty((h_out, w_out), np.float32)
+    ry = np.empty((h_out, w_out), np.float32)
+    check(L.dsm_pinhole_undistort_map(_dp(cal), w_in, h_in, UNDISTORT_MODES[mode], None if oc is None else _fp(oc), w_out, h_out,
+                                      _fp(K), C.byref(pt), _fp(rx), _fp(ry)))
+    if pt.value:
+        return K, True, None, None
+    return K, False, rx, ry
+
+
+class Undistorter:
+    """dsm_undistorter: one camera's undistortion on the device (UPSTREAM-DSO Undistort + PhotometricUndistorter) for
+    Context.upload_images_undistorted.  remap_x / remap_y: float32[h_out, w_out] source coordinates (-1 = outside), None
+    for passthrough; G: 256 floats (the rescaled response), vignette_inv: float32[h_in, w_in]; each optional."""
+
+    def __init__(self, ctx, size_in, size_out, remap_x=None, remap_y=None, G=None, vignette_inv=None, K=None):
+        self.L = _lib.load()
+        self.ctx = ctx
+        (w_in, h_in), (w_out, h_out) = size_in, size_out
+        arrs = []
+        for a, n in ((remap_x, w_out * h_out), (remap_y, w_out * h_out), (G, 256), (vignette_inv, w_in * h_in)):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.float32).reshape(-1)
+            if a.size != n:
+                raise ValueError("Undistorter: table of the wrong size")
+            arrs.append(a)
+        h = C.c_void_p()
+        check(self.L.dsm_undistorter_create(ctx.h, w_in, h_in, w_out, h_out, *[None if a is None else _fp(a) for a in arrs], C.byref(h)))
+        self.h = h
+        self.original_size = (w_in, h_in)
+        self.size = (w_out, h_out)
+        self.K = None if K is None else np.asarray(K, np.float32)
+
+    @classmethod
+    def pinhole(cls, ctx, camera_file=None, calib=None, size_in=None, mode="crop", size_out=None, out_calib=None, G=None,
+                vignette_inv=None):
+        """From a camera file (size_out overrides its fourth line, as benchmarkSetting_width / height do: main.cpp:110-111)
+        or from the values of one"""
+        if camera_file is not None:
+            cf = read_camera_file(camera_file)
+            calib, size_in, mode, out_calib = cf["calib"], cf["size_in"], cf["mode"], cf["out_calib"]
+            size_out = size_out or cf["size_out"]
+        K, _, rx, ry = pinhole_undistort_map(calib, size_in, mode, size_out, out_calib)
+        return cls(ctx, size_in, size_out or size_in, rx, ry, G, vignette_inv, K)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):  # (destroy undistorters before their context)
+                self.L.dsm_undistorter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
 
 
 class Stream:

@@ -282,9 +282,10 @@ int dsm_tracker_upload_image(dsm_tracker *t, int slot, const float *image, float
  * launches per group instead of five per image.  images[i]: level-0 pixels of trackers[i]'s geometry (all trackers of one
  * call share w, h, levels), DSM_PIXEL_F32 (the undistorted float image FrontEnd.cpp:605,680 consume) or DSM_PIXEL_U8
  * (camera bytes, main.cpp:216-217 "mono8"; converted exactly on the device -- valid when no photometric calibration is
- * applied, i.e. float(pixel) is what the reference's undistorter hands on).  row_pitch_bytes: distance between image
- * rows in the caller's buffers, 0 = tight; with a pointer to the crop origin this applies the calibration file's crop
- * (cams/kitti/0_2/camera0.txt:2-4).  Returns when every copy has completed. */
+ * applied, i.e. float(pixel) is what the reference's undistorter hands on; otherwise see dsm_upload_images_undistorted).
+ * row_pitch_bytes: distance between image rows in the caller's buffers, 0 = tight; with a pointer to the crop origin this
+ * approximates the calibration file's crop (cams/kitti/0_2/camera0.txt:2-4) by a window -- upstream's crop rescales the
+ * whole valid image instead.  Returns when every copy has completed. */
 enum { DSM_PIXEL_F32 = 0, DSM_PIXEL_U8 = 1 };
 int dsm_upload_images(dsm_context *ctx, int n, dsm_tracker *const *trackers, const int *slots, const void *const *images,
                       const float *ab_exposures, int pixel_type, size_t row_pitch_bytes);
@@ -308,6 +309,44 @@ int dsm_upload_wait(dsm_context *ctx);
 int dsm_upload_images_enqueue(dsm_context *ctx, int n, dsm_tracker *const *trackers, const int *slots, const void *const *images,
                               const float *ab_exposures, int pixel_type, size_t row_pitch_bytes);
 int dsm_frames_advance(dsm_context *ctx, int n, dsm_tracker *const *trackers, const int *slots);
+
+/* ---- undistortion and photometric calibration at the hand-over (main.cpp:246-256) ---------------------------------------
+ * The reference undistorts both camera images of every frame on the host before addActiveStereoFrame
+ * (undistorterN_->undistort<unsigned char>(&img, 1, 0, 1.0f), UPSTREAM-DSO Undistort::undistort): photometric correction
+ * (response G[256], vignette) followed by a bilinear remap to the output camera.  The calls below do the same on the device
+ * from the raw mono8 camera bytes.  DESIGN.md section 9 lists every upstream quirk that is kept and the one deviation. */
+enum { DSM_UNDISTORT_CROP = 0, DSM_UNDISTORT_NONE = 1, DSM_UNDISTORT_EXPLICIT = 2 };
+/* The remap of UPSTREAM-DSO's Pinhole model (Undistort::readFromFile + makeOptimalK_crop + UndistortPinhole::distortCoordinates),
+ * host code.  calib = fx fy cx cy of the camera file's first line, as read there (double; relative when cx < 1 && cy < 1);
+ * out_mode: CROP (line 3 "crop"), NONE ("none": w_out, h_out must equal w_in, h_in) or EXPLICIT (line 3 = "fx fy cx cy 0",
+ * relative to the output size, out_calib = its first four numbers; ignored otherwise).  Writes the output camera K_out
+ * (fx, fy, cx, cy; what Undistort::getK() returns, i.e. what makeK gets), *passthrough (1 for NONE) and, unless
+ * passthrough, remap_x / remap_y (w_out * h_out source coordinates each, -1 = outside).  All float32, fixed evaluation
+ * order.  DSM_ERR_INVALID when makeOptimalK_crop does not converge in 500 iterations (upstream aborts the process). */
+int dsm_pinhole_undistort_map(const double calib[4], int w_in, int h_in, int out_mode, const float out_calib[4], int w_out, int h_out,
+                              float K_out[4], int *passthrough, float *remap_x, float *remap_y);
+/* Device copy of one camera's undistortion (UPSTREAM-DSO Undistort + PhotometricUndistorter): remap_x / remap_y as
+ * dsm_pinhole_undistort_map writes them (or any caller-made table, e.g. of another camera model); both NULL =
+ * passthrough (w_out, h_out must equal w_in, h_in).  G: 256 floats, the response already rescaled as
+ * PhotometricUndistorter keeps it; vignette_inv: w_in * h_in floats, the inverse vignette.  Each may be NULL
+ * (setting_photometricCalibration 0: neither, 1: G only, 2: both).  The tables are copied once.  Every table entry must
+ * be outside (x < 0) or have its whole bilinear 2x2 footprint inside the source image; anything else returns
+ * DSM_ERR_INVALID naming the first such entry, so the device never reads outside the staged camera image. */
+typedef struct dsm_undistorter dsm_undistorter;
+int dsm_undistorter_create(dsm_context *ctx, int w_in, int h_in, int w_out, int h_out, const float *remap_x, const float *remap_y,
+                           const float *G, const float *vignette_inv, dsm_undistorter **out);
+int dsm_undistorter_destroy(dsm_undistorter *u);
+/* The batched hand-over (dsm_upload_images) from RAW camera bytes: images[i] = w_in x h_in mono8 pixels (row_pitch_bytes
+ * between rows, 0 = tight), pinned or pageable.  Every tracker must have the undistorter's output size.  Level 0 is, bit
+ * for bit, what Undistort::undistort<unsigned char>(img, 1, 0, 1.0f) hands on (photometric value G[byte] or float(byte),
+ * times vignette_inv; bilinear remap in upstream's order; 0 outside); the other levels follow as makeImages builds them.
+ * form: DSM_UPLOAD_SYNC / _ASYNC / _ENQUEUE, with exactly the semantics of dsm_upload_images / dsm_upload_images_async
+ * (DSM_SLOT_NEXT_* + dsm_frames_advance) / dsm_upload_images_enqueue.  ab_exposures as there: the reference passes
+ * exposure 1. */
+enum { DSM_UPLOAD_SYNC = 0, DSM_UPLOAD_ASYNC = 1, DSM_UPLOAD_ENQUEUE = 2 };
+int dsm_upload_images_undistorted(dsm_context *ctx, const dsm_undistorter *u, int n, dsm_tracker *const *trackers, const int *slots,
+                                  const void *const *images_u8, const float *ab_exposures, size_t row_pitch_bytes, int form);
+
 /* pinned host memory for images handed to dsm_tracker_upload_image (straight DMA instead of a staged copy); no reference
  * counterpart -- the reference keeps its images in ordinary host memory */
 int dsm_host_alloc(size_t bytes, void **out);
