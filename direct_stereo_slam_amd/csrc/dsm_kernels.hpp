@@ -235,5 +235,24 @@ void launch_ringkey_knn(hipStream_t s, const float *keysT, int64_t cap, int64_t 
 int ringkey_num_slices(int64_t n_local, int nq, int dim);
 void launch_ringkey_insert(hipStream_t s, float *keysT, int64_t cap, int64_t pos, int dim,
                            const float *d_key, int nkeys);
+// many indexes in one call (dsm_ringdb_query_then_enqueue_many, dsm_loop_detect_batch_many): query q scans its own index
+struct RingKeyScanDesc {
+  const float *keysT; // the index's dimension-major planes
+  long long cap, n_local;
+  float thres;
+  int n_slices; // ringkey_many_slices(n_local)
+};
+// matured key i of the call goes to slot pos of its index's planes
+struct RingKeyInsertDesc {
+  float *keysT;
+  long long cap, pos;
+};
+int ringkey_many_slices(int64_t n_local);
+// one scan over all nq queries (each over its own index, d_queries nq x dim) into d_scratch (n_slices = the largest count of the call),
+// then ringkey_merge_kernel into d_packed_out (nq x k).  four: dim 20 and every capacity a multiple of four (16-byte plane loads)
+void launch_ringkey_knn_many(hipStream_t s, const RingKeyScanDesc *d_descs, int dim, int k, bool four, const float *d_queries, int nq,
+                             int n_slices, unsigned long long *d_scratch, unsigned long long *d_packed_out);
+// one launch appending nkeys keys (nkeys x dim) to their indexes
+void launch_ringkey_insert_many(hipStream_t s, const RingKeyInsertDesc *d_descs, int dim, const float *d_keys, int nkeys);
 
 } // namespace dsm

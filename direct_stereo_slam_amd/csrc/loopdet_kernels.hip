@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "dsm_internal.hpp"
@@ -381,13 +382,15 @@ struct LoopPlan {
   std::vector<JobDev> hj;
   // offsets (bytes) into the input region (pinned + device), the work region (device only), the output region (device + pinned)
   std::vector<size_t> in_xyz, in_ptkf, in_ids, out_small, out_sig_idx, out_sig_val, out_sel, out_sph;
-  size_t in_tab = 0, in_bytes = 0, work_bytes = 0, out_bytes = 0, out_keys = 0, out_cand = 0;
+  size_t in_tab = 0, in_extra = 0, in_bytes = 0, work_bytes = 0, out_bytes = 0, out_keys = 0, out_cand = 0;
   bool any_sc = false;
 };
 // per job "small" outputs: [n_out, n_sig, pad, pad][tfm 16 doubles] -- ring keys of all jobs are one contiguous array (out_keys)
 constexpr size_t kSmallBytes = 16 + 16 * sizeof(double);
 
-int grow(dsm_context *ctx, size_t dev_bytes, size_t pin_bytes) {
+} // namespace
+
+int dsm::loop_arena_grow(dsm_context *ctx, size_t dev_bytes, size_t pin_bytes) {
   if (dev_bytes > ctx->loop_dev_bytes) {
     if (ctx->loop_dev) DSM_HIP(hipFree(ctx->loop_dev));
     ctx->loop_dev = nullptr, ctx->loop_dev_bytes = 0;
@@ -402,6 +405,8 @@ int grow(dsm_context *ctx, size_t dev_bytes, size_t pin_bytes) {
   }
   return DSM_OK;
 }
+
+namespace {
 
 int check_jobs(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double lidar_range, int num_s, int num_r, long long *cells_out) {
   if (!ctx || n_jobs < 1 || !jobs || !(lidar_range > 0) || num_s < 1 || num_r < 1 || num_s > kLdThreads || num_r > kLdThreads)
@@ -420,10 +425,18 @@ int check_jobs(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double li
   return DSM_OK;
 }
 
-// everything up to (and without) the read-back: inputs staged and copied, kernels enqueued.  extra_out_bytes: room at the end of the
-// output region for the caller's own device results (the ring-key search's packed candidates); *d_keys / *d_extra: where they live
-int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double lidar_range, int num_s, int num_r, size_t extra_out_bytes, LoopPlan &P,
-                 float **d_keys, void **d_extra) {
+// The caller's own parts of the arena, for the ring-key search that follows the descriptors: in_bytes staged through the page-locked
+// mirror with the jobs' tables (fill writes them there; one host->device copy for both), work_bytes on the device only, out_bytes at the
+// end of the output region (read back with the descriptors).  d_in / d_work / d_out: where they live on the device (set by loop_enqueue).
+struct LoopExtra {
+  size_t in_bytes = 0, work_bytes = 0, out_bytes = 0;
+  std::function<void(unsigned char *h_in)> fill;
+  unsigned char *d_in = nullptr, *d_work = nullptr, *d_out = nullptr;
+};
+
+// everything up to (and without) the read-back: inputs staged and copied, kernels enqueued; *d_keys: the ring keys on the device
+int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double lidar_range, int num_s, int num_r, LoopExtra &X, LoopPlan &P,
+                 float **d_keys) {
   long long cells = 0;
   int rc = check_jobs(ctx, n_jobs, jobs, lidar_range, num_s, num_r, &cells);
   if (rc) return rc;
@@ -460,6 +473,7 @@ int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double 
     }
   }
   P.in_tab = in.take(sizeof(JobDev) * (size_t)n_jobs);
+  P.in_extra = in.take(X.in_bytes);
   const size_t in_small_bytes = in.used; // [keyframe tables | job table], then the clouds: clouds read directly from page-locked caller
                                          // memory (loop_gather_kernel) do not travel through the mirror at all
   for (int j = 0; j < n_jobs; j++) {
@@ -467,10 +481,11 @@ int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double 
     P.in_ptkf[j] = in.take(sizeof(int) * (size_t)jobs[j].n_pts);
   }
   P.out_keys = out.take(sizeof(float) * (size_t)num_r * n_jobs);
-  P.out_cand = out.take(extra_out_bytes);
+  P.out_cand = out.take(X.out_bytes);
+  const size_t w_extra = work.take(X.work_bytes);
   P.in_bytes = in.used, P.work_bytes = work.used, P.out_bytes = out.used;
   // device arena: [in | work | out]; pinned mirror: [in | out]
-  rc = grow(ctx, P.in_bytes + P.work_bytes + P.out_bytes, P.in_bytes + P.out_bytes);
+  rc = loop_arena_grow(ctx, P.in_bytes + P.work_bytes + P.out_bytes, P.in_bytes + P.out_bytes);
   if (rc) return rc;
   unsigned char *d_in = (unsigned char *)ctx->loop_dev, *d_work = d_in + P.in_bytes, *d_out = d_work + P.work_bytes;
   unsigned char *h_in = (unsigned char *)ctx->loop_pin;
@@ -520,6 +535,7 @@ int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double 
     D.sig_idx = (int *)(d_out + P.out_sig_idx[j]), D.sig_val = (double *)(d_out + P.out_sig_val[j]);
   }
   memcpy(h_in + P.in_tab, P.hj.data(), sizeof(JobDev) * (size_t)n_jobs);
+  if (X.fill) X.fill(h_in + P.in_extra);
   DSM_HIP(hipMemcpyAsync(d_in, h_in, any_staged ? P.in_bytes : in_small_bytes, hipMemcpyHostToDevice, st));
   JobDev *dj = (JobDev *)(d_in + P.in_tab);
   if (any_direct) hipLaunchKernelGGL(loop_gather_kernel, dim3(64, n_jobs), dim3(kLdThreads), 0, st, dj);
@@ -544,7 +560,7 @@ int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double 
   }
   DSM_HIP(hipGetLastError());
   if (d_keys) *d_keys = (float *)(d_out + P.out_keys);
-  if (d_extra) *d_extra = d_out + P.out_cand;
+  X.d_in = d_in + P.in_extra, X.d_work = d_work + w_extra, X.d_out = d_out + P.out_cand;
   return DSM_OK;
 }
 
@@ -589,7 +605,8 @@ extern "C" {
 
 int dsm_loop_descriptors_batch(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double lidar_range, int num_s, int num_r) {
   LoopPlan P;
-  int rc = loop_enqueue(ctx, n_jobs, jobs, lidar_range, num_s, num_r, 0, P, nullptr, nullptr);
+  LoopExtra X;
+  int rc = loop_enqueue(ctx, n_jobs, jobs, lidar_range, num_s, num_r, X, P, nullptr);
   if (rc) return rc;
   return loop_finish(ctx, jobs, P, nullptr);
 }
@@ -613,13 +630,14 @@ int dsm_loop_detect_batch(dsm_context *ctx, dsm_ringdb *db, int n_jobs, const ds
   for (int j = 0; jobs && j < n_jobs; j++)
     if (!jobs[j].ringkey) return invalid("dsm_loop_detect_batch: every job needs its descriptor outputs");
   LoopPlan P;
+  LoopExtra X;
+  X.out_bytes = sizeof(unsigned long long) * (size_t)n_jobs * db->k;
   float *d_keys = nullptr;
-  void *d_cand = nullptr;
   const int k = db->k;
-  int rc = loop_enqueue(ctx, n_jobs, jobs, lidar_range, num_s, num_r, sizeof(unsigned long long) * (size_t)n_jobs * k, P, &d_keys, &d_cand);
+  int rc = loop_enqueue(ctx, n_jobs, jobs, lidar_range, num_s, num_r, X, P, &d_keys);
   if (rc) return rc;
   const bool search = db->size_global > k; // `ringkeys->size() > FLANN_NN`, search_place.h:29 (the index as it stands before the batch)
-  if (search && (rc = dsm::ringdb_knn_device(db, d_keys, n_jobs, (unsigned long long *)d_cand))) return rc;
+  if (search && (rc = dsm::ringdb_knn_device(db, d_keys, n_jobs, (unsigned long long *)X.d_out))) return rc;
   const void *h_cand_v = nullptr;
   rc = loop_finish(ctx, jobs, P, &h_cand_v);
   if (rc) return rc;
@@ -637,57 +655,48 @@ int dsm_loop_detect_batch(dsm_context *ctx, dsm_ringdb *db, int n_jobs, const ds
   std::vector<float> matured; // keys that entered the index during this batch, in order
   const long long base = db->size_global;
   for (int j = 0; j < n_jobs; j++) {
-    const float *key = jobs[j].ringkey;
-    unsigned long long best[4] = {~0ull, ~0ull, ~0ull, ~0ull};
-    const long long size_now = base + (long long)(matured.size() / db->dim);
-    int nb = 0;
-    if (size_now > k) {
-      if (search)
-        for (int i = 0; i < k; i++)
-          if (h_cand[(size_t)j * k + i] != (unsigned long long)DSM_RINGDB_NO_CANDIDATE) best[nb++] = h_cand[(size_t)j * k + i];
-      for (size_t m = 0; m < matured.size() / db->dim; m++) { // flann::L2, as the kernels: groups of four, then the tail
-        const float *kp = matured.data() + m * db->dim;
-        float result = 0.f;
-        int d = 0;
-        for (; d + 3 < db->dim; d += 4) {
-          const float d0 = key[d] - kp[d], d1 = key[d + 1] - kp[d + 1], d2 = key[d + 2] - kp[d + 2], d3 = key[d + 3] - kp[d + 3];
-          result += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-        }
-        for (; d < db->dim; d++) {
-          const float d0 = key[d] - kp[d];
-          result += d0 * d0;
-        }
-        if (!(result < db->thres)) continue;
-        unsigned bits;
-        memcpy(&bits, &result, 4);
-        const unsigned long long c = ((unsigned long long)bits << 32) | (unsigned long long)(base + (long long)m);
-        // insert into the ascending list of at most k
-        int pos = nb < k ? nb : k;
-        for (int i = 0; i < nb && i < k; i++)
-          if (c < best[i]) {
-            pos = i;
-            break;
-          }
-        if (pos < k) {
-          for (int i = (nb < k ? nb : k - 1); i > pos; i--) best[i] = best[i - 1];
-          best[pos] = c;
-          if (nb < k) nb++;
-        }
-      }
-    }
-    int nc = 0;
-    for (int i = 0; i < nb && i < k; i++) {
-      const int idx = (int)(best[i] & 0xFFFFFFFFull);
-      if (idx > 0) cand_out[(size_t)j * k + nc++] = idx - 1; // :34-38
-    }
-    ncand_out[j] = nc;
-    // the enqueue of search_ringkey (:41-56): the slot's old key matures into the index
-    float *slot = db->queue.data() + (size_t)(db->queue_idx % db->margin) * db->dim;
-    if (db->queue_idx >= db->margin) matured.insert(matured.end(), slot, slot + db->dim);
-    memcpy(slot, key, sizeof(float) * db->dim);
-    db->queue_idx++;
+    ncand_out[j] = dsm::ringdb_finish_query(db, jobs[j].ringkey, h_cand + (size_t)j * k, matured.data(), (long long)(matured.size() / db->dim), base,
+                                            cand_out + (size_t)j * k);
+    dsm::ringdb_queue_push(db, jobs[j].ringkey, &matured); // the enqueue of search_ringkey (:41-56): the slot's old key matures into the index
   }
   if (!matured.empty()) return dsm_ringdb_add_points(db, matured.data(), (int64_t)(matured.size() / db->dim));
+  return DSM_OK;
+}
+
+// dsm_loop_detect_batch with one index PER JOB (one sequence's LoopHandler each, search_place.h:25-57 against its own flann index):
+// equal to, job after job, dsm_loop_descriptors_batch of that job followed by dsm_ringdb_query_then_enqueue(dbs[j], its ring key).  The
+// descriptor kernels as in dsm_loop_detect_batch, then one scan launch over every job's own index, one merge, one insert of the keys that
+// mature during the call (ring keys, descriptors of the scan and matured keys travel in the one host->device copy), the one read-back
+// and the one synchronisation; the host merges each job's candidates with the keys its index matured earlier in the call.
+int dsm_loop_detect_batch_many(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, dsm_ringdb *const *dbs, double lidar_range, int num_s,
+                               int num_r, int *cand_out, int *ncand_out) {
+  if (!ctx || n_jobs < 1 || !jobs || !dbs || !cand_out || !ncand_out) return invalid("dsm_loop_detect_batch_many: bad argument");
+  for (int j = 0; j < n_jobs; j++)
+    if (!jobs[j].ringkey) return invalid("dsm_loop_detect_batch_many: every job needs its descriptor outputs");
+  long long cells = 0;
+  int rc = check_jobs(ctx, n_jobs, jobs, lidar_range, num_s, num_r, &cells); // (before any index grows)
+  if (rc) return rc;
+  dsm::RingManyPlan R;
+  rc = dsm::ringdb_many_prepare(ctx, n_jobs, dbs, num_r, "dsm_loop_detect_batch_many", R);
+  if (rc) return rc;
+  LoopPlan P;
+  LoopExtra X;
+  X.in_bytes = R.staged_bytes;
+  X.work_bytes = sizeof(unsigned long long) * dsm::ringdb_many_scratch_words(R);
+  X.out_bytes = sizeof(unsigned long long) * (size_t)n_jobs * R.k;
+  X.fill = [&R](unsigned char *h_in) { dsm::ringdb_many_stage(R, h_in); };
+  float *d_keys = nullptr;
+  rc = loop_enqueue(ctx, n_jobs, jobs, lidar_range, num_s, num_r, X, P, &d_keys);
+  if (rc) return rc;
+  rc = dsm::ringdb_many_launch(ctx->stream, R, X.d_in, d_keys, (unsigned long long *)X.d_work, (unsigned long long *)X.d_out);
+  if (rc) return rc;
+  const void *h_cand = nullptr;
+  // (an empty filtered cloud fails here, before any output or index changes: the inserted planes lie beyond every index's size)
+  rc = loop_finish(ctx, jobs, P, &h_cand);
+  if (rc) return rc;
+  std::vector<const float *> keys(n_jobs);
+  for (int j = 0; j < n_jobs; j++) keys[j] = jobs[j].ringkey;
+  dsm::ringdb_many_finish(R, dbs, keys.data(), (const unsigned long long *)h_cand, cand_out, ncand_out);
   return DSM_OK;
 }
 

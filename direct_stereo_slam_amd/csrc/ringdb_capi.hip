@@ -2,6 +2,7 @@
 // LoopHandler.cpp:35-39 and the function-static delay queue of search_ringkey
 // (search_place.h:41-56).  Host code keeps the queue and the ordinal bookkeeping; the scan runs
 // in ringkey_kernels.hip.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -98,6 +99,180 @@ static int rdb_knn_dev(dsm_ringdb *db, const float *d_queries, int nq, unsigned 
 
 namespace dsm {
 int ringdb_knn_device(dsm_ringdb *db, const float *d_queries, int nq, unsigned long long *d_out) { return rdb_knn_dev(db, d_queries, nq, d_out); }
+
+int ringdb_finish_query(const dsm_ringdb *db, const float *key, const unsigned long long *dev, const float *matured, long long n_matured,
+                        long long base, int *cand_out) {
+  const int k = db->k;
+  unsigned long long best[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+  int nb = 0;
+  if (base + n_matured > k) { // `ringkeys->size() > FLANN_NN`, search_place.h:29, with the index as this query sees it
+    if (dev)
+      for (int i = 0; i < k; i++)
+        if (dev[i] != (unsigned long long)DSM_RINGDB_NO_CANDIDATE) best[nb++] = dev[i];
+    for (long long m = 0; m < n_matured; m++) { // flann::L2, as the kernels: groups of four, then the tail
+      const float *kp = matured + m * db->dim;
+      float result = 0.f;
+      int d = 0;
+      for (; d + 3 < db->dim; d += 4) {
+        const float d0 = key[d] - kp[d], d1 = key[d + 1] - kp[d + 1], d2 = key[d + 2] - kp[d + 2], d3 = key[d + 3] - kp[d + 3];
+        result += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+      }
+      for (; d < db->dim; d++) {
+        const float d0 = key[d] - kp[d];
+        result += d0 * d0;
+      }
+      if (!(result < db->thres)) continue;
+      unsigned bits;
+      memcpy(&bits, &result, 4);
+      const unsigned long long c = ((unsigned long long)bits << 32) | (unsigned long long)(base + m);
+      // insert into the ascending list of at most k
+      int pos = nb < k ? nb : k;
+      for (int i = 0; i < nb && i < k; i++)
+        if (c < best[i]) {
+          pos = i;
+          break;
+        }
+      if (pos < k) {
+        for (int i = (nb < k ? nb : k - 1); i > pos; i--) best[i] = best[i - 1];
+        best[pos] = c;
+        if (nb < k) nb++;
+      }
+    }
+  }
+  int nc = 0;
+  for (int i = 0; i < nb && i < k; i++) {
+    const int idx = (int)(best[i] & 0xFFFFFFFFull);
+    if (idx > 0) cand_out[nc++] = idx - 1; // :34-38
+  }
+  return nc;
+}
+
+void ringdb_queue_push(dsm_ringdb *db, const float *key, std::vector<float> *matured) {
+  float *slot = db->queue.data() + (size_t)(db->queue_idx % db->margin) * db->dim;
+  if (db->queue_idx >= db->margin && matured) matured->insert(matured->end(), slot, slot + db->dim);
+  memcpy(slot, key, sizeof(float) * db->dim);
+  db->queue_idx++;
+}
+
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int ringdb_many_prepare(dsm_context *ctx, int n, dsm_ringdb *const *dbs, int dim, const char *who, RingManyPlan &P) {
+  const std::string w(who);
+  if (n < 1 || !dbs) return invalid((w + ": bad argument").c_str());
+  for (int j = 0; j < n; j++)
+    if (!dbs[j]) return invalid((w + ": null index").c_str());
+  if (!ctx) ctx = dbs[0]->ctx;
+  if (dim < 0) dim = dbs[0]->dim;
+  const int k = dbs[0]->k;
+  for (int j = 0; j < n; j++) {
+    const dsm_ringdb *db = dbs[j];
+    if (db->ctx != ctx) return invalid((w + ": every index must belong to the call's context").c_str());
+    if (db->shard_count != 1) return invalid((w + ": unsharded indexes only (a sharded one searches through dsm_ringdb_query_then_enqueue)").c_str());
+    if (db->dim != dim) return invalid((w + ": every index must have the same key dimension (num_r in the loop form)").c_str());
+    if (db->k != k) return invalid((w + ": every index must have the same k").c_str());
+  }
+  P.n = n, P.dim = dim, P.k = k;
+  // the distinct indexes, in order of first appearance (many_slot is -1 between calls)
+  P.uniq.clear();
+  P.slot_of.resize(n);
+  for (int j = 0; j < n; j++) {
+    if (dbs[j]->many_slot < 0) {
+      dbs[j]->many_slot = (int)P.uniq.size();
+      P.uniq.push_back(dbs[j]);
+    }
+    P.slot_of[j] = dbs[j]->many_slot;
+  }
+  for (dsm_ringdb *db : P.uniq) db->many_slot = -1;
+  const int nu = (int)P.uniq.size();
+  std::vector<int> jobs(nu, 0);
+  P.mat_count.assign(nu, 0);
+  for (int j = 0; j < n; j++) {
+    const int u = P.slot_of[j];
+    if (P.uniq[u]->queue_idx + jobs[u] >= P.uniq[u]->margin) P.mat_count[u]++; // this enqueue moves a key out of the delay queue
+    jobs[u]++;
+  }
+  for (int u = 0; u < nu; u++) {
+    const dsm_ringdb *db = P.uniq[u];
+    if (jobs[u] > db->margin) return invalid((w + ": at most `margin` jobs per index and call").c_str());
+    if (db->size_global + P.mat_count[u] > (int64_t)INT32_MAX) return invalid((w + ": ring-key index full: global ordinals are limited to 2^31 - 1").c_str());
+  }
+  // every index that the matured keys outgrow grows now, before anything is enqueued (a failure leaves every index as it was)
+  DSM_HIP(hipSetDevice(ctx->device));
+  for (int u = 0; u < nu; u++) {
+    const int rc = rdb_reserve(P.uniq[u], P.uniq[u]->n_local + P.mat_count[u]);
+    if (rc) return rc;
+  }
+  P.mat_off.assign(nu, 0);
+  P.base.assign(nu, 0);
+  P.n_matured = 0;
+  for (int u = 0; u < nu; u++) {
+    P.mat_off[u] = P.n_matured;
+    P.n_matured += P.mat_count[u];
+    P.base[u] = P.uniq[u]->size_global;
+  }
+  P.matured.resize((size_t)P.n_matured * dim);
+  P.ins.resize(P.n_matured);
+  P.scan.resize(n);
+  std::fill(jobs.begin(), jobs.end(), 0);
+  std::vector<int> filled(nu, 0);
+  P.n_slices = 1;
+  P.four = dim == 20;
+  for (int j = 0; j < n; j++) {
+    const int u = P.slot_of[j];
+    dsm_ringdb *db = P.uniq[u];
+    const int64_t qi = db->queue_idx + jobs[u]++;
+    if (qi >= db->margin) { // the slot this enqueue overwrites holds the key of its start-of-call state (each slot is overwritten once)
+      const int row = P.mat_off[u] + filled[u];
+      memcpy(P.matured.data() + (size_t)row * dim, db->queue.data() + (size_t)(qi % db->margin) * dim, sizeof(float) * dim);
+      P.ins[row] = RingKeyInsertDesc{db->d_keysT, (long long)db->cap, (long long)(db->n_local + filled[u])};
+      filled[u]++;
+    }
+    RingKeyScanDesc &D = P.scan[j];
+    D.keysT = db->d_keysT, D.cap = db->cap, D.n_local = db->n_local, D.thres = db->thres, D.n_slices = ringkey_many_slices(db->n_local);
+    if (D.n_slices > P.n_slices) P.n_slices = D.n_slices;
+    if (db->cap % 4) P.four = false; // rdb_reserve keeps capacities at 1024 * 2^m: checked, not assumed
+  }
+  P.off_ins = align256(sizeof(RingKeyScanDesc) * (size_t)n);
+  P.off_keys = P.off_ins + align256(sizeof(RingKeyInsertDesc) * (size_t)P.n_matured);
+  P.staged_bytes = P.off_keys + sizeof(float) * P.matured.size();
+  return DSM_OK;
+}
+
+void ringdb_many_stage(const RingManyPlan &P, unsigned char *h_staged) {
+  memcpy(h_staged, P.scan.data(), sizeof(RingKeyScanDesc) * P.scan.size());
+  if (P.n_matured) {
+    memcpy(h_staged + P.off_ins, P.ins.data(), sizeof(RingKeyInsertDesc) * P.ins.size());
+    memcpy(h_staged + P.off_keys, P.matured.data(), sizeof(float) * P.matured.size());
+  }
+}
+
+size_t ringdb_many_scratch_words(const RingManyPlan &P) { return (size_t)P.n_slices * P.n * P.k; }
+
+int ringdb_many_launch(hipStream_t s, const RingManyPlan &P, const unsigned char *d_staged, const float *d_queries,
+                       unsigned long long *d_scratch, unsigned long long *d_packed) {
+  launch_ringkey_knn_many(s, (const RingKeyScanDesc *)d_staged, P.dim, P.k, P.four, d_queries, P.n, P.n_slices, d_scratch, d_packed);
+  if (P.n_matured) // behind the scan on the same stream: the scan sees every index as it stood at the start of the call
+    launch_ringkey_insert_many(s, (const RingKeyInsertDesc *)(d_staged + P.off_ins), P.dim, (const float *)(d_staged + P.off_keys), P.n_matured);
+  DSM_HIP(hipGetLastError());
+  return DSM_OK;
+}
+
+void ringdb_many_finish(const RingManyPlan &P, dsm_ringdb *const *dbs, const float *const *keys, const unsigned long long *h_packed,
+                        int *cand_out, int *ncand_out) {
+  std::vector<int> seen(P.uniq.size(), 0); // matured keys of each index so far
+  for (int j = 0; j < P.n; j++) {
+    const int u = P.slot_of[j];
+    dsm_ringdb *db = dbs[j];
+    ncand_out[j] = ringdb_finish_query(db, keys[j], h_packed + (size_t)j * P.k, P.matured.data() + (size_t)P.mat_off[u] * P.dim, seen[u],
+                                       P.base[u], cand_out + (size_t)j * P.k);
+    if (db->queue_idx >= db->margin) seen[u]++;
+    ringdb_queue_push(db, keys[j], nullptr);
+  }
+  for (size_t u = 0; u < P.uniq.size(); u++) { // their planes were written by the insert launch
+    P.uniq[u]->n_local += P.mat_count[u];
+    P.uniq[u]->size_global += P.mat_count[u];
+  }
+}
 } // namespace dsm
 extern "C" {
 int dsm_ringdb_destroy(dsm_ringdb *db);
@@ -260,6 +435,36 @@ int dsm_ringdb_query_then_enqueue(dsm_ringdb *db, const float *key, int *cand_ou
   }
   *ncand_out = nc;
   return dsm_ringdb_enqueue(db, key);
+}
+
+/* search_ringkey of n sequences in one call, each against its own index: one upload, one scan launch over all indexes, one merge, one
+ * insert of the keys that mature during the call, one read-back and one synchronisation */
+int dsm_ringdb_query_then_enqueue_many(int n, dsm_ringdb *const *dbs, const float *keys, int *cand_out, int *ncand_out) {
+  if (!keys || !cand_out || !ncand_out) return invalid("dsm_ringdb_query_then_enqueue_many: bad argument");
+  RingManyPlan P;
+  int rc = ringdb_many_prepare(nullptr, n, dbs, -1, "dsm_ringdb_query_then_enqueue_many", P);
+  if (rc) return rc;
+  dsm_context *ctx = P.uniq[0]->ctx;
+  hipStream_t st = ctx->stream;
+  // the context's loop-chain arena: device [queries | staged | scratch | candidates], page-locked mirror [queries | staged | candidates]
+  const size_t q_bytes = align256(sizeof(float) * (size_t)n * P.dim), in_bytes = q_bytes + align256(P.staged_bytes);
+  const size_t sc_bytes = align256(sizeof(unsigned long long) * ringdb_many_scratch_words(P)), pk_bytes = sizeof(unsigned long long) * (size_t)n * P.k;
+  rc = loop_arena_grow(ctx, in_bytes + sc_bytes + pk_bytes, in_bytes + pk_bytes);
+  if (rc) return rc;
+  unsigned char *d_in = (unsigned char *)ctx->loop_dev, *h_in = (unsigned char *)ctx->loop_pin;
+  unsigned long long *d_scratch = (unsigned long long *)(d_in + in_bytes), *d_packed = (unsigned long long *)(d_in + in_bytes + sc_bytes);
+  const unsigned long long *h_packed = (const unsigned long long *)(h_in + in_bytes);
+  memcpy(h_in, keys, sizeof(float) * (size_t)n * P.dim);
+  ringdb_many_stage(P, h_in + q_bytes);
+  DSM_HIP(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, st));
+  rc = ringdb_many_launch(st, P, d_in + q_bytes, (const float *)d_in, d_scratch, d_packed);
+  if (rc) return rc;
+  DSM_HIP(hipMemcpyAsync((void *)h_packed, d_packed, pk_bytes, hipMemcpyDeviceToHost, st));
+  DSM_HIP(hipStreamSynchronize(st));
+  std::vector<const float *> kp(n);
+  for (int j = 0; j < n; j++) kp[j] = keys + (size_t)j * P.dim;
+  ringdb_many_finish(P, dbs, kp.data(), h_packed, cand_out, ncand_out);
+  return DSM_OK;
 }
 
 } // extern "C"

@@ -347,6 +347,141 @@ __global__ void ringkey_insert_kernel(float *keysT, long long cap, long long pos
   }
 }
 
+// ---- many indexes in one launch (dsm_ringdb_query_then_enqueue_many, dsm_loop_detect_batch_many): one sequence's ring key per
+// query, each against its own index.  Grid (slice, query); query q's slices follow its own index's size (ringkey_many_slices: the
+// few-query rule, at least 1024 keys per slice), a slice beyond its own count writes "no candidate" and leaves, so the scratch
+// layout ((slice * nq + q) * K + j) and ringkey_merge_kernel are those of the single-index scan.  Same distance expression, same
+// packed candidates, same visiting order per thread as ringkey_knn_fewq4_kernel / ringkey_knn_kernel<0>: bit-identical results.
+
+// the workgroup's K best (every thread holds an ascending list) -> one list of K into the scratch: K rounds of wave-min extraction
+// (the winner lane pops its head) into LDS, then one thread merges the waves' lists
+template <int K>
+__device__ __forceinline__ void many_block_topk(unsigned long long (&best)[K], unsigned long long (&wtop)[kRkThreads / 64][K],
+                                                unsigned long long *__restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int r = 0; r < K; r++) {
+    unsigned long long m = best[0];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const unsigned long long o = __shfl_xor(m, off, 64);
+      m = o < m ? o : m;
+    }
+    if (lane == 0) wtop[wave][r] = m;
+    if (m != kNoCand && best[0] == m) { // packed candidates are unique (index in the low bits)
+#pragma unroll
+      for (int j = 0; j + 1 < K; j++) best[j] = best[j + 1];
+      best[K - 1] = kNoCand;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) t[j] = kNoCand;
+    for (int w = 0; w < kRkThreads / 64; w++)
+#pragma unroll
+      for (int j = 0; j < K; j++)
+        if (wtop[w][j] != kNoCand) topk_insert<K>(t, wtop[w][j]);
+#pragma unroll
+    for (int j = 0; j < K; j++) out[j] = t[j];
+  }
+}
+
+// dim DIM (a multiple of four), every capacity a multiple of four: four consecutive keys per thread, one 16-byte load per plane
+template <int DIM, int K>
+__global__ __launch_bounds__(kRkThreads) void ringkey_knn_many4_kernel(const RingKeyScanDesc *__restrict__ descs,
+                                                                       const float *__restrict__ queries, int nq,
+                                                                       unsigned long long *__restrict__ scratch) {
+  static_assert(DIM % 4 == 0, "flann::L2 main loop only");
+  __shared__ unsigned long long wtop[kRkThreads / 64][K];
+  const int slice = blockIdx.x, q = blockIdx.y;
+  unsigned long long *out = scratch + ((size_t)slice * nq + q) * K;
+  const RingKeyScanDesc d = descs[q];
+  if (slice >= d.n_slices) { // (uniform over the workgroup)
+    if (threadIdx.x < K) out[threadIdx.x] = kNoCand;
+    return;
+  }
+  const long long per = (((d.n_local + d.n_slices - 1) / d.n_slices) + 3) & ~3ll; // slices start on 16-byte boundaries of the planes
+  const long long k0 = (long long)slice * per;
+  const long long k1 = k0 + per < d.n_local ? k0 + per : d.n_local;
+  float qv[DIM];
+#pragma unroll
+  for (int j = 0; j < DIM; j++) qv[j] = queries[(size_t)q * DIM + j];
+  unsigned long long best[K];
+  float cut = d.thres;
+#pragma unroll
+  for (int j = 0; j < K; j++) best[j] = kNoCand;
+  // i + 3 < cap: i < n_local <= cap and both i and cap are multiples of four
+  for (long long i = k0 + 4 * threadIdx.x; i < k1; i += 4 * kRkThreads) {
+    rk_fvec4 kv[DIM];
+#pragma unroll
+    for (int j = 0; j < DIM; j++) kv[j] = __builtin_nontemporal_load((const rk_fvec4 *)(d.keysT + (size_t)j * d.cap + i));
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      float result = 0.f;
+#pragma unroll
+      for (int j = 0; j < DIM; j += 4) { // flann::L2 main loop
+        const float d0 = qv[j] - kv[j][e], d1 = qv[j + 1] - kv[j + 1][e], d2 = qv[j + 2] - kv[j + 2][e], d3 = qv[j + 3] - kv[j + 3][e];
+        result += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+      }
+      if (i + e < k1 && result < cut) topk_insert_cut<K>(best, cut, result, (unsigned long long)(i + e));
+    }
+  }
+  many_block_topk<K>(best, wtop, out);
+}
+
+// any dimension in [1, 32]: one key per thread, flann::L2's groups of four and its tail loop, the query broadcast from LDS
+template <int K>
+__global__ __launch_bounds__(kRkThreads) void ringkey_knn_many_kernel(const RingKeyScanDesc *__restrict__ descs,
+                                                                      const float *__restrict__ queries, int dim, int nq,
+                                                                      unsigned long long *__restrict__ scratch) {
+  __shared__ float qs[32];
+  __shared__ unsigned long long wtop[kRkThreads / 64][K];
+  const int slice = blockIdx.x, q = blockIdx.y;
+  unsigned long long *out = scratch + ((size_t)slice * nq + q) * K;
+  const RingKeyScanDesc d = descs[q];
+  if (slice >= d.n_slices) {
+    if (threadIdx.x < K) out[threadIdx.x] = kNoCand;
+    return;
+  }
+  const long long per = (d.n_local + d.n_slices - 1) / d.n_slices;
+  const long long k0 = (long long)slice * per;
+  const long long k1 = k0 + per < d.n_local ? k0 + per : d.n_local;
+  if (threadIdx.x < dim) qs[threadIdx.x] = queries[(size_t)q * dim + threadIdx.x];
+  __syncthreads();
+  unsigned long long best[K];
+  float cut = d.thres;
+#pragma unroll
+  for (int j = 0; j < K; j++) best[j] = kNoCand;
+  for (long long i = k0 + threadIdx.x; i < k1; i += kRkThreads) {
+    const float *kp = d.keysT + i;
+    float result = 0.f;
+    int j = 0;
+    for (; j + 3 < dim; j += 4) {
+      const float d0 = qs[j] - kp[(size_t)j * d.cap], d1 = qs[j + 1] - kp[(size_t)(j + 1) * d.cap], d2 = qs[j + 2] - kp[(size_t)(j + 2) * d.cap],
+                  d3 = qs[j + 3] - kp[(size_t)(j + 3) * d.cap];
+      result += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+    }
+    for (; j < dim; j++) { // flann::L2 tail loop
+      const float d0 = qs[j] - kp[(size_t)j * d.cap];
+      result += d0 * d0;
+    }
+    if (result < cut) topk_insert_cut<K>(best, cut, result, (unsigned long long)i);
+  }
+  many_block_topk<K>(best, wtop, out);
+}
+
+// matured keys of all indexes of the call: element e = (key e / dim, plane e % dim)
+__global__ void ringkey_insert_many_kernel(const RingKeyInsertDesc *__restrict__ descs, int dim, const float *__restrict__ keys, int nkeys) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < dim * nkeys) {
+    const int kk = e / dim, j = e % dim;
+    const RingKeyInsertDesc d = descs[kk];
+    d.keysT[(size_t)j * d.cap + d.pos] = keys[e];
+  }
+}
+
 constexpr int kRkTwoPerThread = 512; // from here on a thread of ringkey_knn_kernel carries two queries
 constexpr int kRkFewQueries = 32; // up to here the thread-per-key kernel is used (dim 20 only)
 static bool ringkey_use_fewq(int dim, int nq) { return dim == 20 && nq <= kRkFewQueries; }
@@ -427,6 +562,37 @@ void launch_ringkey_insert(hipStream_t s, float *keysT, int64_t cap, int64_t pos
   const int n = dim * nkeys;
   hipLaunchKernelGGL(ringkey_insert_kernel, dim3((n + 255) / 256), dim3(256), 0, s, keysT, (long long)cap,
                      (long long)pos, dim, d_key, nkeys);
+}
+
+int ringkey_many_slices(int64_t n_local) {
+  int64_t s = (n_local + 1023) / 1024; // ringkey_num_slices' few-query rule
+  if (s > 2048) s = 2048;
+  return (int)(s < 1 ? 1 : s);
+}
+
+template <int K>
+static void launch_knn_many_k(hipStream_t s, const RingKeyScanDesc *d_descs, int dim, bool four, const float *d_queries, int nq,
+                              int n_slices, unsigned long long *d_scratch, unsigned long long *d_packed_out) {
+  if (four && dim == 20)
+    hipLaunchKernelGGL((ringkey_knn_many4_kernel<20, K>), dim3(n_slices, nq), dim3(kRkThreads), 0, s, d_descs, d_queries, nq, d_scratch);
+  else
+    hipLaunchKernelGGL((ringkey_knn_many_kernel<K>), dim3(n_slices, nq), dim3(kRkThreads), 0, s, d_descs, d_queries, dim, nq, d_scratch);
+  hipLaunchKernelGGL((ringkey_merge_kernel<K>), dim3(nq), dim3(64), 0, s, d_scratch, nq, n_slices, d_packed_out);
+}
+
+void launch_ringkey_knn_many(hipStream_t s, const RingKeyScanDesc *d_descs, int dim, int k, bool four, const float *d_queries, int nq,
+                             int n_slices, unsigned long long *d_scratch, unsigned long long *d_packed_out) {
+  switch (k) {
+  case 1: launch_knn_many_k<1>(s, d_descs, dim, four, d_queries, nq, n_slices, d_scratch, d_packed_out); break;
+  case 2: launch_knn_many_k<2>(s, d_descs, dim, four, d_queries, nq, n_slices, d_scratch, d_packed_out); break;
+  case 3: launch_knn_many_k<3>(s, d_descs, dim, four, d_queries, nq, n_slices, d_scratch, d_packed_out); break;
+  default: launch_knn_many_k<4>(s, d_descs, dim, four, d_queries, nq, n_slices, d_scratch, d_packed_out); break;
+  }
+}
+
+void launch_ringkey_insert_many(hipStream_t s, const RingKeyInsertDesc *d_descs, int dim, const float *d_keys, int nkeys) {
+  const int n = dim * nkeys;
+  hipLaunchKernelGGL(ringkey_insert_many_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_descs, dim, d_keys, nkeys);
 }
 
 } // namespace dsm

@@ -54,11 +54,35 @@ public:
     for (int i = 0; i < n; i++) candidates.emplace_back(cand[i]);
   }
   dsm_ringdb *handle() { return db_; }
+  int dim() const { return dim_; }
 
 private:
   dsm_ringdb *db_ = nullptr;
   int dim_;
 };
+
+// search_ringkey of many sequences at once: one LoopHandler-like owner per RingKeyIndex, keys[j] searched in (and enqueued into) indexes[j]
+// (dsm_ringdb_query_then_enqueue_many): the same lists as indexes[j]->search_ringkey(keys[j], candidates[j]) for j = 0, 1, ... in that
+// order, in ONE call with one synchronisation.  Candidates are APPENDED to candidates[j] (resized to at least indexes.size()).  An index
+// may appear several times (at most LOOP_MARGIN); all indexes share one context and key dimension and none is sharded.
+inline void search_ringkey_many(const std::vector<RingKeyIndex *> &indexes, const std::vector<const float *> &keys,
+                                std::vector<std::vector<int>> &candidates) {
+  const size_t n = indexes.size();
+  if (keys.size() != n) throw std::runtime_error("search_ringkey_many: one key per index");
+  if (n == 0) return;
+  const int dim = (int)indexes[0]->dim();
+  std::vector<dsm_ringdb *> dbs(n);
+  std::vector<float> flat(n * dim);
+  for (size_t j = 0; j < n; j++) {
+    dbs[j] = indexes[j]->handle();
+    for (int d = 0; d < dim; d++) flat[j * dim + d] = keys[j][d];
+  }
+  std::vector<int> cand(n * kFlannNN), nc(n);
+  loop_check(dsm_ringdb_query_then_enqueue_many((int)n, dbs.data(), flat.data(), cand.data(), nc.data()), "search_ringkey_many");
+  if (candidates.size() < n) candidates.resize(n);
+  for (size_t j = 0; j < n; j++)
+    for (int i = 0; i < nc[j]; i++) candidates[j].emplace_back(cand[j * kFlannNN + i]);
+}
 
 // reference: search_sc(SigType& signature, const std::vector<dso::LoopFrame*>& loop_frames, const std::vector<int>& candidates,
 //                      int sc_width, int& res_idx, float& res_diff)  (search_place.h:59-84).  `signature_of(i)` returns

@@ -179,6 +179,27 @@ class RingKeyDB:
         check(self.L.dsm_ringdb_knn_packed_dev(self.h, C.c_void_p(d_queries_ptr), nq, C.c_void_p(d_out_ptr)))
 
 
+def _handles(dbs):
+    return (C.c_void_p * len(dbs))(*[db.h for db in dbs])
+
+
+def query_then_enqueue_many(dbs, keys):
+    """search_ringkey (search_place.h:25-57) of len(dbs) sequences in one call, key j against its own index dbs[j]
+    (dsm_ringdb_query_then_enqueue_many): the same lists as dbs[j].search_ringkey(keys[j]) for j = 0, 1, ... in that order.  An
+    index may appear several times (at most its margin); all indexes share one context, dim and k, none is sharded.
+    Returns one candidate list per key."""
+    dbs = list(dbs)
+    if not dbs:
+        raise ValueError("query_then_enqueue_many: no index")
+    dim, k = dbs[0].dim, dbs[0].k
+    keys = np.ascontiguousarray(keys, np.float32).reshape(len(dbs), dim)
+    cand = np.zeros((len(dbs), k), np.int32)
+    ncand = np.zeros(len(dbs), np.int32)
+    check(dbs[0].L.dsm_ringdb_query_then_enqueue_many(len(dbs), _handles(dbs), _fp(keys), cand.ctypes.data_as(c_int_p),
+                                                      ncand.ctypes.data_as(c_int_p)))
+    return [[int(c) for c in cand[j, : ncand[j]]] for j in range(len(dbs))]
+
+
 def scancontext_generate(pts_spherical, lidar_range, num_s=60, num_r=20):
     """ScanContext::generate (ScanContext.cpp:78-141) through the C ABI (host code by design).
     Returns (ringkey[num_r] float32, sig_idx int32, sig_val float64, tfm_pca_rig 4x4)."""
@@ -216,13 +237,21 @@ def generate_spherical_points(kf_ids, kf_pose_wc, cur_cw, lidar_range, pt_kf_id,
 
 
 class LoopBatch:
-    """The ctypes job table of dsm_loop_descriptors_batch / dsm_loop_detect_batch and its output arrays, built once: `run()` is the C call
-    alone (a node keeps its clouds and job tables; bench.py times this), `results()` unpacks."""
+    """The ctypes job table of dsm_loop_descriptors_batch / dsm_loop_detect_batch / dsm_loop_detect_batch_many and its output arrays, built
+    once: `run()` is the C call alone (a node keeps its clouds and job tables; bench.py times this), `results()` unpacks."""
 
-    def __init__(self, ctx, jobs, lidar_range, num_s=60, num_r=20, scancontext=True, db=None, selected_points=True, pinned_clouds=False):
+    def __init__(self, ctx, jobs, lidar_range, num_s=60, num_r=20, scancontext=True, db=None, selected_points=True, pinned_clouds=False,
+                 dbs=None):
         """pinned_clouds: the clouds (pt_kf_id, pt_xyz) are kept in page-locked memory (dsm_host_alloc), which the device reads directly:
-        no staging copy on the host"""
-        self.ctx, self.L, self.db = ctx, ctx.L, db
+        no staging copy on the host.  db: one index that every job searches (one sequence); dbs: one index per job (dbs[j] = the index of
+        job j's sequence, dsm_loop_detect_batch_many)"""
+        if db is not None and dbs is not None:
+            raise ValueError("LoopBatch: pass db (one index for every job) or dbs (one index per job), not both")
+        if dbs is not None:
+            dbs = list(dbs)
+            if len(dbs) != len(jobs):
+                raise ValueError("LoopBatch: dbs needs one index per job")
+        self.ctx, self.L, self.db, self.dbs = ctx, ctx.L, db, dbs
         self.lidar_range, self.num_s, self.num_r, self.scancontext, self.selected_points = lidar_range, num_s, num_r, scancontext, selected_points
         self.arr = (_lib.LoopJob * len(jobs))()
         self.keepalive, self.outs = [], []
@@ -257,10 +286,16 @@ class LoopBatch:
         self.cand = self.ncand = None
         if db is not None:
             self.cand, self.ncand = np.full((len(jobs), db.k), -1, np.int32), np.zeros(len(jobs), np.int32)
+        if dbs is not None:
+            self.cand, self.ncand = np.full((len(jobs), dbs[0].k), -1, np.int32), np.zeros(len(jobs), np.int32)
+            self.handles = _handles(dbs)
 
     def run(self):
         ip = c_int_p
-        if self.db is None:
+        if self.dbs is not None:
+            check(self.L.dsm_loop_detect_batch_many(self.ctx.h, len(self.arr), self.arr, self.handles, self.lidar_range, self.num_s, self.num_r,
+                                                    self.cand.ctypes.data_as(ip), self.ncand.ctypes.data_as(ip)))
+        elif self.db is None:
             check(self.L.dsm_loop_descriptors_batch(self.ctx.h, len(self.arr), self.arr, self.lidar_range, self.num_s, self.num_r))
         else:
             check(self.L.dsm_loop_detect_batch(self.ctx.h, self.db.h, len(self.arr), self.arr, self.lidar_range, self.num_s, self.num_r,
@@ -281,14 +316,17 @@ class LoopBatch:
         return res
 
 
-def loop_descriptors_batch(ctx, jobs, lidar_range, num_s=60, num_r=20, scancontext=True, db=None, selected_points=True, pinned_clouds=False):
+def loop_descriptors_batch(ctx, jobs, lidar_range, num_s=60, num_r=20, scancontext=True, db=None, selected_points=True, pinned_clouds=False,
+                           dbs=None):
     """DEVICE form of generate_spherical_points + ScanContext::generate for a batch of keyframes (dsm_loop_descriptors_batch).
     jobs: list of (kf_ids, kf_pose_wc, cur_cw, pt_kf_id, pt_xyz).  Returns, per job, a dict with kf_keep, sel_idx,
     pts_spherical and -- with scancontext -- ringkey, sig_idx, sig_val, tfm_pca_rig.
     db (a RingKeyDB): dsm_loop_detect_batch instead -- the jobs' ring keys are searched in (and enqueued into) the index on the device,
     one enqueue and one read-back for the whole chain; every result also carries `candidates` (search_ringkey's list).
+    dbs (one RingKeyDB per job, e.g. one per concurrent sequence): dsm_loop_detect_batch_many -- job j is searched in and enqueued into
+    its own index dbs[j], still one enqueue and one read-back; `db` and `dbs` exclude each other.
     selected_points = False: sel_idx / pts_spherical stay on the device (NULL outputs)."""
-    b = LoopBatch(ctx, jobs, lidar_range, num_s, num_r, scancontext, db, selected_points, pinned_clouds)
+    b = LoopBatch(ctx, jobs, lidar_range, num_s, num_r, scancontext, db, selected_points, pinned_clouds, dbs)
     b.run()
     return b.results()
 

@@ -576,6 +576,14 @@ int64_t dsm_ringdb_size(dsm_ringdb *db);
  * key): needs dsm_ringdb_attach_comm; every rank scans its shard, the candidates are merged by RCCL all-reduce(min)
  * and every rank returns the same list.  Without a communicator a sharded handle fails with DSM_ERR_STATE. */
 int dsm_ringdb_query_then_enqueue(dsm_ringdb *db, const float *key, int *cand_out, int *ncand_out);
+/* search_ringkey (search_place.h:25-57) of n sequences in ONE call, each against its own index: equal, bit for bit, to
+ * dsm_ringdb_query_then_enqueue(dbs[j], keys + j*dim, cand_out + j*k, ncand_out + j) for j = 0 .. n-1 in that order -- candidates,
+ * counts, and every index's entries, size and delay queue afterwards.  An index may appear several times (two keyframes of one
+ * sequence in the same advance), at most `margin` times per call; query j of an index sees the keys that earlier jobs of the call
+ * moved out of that index's delay queue.  All indexes: one context, unsharded, the same dim and k (thres and margin may differ).
+ * All or nothing: a NULL argument, n < 1, a mixed context, a sharded index, a dim / k mismatch or too many jobs on one index fail
+ * with DSM_ERR_INVALID before any output is written, any key is enqueued or any index changes.  One host synchronisation. */
+int dsm_ringdb_query_then_enqueue_many(int n, dsm_ringdb *const *dbs, const float *keys, int *cand_out, int *ncand_out);
 /* bulk insert (bench / sharded DB): n_keys keys appended directly to the index */
 int dsm_ringdb_add_points(dsm_ringdb *db, const float *keys, int64_t n_keys);
 /* the delay-queue half of search_ringkey alone (search_place.h:41-56): used by sharded callers
@@ -651,7 +659,8 @@ int dsm_generate_spherical_points(int n_kf, const int *kf_ids, const double *kf_
 
 /* DEVICE form of the pair generate_spherical_points + ScanContext::generate (the two calls a marginalised keyframe makes on its
  * way to the ring-key search: LoopHandler.cpp:186-187 and ScanContext.cpp:78-141 via LoopHandler.cpp:240-245), batched over
- * n_jobs keyframes -- one per concurrent sequence sharing the GPU (BASELINE configs[4]).  Per job the inputs are those of
+ * n_jobs keyframes -- of one sequence or of several concurrent sequences sharing the GPU (BASELINE configs[4]); the jobs are
+ * independent.  Per job the inputs are those of
  * dsm_generate_spherical_points; outputs: kf_keep, *n_out, sel_idx, pts_spherical as there, and -- when ringkey is not NULL --
  * ringkey[num_r], the sparse signature (sig_idx / sig_val, capacity num_s*num_r, *n_sig entries) and tfm_pca_rig[16] as
  * dsm_scancontext_generate returns them for pts_spherical.  The voxel "highest point" filter runs as two atomic-min passes
@@ -680,8 +689,10 @@ typedef struct dsm_loop_job {
 } dsm_loop_job;
 int dsm_loop_descriptors_batch(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double lidar_range, int num_s, int num_r);
 /* The per-keyframe loop chain -- generate_spherical_points (LoopHandler.cpp:186), ScanContext::generate (:236), search_ringkey (:247,
- * search_place.h:25-57) -- as ONE enqueue and ONE read-back for the keyframes marginalised in the same advance (one per concurrent
- * sequence; n_jobs <= the index's margin): the ring keys go from the descriptor kernels to the index's k-NN on the device.  Every job
+ * search_place.h:25-57) -- as ONE enqueue and ONE read-back for keyframes of ONE index (n_jobs <= its margin): the ring keys go from
+ * the descriptor kernels to the index's k-NN on the device.  One index is one sequence's search (LoopHandler.cpp:35-39): every job
+ * searches, and is enqueued into, the same index and delay queue.  Keyframes of several concurrent sequences, each with its own index,
+ * go through dsm_loop_detect_batch_many below.  Every job
  * needs its descriptor outputs (ringkey ... tfm_pca_rig); sel_idx / pts_spherical may both be NULL (the selected points -- 0.45 MB per
  * keyframe -- then stay on the device).  Results equal the jobs' dsm_loop_descriptors_batch + dsm_ringdb_query_then_enqueue calls one
  * after the other, bit for bit: cand_out[j * k ...] / ncand_out[j] = search_ringkey's candidate list of job j, and every key is enqueued.
@@ -690,6 +701,13 @@ int dsm_loop_descriptors_batch(dsm_context *ctx, int n_jobs, const dsm_loop_job 
  * BEFORE any output array of any job is written and before any key is enqueued (dsm_loop_descriptors_batch likewise writes nothing). */
 int dsm_loop_detect_batch(dsm_context *ctx, dsm_ringdb *db, int n_jobs, const dsm_loop_job *jobs, double lidar_range, int num_s, int num_r,
                           int *cand_out, int *ncand_out);
+/* dsm_loop_detect_batch with one index PER JOB (dbs[j]: the index of job j's sequence): equal to, per job in order,
+ * dsm_loop_descriptors_batch of that job followed by dsm_ringdb_query_then_enqueue(dbs[j], its ring key, ...).  The indexes follow the
+ * rules of dsm_ringdb_query_then_enqueue_many (the call's context, unsharded, dim = num_r, one k, at most `margin` jobs per index);
+ * every job needs its descriptor outputs.  All or nothing as both calls: on any invalid argument or a job whose filtered cloud is empty,
+ * DSM_ERR_INVALID before any output is written, any key is enqueued or any index changes.  One read-back, one synchronisation. */
+int dsm_loop_detect_batch_many(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, dsm_ringdb *const *dbs, double lidar_range, int num_s,
+                               int num_r, int *cand_out, int *ncand_out);
 
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
