@@ -227,6 +227,7 @@ class NumpyTracker:
             new_id = id_ / pt[2]
         Ku, Kv = fx * u + cx, fy * v + cy
         flow = np.zeros(3, np.float32)
+        flow_terms = (np.zeros(0, np.float32), np.zeros(0, np.float32))
         if lvl == 0 and flow_Ki is not None:  # :754-784 / :1070-1100: every 32nd template index
             s = slice(0, None, 32)
             xs, ys, ids = x[s], y[s], id_[s]
@@ -242,8 +243,9 @@ class NumpyTracker:
                 KuT2, KvT2 = proj([kx[r] - tid[r] for r in range(3)])
                 Ku3, Kv3 = proj([rx[r] - tid[r] for r in range(3)])
             sq = lambda a, b: (a - xs) * (a - xs) + (b - ys) * (b - ys)
-            flow[0] = seq_sum(np.stack([sq(KuT, KvT), sq(KuT2, KvT2)], 1).ravel())
-            flow[1] = seq_sum(np.stack([sq(Ku[s], Kv[s]), sq(Ku3, Kv3)], 1).ravel())
+            flow_terms = (np.stack([sq(KuT, KvT), sq(KuT2, KvT2)], 1).ravel(), np.stack([sq(Ku[s], Kv[s]), sq(Ku3, Kv3)], 1).ravel())
+            flow[0] = seq_sum(flow_terms[0])
+            flow[1] = seq_sum(flow_terms[1])
             flow[2] = seq_sum(np.full(len(xs), 2, np.float32))
         with np.errstate(invalid="ignore"):
             inb = (Ku > 2) & (Kv > 2) & (Ku < f32(wl - 3)) & (Kv < f32(hl - 3)) & (new_id > 0)  # :786 / :1102
@@ -270,7 +272,7 @@ class NumpyTracker:
             rs = np.array([E, n_terms, float(flow[0]) / (float(flow[2]) + 0.1), 0.0, float(flow[1]) / (float(flow[2]) + 0.1),
                            f32(n_sat) / f32(n_terms) if n_terms else np.nan])  # :843-851
         buf = dict(idx=idx[keep], u=u[idx][keep], v=v[idx][keep], new_id=new_id[idx][keep], dx=hit[keep, 1], dy=hit[keep, 2],
-                   residual=residual[keep], hw=hw[keep], refc=refc[keep])
+                   residual=residual[keep], hw=hw[keep], refc=refc[keep], flow_terms=flow_terms)
         return rs, buf
 
     @staticmethod
@@ -288,7 +290,9 @@ class NumpyTracker:
         self.pose_buf = buf
         return rs
 
-    def calc_gs_pose(self, lvl, aff):  # calcGSSSEPose :640-697
+    def pose_jacobian(self, lvl, aff):
+        """calcGSSSEPose's per-point vectors (:658-678) on the buffers of the last calc_res_pose, padded with zero entries to a
+        multiple of 4 (quirk Q3): J = the 8 tangent entries and the residual (9 float32 arrays), and the Huber weights"""
         B = self.pose_buf
         fxl, fyl = self.fx[lvl], self.fy[lvl]
         a = f32(aff_from_to(self.ref_exposure, self.new_exposure, self.ref_aff, aff)[0])
@@ -300,8 +304,11 @@ class NumpyTracker:
         J = [idp * dx, idp * dy, zero - idp * (u * dx + v * dy), zero - ((u * v) * dx + dy * (one + v * v)),
              (u * v) * dy + dx * (one + u * u), u * dy - v * dx, a * (b0 - pad(B["refc"])), np.full(len(u), -1, np.float32),
              pad(B["residual"])]  # :664-678
-        wgt = pad(B["hw"])
-        n = len(u)
+        return J, pad(B["hw"])
+
+    def calc_gs_pose(self, lvl, aff):  # calcGSSSEPose :640-697
+        J, wgt = self.pose_jacobian(lvl, aff)
+        n = len(wgt)
         Hf = np.zeros((9, 9), np.float32)
         for r in range(9):
             Jw = J[r] * wgt
@@ -328,7 +335,9 @@ class NumpyTracker:
         self.scale_buf = buf
         return rs
 
-    def calc_gs_scale(self, lvl, scale):  # calcGSSSEScale :966-1005
+    def scale_jacobian(self, lvl, scale):
+        """calcGSSSEScale's per-point values (:983-999) on the buffers of the last calc_res_scale, padded with zero entries to a
+        multiple of 4 (quirk Q3): J0 (d residual / d scale), J1 (the residual) and the Huber weights"""
         B = self.scale_buf
         pad = self._pad4
         t = self.T10[:3, 3].astype(np.float32)
@@ -340,7 +349,10 @@ class NumpyTracker:
             deno = one / (deno_sqrt * deno_sqrt)
             xno, yno = rx1 * tz - rx3 * tx, rx2 * tz - rx3 * ty
             J0 = dxfx * (deno * xno) + dyfy * (deno * yno)
-        J1, w = pad(B["residual"]), pad(B["hw"])
+        return J0, pad(B["residual"]), pad(B["hw"])
+
+    def calc_gs_scale(self, lvl, scale):  # calcGSSSEScale :966-1005
+        J0, J1, w = self.scale_jacobian(lvl, scale)
         n = len(J0)
         J0w = J0 * w
         h00, h01 = (lane_accumulate(J0w * J0), lane_accumulate(J0w * J1)) if n else (f32(0), f32(0))
