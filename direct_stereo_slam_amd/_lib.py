@@ -114,6 +114,13 @@ class LoopJob(C.Structure):
     ]
 
 
+
+class IcpJob(C.Structure):
+    _fields_ = [
+        ("n_src", C.c_int), ("src_xyz", c_double_p), ("n_tgt", C.c_int), ("tgt_xyz", c_double_p), ("tfm_target_source", c_double_p),
+        ("score", c_float_p), ("ok", c_int_p), ("iterations", c_int_p), ("state", c_int_p), ("corr_counts", c_int_p),
+    ]
+
 # every symbol include/dsm_hotpath.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _pp_f = C.POINTER(c_float_p)
@@ -223,6 +230,7 @@ SYMBOLS = {
     "dsm_loop_descriptors_batch": (C.c_int, [_vp, C.c_int, C.POINTER(LoopJob), C.c_double, C.c_int, C.c_int]),
     "dsm_loop_detect_batch": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(LoopJob), C.c_double, C.c_int, C.c_int, c_int_p, c_int_p]),
     "dsm_loop_detect_batch_many": (C.c_int, [_vp, C.c_int, C.POINTER(LoopJob), C.POINTER(_vp), C.c_double, C.c_int, C.c_int, c_int_p, c_int_p]),
+    "dsm_icp_batch": (C.c_int, [_vp, C.c_int, C.POINTER(IcpJob), C.c_int, C.c_double, C.c_double, C.c_double]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

@@ -1,5 +1,5 @@
 // LoopDetection.hpp -- C++ host adaptor for the loop-detection half of the hot path: the surface of
-// src/loop_closure/loop_detection/{search_place.h, ScanContext.h, generate_spherical_points.h} and of the flann index
+// src/loop_closure/loop_detection/{search_place.h, ScanContext.h, generate_spherical_points.h}, of pose_estimation/icp.h and of the flann index
 // LoopHandler owns (LoopHandler.cpp:35-39), on top of the C ABI (include/dsm_hotpath.h).  Same names, argument meaning
 // and error behaviour as the reference; no Eigen / FLANN types at the boundary: points are rows of three doubles,
 // ring keys are float arrays, SigType is the reference's own typedef.
@@ -166,6 +166,47 @@ inline void generate_spherical_points(std::vector<std::pair<int, std::vector<dou
     new_pts.push_back(pts_nearby[sel[i]]);                                                             // :80
   }
   pts_nearby.swap(new_pts); // :84
+}
+
+// reference: icp(pts_source, pts_target, tfm_target_source, icp_score) (pose_estimation/icp.h:44-71), PCL's IterativeClosestPoint with
+// the reference's settings, on the device (dsm_icp_batch; semantics: DESIGN.md section 10).  pts_source: the matched keyframe's
+// pts_spherical, pts_target: the current keyframe's, as n rows of (x, y, z); tfm_target_source: row-major 4x4, the guess on entry and the
+// result on return.  Returns icp_score < ICP_THRES.
+inline bool icp(dsm_context *ctx, const std::vector<double> &pts_source_xyz, const std::vector<double> &pts_target_xyz,
+                double tfm_target_source[16], float &icp_score) {
+  int ok = 0, iterations = 0, state = 0;
+  dsm_icp_job job = {(int)(pts_source_xyz.size() / 3), pts_source_xyz.data(), (int)(pts_target_xyz.size() / 3), pts_target_xyz.data(),
+                     tfm_target_source, &icp_score, &ok, &iterations, &state, nullptr};
+  loop_check(dsm_icp_batch(ctx, 1, &job, DSM_ICP_MAX_ITERATIONS, DSM_ICP_TRANSFORMATION_EPSILON, DSM_ICP_MAX_CORRESPONDENCE_DISTANCE,
+                           DSM_ICP_THRES),
+             "icp");
+  return ok != 0;
+}
+
+// one match of icp_many: the arguments of icp() and its results
+struct IcpMatch {
+  const std::vector<double> *pts_source = nullptr, *pts_target = nullptr; // rows of (x, y, z)
+  double tfm_target_source[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; // in: the guess, out: the result
+  float icp_score = 0.f;
+  bool ok = false;
+  int iterations = 0, state = 0; // DSM_ICP_STATE_*
+};
+
+// icp() of many independent matches (several sequences' loop candidates) in ONE call: each match's results equal those of icp() alone
+inline void icp_many(dsm_context *ctx, std::vector<IcpMatch> &matches) {
+  if (matches.empty()) return;
+  std::vector<dsm_icp_job> jobs(matches.size());
+  std::vector<int> ok(matches.size());
+  for (size_t j = 0; j < matches.size(); j++) {
+    IcpMatch &m = matches[j];
+    if (!m.pts_source || !m.pts_target) throw std::runtime_error("icp_many: a match without its clouds");
+    jobs[j] = {(int)(m.pts_source->size() / 3), m.pts_source->data(), (int)(m.pts_target->size() / 3), m.pts_target->data(),
+               m.tfm_target_source, &m.icp_score, &ok[j], &m.iterations, &m.state, nullptr};
+  }
+  loop_check(dsm_icp_batch(ctx, (int)jobs.size(), jobs.data(), DSM_ICP_MAX_ITERATIONS, DSM_ICP_TRANSFORMATION_EPSILON,
+                           DSM_ICP_MAX_CORRESPONDENCE_DISTANCE, DSM_ICP_THRES),
+             "icp_many");
+  for (size_t j = 0; j < matches.size(); j++) matches[j].ok = ok[j] != 0;
 }
 
 // reference: the file output of LoopHandler::savePose (LoopHandler.cpp:59-80)

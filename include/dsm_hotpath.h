@@ -709,6 +709,53 @@ int dsm_loop_detect_batch(dsm_context *ctx, dsm_ringdb *db, int n_jobs, const ds
 int dsm_loop_detect_batch_many(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, dsm_ringdb *const *dbs, double lidar_range, int num_s,
                                int num_r, int *cand_out, int *ncand_out);
 
+/* The ICP fallback of loop closure: replaces icp() (src/loop_closure/pose_estimation/icp.h:44-71), which LoopHandler::run calls when direct
+ * alignment rejects a ScanContext match (LoopHandler.cpp:284-288) -- PCL's IterativeClosestPoint<PointXYZ, PointXYZ> with the settings of
+ * icp.h:58-61 -- batched over independent matches (of one sequence or of several).  Semantics: DESIGN.md section 10, quirks P1-P9 and
+ * deviations D1-D4; in short, per job:
+ *   - the source (matched keyframe's pts_spherical) is moved by the guess tfm_target_source in double and rounded to float, the target
+ *     (current keyframe's pts_spherical) rounded to float;
+ *   - up to max_iterations rounds of: exact nearest target of every source point, pairs kept within max_corr_dist, Umeyama (no scale)
+ *     increment, the convergence tests of PCL's DefaultConvergenceCriteria; fewer than 3 pairs end the loop (NO_CORRESPONDENCES);
+ *   - tfm_target_source = double(final) * tfm_target_source; score = getFitnessScore() (the guess-moved source moved by the final
+ *     transformation, mean squared nearest-neighbour distance, no limit); ok = score < score_thres;
+ *   - an empty source or target (D3) leaves tfm_target_source unchanged: score = +inf, ok = 0, iterations = 0, state = EMPTY.
+ * The RANSAC threshold of icp.h:61 has no effect in PCL (no rejector is installed): it is not a parameter (P7).
+ * One launch sequence and one read-back for the whole batch; a job's results do not depend on the other jobs of the call.  Points are
+ * expected finite.  Validation is all or nothing, before any output is written: DSM_ERR_INVALID for NULL pointers, negative sizes or more
+ * than DSM_ICP_MAX_POINTS points, max_iterations outside [1, DSM_ICP_ITERATIONS_LIMIT], a non-finite or negative max_corr_dist, a
+ * non-finite transformation_epsilon, a NaN score_thres or a non-finite guess.  The steady state allocates nothing (the loop chain's
+ * device arena and page-locked mirror of the context). */
+#define DSM_ICP_MAX_ITERATIONS 5                /* icp.h:58 setMaximumIterations */
+#define DSM_ICP_TRANSFORMATION_EPSILON 0.01     /* icp.h:59 setTransformationEpsilon */
+#define DSM_ICP_MAX_CORRESPONDENCE_DISTANCE 2.0 /* icp.h:60 setMaxCorrespondenceDistance */
+#define DSM_ICP_RANSAC_THRESHOLD 0.5            /* icp.h:61 setRANSACOutlierRejectionThreshold: no effect (P7), not used */
+#define DSM_ICP_THRES 1.5                       /* icp.h:20 ICP_THRES: a match is accepted iff score < it */
+#define DSM_ICP_ITERATIONS_LIMIT 64             /* largest max_iterations accepted */
+#define DSM_ICP_MAX_POINTS (1 << 24)            /* largest cloud accepted */
+/* end states (dsm_icp_job.state): PCL's ConvergenceState values; 4 (relative MSE) is never reached (P6), 6 is D3 */
+#define DSM_ICP_STATE_NOT_CONVERGED 0
+#define DSM_ICP_STATE_ITERATIONS 1
+#define DSM_ICP_STATE_TRANSFORM 2
+#define DSM_ICP_STATE_ABS_MSE 3
+#define DSM_ICP_STATE_NO_CORRESPONDENCES 5
+#define DSM_ICP_STATE_EMPTY 6
+typedef struct dsm_icp_job {
+  int n_src;                 /* pts_source: the matched keyframe's pts_spherical */
+  const double *src_xyz;     /* n_src x 3 */
+  int n_tgt;                 /* pts_target: the current keyframe's pts_spherical */
+  const double *tgt_xyz;     /* n_tgt x 3 */
+  double *tfm_target_source; /* in: the guess (LoopHandler.cpp:266-268), out: the ICP result; row-major 4x4 */
+  float *score;              /* out: icp_score */
+  int *ok;                   /* out: icp()'s return value */
+  int *iterations;           /* out: iterations run (increments applied) */
+  int *state;                /* out: DSM_ICP_STATE_* */
+  int *corr_counts;          /* out, optional (NULL): capacity max_iterations; the pairs kept by each correspondence search in order,
+                                -1 past the last search (the last one is the failing search of a NO_CORRESPONDENCES end) */
+} dsm_icp_job;
+int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_iterations, double transformation_epsilon, double max_corr_dist,
+                  double score_thres);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.

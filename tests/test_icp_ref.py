@@ -1,0 +1,182 @@
+"""CPU: the ICP fallback's interface (dsm_icp_batch) is exported and bound, the numpy checker (tests/_icp_ref.py) behaves as the contract
+P1-P9 says, the device's Umeyama step (csrc/icp_internal.hpp, built for the host) equals the checker's, and the C++ adaptor compiles."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import _icp_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_icp_symbols_exported_and_bound(built):
+    from direct_stereo_slam_amd import _lib, icp
+
+    L = _lib.load()
+    assert hasattr(L, "dsm_icp_batch") and "dsm_icp_batch" in _lib.SYMBOLS
+    assert [f[0] for f in _lib.IcpJob._fields_] == ["n_src", "src_xyz", "n_tgt", "tgt_xyz", "tfm_target_source", "score", "ok", "iterations",
+                                                    "state", "corr_counts"]
+    hdr = open(os.path.join(ROOT, "include", "dsm_hotpath.h")).read()
+    consts = dict(re.findall(r"#define (DSM_ICP_[A-Z_]+) (\S+)", hdr))
+    assert float(consts["DSM_ICP_THRES"]) == icp.ICP_THRES == 1.5
+    assert int(consts["DSM_ICP_MAX_ITERATIONS"]) == icp.MAX_ITERATIONS == 5
+    assert float(consts["DSM_ICP_TRANSFORMATION_EPSILON"]) == icp.TRANSFORMATION_EPSILON
+    assert float(consts["DSM_ICP_MAX_CORRESPONDENCE_DISTANCE"]) == icp.MAX_CORRESPONDENCE_DISTANCE
+    assert int(consts["DSM_ICP_ITERATIONS_LIMIT"]) == icp.ITERATIONS_LIMIT
+    for name, value in (("ITERATIONS", 1), ("TRANSFORM", 2), ("ABS_MSE", 3), ("NO_CORRESPONDENCES", 5), ("EMPTY", 6)):
+        assert int(consts["DSM_ICP_STATE_" + name]) == value == getattr(R, name)
+
+
+def test_checker_recovers_rigid_motion():
+    for src, tgt, T in (R.scene(5, 3000, rotvec=(0.01, 0.03, 0.0), trans=(0.3, 0.05, 0.2), overlap=0.7),
+                        R.blobs(7, 3000, (0.02, 0.05, 0.0), (0.3, 0.2, 0.1))):
+        r = R.icp(src, tgt[: int(0.8 * len(tgt))], np.eye(4), max_iterations=40, eps=1e-8)
+        assert r["state"] == R.TRANSFORM and r["ok"]
+        ang, tr = R.pose_error(r["tfm"], T)
+        assert ang < 0.1 and tr < 0.05, (ang, tr)
+    # the guess is applied to the source before the iterations (P1) and folded into the result (P8)
+    src, tgt, T = R.blobs(8, 1500, (0.0, 0.04, 0.0), (0.2, 0.0, 0.1))
+    guess = R.rigid(R.rot((0.0, 0.03, 0.0)), [0.15, 0.0, 0.05])
+    r = R.icp(src, tgt, guess, max_iterations=40, eps=1e-8)
+    assert R.pose_error(r["tfm"], T)[1] < 0.01
+
+
+def _rotation_fit_cases():
+    rng = np.random.default_rng(3)
+    Rt = R.rot(rng.normal(0, 0.5, 3))
+    t = rng.normal(0, 2, 3)
+    full = rng.normal(0, 3, (40, 3))
+    planar = np.column_stack([rng.normal(0, 3, (40, 2)), np.zeros(40)])
+    return Rt, t, [("full", full), ("planar", planar)]
+
+
+def test_umeyama_equals_closed_form_fit():
+    from scipy.spatial.transform import Rotation
+
+    Rt, t, cases = _rotation_fit_cases()
+    for name, src in cases:
+        dst = src @ Rt.T + t
+        Rm, tm = R.umeyama(src, dst)
+        np.testing.assert_allclose(Rm, Rt, atol=1e-9, err_msg=name)
+        np.testing.assert_allclose(tm, t, atol=1e-9, err_msg=name)
+        # scipy's Kabsch fit of the centred sets
+        rs, _ = Rotation.align_vectors(dst - dst.mean(0), src - src.mean(0))
+        np.testing.assert_allclose(Rm, rs.as_matrix(), atol=1e-9, err_msg=name)
+    # a reflected (planar) target: the unconstrained fit is a reflection, the determinant fix keeps a rotation
+    src = cases[1][1]
+    dst = src * np.array([1.0, -1.0, 1.0])
+    Rm, _ = R.umeyama(src, dst)
+    assert abs(np.linalg.det(Rm) - 1) < 1e-12 and np.allclose(Rm @ Rm.T, np.eye(3), atol=1e-12)
+    # collinear pairs: the rotation is not unique, but it is one, and it maps the line onto the line
+    d = np.array([1.0, 2.0, -0.5]) / np.linalg.norm([1.0, 2.0, -0.5])
+    line = np.outer(np.linspace(-3, 3, 20), d)
+    Rm, tm = R.umeyama(line, line @ Rt.T + t)
+    assert abs(np.linalg.det(Rm) - 1) < 1e-12
+    np.testing.assert_allclose(Rm @ d, Rt @ d, atol=1e-9)
+
+
+_UMEYAMA_MAIN = r"""
+#include <cstdio>
+#include "icp_internal.hpp"
+int main(int argc, char **argv) {
+  FILE *f = fopen(argv[1], "rb");
+  int n;
+  if (fread(&n, sizeof n, 1, f) != 1) return 1;
+  for (int c = 0; c < n; c++) {
+    double in[15], Rm[9], t[3];
+    if (fread(in, sizeof(double), 15, f) != 15) return 1;
+    dsm::icp_umeyama(in, in + 9, in + 12, Rm, t);
+    for (int i = 0; i < 9; i++) printf("%.17g ", Rm[i]);
+    printf("%.17g %.17g %.17g\n", t[0], t[1], t[2]);
+  }
+  return 0;
+}
+"""
+
+
+def test_device_umeyama_built_for_the_host_equals_checker(tmp_path):
+    """the Jacobi SVD + Umeyama step the step kernel runs (icp_internal.hpp, __host__ __device__), compiled for the host"""
+    Rt, t, cases = _rotation_fit_cases()
+    rng = np.random.default_rng(9)
+    noisy = rng.normal(0, 2, (60, 3))
+    pairs = [(src, src @ Rt.T + t) for _, src in cases] + [(noisy, noisy @ Rt.T + t + rng.normal(0, 0.3, noisy.shape)),
+                                                          (cases[1][1], cases[1][1] * np.array([1.0, -1.0, 1.0]))]
+    d = np.array([1.0, 2.0, -0.5]) / np.linalg.norm([1.0, 2.0, -0.5])
+    line = np.outer(np.linspace(-3, 3, 20), d)
+    pairs.append((line, line @ Rt.T + t))
+    pairs.append((np.ones((5, 3)), np.ones((5, 3)) * 2))  # Sigma = 0
+    blob = bytearray(np.int32(len(pairs)).tobytes())
+    for src, dst in pairs:
+        sm, dm = src.mean(0), dst.mean(0)
+        sigma = (dst - dm).T @ (src - sm) / len(src)
+        blob += np.concatenate([sigma.ravel(), sm, dm]).tobytes()
+    (tmp_path / "cases.bin").write_bytes(bytes(blob))
+    (tmp_path / "main.cpp").write_text(_UMEYAMA_MAIN)
+    exe = tmp_path / "umeyama"
+    csrc = os.path.join(ROOT, "direct_stereo_slam_amd", "csrc")
+    subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-I", csrc, "-o", str(exe),
+                    str(tmp_path / "main.cpp")], check=True, capture_output=True)
+    out = subprocess.run([str(exe), str(tmp_path / "cases.bin")], check=True, capture_output=True, text=True).stdout.split("\n")
+    for k, (src, dst) in enumerate(pairs):
+        v = np.array(out[k].split(), np.float64)
+        Rd, td = v[:9].reshape(3, 3), v[9:]
+        assert abs(np.linalg.det(Rd) - 1) < 1e-12 and np.allclose(Rd @ Rd.T, np.eye(3), atol=1e-12), k
+        if k < 4:  # full rank or planar: the rotation is unique
+            Rm, tm = R.umeyama(src, dst)
+            np.testing.assert_allclose(Rd, Rm, atol=1e-10, err_msg=str(k))
+            np.testing.assert_allclose(td, tm, atol=1e-9, err_msg=str(k))
+        elif k == 4:  # collinear: the line maps onto the line
+            np.testing.assert_allclose(Rd @ d, Rt @ d, atol=1e-9)
+        else:  # Sigma = 0: the identity
+            np.testing.assert_allclose(Rd, np.eye(3), atol=0)
+
+
+def test_each_end_state_is_reached():
+    src, tgt, _ = R.scene(1, 2000)
+    r = R.icp(src, tgt, np.eye(4))
+    assert r["state"] == R.TRANSFORM and r["iterations"] == 1 and r["ok"]
+    src, tgt, _ = R.blobs(3, 2000, (0, 0.1, 0), (1.5, 0.5, 0))
+    r = R.icp(src, tgt, np.eye(4))
+    assert r["state"] == R.ITERATIONS and r["iterations"] == 5 and len(r["corr_counts"]) == 5
+    # no transformation test (epsilon < 0): identical clouds stop moving, the MSE repeats exactly
+    pts = np.random.default_rng(1).normal(0, 3, (500, 3))
+    r = R.icp(pts, pts, np.eye(4), eps=-1.0)
+    assert r["state"] == R.ABS_MSE and r["iterations"] == 2 and r["score"] == 0
+    # every pair beyond 2 m: the first search ends the loop, the result is the guess
+    guess = R.rigid(R.rot((0, 0.1, 0)), [0.5, 0, 0])
+    r = R.icp(pts, pts + 20, guess)
+    assert r["state"] == R.NO_CORRESPONDENCES and r["iterations"] == 0 and r["corr_counts"] == [0] and not r["ok"]
+    assert np.array_equal(r["tfm"], guess) and r["score"] > 100
+    # D3
+    for s, t in ((pts[:0], pts), (pts, pts[:0])):
+        r = R.icp(s, t, guess)
+        assert r["state"] == R.EMPTY and r["iterations"] == 0 and r["score"] == np.inf and not r["ok"] and np.array_equal(r["tfm"], guess)
+
+
+def test_checker_breaks_exact_ties_by_the_smallest_index():
+    src, tgt, tgt_swapped = R.ties(7)
+    n = len(src)
+    for t in (tgt, tgt_swapped):
+        idx, d = R.nearest(R.transform_double(src, np.eye(4)), R.transform_double(t, np.eye(4)))
+        assert np.all(d == np.float32(0.25))  # every source point: two targets at exactly this distance
+        h = n // 2
+        lower = np.concatenate([2 * np.arange(h), h + np.arange(h, n)])  # where each point's first-listed target sits
+        np.testing.assert_array_equal(idx, lower)
+    a, b = R.icp(src, tgt, np.eye(4)), R.icp(src, tgt_swapped, np.eye(4))
+    assert np.abs(a["tfm"][:3, 3] - b["tfm"][:3, 3]).max() > 0.1  # the tie-break decides the result
+
+
+def test_adaptor_header_compiles_without_a_gpu(tmp_path):
+    src = tmp_path / "use_icp.cpp"
+    src.write_text('#include "LoopDetection.hpp"\n'
+                   "bool f(dsm_context *ctx, const std::vector<double> &a, const std::vector<double> &b, double tfm[16], float &score) {\n"
+                   "  std::vector<dsm_host::IcpMatch> m(1);\n"
+                   "  m[0].pts_source = &a; m[0].pts_target = &b;\n"
+                   "  dsm_host::icp_many(ctx, m);\n"
+                   "  return dsm_host::icp(ctx, a, b, tfm, score) && m[0].ok;\n}\n")
+    subprocess.run(["g++", "-std=c++11", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "direct_stereo_slam_amd", "host"), str(src)],
+                   check=True)
