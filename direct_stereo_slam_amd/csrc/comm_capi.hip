@@ -27,11 +27,6 @@ using namespace dsm;
 
 namespace {
 
-int invalid(const char *m) {
-  set_error(m);
-  return DSM_ERR_INVALID;
-}
-
 // ---- RCCL, resolved at run time ----------------------------------------------------------------------------------
 struct Rccl {
   void *handle = nullptr;

@@ -5,7 +5,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <vector>
 
 #include "dsm_internal.hpp"
@@ -23,7 +22,7 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line) {
   return DSM_ERR_HIP;
 }
 
-static int invalid(const char *msg) {
+int invalid(const char *msg) {
   set_error(msg);
   return DSM_ERR_INVALID;
 }
@@ -35,26 +34,10 @@ static size_t plane_bytes(int w, int h) { return sizeof(float) * ((size_t)w * h 
 
 int ensure_stage(dsm_context *ctx, size_t floats) {
   if (floats <= ctx->stage_floats) return DSM_OK;
-  if (ctx->d_stage) DSM_HIP(hipFree(ctx->d_stage));
-  ctx->d_stage = nullptr;
   ctx->stage_floats = 0;
-  DSM_HIP(hipMalloc(&ctx->d_stage, floats * sizeof(float)));
+  const int rc = realloc_dev(&ctx->d_stage, floats);
+  if (rc) return rc;
   ctx->stage_floats = floats;
-  return DSM_OK;
-}
-
-template <typename T>
-static int realloc_dev(T **p, size_t n) {
-  if (*p) DSM_HIP(hipFree(*p));
-  *p = nullptr;
-  DSM_HIP(hipMalloc(p, n * sizeof(T)));
-  return DSM_OK;
-}
-template <typename T>
-static int realloc_pinned(T **p, size_t n) {
-  if (*p) DSM_HIP(hipHostFree(*p));
-  *p = nullptr;
-  DSM_HIP(hipHostMalloc(p, n * sizeof(T), hipHostMallocDefault));
   return DSM_OK;
 }
 
@@ -1176,145 +1159,6 @@ static int prepare_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mo
 }
 
 } // extern "C"
-namespace dsm {
-hipEvent_t get_event(dsm_context *ctx, size_t idx) {
-  while (ctx->ev_pool.size() <= idx) {
-    hipEvent_t ev;
-    if (hipEventCreate(&ev) != hipSuccess) return nullptr;
-    ctx->ev_pool.push_back(ev);
-  }
-  return ctx->ev_pool[idx];
-}
-
-// streams of the segments of a launch schedule: `ng` stream groups (the context's stream + ng - 1 extra ones) and, on
-// request, the companion stream
-// Do kernels of streams a and b run at the same time?  (The runtime maps streams onto a few hardware queues -- four by default --
-// round robin, together with every other stream of the process; two streams that share a queue serialise.  Measured in round 5: a
-// hipMemset on the null stream in dsm_tracker_create shifted the assignment, two of the three stream groups of dsm_stream_* landed on
-// one queue, and the bench lost 6 % on 512 frames, 15 % on 256 and 30 % on the sparse template -- profiles/r05_ab_bisect.log.)
-// A kernel that stays resident for 400 us on a, an empty one on b behind it in host order: b's finishes early only on another queue.
-static int streams_overlap(dsm_context *ctx, hipStream_t a, hipStream_t b, bool *overlap) {
-  int khz = 0;
-  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess || khz <= 0) khz = 100000;
-  const double wait_ms = 0.4;
-  hipEvent_t e0, e1;
-  DSM_HIP(hipEventCreate(&e0));
-  DSM_HIP(hipEventCreate(&e1));
-  int rc = DSM_OK;
-  float ms = 0.f;
-  hipError_t e = hipSuccess;
-  for (int pass = 0; pass < 2 && e == hipSuccess; pass++) { // (pass 0 loads the two kernels)
-    e = hipEventRecord(e0, a);
-    launch_queue_probe_wait(a, pass == 0 ? 1 : (long long)(wait_ms * khz));
-    launch_queue_probe_empty(b);
-    if (e == hipSuccess) e = hipEventRecord(e1, b);
-    if (e == hipSuccess) e = hipStreamSynchronize(a);
-    if (e == hipSuccess) e = hipStreamSynchronize(b);
-  }
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  if (e != hipSuccess) rc = hip_fail(e, "queue probe", __FILE__, __LINE__);
-  *overlap = ms < 0.5 * wait_ms;
-  return rc;
-}
-// a new stream whose kernels run concurrently with those of every stream in `with` (up to 12 candidates: the runtime hands out its
-// queues round robin, so a few rejected candidates later one on a free queue comes up); none found -- fewer hardware queues than
-// streams wanted (GPU_MAX_HW_QUEUES) --: the last candidate, counted in ctx->streams_sharing_a_queue
-static int create_concurrent_stream(dsm_context *ctx, const std::vector<hipStream_t> &with, hipStream_t *out) {
-  std::vector<hipStream_t> rejected;
-  hipStream_t found = nullptr;
-  int rc = DSM_OK;
-  for (int attempt = 0; attempt < 12 && !found && rc == DSM_OK; attempt++) {
-    hipStream_t st;
-    const hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-      rc = hip_fail(e, "hipStreamCreateWithFlags", __FILE__, __LINE__);
-      break;
-    }
-    bool ok = true;
-    for (size_t i = 0; i < with.size() && ok && rc == DSM_OK; i++) rc = streams_overlap(ctx, with[i], st, &ok);
-    if (ok && rc == DSM_OK)
-      found = st;
-    else
-      rejected.push_back(st);
-  }
-  if (!found && rc == DSM_OK && !rejected.empty()) {
-    found = rejected.back();
-    rejected.pop_back();
-    ctx->streams_sharing_a_queue++;
-  }
-  for (hipStream_t st : rejected) hipStreamDestroy(st);
-  *out = found;
-  return rc;
-}
-
-int ensure_streams(dsm_context *ctx, int ng, bool companion) {
-  auto in_use = [&]() {
-    std::vector<hipStream_t> v{ctx->stream};
-    v.insert(v.end(), ctx->extra_streams.begin(), ctx->extra_streams.end());
-    if (ctx->companion_stream) v.push_back(ctx->companion_stream);
-    return v;
-  };
-  while ((int)ctx->extra_streams.size() < ng - 1) { // (the groups first: they carry the large kernels)
-    hipStream_t st;
-    const int rc = create_concurrent_stream(ctx, in_use(), &st);
-    if (rc) return rc;
-    ctx->extra_streams.push_back(st);
-    hipEvent_t ev;
-    DSM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    ctx->join_events.push_back(ev);
-  }
-  if (companion && !ctx->companion_stream) {
-    const int rc = create_concurrent_stream(ctx, in_use(), &ctx->companion_stream);
-    if (rc) return rc;
-    DSM_HIP(hipEventCreateWithFlags(&ctx->companion_event, hipEventDisableTiming));
-  }
-  return DSM_OK;
-}
-
-// timing enabled: per-level sums and interval unions of the eval dispatches bracketed by ev_pool[2 i], ev_pool[2 i + 1]
-// (level ev_lvl[i]), relative to ev_total[0] (the stream groups' dispatches overlap; the union is the time during which the
-// level's kernel ran at all)
-void collect_eval_timing(dsm_context *ctx, const std::vector<int> &ev_lvl, int nlevels, dsm_stats &st) {
-  std::vector<std::pair<float, float>> iv[DSM_MAX_LEVELS];
-  for (size_t i = 0; i < ev_lvl.size(); i++) {
-    float m = 0, a = 0;
-    if (hipEventElapsedTime(&m, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]) == hipSuccess &&
-        hipEventElapsedTime(&a, ctx->ev_total[0], ctx->ev_pool[2 * i]) == hipSuccess) {
-      st.eval_kernel_ms[ev_lvl[i]] += m;
-      st.eval_dispatches[ev_lvl[i]]++;
-      iv[ev_lvl[i]].push_back(std::make_pair(a, a + m));
-    }
-  }
-  for (int l = 0; l < nlevels; l++) {
-    std::sort(iv[l].begin(), iv[l].end());
-    double busy = 0, cs = 0, ce = -1;
-    for (auto &p : iv[l]) {
-      if (ce < 0) {
-        cs = p.first, ce = p.second;
-      } else if (p.first > ce) {
-        busy += ce - cs;
-        cs = p.first, ce = p.second;
-      } else if (p.second > ce)
-        ce = p.second;
-    }
-    if (ce >= 0) busy += ce - cs;
-    st.eval_kernel_union_ms[l] += busy; // (+=: a stream's statistics are cumulative; the batch calls clear theirs per call)
-  }
-}
-} // namespace dsm
-extern "C" {
-
-// fork: the extra streams (and the companion's) start after everything enqueued on the main stream so far
-static int fork_from_main(dsm_context *ctx, int ng, bool companion) {
-  if (ng > 1 || companion) {
-    DSM_HIP(hipEventRecord(ctx->fork_event, ctx->stream));
-    for (int g = 1; g < ng; g++) DSM_HIP(hipStreamWaitEvent(ctx->extra_streams[g - 1], ctx->fork_event, 0));
-    if (companion) DSM_HIP(hipStreamWaitEvent(ctx->companion_stream, ctx->fork_event, 0));
-  }
-  return DSM_OK;
-}
 
 // Work-queue form: one launch of persistent workgroups for the whole call (queue_kernel).  Scheduling only:
 // results are bit-identical to the launch-per-step form (run_passes).
@@ -1341,10 +1185,9 @@ static int run_queue(dsm_context *ctx, dsm_tracker *const *ts, int n, int mode, 
   size_t qcap = 1024; // outstanding items <= problems x chunks of one evaluation: a problem has one evaluation in flight
   while (qcap < (size_t)n * max_items) qcap <<= 1;
   if (qcap > ctx->qcap) {
-    if (ctx->d_qitems) DSM_HIP(hipFree(ctx->d_qitems));
-    ctx->d_qitems = nullptr;
     ctx->qcap = 0;
-    DSM_HIP(hipMalloc(&ctx->d_qitems, qcap * sizeof(unsigned long long)));
+    const int rc = realloc_dev(&ctx->d_qitems, qcap);
+    if (rc) return rc;
     ctx->qcap = qcap;
   }
   if (!ctx->d_queue) DSM_HIP(hipMalloc(&ctx->d_queue, sizeof(WorkQueue)));
@@ -1389,23 +1232,15 @@ static int queue_outcome(dsm_context *ctx) {
 // chunk runs its LM loop in one launch, down to its first level of several chunks.  One launch per stream group and one for the
 // companion segment.  top / top2 (in: the coarsest level, -1 for no companion): the first level of each segment that the
 // launch-per-step schedule has to run.
-static int run_chain_prefix(dsm_context *ctx, dsm_tracker *const *ts, int n, int n2, int mode, int mode2, int coarsest, int ng, int &top,
-                            int &top2) {
+static int run_chain_prefix(dsm_context *ctx, dsm_tracker *const *ts, int n, int n2, const std::vector<Seg> &segs, int coarsest, int &top, int &top2) {
   const int N = n + n2;
   auto one_chunk = [&](int i, int L) { return level_chunks(ts[i]->desc, L) <= 1; };
   bool any = false;
   for (int i = 0; i < N && !any; i++) any = one_chunk(i, coarsest);
   if (!any) return DSM_OK;
-  {
-    const int rc = fork_from_main(ctx, ng, top2 >= 0);
-    if (rc) return rc;
-  }
-  for (int g = 0; g < ng; g++) {
-    const int g0 = (int)((long long)n * g / ng), g1 = (int)((long long)n * (g + 1) / ng);
-    if (g1 <= g0) continue;
-    launch_chain(g == 0 ? ctx->stream : ctx->extra_streams[g - 1], mode, g1 - g0, ctx->d_tracker_ptrs + g0, ctx->d_states + g0, ctx->d_status + 2 * g0);
-  }
-  if (n2 > 0) launch_chain(ctx->companion_stream, mode2, n2, ctx->d_tracker_ptrs + n, ctx->d_states + n, ctx->d_status + 2 * n);
+  const int rc = fork_segments(ctx, segs, top2 >= 0);
+  if (rc) return rc;
+  for (const Seg &sg : segs) launch_chain(sg.st, sg.mode, sg.i1 - sg.i0, ctx->d_tracker_ptrs + sg.i0, ctx->d_states + sg.i0, ctx->d_status + 2 * sg.i0);
   ctx->stats.coarse_launches = 1;
   auto first_launch_level = [&](int i0, int i1) { // (the launch-per-step schedule starts at the first level some problem cannot chain through)
     int t = -1;
@@ -1429,16 +1264,19 @@ static int run_chain_prefix(dsm_context *ctx, dsm_tracker *const *ts, int n, int
 // read back ONCE per pass.  Problems that finish a level early idle through the remaining
 // launches (their workgroups exit on the first instruction); problems that need more simply stay
 // at their level and are continued by the next pass.  Results do not depend on the schedule.
-// top / top2: the first level of the main / companion segment (-1: nothing to run); ev_lvl: the level of each timed eval dispatch.
-static int run_passes(dsm_context *ctx, dsm_tracker *const *ts, int n, int n2, int mode, int mode2, int ng, int top, int top2,
-                      std::vector<int> &ev_lvl) {
-  const int nlevels = ts[0]->nlevels;
-  const dsm_params &P = ts[0]->params;
-  const int N = n + n2;
-  size_t ev_used = 0;
-  int rc_build = DSM_OK;
-  int worst[DSM_MAX_LEVELS], grid_x[DSM_MAX_LEVELS], level_pts[DSM_MAX_LEVELS];
-  bool spec[DSM_MAX_LEVELS];
+struct PassRun { // what the passes of one call share
+  dsm_context *ctx;
+  const dsm_params &P;
+  std::vector<Seg> &segs;
+  int mode, mode2;
+  LMBuffers B;
+  EvalTimer tm;
+  int worst[DSM_MAX_LEVELS]; // upper bound of evaluations at one level
+  RoundShape shape[DSM_MAX_LEVELS];
+};
+
+static void plan_levels(PassRun &run, dsm_tracker *const *ts, int N, int nlevels) {
+  dsm_context *ctx = run.ctx;
   for (int L = 0; L < nlevels; L++) {
     int max_chunks = 1, max_it = 0, max_n = 0;
     for (int i = 0; i < N; i++) {
@@ -1448,181 +1286,121 @@ static int run_passes(dsm_context *ctx, dsm_tracker *const *ts, int n, int n2, i
       const int it_i = ts[i]->params.fixed_schedule > 0 ? ts[i]->params.fixed_schedule : ts[i]->params.max_iterations[L];
       if (it_i > max_it) max_it = it_i;
     }
-    grid_x[L] = max_chunks < 8 ? max_chunks : round8(max_chunks);
-    level_pts[L] = max_n;
-    worst[L] = 2 * (7 + (max_it > 0 ? max_it : 0)); // upper bound of evaluations at one level
-    // Speculative second candidate (dsm_device.hpp): doubles the evaluation work of a step to save the launches of
-    // rejected steps.  It pays where a launch is latency- and not bandwidth-bound and rejections come in runs: the
-    // small levels (a few thousand points).  Measured (S2 dense, launch form): 64 frames +12 %, 512 frames +-0 %, one
-    // frame -1 % when applied to every level (the fine levels end on their first rejection), DESIGN.md section 4.3.
-    // "Latency-bound" is a property of the launch, not of the level alone: a stream group's launch over G problems of n points
-    // evaluates G * n points, and above about a million of them the doubled work costs more than the saved launches give back
-    // (S2 dense, 512 + 103 problems in two groups, level 3 = 2.3 M points per launch: 51.3-51.8 k frames/s with the second
-    // candidate there, 52.3-52.6 k without; levels 4 and 5, 0.58 M and 0.14 M points, make no measurable difference).
-    {
-      int groups = ctx->n_streams < 1 ? 1 : ctx->n_streams;
-      if (groups > N) groups = N;
-      const long long launch_points = (long long)((N + groups - 1) / groups) * max_n;
-      spec[L] = P.fixed_schedule <= 0 && (P.speculate >= 2 || (P.speculate == 1 && max_n <= 8192 && launch_points <= 1000000ll));
-    }
+    run.worst[L] = 2 * (7 + (max_it > 0 ? max_it : 0));
+    // the points of one launch, for the speculative candidate's rule: a stream group's share of the call's problems
+    int groups = ctx->n_streams < 1 ? 1 : ctx->n_streams;
+    if (groups > N) groups = N;
+    run.shape[L] = RoundShape{max_chunks < 8 ? max_chunks : round8(max_chunks), max_n, (long long)((N + groups - 1) / groups) * max_n, 0, false};
   }
-  const int *sched = ctx->sched[mode], *sched2 = ctx->sched[mode2];
-  const int *bulk = ctx->sched_bulk[mode], *bulk2 = ctx->sched_bulk[mode2];
-  // Segments of the launch schedule: the stream groups of the main batch (the batch is split into `ng` contiguous groups,
-  // each with its own HIP stream: a group's lm_kernel -- one small workgroup per problem -- and its small-level eval kernels
-  // leave most of the chip idle; another group's kernels fill it) and the companion segment.  Per-problem results do not
-  // depend on the split.
-  struct Seg {
-    hipStream_t st;
-    int i0, i1, mode;
-    bool companion;
-    int rows; // >= 0: compact launches over the first `rows` entries of the segment's row map; -1: one row per problem
+}
+
+// one (evaluate, step) round of a segment at level L: the fused step for segments of few problems and for compact launches
+static int batch_round(PassRun &run, const Seg &sg, int L, int k) {
+  RoundShape R = run.shape[L];
+  R.fuse_count = sg.i1 - sg.i0;
+  R.fuse_also = sg.rows[L] >= 0;
+  return launch_round(run.ctx, run.B, run.P, sg, L, k, run.ctx->d_rowmap + sg.i0, R, run.tm);
+}
+
+// row map of a segment: the problems (relative to its first) for which `keep(status, level)` holds, from h_status
+template <typename Keep>
+static int build_rowmap(dsm_context *ctx, const Seg &sg, Keep keep, int *rows) {
+  int r = 0;
+  for (int i = sg.i0; i < sg.i1; i++)
+    if (keep(ctx->h_status[2 * i], ctx->h_status[2 * i + 1])) ctx->h_rowmap[sg.i0 + r++] = i - sg.i0;
+  *rows = r;
+  if (r > 0) DSM_HIP(hipMemcpyAsync(ctx->d_rowmap + sg.i0, ctx->h_rowmap + sg.i0, sizeof(int) * r, hipMemcpyHostToDevice, sg.st));
+  return DSM_OK;
+}
+
+// Level L of a pass; steps / steps2: the rounds of the main segments / the companion.
+// Phase A: the rounds most problems need (up to the third quartile of what recent calls' problems took), one row per
+// problem.  Phase B, first pass only: ONE read-back of the level's status, then the remaining rounds as compact
+// launches over the problems still at this level -- the stragglers (a level's last rounds are needed by a handful of
+// problems: 52 launches at levels 2 and 3 of 512 distinct S2 frames where the median problem needs 6 and 10).
+static int run_level(PassRun &run, int L, int pass, bool compact_ok, int steps, int steps2) {
+  dsm_context *ctx = run.ctx;
+  std::vector<Seg> &segs = run.segs;
+  auto seg_steps = [&](const Seg &sg) { return sg.companion ? steps2 : steps; };
+  auto seg_bulk = [&](const Seg &sg) {
+    const int st = seg_steps(sg), bk = ctx->sched_bulk[sg.companion ? run.mode2 : run.mode][L];
+    const bool worth = compact_ok && pass == 0 && sg.i1 - sg.i0 >= 32 && (long long)run.shape[L].grid_x * (sg.i1 - sg.i0) >= 1024 && st - bk >= 3;
+    return worth ? bk : st;
   };
-  std::vector<Seg> segs;
-  for (int g = 0; g < ng; g++) {
-    const int g0 = (int)((long long)n * g / ng), g1 = (int)((long long)n * (g + 1) / ng);
-    if (g1 > g0) segs.push_back(Seg{g == 0 ? ctx->stream : ctx->extra_streams[g - 1], g0, g1, mode, false, -1});
-  }
-  if (n2 > 0) segs.push_back(Seg{ctx->companion_stream, n, N, mode2, true, -1});
-  // one (evaluate, step) round of a segment at level L
-  auto launch_round = [&](const Seg &sg, int L, int k, int pass) -> int {
-    const int np = sg.i1 - sg.i0, rows = sg.rows >= 0 ? sg.rows : np;
-    if (rows == 0) return DSM_OK;
-    const int *rowmap = sg.rows >= 0 ? ctx->d_rowmap + sg.i0 : nullptr;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (ctx->timing && !sg.companion) {
-      ea = get_event(ctx, ev_used++);
-      eb = get_event(ctx, ev_used++);
-      ev_lvl.push_back(L);
-      if (ea) DSM_HIP(hipEventRecord(ea, sg.st));
+  int kmax = 0;
+  for (const Seg &sg : segs) kmax = seg_bulk(sg) > kmax ? seg_bulk(sg) : kmax;
+  for (int k = 0; k < kmax; k++)
+    for (int si = (int)segs.size() - 1; si >= 0; si--) { // (the companion's round first, as before)
+      const Seg &sg = segs[si];
+      if (k < seg_bulk(sg)) {
+        const int rc = batch_round(run, sg, L, k);
+        if (rc) return rc;
+      }
     }
-    // levels >= 1: the eval kernel's last-arriving workgroup per problem can perform the LM step itself (one launch per
-    // round instead of two): for launches of few problems -- small batches (measured: -6 % latency for one frame in flight,
-    // -11 % throughput at 256) and compact launches over a handful of stragglers.
-    // (Measured on 512 all-distinct S2 frames, same box: fused compact rounds 39.7-40.2 k frames/s, pairs above 8 rows
-    // 38.6-38.8 k, the speculative candidate on every level of the compact rounds 38.9 k: the pair's second launch and the
-    // doubled rows cost what they save.)
-    const bool fused = L > 0 && (P.fuse_lm >= 2 || (P.fuse_lm == 1 && (np <= 8 || sg.rows >= 0)));
-    // Large levels: the residual-only evaluations (the level's last ones, tracker_kernels.hip) get a launch of their own
-    // behind the full ones -- an instantiation without the 45 accumulators, 30-41 VGPRs = eight waves per SIMD instead
-    // of four or five.  Never in a level's first round (its evaluation is the level's first).  Measured (S2 dense, 512
-    // frames): level-0 evaluations 4.62 -> 4.40 ms per step, 54.3 -> 55.7 k frames/s with levels 0 and 1 split; with
-    // level 2 as well 53.7-55.3 k (the extra launch costs more than it gives there); one frame in flight 0.70 -> 0.74 ms
-    // (three more launches), hence the floor on the points per launch.
-    const bool split_ro = !sg.companion && !fused && k > 0 && level_pts[L] >= 100000 && (long long)rows * level_pts[L] >= 8000000ll;
-    launch_eval(sg.st, sg.mode, L, grid_x[L], rows, ctx->d_tracker_ptrs + sg.i0, ctx->d_states + sg.i0,
-                ctx->d_partials + (size_t)sg.i0 * ctx->partial_stride, ctx->partial_stride, fused ? ctx->d_tickets + sg.i0 : nullptr,
-                ctx->d_status + 2 * sg.i0, spec[L], split_ro, rowmap);
-    if (eb) DSM_HIP(hipEventRecord(eb, sg.st));
-    if (!fused)
-      launch_lm(sg.st, sg.mode, LM_OP_STEP, L, rows, ctx->d_tracker_ptrs + sg.i0, ctx->d_states + sg.i0,
-                ctx->d_partials + (size_t)sg.i0 * ctx->partial_stride, ctx->partial_stride, nullptr, nullptr, ctx->d_status + 2 * sg.i0,
-                spec[L], rowmap);
-    return DSM_OK;
+  bool any_tail = false;
+  for (const Seg &sg : segs) any_tail = any_tail || seg_bulk(sg) < seg_steps(sg);
+  if (!any_tail) return DSM_OK;
+  for (const Seg &sg : segs)
+    if (seg_bulk(sg) < seg_steps(sg))
+      DSM_HIP(hipMemcpyAsync(ctx->h_status + 2 * sg.i0, ctx->d_status + 2 * sg.i0, sizeof(int) * 2 * (sg.i1 - sg.i0), hipMemcpyDeviceToHost, sg.st));
+  // the segments in the order their read-backs complete (the others keep their queues busy meanwhile): whichever stream is
+  // idle already, else the first one still pending
+  std::vector<char> tail_done(segs.size(), 0);
+  DSM_HIP(hipGetLastError()); // (launch errors so far; a "not ready" answer below is consumed where it is returned)
+  auto idle = [](hipStream_t st) {
+    const hipError_t q = hipStreamQuery(st);
+    if (q == hipErrorNotReady) (void)hipGetLastError();
+    return q == hipSuccess;
   };
-  // row map of a segment: the problems (relative to its first) for which `keep(status, level)` holds, from h_status
-  auto build_rowmap = [&](Seg &sg, auto keep) -> int {
-    int r = 0;
-    for (int i = sg.i0; i < sg.i1; i++)
-      if (keep(ctx->h_status[2 * i], ctx->h_status[2 * i + 1])) ctx->h_rowmap[sg.i0 + r++] = i - sg.i0;
-    sg.rows = r;
-    if (r > 0) DSM_HIP(hipMemcpyAsync(ctx->d_rowmap + sg.i0, ctx->h_rowmap + sg.i0, sizeof(int) * r, hipMemcpyHostToDevice, sg.st));
-    return DSM_OK;
-  };
+  for (size_t done = 0; done < segs.size(); done++) {
+    int pick = -1;
+    for (size_t si = 0; si < segs.size() && pick < 0; si++)
+      if (!tail_done[si] && (seg_bulk(segs[si]) >= seg_steps(segs[si]) || idle(segs[si].st))) pick = (int)si;
+    for (size_t si = 0; si < segs.size() && pick < 0; si++)
+      if (!tail_done[si]) pick = (int)si;
+    tail_done[pick] = 1;
+    Seg &sg = segs[pick];
+    const int kb = seg_bulk(sg), ks = seg_steps(sg);
+    if (kb >= ks) continue;
+    DSM_HIP(hipStreamSynchronize(sg.st));
+    int rc = build_rowmap(ctx, sg, [L](int st, int lv) { return st == ST_RUNNING && lv == L; }, &sg.rows[L]);
+    for (int k = kb; k < ks && !rc; k++) rc = batch_round(run, sg, L, k);
+    if (rc) return rc;
+  }
+  ctx->stats.polls++;
+  return DSM_OK;
+}
+
+// top / top2: the first level of the main / companion segment (-1: nothing to run)
+static int run_passes(PassRun &run, dsm_tracker *const *ts, int n, int n2, int top, int top2) {
+  dsm_context *ctx = run.ctx;
+  const dsm_params &P = run.P;
+  const int N = n + n2;
+  plan_levels(run, ts, N, ts[0]->nlevels);
+  const int *sched = ctx->sched[run.mode], *sched2 = ctx->sched[run.mode2];
   for (int pass = 0;; pass++) {
-    {
-      const int rc = fork_from_main(ctx, ng, top2 >= 0);
-      if (rc) return rc;
-    }
+    int rc = fork_segments(ctx, run.segs, top2 >= 0);
+    if (rc) return rc;
     // Later passes only continue what the previous one left unfinished: compact launches over the problems still running
     // (a launch over all problems of a batch costs ~1.6 ns per idle workgroup: 100 us for a level-0 grid of 512 problems).
     const bool compact_ok = P.adaptive_schedule != 0 && P.compact_tail != 0;
-    for (Seg &sg : segs) {
-      sg.rows = -1;
-      if (pass > 0 && compact_ok) {
-        rc_build = build_rowmap(sg, [](int st, int) { return st == ST_RUNNING; });
-        if (rc_build) return rc_build;
-      }
+    for (Seg &sg : run.segs) {
+      int rows = -1;
+      if (pass > 0 && compact_ok && (rc = build_rowmap(ctx, sg, [](int st, int) { return st == ST_RUNNING; }, &rows))) return rc;
+      std::fill(sg.rows, sg.rows + DSM_MAX_LEVELS, rows);
     }
     for (int L = top > top2 ? top : top2; L >= 0; L--) {
-      int steps = P.adaptive_schedule ? sched[L] << (pass > 3 ? 3 : pass) : worst[L];
-      if (steps > worst[L]) steps = worst[L];
-      if (steps < 1) steps = 1;
-      if (L > top) steps = 0;
-      int steps2 = 0;
-      if (L <= top2) {
-        steps2 = P.adaptive_schedule ? sched2[L] << (pass > 3 ? 3 : pass) : worst[L];
-        if (steps2 > worst[L]) steps2 = worst[L];
-        if (steps2 < 1) steps2 = 1;
-      }
-      // Phase A: the rounds most problems need (up to the third quartile of what recent calls' problems took), one row per
-      // problem.  Phase B, first pass only: ONE read-back of the level's status, then the remaining rounds as compact
-      // launches over the problems still at this level -- the stragglers (a level's last rounds are needed by a handful of
-      // problems: 52 launches at levels 2 and 3 of 512 distinct S2 frames where the median problem needs 6 and 10).
-      auto seg_steps = [&](const Seg &sg) { return sg.companion ? steps2 : steps; };
-      auto seg_bulk = [&](const Seg &sg) {
-        const int st = seg_steps(sg), bk = (sg.companion ? bulk2 : bulk)[L];
-        const bool worth = compact_ok && pass == 0 && sg.i1 - sg.i0 >= 32 && (long long)grid_x[L] * (sg.i1 - sg.i0) >= 1024 && st - bk >= 3;
-        return worth ? bk : st;
+      auto rounds = [&](const int *sch) {
+        const int s = P.adaptive_schedule ? sch[L] << (pass > 3 ? 3 : pass) : run.worst[L];
+        return s > run.worst[L] ? run.worst[L] : s < 1 ? 1 : s;
       };
-      int kmax = 0;
-      for (const Seg &sg : segs) kmax = seg_bulk(sg) > kmax ? seg_bulk(sg) : kmax;
-      for (int k = 0; k < kmax; k++)
-        for (int si = (int)segs.size() - 1; si >= 0; si--) { // (the companion's round first, as before)
-          const Seg &sg = segs[si];
-          if (k < seg_bulk(sg)) {
-            const int rc = launch_round(sg, L, k, pass);
-            if (rc) return rc;
-          }
-        }
-      bool any_tail = false;
-      for (const Seg &sg : segs) any_tail = any_tail || seg_bulk(sg) < seg_steps(sg);
-      if (any_tail) {
-        for (const Seg &sg : segs)
-          if (seg_bulk(sg) < seg_steps(sg))
-            DSM_HIP(hipMemcpyAsync(ctx->h_status + 2 * sg.i0, ctx->d_status + 2 * sg.i0, sizeof(int) * 2 * (sg.i1 - sg.i0), hipMemcpyDeviceToHost, sg.st));
-        // the segments in the order their read-backs complete (the others keep their queues busy meanwhile): whichever stream is
-        // idle already, else the first one still pending
-        std::vector<char> tail_done(segs.size(), 0);
-        DSM_HIP(hipGetLastError()); // (launch errors so far; a "not ready" answer below is consumed where it is returned)
-        auto idle = [](hipStream_t st) {
-          const hipError_t q = hipStreamQuery(st);
-          if (q == hipErrorNotReady) (void)hipGetLastError();
-          return q == hipSuccess;
-        };
-        for (size_t done = 0; done < segs.size(); done++) {
-          int pick = -1;
-          for (size_t si = 0; si < segs.size() && pick < 0; si++)
-            if (!tail_done[si] && (seg_bulk(segs[si]) >= seg_steps(segs[si]) || idle(segs[si].st))) pick = (int)si;
-          for (size_t si = 0; si < segs.size() && pick < 0; si++)
-            if (!tail_done[si]) pick = (int)si;
-          tail_done[pick] = 1;
-          Seg &sg = segs[pick];
-          const int kb = seg_bulk(sg), ks = seg_steps(sg);
-          if (kb >= ks) continue;
-          DSM_HIP(hipStreamSynchronize(sg.st));
-          rc_build = build_rowmap(sg, [L](int st, int lv) { return st == ST_RUNNING && lv == L; });
-          if (rc_build) return rc_build;
-          for (int k = kb; k < ks; k++) {
-            const int rc = launch_round(sg, L, k, pass);
-            if (rc) return rc;
-          }
-          sg.rows = -1; // the next level starts with one row per problem again
-        }
-        ctx->stats.polls++;
-      }
+      const int steps = L > top ? 0 : rounds(sched), steps2 = L > top2 ? 0 : rounds(sched2);
+      if ((rc = run_level(run, L, pass, compact_ok, steps, steps2))) return rc;
       ctx->stats.launches[L] += steps;
       ctx->stats2.launches[L] += steps2;
     }
     DSM_HIP(hipGetLastError()); // launch-configuration errors of the kernels enqueued above
-    for (int g = 1; g < ng; g++) { // join
-      DSM_HIP(hipEventRecord(ctx->join_events[g - 1], ctx->extra_streams[g - 1]));
-      DSM_HIP(hipStreamWaitEvent(ctx->stream, ctx->join_events[g - 1], 0));
-    }
-    if (top2 >= 0) {
-      DSM_HIP(hipEventRecord(ctx->companion_event, ctx->companion_stream));
-      DSM_HIP(hipStreamWaitEvent(ctx->stream, ctx->companion_event, 0));
-    }
+    if ((rc = join_segments(ctx, run.segs, top2 >= 0))) return rc;
     DSM_HIP(hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(int) * 2 * N, hipMemcpyDeviceToHost, ctx->stream));
     DSM_HIP(hipStreamSynchronize(ctx->stream));
     ctx->stats.polls++;
@@ -1659,24 +1437,19 @@ static int account_and_learn(dsm_context *ctx, dsm_tracker *const *ts, int n, in
       if ((int)S.rounds[l] > nd[l]) nd[l] = (int)S.rounds[l]; // launches this problem needed at the level
       st.evals[l] += S.evals[l];
       st.evals_residual_only[l] += S.evals_ro[l];
-      // compulsory bytes of one evaluation (what calcRes* reads): the template once + the target image once,
-      // or, for a sparse template, the four 12-byte taps of every point if that is less
-      const long long nl = ts[i]->desc.lv[l].n, img = 12ll * (ts[i]->w >> l) * (ts[i]->h >> l);
-      st.algorithmic_bytes += S.evals[l] * (16ll * nl + (48ll * nl < img ? 48ll * nl : img));
+      st.algorithmic_bytes += S.evals[l] * eval_bytes(ts[i], l);
     }
   }
   // the third quartile of the rounds per problem and level: where the next call's launches turn to the fused form
-  {
-    std::vector<int> r;
-    for (int seg = 0; seg < (n2 > 0 ? 2 : 1); seg++) {
-      const int i0 = seg ? n : 0, i1 = seg ? N : n;
-      int *dst = ctx->sched_bulk[seg ? mode2 : mode];
-      for (int l = 0; l < nlevels; l++) {
-        r.clear();
-        for (int i = i0; i < i1; i++) r.push_back((int)ctx->h_states[i].rounds[l]);
-        std::nth_element(r.begin(), r.begin() + (3 * r.size()) / 4, r.end());
-        dst[l] = r[(3 * r.size()) / 4] + 1;
-      }
+  std::vector<int> r;
+  for (int seg = 0; seg < (n2 > 0 ? 2 : 1); seg++) {
+    const int i0 = seg ? n : 0, i1 = seg ? N : n;
+    int *dst = ctx->sched_bulk[seg ? mode2 : mode];
+    for (int l = 0; l < nlevels; l++) {
+      r.clear();
+      for (int i = i0; i < i1; i++) r.push_back((int)ctx->h_states[i].rounds[l]);
+      std::nth_element(r.begin(), r.begin() + (3 * r.size()) / 4, r.end());
+      dst[l] = r[(3 * r.size()) / 4] + 1;
     }
   }
   // next call's schedule: what this batch needed plus one, decaying slowly towards it
@@ -1712,50 +1485,60 @@ static int run_lm_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mod
     launch_lm(ctx->stream, mode2, LM_OP_START, coarsest, n2, ctx->d_tracker_ptrs + n, ctx->d_states + n,
               ctx->d_partials + (size_t)n * ctx->partial_stride, ctx->partial_stride, ctx->d_start + n, nullptr, ctx->d_status + 2 * n);
   const bool use_queue = queue_wanted(P, n, n2, ts);
-  if (use_queue) {
-    const int rc = run_queue(ctx, ts, n, mode, coarsest);
-    if (rc) return rc;
-  }
+  int rc;
+  if (use_queue && (rc = run_queue(ctx, ts, n, mode, coarsest))) return rc;
   // the learnt "rounds most problems need" belong to calls of this size and form: another batch-size bucket (powers of four)
   // or form must not inherit them (a batch of hundreds following a single-frame call would switch to compact launches after
   // one round, covering almost every problem)
-  {
-    int bucket = 0;
-    for (int v = N; v >= 4; v >>= 2) bucket++;
-    const int key = bucket * 4 + (use_queue ? 2 : 0) + (P.persistent_coarse < 0 ? 1 : 0);
-    if (key != ctx->sched_bulk_key) {
-      for (int m = 0; m < 3; m++)
-        for (int l = 0; l < DSM_MAX_LEVELS; l++) ctx->sched_bulk[m][l] = 1 << 30;
-      ctx->sched_bulk_key = key;
-    }
+  int bucket = 0;
+  for (int v = N; v >= 4; v >>= 2) bucket++;
+  const int key = bucket * 4 + (use_queue ? 2 : 0) + (P.persistent_coarse < 0 ? 1 : 0);
+  if (key != ctx->sched_bulk_key) {
+    for (int m = 0; m < 3; m++)
+      for (int l = 0; l < DSM_MAX_LEVELS; l++) ctx->sched_bulk[m][l] = 1 << 30;
+    ctx->sched_bulk_key = key;
   }
-  int ng = ctx->n_streams < 1 ? 1 : ctx->n_streams;
-  if (ng > n) ng = n;
-  {
-    const int rc = ensure_streams(ctx, ng, n2 > 0);
-    if (rc) return rc;
-  }
-  std::vector<int> ev_lvl;
+  std::vector<Seg> segs = build_segments(ctx->n_streams, n, mode, n2, mode2);
+  if ((rc = bind_streams(ctx, segs))) return rc;
+  PassRun run{ctx, P, segs, mode, mode2,
+              LMBuffers{ctx->d_tracker_ptrs, ctx->d_states, ctx->d_partials, ctx->partial_stride, ctx->d_tickets, ctx->d_status}, EvalTimer{}, {}, {}};
   if (!use_queue) {
     int top = coarsest, top2 = n2 > 0 ? coarsest : -1;
-    int rc = P.persistent_coarse < 0 ? run_chain_prefix(ctx, ts, n, n2, mode, mode2, coarsest, ng, top, top2) : DSM_OK;
-    if (!rc) rc = run_passes(ctx, ts, n, n2, mode, mode2, ng, top, top2, ev_lvl);
+    rc = P.persistent_coarse < 0 ? run_chain_prefix(ctx, ts, n, n2, segs, coarsest, top, top2) : DSM_OK;
+    if (!rc) rc = run_passes(run, ts, n, n2, top, top2);
     if (rc) return rc;
   }
   DSM_HIP(hipMemcpyAsync(ctx->h_states, ctx->d_states, sizeof(LMState) * N, hipMemcpyDeviceToHost, ctx->stream));
   DSM_HIP(hipEventRecord(ctx->ev_total[1], ctx->stream));
   DSM_HIP(hipStreamSynchronize(ctx->stream));
-  if (use_queue) {
-    const int rc = queue_outcome(ctx);
-    if (rc) return rc;
-  }
+  if (use_queue && (rc = queue_outcome(ctx))) return rc;
   float ms = 0;
   DSM_HIP(hipEventElapsedTime(&ms, ctx->ev_total[0], ctx->ev_total[1]));
   ctx->stats.total_ms = ms;
   ctx->stats2.total_ms = ms;
-  if (ctx->timing) collect_eval_timing(ctx, ev_lvl, nlevels, ctx->stats);
+  if (ctx->timing) collect_eval_timing(ctx, run.tm.lvl, nlevels, ctx->stats);
   return account_and_learn(ctx, ts, n, n2, mode, mode2);
 }
+
+// the start values and the read-out of n track problems / n scale problems, as the batch calls' arguments hold them
+static void fill_track_starts(StartInfo *I, int n, const double *pose, const double *aff, const double *min_res, int coarsest) {
+  for (int i = 0; i < n; i++) fill_track_start(I[i], pose + 7 * i, aff + 2 * i, min_res ? min_res + DSM_MAX_LEVELS * i : nullptr, coarsest);
+}
+static void fill_scale_starts(StartInfo *I, int n, const float *scale, int coarsest) {
+  for (int i = 0; i < n; i++) fill_scale_start(I[i], scale[i], coarsest);
+}
+static void read_track_batch(const LMState *S, int n, double *pose_io, double *aff_io, double *last_residuals, double *flow_out, int *good) {
+  for (int i = 0; i < n; i++) {
+    read_track(S[i], pose_io + 7 * i, aff_io + 2 * i, good ? good + i : nullptr);
+    if (last_residuals) memcpy(last_residuals + DSM_MAX_LEVELS * i, S[i].last_residuals, sizeof(double) * DSM_MAX_LEVELS);
+    if (flow_out) memcpy(flow_out + 3 * i, S[i].flow, sizeof(double) * 3);
+  }
+}
+static void read_scale_batch(const LMState *S, int n, float *scale_io, float *err_out) {
+  for (int i = 0; i < n; i++) read_scale(S[i], scale_io + i, err_out ? err_out + i : nullptr);
+}
+
+extern "C" {
 
 int dsm_track_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, double *pose_io, double *aff_io,
                     int coarsest_lvl, const double *min_res_for_abort, double *last_residuals, double *flow_out,
@@ -1763,31 +1546,10 @@ int dsm_track_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, double *pos
   if (!pose_io || !aff_io) return invalid("dsm_track_batch: null pose/aff");
   int rc = prepare_batch(ctx, n, ts, 0);
   if (rc) return rc;
-  for (int i = 0; i < n; i++) {
-    StartInfo &I = ctx->h_start[i];
-    memset(&I, 0, sizeof I);
-    memcpy(I.pose, pose_io + 7 * i, sizeof I.pose);
-    memcpy(I.aff, aff_io + 2 * i, sizeof I.aff);
-    for (int l = 0; l < DSM_MAX_LEVELS; l++)
-      I.min_res[l] = min_res_for_abort ? min_res_for_abort[DSM_MAX_LEVELS * i + l] : std::numeric_limits<double>::quiet_NaN();
-    I.scale = 1.0f;
-    I.coarsest = coarsest_lvl;
-  }
+  fill_track_starts(ctx->h_start, n, pose_io, aff_io, min_res_for_abort, coarsest_lvl);
   rc = run_lm_batch(ctx, n, ts, 0, coarsest_lvl);
   if (rc) return rc;
-  for (int i = 0; i < n; i++) {
-    const LMState &S = ctx->h_states[i];
-    const bool ok = S.status == ST_GOOD;
-    // the reference writes lastToNew_out / aff_g2l_out at :612-613, i.e. also when the later
-    // affine plausibility checks (:615-626) fail, but not when a level aborts (:598)
-    if (S.status == ST_GOOD || S.status == ST_BAD_AFFINE) {
-      memcpy(pose_io + 7 * i, S.cur, sizeof(double) * 7);
-      memcpy(aff_io + 2 * i, S.aff_cur, sizeof(double) * 2);
-    }
-    if (last_residuals) memcpy(last_residuals + DSM_MAX_LEVELS * i, S.last_residuals, sizeof(double) * DSM_MAX_LEVELS);
-    if (flow_out) memcpy(flow_out + 3 * i, S.flow, sizeof(double) * 3);
-    if (good) good[i] = ok ? 1 : 0;
-  }
+  read_track_batch(ctx->h_states, n, pose_io, aff_io, last_residuals, flow_out, good);
   return DSM_OK;
 }
 
@@ -1803,21 +1565,10 @@ int dsm_optimize_scale_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, fl
   if (!scale_io) return invalid("dsm_optimize_scale_batch: null scale");
   int rc = prepare_batch(ctx, n, ts, 1);
   if (rc) return rc;
-  for (int i = 0; i < n; i++) {
-    StartInfo &I = ctx->h_start[i];
-    memset(&I, 0, sizeof I);
-    I.pose[3] = 1.0;
-    for (int l = 0; l < DSM_MAX_LEVELS; l++) I.min_res[l] = std::numeric_limits<double>::quiet_NaN();
-    I.scale = scale_io[i];
-    I.coarsest = coarsest_lvl;
-  }
+  fill_scale_starts(ctx->h_start, n, scale_io, coarsest_lvl);
   rc = run_lm_batch(ctx, n, ts, 1, coarsest_lvl);
   if (rc) return rc;
-  for (int i = 0; i < n; i++) {
-    const LMState &S = ctx->h_states[i];
-    scale_io[i] = S.scale_cur;                               // :954
-    if (err_out) err_out[i] = (float)S.last_residuals[0];    // :963
-  }
+  read_scale_batch(ctx->h_states, n, scale_io, err_out);
   return DSM_OK;
 }
 
@@ -1834,41 +1585,12 @@ int dsm_track_and_scale_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, d
   all.insert(all.end(), ts_scale, ts_scale + n_scale);
   int rc = prepare_batch(ctx, n, all.data(), 0, n_scale, 1);
   if (rc) return rc;
-  for (int i = 0; i < n; i++) {
-    StartInfo &I = ctx->h_start[i];
-    memset(&I, 0, sizeof I);
-    memcpy(I.pose, pose_io + 7 * i, sizeof I.pose);
-    memcpy(I.aff, aff_io + 2 * i, sizeof I.aff);
-    for (int l = 0; l < DSM_MAX_LEVELS; l++)
-      I.min_res[l] = min_res_for_abort ? min_res_for_abort[DSM_MAX_LEVELS * i + l] : std::numeric_limits<double>::quiet_NaN();
-    I.scale = 1.0f;
-    I.coarsest = coarsest_lvl;
-  }
-  for (int i = 0; i < n_scale; i++) {
-    StartInfo &I = ctx->h_start[n + i];
-    memset(&I, 0, sizeof I);
-    I.pose[3] = 1.0;
-    for (int l = 0; l < DSM_MAX_LEVELS; l++) I.min_res[l] = std::numeric_limits<double>::quiet_NaN();
-    I.scale = scale_io[i];
-    I.coarsest = coarsest_lvl;
-  }
+  fill_track_starts(ctx->h_start, n, pose_io, aff_io, min_res_for_abort, coarsest_lvl);
+  fill_scale_starts(ctx->h_start + n, n_scale, scale_io, coarsest_lvl);
   rc = run_lm_batch(ctx, n, all.data(), 0, coarsest_lvl, n_scale, 1);
   if (rc) return rc;
-  for (int i = 0; i < n; i++) {
-    const LMState &S = ctx->h_states[i];
-    if (S.status == ST_GOOD || S.status == ST_BAD_AFFINE) { // as dsm_track_batch
-      memcpy(pose_io + 7 * i, S.cur, sizeof(double) * 7);
-      memcpy(aff_io + 2 * i, S.aff_cur, sizeof(double) * 2);
-    }
-    if (last_residuals) memcpy(last_residuals + DSM_MAX_LEVELS * i, S.last_residuals, sizeof(double) * DSM_MAX_LEVELS);
-    if (flow_out) memcpy(flow_out + 3 * i, S.flow, sizeof(double) * 3);
-    if (good) good[i] = S.status == ST_GOOD ? 1 : 0;
-  }
-  for (int i = 0; i < n_scale; i++) {
-    const LMState &S = ctx->h_states[n + i];
-    scale_io[i] = S.scale_cur;                             // :954
-    if (err_out) err_out[i] = (float)S.last_residuals[0];  // :963
-  }
+  read_track_batch(ctx->h_states, n, pose_io, aff_io, last_residuals, flow_out, good);
+  read_scale_batch(ctx->h_states + n, n_scale, scale_io, err_out);
   return DSM_OK;
 }
 
@@ -1992,12 +1714,10 @@ int dsm_pose_estimator_estimate(dsm_pose_estimator *pe, int n_pts, const double 
   dsm_tracker *ts[1] = {t};
   rc = prepare_batch(ctx, 1, ts, 2);
   if (rc) return rc;
-  StartInfo &I = ctx->h_start[0];
-  memset(&I, 0, sizeof I);
-  se3_from_matrix(ref_to_new_io, I.pose); // SE3(R, t) constructor, :321-322
-  for (int l = 0; l < DSM_MAX_LEVELS; l++) I.min_res[l] = std::numeric_limits<double>::quiet_NaN();
-  I.scale = 1.0f;
-  I.coarsest = coarsest_lvl;
+  double pose0[7];
+  const double aff0[2] = {0.0, 0.0};
+  se3_from_matrix(ref_to_new_io, pose0); // SE3(R, t) constructor, :321-322
+  fill_track_start(ctx->h_start[0], pose0, aff0, nullptr, coarsest_lvl);
   rc = run_lm_batch(ctx, 1, ts, 2, coarsest_lvl);
   if (rc) return rc;
   const LMState &S = ctx->h_states[0];

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -125,12 +127,114 @@ struct dsm_undistorter {
 };
 
 namespace dsm {
+int invalid(const char *msg); // set_error + DSM_ERR_INVALID
 int ensure_batch_capacity(dsm_context *ctx, int nprob, int partial_stride);
 int ensure_stage(dsm_context *ctx, size_t floats);
 int sync_desc(dsm_tracker *t);
 int sync_descs(dsm_context *ctx, dsm_tracker *const *ts, int n);
 int check_ready(dsm_tracker *t, int mode);
+
+// a device / pinned array of n elements into *p, which is null or holds an earlier allocation (freed first)
+template <typename T>
+int realloc_dev(T **p, size_t n) {
+  if (*p) DSM_HIP(hipFree(*p));
+  *p = nullptr;
+  DSM_HIP(hipMalloc(p, n * sizeof(T)));
+  return DSM_OK;
+}
+template <typename T>
+int realloc_pinned(T **p, size_t n) {
+  if (*p) DSM_HIP(hipHostFree(*p));
+  *p = nullptr;
+  DSM_HIP(hipHostMalloc(p, n * sizeof(T), hipHostMallocDefault));
+  return DSM_OK;
+}
+
+// ---- lm_schedule.hip: what the schedulers of the LM kernels share (the batch form, run_lm_batch in dsm_capi.hip; the pass
+// engine and the tick engine of stream_capi.hip) ----
+
+// A segment of a launch schedule: problems (or slots) [i0, i1) of one mode on one HIP stream.  The main batch is split into
+// contiguous stream groups, each with its own HIP stream: a group's lm_kernel -- one small workgroup per problem -- and its
+// small-level eval kernels leave most of the chip idle; another group's kernels fill it.  The companion segment (the scale
+// problems next to the track problems) follows the groups.  Per-problem results do not depend on the split.
+struct Seg {
+  hipStream_t st;
+  int i0, i1, mode;
+  bool companion;
+  int rows[DSM_MAX_LEVELS]; // per level, >= 0: compact launches over the first `rows` entries of the segment's row map; -1: one row per problem
+};
+// n problems of `mode` in min(n_streams, n) contiguous groups, then n2 companion problems of `mode2`
+std::vector<Seg> build_segments(int n_streams, int n, int mode, int n2, int mode2);
+// segment 0 on the context's stream, the other groups on the extra streams, the companion on its own (created on first use)
+int bind_streams(dsm_context *ctx, std::vector<Seg> &segs);
+// fork: the other segments' streams start after everything enqueued on the main stream so far; join: the main stream waits for them
+int fork_segments(dsm_context *ctx, const std::vector<Seg> &segs, bool with_companion = true);
+int join_segments(dsm_context *ctx, const std::vector<Seg> &segs, bool with_companion = true);
+
+struct LMBuffers { // the arrays a scheduler's launches index by problem or slot (dsm_context's batch workspaces, dsm_stream's slot arrays)
+  TrackerDev **trackers;
+  LMState *states;
+  float *partials;
+  int partial_stride;
+  int *tickets, *status;
+};
+struct EvalTimer { // a timed call (dsm_context_set_timing): ev_pool[2 i], ev_pool[2 i + 1] bracket evaluation dispatch i, of level lvl[i]
+  size_t used = 0;
+  std::vector<int> lvl;
+};
 hipEvent_t get_event(dsm_context *ctx, size_t idx);
-int ensure_streams(dsm_context *ctx, int ng, bool companion);
+// timing on and a main segment: the next pair of events, the first recorded here, *end to be recorded behind the dispatch
+int timed_eval_begin(dsm_context *ctx, const Seg &sg, int L, EvalTimer &tm, hipEvent_t *end);
 void collect_eval_timing(dsm_context *ctx, const std::vector<int> &ev_lvl, int nlevels, dsm_stats &st);
+struct RoundShape { // what differs between the schedulers in one (evaluate, step) round; the rules are launch_round's
+  int grid_x, level_pts;   // of the level: chunks per row of the launch, points of the largest template
+  long long launch_points; // points one launch evaluates, as the scheduler counts them
+  int fuse_count;          // the fused step is for launches of few problems: this count is few ...
+  bool fuse_also;          // ... or this holds
+};
+// round k of level L of a segment; rowmap: the segment's row map for this level (read when sg.rows[L] >= 0)
+int launch_round(dsm_context *ctx, const LMBuffers &B, const dsm_params &P, const Seg &sg, int L, int k, const int *rowmap, const RoundShape &R,
+                 EvalTimer &tm);
+
+long long eval_bytes(const dsm_tracker *t, int lvl); // compulsory bytes of one evaluation (dsm_stats.algorithmic_bytes)
+void fill_track_start(StartInfo &I, const double pose[7], const double aff[2], const double *min_res, int coarsest); // min_res: NULL = no abort
+void fill_scale_start(StartInfo &I, float scale, int coarsest);
+bool wrote_pose(int status);
+
+// Outputs of a terminated problem; S: its LMState or its TickResult (the same field names).  pose / aff hold what the problem
+// started from and keep it unless the problem wrote them (wrote_pose).
+template <typename R>
+void read_track(const R &S, double pose[7], double aff[2], int *good) {
+  if (wrote_pose(S.status)) {
+    memcpy(pose, S.cur, sizeof(double) * 7);
+    memcpy(aff, S.aff_cur, sizeof(double) * 2);
+  }
+  if (good) *good = S.status == ST_GOOD ? 1 : 0;
+}
+template <typename R>
+void read_scale(const R &S, float *scale, float *err) {
+  *scale = S.scale_cur;                       // TrackerAndScaler.cpp:954
+  if (err) *err = (float)S.last_residuals[0]; // :963
+}
+template <typename R>
+void fill_stream_result(dsm_stream_result &r, const R &S, int mode, uint64_t ticket, int passes, const double *pose0, const double *aff0) {
+  memset(&r, 0, sizeof r);
+  r.ticket = ticket;
+  r.kind = mode;
+  r.status = S.status;
+  r.passes = passes;
+  if (mode == 0) {
+    memcpy(r.pose, pose0, sizeof r.pose);
+    memcpy(r.aff, aff0, sizeof r.aff);
+    read_track(S, r.pose, r.aff, &r.good);
+    memcpy(r.flow, S.flow, sizeof r.flow);
+    r.scale = 1.0f;
+  } else {
+    r.good = 1;
+    read_scale(S, &r.scale, &r.err);
+    r.pose[3] = 1.0;
+  }
+  memcpy(r.last_residuals, S.last_residuals, sizeof r.last_residuals);
+  for (int l = 0; l < DSM_MAX_LEVELS; l++) r.evals[l] = S.evals[l];
+}
 } // namespace dsm

@@ -25,11 +25,6 @@ using namespace dsm;
 
 namespace {
 
-int invalid(const char *m) {
-  set_error(m);
-  return DSM_ERR_INVALID;
-}
-
 constexpr unsigned long long kIcpNoKey = ~0ull; // no candidate yet: its distance bits are a NaN, which never passes a `<=` test
 
 // P5: ((r0 x + r1 y) + r2 z) + t per row, in float (-ffp-contract=off: no fused multiply-add)

@@ -33,11 +33,6 @@ using namespace dsm;
 
 namespace {
 
-int invalid(const char *m) {
-  set_error(m);
-  return DSM_ERR_INVALID;
-}
-
 constexpr int kLdThreads = 256;
 constexpr unsigned long long kEmptyKey = ~0ull;
 constexpr int kEmptyIdx = 0x7FFFFFFF;

@@ -14,11 +14,6 @@
 
 using namespace dsm;
 
-static int invalid(const char *m) {
-  set_error(m);
-  return DSM_ERR_INVALID;
-}
-
 static int rdb_reserve(dsm_ringdb *db, int64_t need_local) {
   if (need_local <= db->cap) return DSM_OK;
   int64_t ncap = db->cap > 0 ? db->cap : 1024;

@@ -7,17 +7,25 @@
 // LM loop of a frame is sequential (TrackerAndScaler.cpp:505-593); frames of different sequences are independent
 // (FrontEnd.cpp:585-686): the only parallelism there is lies ACROSS frames, and nothing says they must start and end together.
 //
-// A dsm_stream is a pool of resident LM problems (slots) advanced in PASSES.  One pass = one sweep down the pyramid,
-// coarsest level first, with a fixed number of rounds per level -- the rounds MOST problems need (a quantile of what
-// recently retired problems took).  A problem that has not finished its level when the pass moves on simply stays where it
-// is -- its LMState is resident in device memory and resumable by construction -- and is CARRIED: in the next pass it
-// rides with the newly admitted problems' launches at that level, so a straggler's extra rounds cost no launches of their
-// own.  Problems retire individually at the end of the pass in which they finish; the slots they free are refilled from the
-// waiting queue before the next pass.  No launch in a pass depends on a host read-back (the launch list is fixed when the
-// pass starts), the state is read back once per pass.
+// A dsm_stream is a pool of resident LM problems (slots: track slots first, then scale slots) with a waiting queue in front and
+// a result queue behind.  Problems take a slot when one is free and retire individually; dsm_stream_advance moves everything
+// resident forward, by one of two engines over the same slot states (dsm_stream_set_engine; a switch wants the stream empty):
+//  * TICK engine (engine 1, the default; tick_setup / tick_advance / tick_collect): one tick advances every resident problem by one
+//    LM round, whatever level it stands on -- per segment one evaluation launch over a device-built item list and one LM launch.
+//    Admission and retirement happen ON THE DEVICE: the host appends waiting problems to a ring, a slot freed by a retirement
+//    takes the next one on the spot, results come back through a result ring.  An advance is a number of ticks, PIPELINED: it
+//    returns once enqueued and reads back the advance before it.  One-chunk evaluations may run several rounds inside a tick
+//    (chains, dsm_stream_set_chain).
+//  * PASS engine (engine 0; pass_advance and its steps): one pass = one sweep down the pyramid, coarsest level first, with a
+//    fixed number of rounds per level -- the rounds MOST problems need (a quantile of what recently retired problems took).  A
+//    problem that has not finished its level when the pass moves on simply stays where it is -- its LMState is resident in
+//    device memory and resumable by construction -- and is CARRIED: in the next pass it rides with the newly admitted
+//    problems' launches at that level, so a straggler's extra rounds cost no launches of their own.  The host admits and
+//    retires between passes; no launch in a pass depends on a host read-back, the state is read back once per pass.
 //
-// Same evaluations, same LM steps, same partial order per problem as the batch form: results are bit-identical
-// (tests/test_stream.py).  The work-queue kernel -- every problem at its own pace inside one launch -- was the other
+// Same evaluations, same LM steps, same partial order per problem as the batch form, in either engine: results are
+// bit-identical (tests/test_stream.py); segments, fork / join, the (evaluate, step) round and the start / read-out rules are the
+// batch form's own (lm_schedule.hip).  The work-queue kernel -- every problem at its own pace inside one launch -- was the other
 // candidate for this; measured with the tail amortised over 2048 frames it runs at 42.7 k frames/s against 48.5 k for the
 // launch form (profiles/r04_queue_form_b2048.json, r04_launch_form_b2048.json): its per-item cost is there in steady
 // state too, so the streaming form is built on the launches.
@@ -29,7 +37,6 @@
 #include <cmath>
 #include <cstring>
 #include <deque>
-#include <limits>
 #include <unordered_map>
 #include <vector>
 
@@ -47,7 +54,6 @@ struct Slot {
   dsm_tracker *trk = nullptr;
   int lvl = 0;    // NEW: coarsest level; RUNNING: the level the problem stood at after the last pass
   int passes = 0; // passes it has been resident for
-  double pose0[7] = {0, 0, 0, 1, 0, 0, 0}, aff0[2] = {0, 0};
   long long seen_evals[DSM_MAX_LEVELS] = {}, seen_ro[DSM_MAX_LEVELS] = {}; // evaluations already counted in the statistics
 };
 
@@ -56,31 +62,6 @@ struct Waiting {
   dsm_tracker *trk;
   StartInfo start;
 };
-
-struct Seg {
-  hipStream_t st;
-  int i0, i1, mode;
-  bool companion;
-  int rows[DSM_MAX_LEVELS];
-};
-
-template <typename T>
-int alloc_dev(T **p, size_t n) {
-  *p = nullptr;
-  DSM_HIP(hipMalloc(p, n * sizeof(T)));
-  return DSM_OK;
-}
-template <typename T>
-int alloc_pinned(T **p, size_t n) {
-  *p = nullptr;
-  DSM_HIP(hipHostMalloc(p, n * sizeof(T), hipHostMallocDefault));
-  return DSM_OK;
-}
-
-int invalid(const char *msg) {
-  set_error(msg);
-  return DSM_ERR_INVALID;
-}
 
 constexpr size_t kHistCap = 4096; // retired problems whose round counts the schedule looks at
 
@@ -161,11 +142,10 @@ struct dsm_stream {
   long long handed[2] = {0, 0}; // problems appended to the device's waiting ring so far
   struct Seen {
     long long admitted, retired;
-    long long evals[DSM_MAX_LEVELS], ro[DSM_MAX_LEVELS];
   } seen[2];
   int inflight_parity[2] = {0, 0};
   bool inflight_timed[2] = {false, false}; // the advance was enqueued with per-dispatch events (dsm_context_set_timing)
-  std::vector<int> ev_lvl;
+  EvalTimer tm; // per-dispatch events of the advance in flight
   // scheduling switches of the problems in flight, BY VALUE (a tracker may be destroyed as soon as its own result is back -- ADVICE r04:
   // the stream used to keep a pointer into the first submitted tracker's params for its whole life); refreshed at every hand-over
   bool have_sched = false;
@@ -188,10 +168,13 @@ struct dsm_stream {
   int hyp_window = 0; // tries of a group waiting or resident at once after try 0; 0 = all
 };
 
+static void free_dev(void *p) { if (p) hipFree(p); }
+static void free_pinned(void *p) { if (p) hipHostFree(p); }
+
 // the tick engine's resources (tick_setup); safe on a partially set-up stream, leaves every pointer null
 static void tick_free(dsm_stream *s) {
-  auto dev = [](auto *&p) { if (p) hipFree(p); p = nullptr; };
-  auto pin = [](auto *&p) { if (p) hipHostFree(p); p = nullptr; };
+  auto dev = [](auto *&p) { free_dev(p), p = nullptr; };
+  auto pin = [](auto *&p) { free_pinned(p), p = nullptr; };
   dev(s->d_segctl), pin(s->h_segctl), dev(s->d_modectl), pin(s->h_modectl);
   for (unsigned *&p : s->d_items) dev(p);
   s->d_items.clear();
@@ -206,17 +189,8 @@ static void tick_free(dsm_stream *s) {
 }
 
 static void stream_free(dsm_stream *s) {
-  hipFree(s->d_tracker_ptrs);
-  if (s->h_tracker_ptrs) hipHostFree(s->h_tracker_ptrs);
-  hipFree(s->d_states);
-  if (s->h_states) hipHostFree(s->h_states);
-  hipFree(s->d_partials);
-  hipFree(s->d_start);
-  if (s->h_start) hipHostFree(s->h_start);
-  hipFree(s->d_status);
-  hipFree(s->d_tickets);
-  hipFree(s->d_rowmap);
-  if (s->h_rowmap) hipHostFree(s->h_rowmap);
+  free_dev(s->d_tracker_ptrs), free_pinned(s->h_tracker_ptrs), free_dev(s->d_states), free_pinned(s->h_states), free_dev(s->d_partials);
+  free_dev(s->d_start), free_pinned(s->h_start), free_dev(s->d_status), free_dev(s->d_tickets), free_dev(s->d_rowmap), free_pinned(s->h_rowmap);
   tick_free(s);
   delete s;
 }
@@ -230,14 +204,14 @@ static int stream_bind_geometry(dsm_stream *s, dsm_tracker *t) {
   DSM_HIP(hipSetDevice(s->ctx->device));
   s->w = t->w, s->h = t->h, s->nlevels = t->nlevels;
   const int ps = 2 * max_chunks_upto(t->w * t->h) * kPartialStride; // second half: the speculative candidate's partials
-  int rc = alloc_dev(&s->d_partials, (size_t)s->N * ps);
+  int rc = realloc_dev(&s->d_partials, (size_t)s->N * ps);
   if (rc) return rc;
   s->partial_stride = ps;
   return DSM_OK;
 }
 
 static int tick_advance(dsm_stream *s);
-static int tick_sync(dsm_stream *s);
+static int tick_sync(dsm_stream *s, long long upto = -1);
 
 extern "C" {
 
@@ -251,16 +225,16 @@ int dsm_stream_create(dsm_context *ctx, int track_slots, int scale_slots, dsm_st
   const int N = s->N = track_slots + scale_slots;
   s->slots.resize(N);
   int rc = DSM_OK;
-  if (!rc) rc = alloc_dev(&s->d_tracker_ptrs, N);
-  if (!rc) rc = alloc_pinned(&s->h_tracker_ptrs, N);
-  if (!rc) rc = alloc_dev(&s->d_states, N);
-  if (!rc) rc = alloc_pinned(&s->h_states, N);
-  if (!rc) rc = alloc_dev(&s->d_start, N);
-  if (!rc) rc = alloc_pinned(&s->h_start, N);
-  if (!rc) rc = alloc_dev(&s->d_status, 2 * (size_t)N);
-  if (!rc) rc = alloc_dev(&s->d_tickets, N);
-  if (!rc) rc = alloc_dev(&s->d_rowmap, (size_t)(DSM_MAX_LEVELS + 1) * N);
-  if (!rc) rc = alloc_pinned(&s->h_rowmap, (size_t)(DSM_MAX_LEVELS + 1) * N);
+  if (!rc) rc = realloc_dev(&s->d_tracker_ptrs, N);
+  if (!rc) rc = realloc_pinned(&s->h_tracker_ptrs, N);
+  if (!rc) rc = realloc_dev(&s->d_states, N);
+  if (!rc) rc = realloc_pinned(&s->h_states, N);
+  if (!rc) rc = realloc_dev(&s->d_start, N);
+  if (!rc) rc = realloc_pinned(&s->h_start, N);
+  if (!rc) rc = realloc_dev(&s->d_status, 2 * (size_t)N);
+  if (!rc) rc = realloc_dev(&s->d_tickets, N);
+  if (!rc) rc = realloc_dev(&s->d_rowmap, (size_t)(DSM_MAX_LEVELS + 1) * N);
+  if (!rc) rc = realloc_pinned(&s->h_rowmap, (size_t)(DSM_MAX_LEVELS + 1) * N);
   if (!rc) {
     hipError_t e = hipMemsetAsync(s->d_tickets, 0, sizeof(int) * N, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_states, 0, sizeof(LMState) * N, ctx->stream);
@@ -349,25 +323,22 @@ static int submit_common(dsm_stream *s, int mode, int n, dsm_tracker *const *ts,
 
 } // extern "C"
 
-// one trackNewestCoarse problem into the host's waiting queue (min_res: DSM_MAX_LEVELS thresholds, NULL = no abort); returns its ticket
-static uint64_t enqueue_track(dsm_stream *s, dsm_tracker *t, const double *pose0, const double *aff0, int coarsest_lvl, const double *min_res) {
-  Waiting wq;
-  wq.ticket = s->next_ticket++;
-  wq.trk = t;
-  StartInfo &I = wq.start;
-  memset(&I, 0, sizeof I);
-  memcpy(I.pose, pose0, sizeof I.pose);
-  memcpy(I.aff, aff0, sizeof I.aff);
-  for (int l = 0; l < DSM_MAX_LEVELS; l++) I.min_res[l] = min_res ? min_res[l] : std::numeric_limits<double>::quiet_NaN();
-  I.scale = 1.0f;
-  I.coarsest = coarsest_lvl;
+// a problem of kind `mode` into the host's waiting queue; returns its ticket
+static uint64_t enqueue(dsm_stream *s, int mode, dsm_tracker *t, const StartInfo &start) {
+  const Waiting wq{s->next_ticket++, t, start};
   dsm_stream::Origin og;
   og.trk = t, og.admitted_at = -1;
-  memcpy(og.pose0, I.pose, sizeof og.pose0);
-  memcpy(og.aff0, I.aff, sizeof og.aff0);
+  memcpy(og.pose0, start.pose, sizeof og.pose0);
+  memcpy(og.aff0, start.aff, sizeof og.aff0);
   s->origin[wq.ticket] = og;
-  s->waiting[0].push_back(wq);
+  s->waiting[mode].push_back(wq);
   return wq.ticket;
+}
+// one trackNewestCoarse problem (min_res: DSM_MAX_LEVELS thresholds, NULL = no abort)
+static uint64_t enqueue_track(dsm_stream *s, dsm_tracker *t, const double *pose0, const double *aff0, int coarsest_lvl, const double *min_res) {
+  StartInfo start;
+  fill_track_start(start, pose0, aff0, min_res, coarsest_lvl);
+  return enqueue(s, 0, t, start);
 }
 
 // ---- hypothesis groups ----
@@ -438,6 +409,253 @@ static void route_result(dsm_stream *s, const dsm_stream_result &r) {
   }
 }
 
+template <typename T>
+static int pop_results(std::deque<T> &q, int max_results, T *out) {
+  int k = 0;
+  for (; k < max_results && !q.empty(); q.pop_front()) out[k++] = q.front();
+  return k;
+}
+
+// ---- pass engine (engine 0) --------------------------------------------------------------------------------------------
+// One pass.  (i) waiting problems are admitted into free slots, (ii) their state machines are started, (iii) every level
+// from the coarsest a resident problem stands on down to level 0 gets its rounds -- compact launches over the slots that
+// can be at that level in this pass: the new ones and the carried ones standing at or above it -- (iv) the states are read
+// back once; problems that terminated retire (dsm_stream_results), the others are carried.
+struct Pass {
+  std::vector<Seg> segs;            // the track slots' stream groups, then the scale slots
+  std::vector<dsm_tracker *> fresh; // trackers of the problems admitted in this pass
+  int n_new[2] = {0, 0};
+  int n_live = 0, top = -1, top2 = -1; // resident problems; the coarsest level a track / a scale problem stands on
+  const dsm_params *P = nullptr;       // scheduling switches: those of the first resident problem
+  bool draining = false;
+  int grid_x[DSM_MAX_LEVELS], level_pts[DSM_MAX_LEVELS];
+  EvalTimer tm;
+};
+
+// (i) admission: a free slot of the problem's kind, in the stream group with the fewest resident problems
+static void pass_admit(dsm_stream *s, Pass &p) {
+  const int N = s->N, cap0 = s->cap[0];
+  std::vector<Seg> &segs = p.segs;
+  const int n_track_segs = (int)segs.size() - (s->cap[1] > 0 ? 1 : 0);
+  for (int mode = 0; mode < 2; mode++) {
+    std::deque<Waiting> &wq = s->waiting[mode];
+    if (wq.empty()) continue;
+    const int sg0 = mode == 0 ? 0 : n_track_segs, sg1 = mode == 0 ? n_track_segs : (int)segs.size();
+    std::vector<int> live(segs.size(), 0), cursor(segs.size(), 0);
+    for (int si = sg0; si < sg1; si++) {
+      cursor[si] = segs[si].i0;
+      for (int i = segs[si].i0; i < segs[si].i1; i++) live[si] += s->slots[i].state != SLOT_FREE;
+    }
+    while (!wq.empty()) {
+      int best = -1;
+      for (int si = sg0; si < sg1; si++)
+        if (live[si] < segs[si].i1 - segs[si].i0 && (best < 0 || live[si] < live[best])) best = si;
+      if (best < 0) break; // every slot of this kind is taken
+      int &c = cursor[best];
+      while (s->slots[c].state != SLOT_FREE) c++;
+      const Waiting &wt = wq.front();
+      Slot &sl = s->slots[c];
+      sl = Slot();
+      sl.state = SLOT_NEW;
+      sl.ticket = wt.ticket;
+      sl.trk = wt.trk;
+      sl.lvl = wt.start.coarsest;
+      s->h_start[c] = wt.start;
+      s->h_tracker_ptrs[c] = wt.trk->d_desc;
+      s->h_rowmap[(size_t)DSM_MAX_LEVELS * N + (mode == 0 ? 0 : cap0) + p.n_new[mode]] = c - (mode == 0 ? 0 : cap0);
+      p.n_new[mode]++;
+      p.fresh.push_back(wt.trk);
+      live[best]++;
+      wq.pop_front();
+    }
+  }
+}
+
+// what is resident after the admission; false: nothing
+static bool pass_survey(dsm_stream *s, Pass &p) {
+  for (int i = 0; i < s->N; i++) {
+    const Slot &sl = s->slots[i];
+    if (sl.state == SLOT_FREE) continue;
+    p.n_live++;
+    if (!p.P) p.P = &sl.trk->params;
+    if (i < s->cap[0])
+      p.top = sl.lvl > p.top ? sl.lvl : p.top;
+    else
+      p.top2 = sl.lvl > p.top2 ? sl.lvl : p.top2;
+  }
+  // Nothing is waiting and the pool is at most a quarter full: what is resident is the END of the job -- nothing rides with
+  // the stragglers any more, so a pass gives every level the rounds the slowest retired problem needed (they finish in one or
+  // two passes instead of one level per pass) and evaluates and steps in one fused launch per round.
+  p.draining = s->waiting[0].empty() && s->waiting[1].empty() && 4 * p.n_live <= s->N;
+  return p.n_live > 0;
+}
+
+// row maps: level L of segment sg = its slots that can stand on level L during this pass
+static int pass_row_maps(dsm_stream *s, Pass &p) {
+  const int N = s->N;
+  for (int L = 0; L < s->nlevels; L++) {
+    int max_chunks = 1, max_n = 0;
+    for (int i = 0; i < N; i++) {
+      const Slot &sl = s->slots[i];
+      if (sl.state == SLOT_FREE) continue;
+      const int n_l = sl.trk->desc.lv[L].n, c = level_chunks(sl.trk->desc, L);
+      if (c > max_chunks) max_chunks = c;
+      if (n_l > max_n) max_n = n_l;
+    }
+    p.grid_x[L] = max_chunks < 8 ? max_chunks : (max_chunks + 7) & ~7;
+    p.level_pts[L] = max_n;
+    for (Seg &sg : p.segs) {
+      int r = 0;
+      for (int i = sg.i0; i < sg.i1; i++)
+        if (s->slots[i].state != SLOT_FREE && s->slots[i].lvl >= L) s->h_rowmap[(size_t)L * N + sg.i0 + r++] = i - sg.i0;
+      sg.rows[L] = r;
+    }
+  }
+  DSM_HIP(hipMemcpyAsync(s->d_rowmap, s->h_rowmap, sizeof(int) * (size_t)(DSM_MAX_LEVELS + 1) * N, hipMemcpyHostToDevice, s->ctx->stream));
+  return DSM_OK;
+}
+
+// (ii) start the admitted problems (LM_OP_START over the list of new slots of each kind)
+static int pass_start_admitted(dsm_stream *s, const Pass &p) {
+  dsm_context *ctx = s->ctx;
+  const int N = s->N;
+  if (p.n_new[0] + p.n_new[1] == 0) return DSM_OK;
+  DSM_HIP(hipMemcpyAsync(s->d_tracker_ptrs, s->h_tracker_ptrs, sizeof(TrackerDev *) * N, hipMemcpyHostToDevice, ctx->stream));
+  DSM_HIP(hipMemcpyAsync(s->d_start, s->h_start, sizeof(StartInfo) * N, hipMemcpyHostToDevice, ctx->stream));
+  for (int mode = 0; mode < 2; mode++) {
+    if (!p.n_new[mode]) continue;
+    const int base = mode == 0 ? 0 : s->cap[0];
+    launch_lm(ctx->stream, mode, LM_OP_START, 0, p.n_new[mode], s->d_tracker_ptrs + base, s->d_states + base,
+              s->d_partials + (size_t)base * s->partial_stride, s->partial_stride, s->d_start + base, nullptr, s->d_status + 2 * base, false,
+              s->d_rowmap + (size_t)DSM_MAX_LEVELS * N + base);
+  }
+  return DSM_OK;
+}
+
+// (iii) the pass: the other segments' streams start behind the uploads and the START launches
+static int pass_rounds(dsm_stream *s, Pass &p) {
+  dsm_context *ctx = s->ctx;
+  const LMBuffers B{s->d_tracker_ptrs, s->d_states, s->d_partials, s->partial_stride, s->d_tickets, s->d_status};
+  int rc = fork_segments(ctx, p.segs);
+  if (rc) return rc;
+  for (int L = p.top > p.top2 ? p.top : p.top2; L >= 0; L--) {
+    auto seg_rounds = [&](const Seg &sg) {
+      int r = s->fixed_rounds[sg.mode][L] > 0 ? s->fixed_rounds[sg.mode][L] : p.draining ? s->rounds_max[sg.mode][L] : s->rounds[sg.mode][L];
+      if (p.P->fixed_schedule > 0) r = 1 + p.P->fixed_schedule; // the benchmark schedule: every problem needs exactly 1 + K rounds
+      return r < 1 ? 1 : r;
+    };
+    int kmax = 0;
+    for (const Seg &sg : p.segs)
+      if (sg.rows[L] > 0 && seg_rounds(sg) > kmax) kmax = seg_rounds(sg);
+    for (int k = 0; k < kmax; k++)
+      for (int si = (int)p.segs.size() - 1; si >= 0; si--) { // (the companion's round first, as in run_lm_batch)
+        const Seg &sg = p.segs[si];
+        if (k >= seg_rounds(sg)) continue;
+        // a launch's points are its rows'; the fused step also for the drain's launches of up to 128 rows
+        const int rows = sg.rows[L];
+        const RoundShape R{p.grid_x[L], p.level_pts[L], (long long)rows * p.level_pts[L], rows, p.draining && rows <= 128};
+        if ((rc = launch_round(ctx, B, *p.P, sg, L, k, s->d_rowmap + (size_t)L * s->N + sg.i0, R, p.tm))) return rc;
+      }
+    for (const Seg &sg : p.segs)
+      if (sg.rows[L] > 0) s->stats[sg.mode].launches[L] += seg_rounds(sg);
+  }
+  DSM_HIP(hipGetLastError());
+  return join_segments(ctx, p.segs);
+}
+
+// a resident problem has terminated: its result, its rounds into the schedule's history, its slot free
+static void pass_retire(dsm_stream *s, Slot &sl, const LMState &S, int mode) {
+  dsm_stream_result r;
+  const auto og = s->origin.find(sl.ticket); // (what the problem started from: kept since its submission)
+  fill_stream_result(r, S, mode, sl.ticket, sl.passes, og->second.pose0, og->second.aff0);
+  s->origin.erase(og);
+  route_result(s, r);
+  s->retired[mode]++;
+  for (int l = 0; l < s->nlevels; l++) {
+    std::vector<int> &hv = s->hist[mode][l];
+    if (hv.size() < kHistCap)
+      hv.push_back((int)S.rounds[l]);
+    else
+      hv[s->hist_pos[mode] % kHistCap] = (int)S.rounds[l];
+  }
+  s->hist_pos[mode]++;
+  sl = Slot();
+}
+
+// (iv) one read-back; what THIS pass evaluated goes into the statistics; terminated problems retire, the others are carried
+static int pass_read_back(dsm_stream *s, Pass &p) {
+  dsm_context *ctx = s->ctx;
+  const int N = s->N, nlevels = s->nlevels;
+  DSM_HIP(hipMemcpyAsync(s->h_states, s->d_states, sizeof(LMState) * N, hipMemcpyDeviceToHost, ctx->stream));
+  DSM_HIP(hipEventRecord(ctx->ev_total[1], ctx->stream));
+  DSM_HIP(hipStreamSynchronize(ctx->stream));
+  s->passes++;
+  float ms = 0;
+  DSM_HIP(hipEventElapsedTime(&ms, ctx->ev_total[0], ctx->ev_total[1]));
+  s->stats[0].total_ms += ms, s->stats[1].total_ms += ms;
+  s->stats[0].polls += 1;
+  if (ctx->timing) collect_eval_timing(ctx, p.tm.lvl, nlevels, s->stats[0]);
+  for (int i = 0; i < N; i++) {
+    Slot &sl = s->slots[i];
+    if (sl.state == SLOT_FREE) continue;
+    const int mode = i < s->cap[0] ? 0 : 1;
+    const LMState &S = s->h_states[i];
+    dsm_stats &st = s->stats[mode];
+    sl.passes++;
+    for (int l = 0; l < nlevels; l++) {
+      const long long de = S.evals[l] - sl.seen_evals[l], dr = S.evals_ro[l] - sl.seen_ro[l];
+      sl.seen_evals[l] = S.evals[l], sl.seen_ro[l] = S.evals_ro[l];
+      st.evals[l] += de;
+      st.evals_residual_only[l] += dr;
+      st.algorithmic_bytes += de * eval_bytes(sl.trk, l);
+    }
+    if (S.status != ST_RUNNING) {
+      pass_retire(s, sl, S, mode);
+      continue;
+    }
+    if (sl.passes > 4096) {
+      set_error("internal: a resident problem did not terminate within 4096 passes");
+      return DSM_ERR_STATE;
+    }
+    sl.state = SLOT_RUNNING;
+    sl.lvl = S.lvl;
+    s->carried_slot_passes++;
+  }
+  return DSM_OK;
+}
+
+// the next pass's rounds per level: the quantile of what the recently retired problems needed
+static void pass_learn(dsm_stream *s) {
+  for (int mode = 0; mode < 2; mode++) {
+    if (s->hist[mode][0].size() < 16) continue;
+    std::vector<int> r;
+    for (int l = 0; l < s->nlevels; l++) {
+      r = s->hist[mode][l];
+      size_t k = (size_t)(s->quantile[l] * (double)(r.size() - 1) + 0.5);
+      if (k >= r.size()) k = r.size() - 1;
+      std::nth_element(r.begin(), r.begin() + k, r.end());
+      s->rounds[mode][l] = r[k] < 1 ? 1 : r[k];
+      s->rounds_max[mode][l] = *std::max_element(r.begin(), r.end()) + 1;
+    }
+  }
+}
+
+static int pass_advance(dsm_stream *s) {
+  dsm_context *ctx = s->ctx;
+  DSM_HIP(hipSetDevice(ctx->device));
+  Pass p;
+  p.segs = build_segments(ctx->n_streams, s->cap[0], 0, s->cap[1], 1);
+  pass_admit(s, p);
+  if (!pass_survey(s, p)) return DSM_OK;
+  int rc = bind_streams(ctx, p.segs);
+  if (rc) return rc;
+  if (!p.fresh.empty() && (rc = sync_descs(ctx, p.fresh.data(), (int)p.fresh.size()))) return rc;
+  DSM_HIP(hipEventRecord(ctx->ev_total[0], ctx->stream));
+  if ((rc = pass_row_maps(s, p)) || (rc = pass_start_admitted(s, p)) || (rc = pass_rounds(s, p)) || (rc = pass_read_back(s, p))) return rc;
+  pass_learn(s);
+  return DSM_OK;
+}
+
 extern "C" {
 
 int dsm_stream_submit_track(dsm_stream *s, int n, dsm_tracker *const *ts, const double *pose0, const double *aff0, int coarsest_lvl,
@@ -476,12 +694,7 @@ int dsm_stream_submit_hypotheses(dsm_stream *s, dsm_tracker *tracker, int n_trie
 
 int dsm_stream_hypotheses_results(dsm_stream *s, int max_results, dsm_stream_hyp_result *out, int *n_out) {
   if (!s || max_results < 0 || (max_results && !out) || !n_out) return invalid("dsm_stream_hypotheses_results: bad argument");
-  int k = 0;
-  while (k < max_results && !s->hyp_done.empty()) {
-    out[k++] = s->hyp_done.front();
-    s->hyp_done.pop_front();
-  }
-  *n_out = k;
+  *n_out = pop_results(s->hyp_done, max_results, out);
   return DSM_OK;
 }
 
@@ -503,21 +716,10 @@ int dsm_stream_submit_scale(dsm_stream *s, int n, dsm_tracker *const *ts, const 
   int rc = submit_common(s, 1, n, ts, coarsest_lvl, tickets_out);
   if (rc) return rc;
   for (int i = 0; i < n; i++) {
-    Waiting wq;
-    wq.ticket = s->next_ticket++;
-    wq.trk = ts[i];
-    StartInfo &I = wq.start;
-    memset(&I, 0, sizeof I);
-    I.pose[3] = 1.0;
-    for (int l = 0; l < DSM_MAX_LEVELS; l++) I.min_res[l] = std::numeric_limits<double>::quiet_NaN();
-    I.scale = scale0[i];
-    I.coarsest = coarsest_lvl;
-    if (tickets_out) tickets_out[i] = wq.ticket;
-    dsm_stream::Origin og;
-    memset(&og, 0, sizeof og);
-    og.trk = ts[i], og.admitted_at = -1;
-    s->origin[wq.ticket] = og;
-    s->waiting[1].push_back(wq);
+    StartInfo start;
+    fill_scale_start(start, scale0[i], coarsest_lvl);
+    const uint64_t tk = enqueue(s, 1, ts[i], start);
+    if (tickets_out) tickets_out[i] = tk;
   }
   return DSM_OK;
 }
@@ -539,12 +741,7 @@ int dsm_stream_counts(dsm_stream *s, int *resident_out, int *waiting_out, int *r
 
 int dsm_stream_results(dsm_stream *s, int max_results, dsm_stream_result *out, int *n_out) {
   if (!s || max_results < 0 || (max_results && !out) || !n_out) return invalid("dsm_stream_results: bad argument");
-  int k = 0;
-  while (k < max_results && !s->done.empty()) {
-    out[k++] = s->done.front();
-    s->done.pop_front();
-  }
-  *n_out = k;
+  *n_out = pop_results(s->done, max_results, out);
   return DSM_OK;
 }
 
@@ -565,304 +762,27 @@ int dsm_stream_get_schedule(dsm_stream *s, int mode, int *rounds_out, long long 
   return DSM_OK;
 }
 
-// One pass.  (i) waiting problems are admitted into free slots, (ii) their state machines are started, (iii) every level
-// from the coarsest a resident problem stands on down to level 0 gets its rounds -- compact launches over the slots that
-// can be at that level in this pass: the new ones and the carried ones standing at or above it -- (iv) the states are read
-// back once; problems that terminated retire (dsm_stream_results), the others are carried.
 int dsm_stream_advance(dsm_stream *s) {
   if (!s) return invalid("null stream");
-  if (s->engine == 1) return tick_advance(s);
-  dsm_context *ctx = s->ctx;
-  DSM_HIP(hipSetDevice(ctx->device));
-  const int N = s->N, cap0 = s->cap[0];
-  int ng = ctx->n_streams < 1 ? 1 : ctx->n_streams;
-  if (ng > cap0) ng = cap0 > 0 ? cap0 : 1;
-  // ---- (i) admission: a free slot of the problem's kind, in the stream group with the fewest resident problems ----
-  std::vector<Seg> segs;
-  if (cap0 > 0)
-    for (int g = 0; g < ng; g++) {
-      const int g0 = (int)((long long)cap0 * g / ng), g1 = (int)((long long)cap0 * (g + 1) / ng);
-      if (g1 > g0) segs.push_back(Seg{nullptr, g0, g1, 0, false, {}});
-    }
-  const int n_track_segs = (int)segs.size();
-  if (s->cap[1] > 0) segs.push_back(Seg{nullptr, cap0, N, 1, true, {}});
-  std::vector<dsm_tracker *> fresh;
-  int n_new[2] = {0, 0};
-  for (int mode = 0; mode < 2; mode++) {
-    std::deque<Waiting> &wq = s->waiting[mode];
-    if (wq.empty()) continue;
-    const int sg0 = mode == 0 ? 0 : n_track_segs, sg1 = mode == 0 ? n_track_segs : (int)segs.size();
-    std::vector<int> live(segs.size(), 0), cursor(segs.size(), 0);
-    for (int si = sg0; si < sg1; si++) {
-      cursor[si] = segs[si].i0;
-      for (int i = segs[si].i0; i < segs[si].i1; i++) live[si] += s->slots[i].state != SLOT_FREE;
-    }
-    while (!wq.empty()) {
-      int best = -1;
-      for (int si = sg0; si < sg1; si++)
-        if (live[si] < segs[si].i1 - segs[si].i0 && (best < 0 || live[si] < live[best])) best = si;
-      if (best < 0) break; // every slot of this kind is taken
-      int &c = cursor[best];
-      while (s->slots[c].state != SLOT_FREE) c++;
-      const Waiting &wt = wq.front();
-      Slot &sl = s->slots[c];
-      sl = Slot();
-      sl.state = SLOT_NEW;
-      sl.ticket = wt.ticket;
-      sl.trk = wt.trk;
-      sl.lvl = wt.start.coarsest;
-      memcpy(sl.pose0, wt.start.pose, sizeof sl.pose0);
-      memcpy(sl.aff0, wt.start.aff, sizeof sl.aff0);
-      s->h_start[c] = wt.start;
-      s->h_tracker_ptrs[c] = wt.trk->d_desc;
-      s->h_rowmap[(size_t)DSM_MAX_LEVELS * N + (mode == 0 ? 0 : cap0) + n_new[mode]] = c - (mode == 0 ? 0 : cap0);
-      n_new[mode]++;
-      fresh.push_back(wt.trk);
-      live[best]++;
-      wq.pop_front();
-    }
-  }
-  int n_live = 0, top = -1, top2 = -1;
-  const dsm_params *P = nullptr;
-  for (int i = 0; i < N; i++) {
-    const Slot &sl = s->slots[i];
-    if (sl.state == SLOT_FREE) continue;
-    n_live++;
-    if (!P) P = &sl.trk->params;
-    if (i < cap0)
-      top = sl.lvl > top ? sl.lvl : top;
-    else
-      top2 = sl.lvl > top2 ? sl.lvl : top2;
-  }
-  if (n_live == 0) return DSM_OK;
-  // Nothing is waiting and the pool is at most a quarter full: what is resident is the END of the job -- nothing rides with
-  // the stragglers any more, so a pass gives every level the rounds the slowest retired problem needed (they finish in one or
-  // two passes instead of one level per pass) and evaluates and steps in one fused launch per round.
-  const bool draining = s->waiting[0].empty() && s->waiting[1].empty() && 4 * n_live <= N;
-  const int nlevels = s->nlevels;
-  int rc = ensure_streams(ctx, ng, s->cap[1] > 0);
-  if (rc) return rc;
-  for (int si = 0; si < (int)segs.size(); si++) // (a stream without track slots runs its scale segment on the context's stream)
-    segs[si].st = si == 0 ? ctx->stream : segs[si].companion ? ctx->companion_stream : ctx->extra_streams[si - 1];
-  if (!fresh.empty()) {
-    rc = sync_descs(ctx, fresh.data(), (int)fresh.size());
-    if (rc) return rc;
-  }
-  DSM_HIP(hipEventRecord(ctx->ev_total[0], ctx->stream));
-  // ---- row maps: level L of segment sg = its slots that can stand on level L during this pass ----
-  int grid_x[DSM_MAX_LEVELS], level_pts[DSM_MAX_LEVELS];
-  for (int L = 0; L < nlevels; L++) {
-    int max_chunks = 1, max_n = 0;
-    for (int i = 0; i < N; i++) {
-      const Slot &sl = s->slots[i];
-      if (sl.state == SLOT_FREE) continue;
-      const int n_l = sl.trk->desc.lv[L].n, c = level_chunks(sl.trk->desc, L);
-      if (c > max_chunks) max_chunks = c;
-      if (n_l > max_n) max_n = n_l;
-    }
-    grid_x[L] = max_chunks < 8 ? max_chunks : (max_chunks + 7) & ~7;
-    level_pts[L] = max_n;
-    for (Seg &sg : segs) {
-      int r = 0;
-      for (int i = sg.i0; i < sg.i1; i++)
-        if (s->slots[i].state != SLOT_FREE && s->slots[i].lvl >= L) s->h_rowmap[(size_t)L * N + sg.i0 + r++] = i - sg.i0;
-      sg.rows[L] = r;
-    }
-  }
-  DSM_HIP(hipMemcpyAsync(s->d_rowmap, s->h_rowmap, sizeof(int) * (size_t)(DSM_MAX_LEVELS + 1) * N, hipMemcpyHostToDevice, ctx->stream));
-  // ---- (ii) start the admitted problems (LM_OP_START over the list of new slots of each kind) ----
-  if (n_new[0] + n_new[1] > 0) {
-    DSM_HIP(hipMemcpyAsync(s->d_tracker_ptrs, s->h_tracker_ptrs, sizeof(TrackerDev *) * N, hipMemcpyHostToDevice, ctx->stream));
-    DSM_HIP(hipMemcpyAsync(s->d_start, s->h_start, sizeof(StartInfo) * N, hipMemcpyHostToDevice, ctx->stream));
-    for (int mode = 0; mode < 2; mode++) {
-      if (!n_new[mode]) continue;
-      const int base = mode == 0 ? 0 : cap0;
-      launch_lm(ctx->stream, mode, LM_OP_START, 0, n_new[mode], s->d_tracker_ptrs + base, s->d_states + base,
-                s->d_partials + (size_t)base * s->partial_stride, s->partial_stride, s->d_start + base, nullptr, s->d_status + 2 * base, false,
-                s->d_rowmap + (size_t)DSM_MAX_LEVELS * N + base);
-    }
-  }
-  // ---- (iii) the pass ----
-  size_t ev_used = 0;
-  std::vector<int> ev_lvl;
-  auto launch_round = [&](const Seg &sg, int L, int k) -> int {
-    const int rows = sg.rows[L];
-    if (rows == 0) return DSM_OK;
-    const int *rowmap = s->d_rowmap + (size_t)L * N + sg.i0;
-    // the speculative second candidate, the fused LM step and the split of the residual-only evaluations: the rules of
-    // run_lm_batch (dsm_capi.hip), applied to this launch's rows
-    const bool spec = P->fixed_schedule <= 0 && (P->speculate >= 2 || (P->speculate == 1 && level_pts[L] <= 8192 && (long long)rows * level_pts[L] <= 1000000ll));
-    const bool fused = L > 0 && (P->fuse_lm >= 2 || (P->fuse_lm == 1 && (rows <= 8 || (draining && rows <= 128))));
-    const bool split_ro = !sg.companion && !fused && k > 0 && level_pts[L] >= 100000 && (long long)rows * level_pts[L] >= 8000000ll;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (ctx->timing && !sg.companion) {
-      ea = get_event(ctx, ev_used++);
-      eb = get_event(ctx, ev_used++);
-      ev_lvl.push_back(L);
-      if (ea) DSM_HIP(hipEventRecord(ea, sg.st));
-    }
-    float *part = s->d_partials + (size_t)sg.i0 * s->partial_stride;
-    launch_eval(sg.st, sg.mode, L, grid_x[L], rows, s->d_tracker_ptrs + sg.i0, s->d_states + sg.i0, part, s->partial_stride,
-                fused ? s->d_tickets + sg.i0 : nullptr, s->d_status + 2 * sg.i0, spec, split_ro, rowmap);
-    if (eb) DSM_HIP(hipEventRecord(eb, sg.st));
-    if (!fused)
-      launch_lm(sg.st, sg.mode, LM_OP_STEP, L, rows, s->d_tracker_ptrs + sg.i0, s->d_states + sg.i0, part, s->partial_stride, nullptr, nullptr,
-                s->d_status + 2 * sg.i0, spec, rowmap);
-    return DSM_OK;
-  };
-  if (segs.size() > 1) { // fork: the other segments' streams start behind the uploads and the START launches
-    DSM_HIP(hipEventRecord(ctx->fork_event, ctx->stream));
-    for (size_t si = 1; si < segs.size(); si++) DSM_HIP(hipStreamWaitEvent(segs[si].st, ctx->fork_event, 0));
-  }
-  for (int L = top > top2 ? top : top2; L >= 0; L--) {
-    auto seg_rounds = [&](const Seg &sg) {
-      int r = s->fixed_rounds[sg.mode][L] > 0 ? s->fixed_rounds[sg.mode][L] : draining ? s->rounds_max[sg.mode][L] : s->rounds[sg.mode][L];
-      if (P->fixed_schedule > 0) r = 1 + P->fixed_schedule; // the benchmark schedule: every problem needs exactly 1 + K rounds
-      return r < 1 ? 1 : r;
-    };
-    int kmax = 0;
-    for (const Seg &sg : segs)
-      if (sg.rows[L] > 0 && seg_rounds(sg) > kmax) kmax = seg_rounds(sg);
-    for (int k = 0; k < kmax; k++)
-      for (int si = (int)segs.size() - 1; si >= 0; si--) { // (the companion's round first, as in run_lm_batch)
-        const Seg &sg = segs[si];
-        if (k < seg_rounds(sg)) {
-          rc = launch_round(sg, L, k);
-          if (rc) return rc;
-        }
-      }
-    for (const Seg &sg : segs)
-      if (sg.rows[L] > 0) s->stats[sg.mode].launches[L] += seg_rounds(sg);
-  }
-  DSM_HIP(hipGetLastError());
-  for (size_t si = 1; si < segs.size(); si++) { // join
-    hipEvent_t ev = segs[si].companion ? ctx->companion_event : ctx->join_events[si - 1];
-    DSM_HIP(hipEventRecord(ev, segs[si].st));
-    DSM_HIP(hipStreamWaitEvent(ctx->stream, ev, 0));
-  }
-  // ---- (iv) one read-back ----
-  DSM_HIP(hipMemcpyAsync(s->h_states, s->d_states, sizeof(LMState) * N, hipMemcpyDeviceToHost, ctx->stream));
-  DSM_HIP(hipEventRecord(ctx->ev_total[1], ctx->stream));
-  DSM_HIP(hipStreamSynchronize(ctx->stream));
-  s->passes++;
-  float ms = 0;
-  DSM_HIP(hipEventElapsedTime(&ms, ctx->ev_total[0], ctx->ev_total[1]));
-  s->stats[0].total_ms += ms, s->stats[1].total_ms += ms;
-  s->stats[0].polls += 1;
-  if (ctx->timing) collect_eval_timing(ctx, ev_lvl, nlevels, s->stats[0]);
-  for (int i = 0; i < N; i++) {
-    Slot &sl = s->slots[i];
-    if (sl.state == SLOT_FREE) continue;
-    const int mode = i < cap0 ? 0 : 1;
-    const LMState &S = s->h_states[i];
-    dsm_stats &st = s->stats[mode];
-    sl.passes++;
-    for (int l = 0; l < nlevels; l++) { // what THIS pass evaluated
-      const long long de = S.evals[l] - sl.seen_evals[l], dr = S.evals_ro[l] - sl.seen_ro[l];
-      sl.seen_evals[l] = S.evals[l], sl.seen_ro[l] = S.evals_ro[l];
-      st.evals[l] += de;
-      st.evals_residual_only[l] += dr;
-      const long long nl = sl.trk->desc.lv[l].n, img = 12ll * (sl.trk->w >> l) * (sl.trk->h >> l);
-      st.algorithmic_bytes += de * (16ll * nl + (48ll * nl < img ? 48ll * nl : img)); // SURVEY.md 8d, as run_lm_batch
-    }
-    if (S.status == ST_RUNNING) {
-      if (sl.passes > 4096) {
-        set_error("internal: a resident problem did not terminate within 4096 passes");
-        return DSM_ERR_STATE;
-      }
-      sl.state = SLOT_RUNNING;
-      sl.lvl = S.lvl;
-      s->carried_slot_passes++;
-      continue;
-    }
-    dsm_stream_result r;
-    memset(&r, 0, sizeof r);
-    r.ticket = sl.ticket;
-    r.kind = mode;
-    r.status = S.status;
-    r.passes = sl.passes;
-    if (mode == 0) {
-      // the reference writes lastToNew_out / aff_g2l_out at :612-613, i.e. also when the later affine plausibility checks
-      // (:615-626) fail, but not when a level aborts (:598): as dsm_track_batch
-      const bool wrote = S.status == ST_GOOD || S.status == ST_BAD_AFFINE;
-      memcpy(r.pose, wrote ? S.cur : sl.pose0, sizeof r.pose);
-      memcpy(r.aff, wrote ? S.aff_cur : sl.aff0, sizeof r.aff);
-      r.good = S.status == ST_GOOD ? 1 : 0;
-      memcpy(r.flow, S.flow, sizeof r.flow);
-      r.scale = 1.0f;
-    } else {
-      r.good = 1;
-      r.scale = S.scale_cur;                    // :954
-      r.err = (float)S.last_residuals[0];       // :963
-      r.pose[3] = 1.0;
-    }
-    memcpy(r.last_residuals, S.last_residuals, sizeof r.last_residuals);
-    for (int l = 0; l < DSM_MAX_LEVELS; l++) r.evals[l] = S.evals[l];
-    s->origin.erase(sl.ticket);
-    route_result(s, r);
-    s->retired[mode]++;
-    for (int l = 0; l < nlevels; l++) {
-      std::vector<int> &hv = s->hist[mode][l];
-      if (hv.size() < kHistCap)
-        hv.push_back((int)S.rounds[l]);
-      else
-        hv[s->hist_pos[mode] % kHistCap] = (int)S.rounds[l];
-    }
-    s->hist_pos[mode]++;
-    sl = Slot();
-  }
-  // ---- the next pass's rounds per level: the quantile of what the recently retired problems needed ----
-  for (int mode = 0; mode < 2; mode++) {
-    if (s->hist[mode][0].size() < 16) continue;
-    std::vector<int> r;
-    for (int l = 0; l < nlevels; l++) {
-      r = s->hist[mode][l];
-      size_t k = (size_t)(s->quantile[l] * (double)(r.size() - 1) + 0.5);
-      if (k >= r.size()) k = r.size() - 1;
-      std::nth_element(r.begin(), r.begin() + k, r.end());
-      s->rounds[mode][l] = r[k] < 1 ? 1 : r[k];
-      s->rounds_max[mode][l] = *std::max_element(r.begin(), r.end()) + 1;
-    }
-  }
-  return DSM_OK;
+  return s->engine == 1 ? tick_advance(s) : pass_advance(s);
 }
-
 
 } // extern "C"
 
-// ---- tick engine -------------------------------------------------------------------------------------------------------
-template <typename T>
-static int regrow_dev(T **p, size_t n) {
-  if (*p) DSM_HIP(hipFree(*p));
-  return alloc_dev(p, n);
-}
-template <typename T>
-static int regrow_pinned(T **p, size_t n) {
-  if (*p) DSM_HIP(hipHostFree(*p));
-  return alloc_pinned(p, n);
-}
-
+// ---- tick engine (engine 1) --------------------------------------------------------------------------------------------
 static int tick_setup(dsm_stream *s) {
   dsm_context *ctx = s->ctx;
   const int cap0 = s->cap[0], N = s->N;
-  int ng = ctx->n_streams < 1 ? 1 : ctx->n_streams;
-  if (ng > cap0) ng = cap0 > 0 ? cap0 : 1;
-  s->tsegs.clear();
-  if (cap0 > 0)
-    for (int g = 0; g < ng; g++) {
-      const int g0 = (int)((long long)cap0 * g / ng), g1 = (int)((long long)cap0 * (g + 1) / ng);
-      if (g1 > g0) s->tsegs.push_back(Seg{nullptr, g0, g1, 0, false, {}});
-    }
-  if (s->cap[1] > 0) s->tsegs.push_back(Seg{nullptr, cap0, N, 1, true, {}});
+  s->tsegs = build_segments(ctx->n_streams, cap0, 0, s->cap[1], 1);
   const int nseg = (int)s->tsegs.size();
   tick_free(s); // (an earlier attempt that failed half way left its allocations behind: ADVICE r04)
-  int rc = alloc_dev(&s->d_segctl, nseg);
-  if (!rc) rc = alloc_pinned(&s->h_segctl, 2 * (size_t)nseg);
-  if (!rc) rc = alloc_dev(&s->d_modectl, 2);
-  if (!rc) rc = alloc_pinned(&s->h_modectl, 2 * 2);
-  if (!rc) rc = alloc_pinned(&s->h_count_word, 4);
-  if (!rc) rc = alloc_dev(&s->d_slot_ticket, N);
-  if (!rc) rc = alloc_dev(&s->d_admit_idx, N);
+  int rc = realloc_dev(&s->d_segctl, nseg);
+  if (!rc) rc = realloc_pinned(&s->h_segctl, 2 * (size_t)nseg);
+  if (!rc) rc = realloc_dev(&s->d_modectl, 2);
+  if (!rc) rc = realloc_pinned(&s->h_modectl, 2 * 2);
+  if (!rc) rc = realloc_pinned(&s->h_count_word, 4);
+  if (!rc) rc = realloc_dev(&s->d_slot_ticket, N);
+  if (!rc) rc = realloc_dev(&s->d_admit_idx, N);
   if (rc) return rc;
   // an item list holds at most one evaluation (+ its speculative twin) per slot of the segment
   const int maxpos = 8 * ((max_chunks_upto(s->w * s->h) + 7) / 8);
@@ -877,7 +797,7 @@ static int tick_setup(dsm_stream *s) {
     const int cap = ns * 2 * maxpos + 64;
     s->items_cap[si] = cap;
     for (int b = 0; b < 2; b++) // item slots [0, cap), then one chain entry per slot of the segment
-      if ((rc = alloc_dev(&s->d_items[2 * si + b], (size_t)cap + ns))) return rc;
+      if ((rc = realloc_dev(&s->d_items[2 * si + b], (size_t)cap + ns))) return rc;
   }
   DSM_HIP(hipMemsetAsync(s->d_segctl, 0, sizeof(TickSegCtl) * nseg, ctx->stream));
   DSM_HIP(hipMemsetAsync(s->d_slot_ticket, 0, sizeof(unsigned long long) * N, ctx->stream));
@@ -887,8 +807,8 @@ static int tick_setup(dsm_stream *s) {
     int ring = 1024;
     while (ring < 4 * s->cap[mode]) ring <<= 1;
     s->ring[mode] = ring;
-    if ((rc = alloc_dev(&s->d_pending[mode], ring)) || (rc = alloc_pinned(&s->h_pending[mode], ring)) || (rc = alloc_dev(&s->d_results[mode], ring)) ||
-        (rc = alloc_pinned(&s->h_results[mode], 2 * (size_t)ring)))
+    if ((rc = realloc_dev(&s->d_pending[mode], ring)) || (rc = realloc_pinned(&s->h_pending[mode], ring)) || (rc = realloc_dev(&s->d_results[mode], ring)) ||
+        (rc = realloc_pinned(&s->h_results[mode], 2 * (size_t)ring)))
       return rc;
     TickModeCtl mc;
     memset(&mc, 0, sizeof mc);
@@ -915,7 +835,7 @@ static int tick_collect(dsm_stream *s, long long k) {
   DSM_HIP(hipEventElapsedTime(&ms, s->ev_begin[par], s->ev_end[par]));
   s->stats[0].total_ms += ms, s->stats[1].total_ms += ms; // (the stream's statistics are cumulative)
   s->stats[0].polls += 1;
-  if (s->inflight_timed[par]) collect_eval_timing(ctx, s->ev_lvl, 1, s->stats[0]);
+  if (s->inflight_timed[par]) collect_eval_timing(ctx, s->tm.lvl, 1, s->stats[0]);
   for (int si = 0; si < nseg; si++) {
     const TickSegCtl &sc = s->h_segctl[par * nseg + si];
     if (sc.overflow) {
@@ -935,12 +855,7 @@ static int tick_collect(dsm_stream *s, long long k) {
       return DSM_ERR_STATE;
     }
     dsm_stats &st = s->stats[mode];
-    for (int l = 0; l < s->nlevels; l++) {
-      st.evals[l] += mc.sched_evals[l] - sn.evals[l];
-      st.evals_residual_only[l] += mc.sched_ro[l] - sn.ro[l];
-      sn.evals[l] = mc.sched_evals[l], sn.ro[l] = mc.sched_ro[l];
-      st.launches[l] += s->inflight_ticks[par];
-    }
+    for (int l = 0; l < s->nlevels; l++) st.launches[l] += s->inflight_ticks[par];
     const TickResult *res = s->h_results[mode] + (size_t)par * ring;
     long long life_sum = 0;
     for (long long i = 0; i < new_ret; i++) {
@@ -953,30 +868,15 @@ static int tick_collect(dsm_stream *s, long long k) {
       }
       const dsm_stream::Origin &og = it->second;
       dsm_stream_result r;
-      memset(&r, 0, sizeof r);
-      r.ticket = R.ticket;
-      r.kind = mode;
-      r.status = R.status;
-      r.passes = (int)(k - og.admitted_at + 1);
-      if (mode == 0) {
-        const bool wrote = R.status == ST_GOOD || R.status == ST_BAD_AFFINE; // as dsm_track_batch (:612-613 / :598)
-        memcpy(r.pose, wrote ? R.cur : og.pose0, sizeof r.pose);
-        memcpy(r.aff, wrote ? R.aff_cur : og.aff0, sizeof r.aff);
-        r.good = R.status == ST_GOOD ? 1 : 0;
-        memcpy(r.flow, R.flow, sizeof r.flow);
-        r.scale = 1.0f;
-      } else {
-        r.good = 1;
-        r.scale = R.scale_cur;                  // :954
-        r.err = (float)R.last_residuals[0];     // :963
-        r.pose[3] = 1.0;
-      }
-      memcpy(r.last_residuals, R.last_residuals, sizeof r.last_residuals);
-      for (int l = 0; l < DSM_MAX_LEVELS; l++) {
-        r.evals[l] = R.evals[l];
-        // SURVEY.md 8d's bytes, booked when the problem retires (exact per problem; a long run's average equals the bytes moved)
-        const long long nl = og.trk->desc.lv[l].n, img = 12ll * (og.trk->w >> l) * (og.trk->h >> l);
-        if (l < s->nlevels) st.algorithmic_bytes += R.evals[l] * (16ll * nl + (48ll * nl < img ? 48ll * nl : img));
+      fill_stream_result(r, R, mode, R.ticket, (int)(k - og.admitted_at + 1), og.pose0, og.aff0);
+      // evaluations and SURVEY.md 8d's bytes, booked when the problem retires (exact per problem; a long run's average equals the
+      // bytes moved).  Not from the device's count of staged evaluations (TickModeCtl::sched_evals / sched_ro): a speculative
+      // candidate that the LM step consumes is an evaluation of the problem's (LMState::evals, as the batch form counts) and is
+      // not staged as one -- a drained stream reported fewer residual-only evaluations than the batch calls (15 against 20 on a level).
+      for (int l = 0; l < s->nlevels; l++) {
+        st.evals[l] += R.evals[l];
+        st.evals_residual_only[l] += R.evals_ro[l];
+        st.algorithmic_bytes += R.evals[l] * eval_bytes(og.trk, l);
       }
       s->retired[mode]++;
       s->origin.erase(it); // (before route_result: a group's next tries are added to `origin`)
@@ -993,9 +893,9 @@ static int tick_collect(dsm_stream *s, long long k) {
   return DSM_OK;
 }
 
-// everything in flight is read back
-static int tick_sync(dsm_stream *s) {
-  while (s->collected < s->advances) {
+// the advances before `upto` are read back (default: everything in flight)
+static int tick_sync(dsm_stream *s, long long upto) {
+  while (s->collected < (upto < 0 ? s->advances : upto)) {
     const int rc = tick_collect(s, s->collected);
     if (rc) return rc;
     s->collected++;
@@ -1009,33 +909,22 @@ static int tick_sync(dsm_stream *s) {
 // The call returns as soon as that is ENQUEUED; what it reads back is the PREVIOUS advance's (its kernels ran while the host
 // prepared this one), so results surface one advance late and the device never waits for the host (dsm_stream_sync / drain wait
 // for everything).  With dsm_context_set_timing the advance is synchronous (its events are read right away).
-static int tick_advance(dsm_stream *s) {
+struct Advance {
+  long long k, par; // its number; its pinned copies are those of parity par = k & 1
+  int n_new[2];      // problems handed over, per kind
+  bool may_admit[2]; // something may be waiting on the device
+  int T, speculate, chain_rounds;
+};
+
+// waiting problems -> the device's ring: as many as the waiting ring and the result ring have room for
+static int tick_hand_over(dsm_stream *s, Advance &a) {
   dsm_context *ctx = s->ctx;
-  DSM_HIP(hipSetDevice(ctx->device));
-  if (!s->partial_stride) return DSM_OK; // nothing was ever submitted
-  int rc;
-  if (!s->tick_ready && (rc = tick_setup(s))) return rc;
-  if (s->collected == s->advances && s->resident[0] + s->resident[1] == 0 && s->waiting[0].empty() && s->waiting[1].empty() &&
-      s->handed[0] == s->seen[0].admitted && s->handed[1] == s->seen[1].admitted)
-    return DSM_OK; // idle
-  const int nseg = (int)s->tsegs.size();
-  const int n_track_segs = s->cap[1] > 0 ? nseg - 1 : nseg;
-  rc = ensure_streams(ctx, n_track_segs < 1 ? 1 : n_track_segs, s->cap[1] > 0 && n_track_segs > 0);
-  if (rc) return rc;
-  for (int si = 0; si < nseg; si++)
-    s->tsegs[si].st = si == 0 ? ctx->stream : s->tsegs[si].companion ? ctx->companion_stream : ctx->extra_streams[si - 1];
-  if ((s->advances - s->collected >= 2 || ctx->timing) && (rc = tick_sync(s))) return rc; // (at most one advance behind: the pinned copies are two deep;
-                                                                                          // a timed advance reads its own events alone)
-  const long long k = s->advances;
-  const int par = (int)(k & 1);
-  // ---- waiting problems -> the device's ring: as many as the waiting ring and the result ring have room for ----
   std::vector<dsm_tracker *> fresh;
-  int n_new[2] = {0, 0};
   for (int mode = 0; mode < 2; mode++) {
     const int ring = s->ring[mode];
     const long long room = std::min<long long>(ring - (s->handed[mode] - s->seen[mode].admitted), ring - (s->handed[mode] - s->seen[mode].retired));
     const int n = (int)std::min<long long>((long long)s->waiting[mode].size(), room > 0 ? room : 0);
-    n_new[mode] = n;
+    a.n_new[mode] = n;
     for (int i = 0; i < n; i++) {
       const Waiting &wt = s->waiting[mode].front();
       TickPending &pd = s->h_pending[mode][(s->handed[mode] + i) & (ring - 1)];
@@ -1045,38 +934,33 @@ static int tick_advance(dsm_stream *s) {
       fresh.push_back(wt.trk);
       s->sched_fixed_schedule = wt.trk->params.fixed_schedule, s->sched_speculate = wt.trk->params.speculate, s->have_sched = true;
       auto it = s->origin.find(wt.ticket);
-      if (it != s->origin.end()) it->second.admitted_at = k;
+      if (it != s->origin.end()) it->second.admitted_at = a.k;
       s->waiting[mode].pop_front();
     }
   }
   if (!s->have_sched) return invalid("dsm_stream: internal: no problem was ever handed over");
+  int rc;
   if (!fresh.empty() && (rc = sync_descs(ctx, fresh.data(), (int)fresh.size()))) return rc;
-  DSM_HIP(hipEventRecord(s->ev_begin[par], ctx->stream));
+  DSM_HIP(hipEventRecord(s->ev_begin[a.par], ctx->stream));
   if (ctx->timing) DSM_HIP(hipEventRecord(ctx->ev_total[0], ctx->stream)); // (collect_eval_timing places the dispatches relative to it)
   for (int mode = 0; mode < 2; mode++) {
-    if (!n_new[mode]) continue;
+    if (!a.n_new[mode]) continue;
     const int ring = s->ring[mode];
-    const int first = (int)(s->handed[mode] & (ring - 1)), n1 = std::min(n_new[mode], ring - first);
+    const int first = (int)(s->handed[mode] & (ring - 1)), n1 = std::min(a.n_new[mode], ring - first);
     DSM_HIP(hipMemcpyAsync(s->d_pending[mode] + first, s->h_pending[mode] + first, sizeof(TickPending) * n1, hipMemcpyHostToDevice, ctx->stream));
-    if (n_new[mode] > n1)
-      DSM_HIP(hipMemcpyAsync(s->d_pending[mode], s->h_pending[mode], sizeof(TickPending) * (n_new[mode] - n1), hipMemcpyHostToDevice, ctx->stream));
-    s->handed[mode] += n_new[mode];
-    s->h_count_word[par * 2 + mode] = s->handed[mode];
-    DSM_HIP(hipMemcpyAsync(&s->d_modectl[mode].pending_count, &s->h_count_word[par * 2 + mode], sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    if (a.n_new[mode] > n1)
+      DSM_HIP(hipMemcpyAsync(s->d_pending[mode], s->h_pending[mode], sizeof(TickPending) * (a.n_new[mode] - n1), hipMemcpyHostToDevice, ctx->stream));
+    s->handed[mode] += a.n_new[mode];
+    s->h_count_word[a.par * 2 + mode] = s->handed[mode];
+    DSM_HIP(hipMemcpyAsync(&s->d_modectl[mode].pending_count, &s->h_count_word[a.par * 2 + mode], sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
   }
-  const bool may_admit[2] = {s->handed[0] > s->seen[0].admitted, s->handed[1] > s->seen[1].admitted}; // (something may be waiting on the device)
-  if (may_admit[0] || may_admit[1]) {
-    TickReserveArgs ra;
-    if (nseg > kTickMaxSegs) return invalid("dsm_stream: too many stream groups");
-    ra.nseg = nseg;
-    for (int si = 0; si < nseg; si++) ra.seg[si] = TickSegDesc{s->tsegs[si].mode, s->tsegs[si].i0, s->tsegs[si].i1 - s->tsegs[si].i0};
-    launch_tick_reserve(ctx->stream, ra, s->d_states, s->d_modectl, s->d_admit_idx);
-  }
-  if (nseg > 1) {
-    DSM_HIP(hipEventRecord(ctx->fork_event, ctx->stream));
-    for (int si = 1; si < nseg; si++) DSM_HIP(hipStreamWaitEvent(s->tsegs[si].st, ctx->fork_event, 0));
-  }
-  int T = s->ticks;
+  for (int mode = 0; mode < 2; mode++) a.may_admit[mode] = s->handed[mode] > s->seen[mode].admitted;
+  return DSM_OK;
+}
+
+// the advance's ticks and the switches of its launches
+static void tick_plan(dsm_stream *s, Advance &a) {
+  a.T = s->ticks;
   if (s->auto_ticks && s->life_ticks > 0.0) {
     const int m = s->cap[0] > 0 ? 0 : 1;
     // sized to retire 7/8 of what the advance hands over: the rest stays in the device's waiting ring as the buffer from which a slot
@@ -1085,25 +969,52 @@ static int tick_advance(dsm_stream *s) {
     // (With dsm_params.fixed_schedule every problem lives the same number of ticks and a cohort admitted together stays on one level,
     // which evaluates in larger single-level launches: there an advance is one cohort's whole life.)
     const double share = s->sched_fixed_schedule > 0 ? 1.0 : 0.875;
-    const double t = n_new[m] > 0 ? share * (double)n_new[m] * s->life_ticks / (double)s->cap[m] : s->life_ticks;
-    T = (int)std::ceil(t);
-    T = T < 8 ? 8 : T > 256 ? 256 : T;
+    const double t = a.n_new[m] > 0 ? share * (double)a.n_new[m] * s->life_ticks / (double)s->cap[m] : s->life_ticks;
+    a.T = (int)std::ceil(t);
+    a.T = a.T < 8 ? 8 : a.T > 256 ? 256 : a.T;
   }
-  s->inflight_ticks[par] = T;
-  size_t ev_used = 0;
-  s->ev_lvl.clear();
-  const int speculate = s->sched_fixed_schedule > 0 ? 0 : s->sched_speculate;
+  s->inflight_ticks[a.par] = a.T;
+  a.speculate = s->sched_fixed_schedule > 0 ? 0 : s->sched_speculate;
   // (with dsm_params.fixed_schedule a cohort moves in lock step and an advance is its whole life: chains would only unbalance it)
-  const int chain_rounds = (s->sched_fixed_schedule > 0 || !s->chain_possible) ? 0 : s->chain_rounds;
+  a.chain_rounds = (s->sched_fixed_schedule > 0 || !s->chain_possible) ? 0 : s->chain_rounds;
+}
+
+// the list of segment si that buffer `buf` of its items is
+static TickList tick_list(const dsm_stream *s, int si, int buf, int chain_rounds) {
+  const Seg &sg = s->tsegs[si];
+  return TickList{s->d_items[2 * si + buf], s->d_segctl + si, buf, s->items_cap[si], chain_rounds > 0 ? sg.i1 - sg.i0 : 0, s->chain_max_n0};
+}
+
+// which free slot takes which waiting problem (one launch, before the stream groups fork), then every segment's free slots take theirs
+static int tick_reserve_and_admit(dsm_stream *s, const Advance &a) {
+  dsm_context *ctx = s->ctx;
+  const int nseg = (int)s->tsegs.size();
+  if (a.may_admit[0] || a.may_admit[1]) {
+    TickReserveArgs ra;
+    if (nseg > kTickMaxSegs) return invalid("dsm_stream: too many stream groups");
+    ra.nseg = nseg;
+    for (int si = 0; si < nseg; si++) ra.seg[si] = TickSegDesc{s->tsegs[si].mode, s->tsegs[si].i0, s->tsegs[si].i1 - s->tsegs[si].i0};
+    launch_tick_reserve(ctx->stream, ra, s->d_states, s->d_modectl, s->d_admit_idx);
+  }
+  const int rc = fork_segments(ctx, s->tsegs);
+  if (rc) return rc;
   for (int si = nseg - 1; si >= 0; si--) {
     const Seg &sg = s->tsegs[si];
     const int i0 = sg.i0, ns = sg.i1 - sg.i0, mode = sg.mode;
-    if (may_admit[mode]) // (free slots take what tick_reserve_kernel gave them)
-      launch_tick_admit(sg.st, mode, ns, (const TrackerDev **)s->d_tracker_ptrs + i0, s->d_states + i0,
-                        TickList{s->d_items[2 * si + s->parity], s->d_segctl + si, s->parity, s->items_cap[si], chain_rounds > 0 ? ns : 0, s->chain_max_n0},
+    if (a.may_admit[mode]) // (free slots take what tick_reserve_kernel gave them)
+      launch_tick_admit(sg.st, mode, ns, (const TrackerDev **)s->d_tracker_ptrs + i0, s->d_states + i0, tick_list(s, si, s->parity, a.chain_rounds),
                         s->d_modectl + mode, s->d_pending[mode], s->d_slot_ticket + i0, s->d_admit_idx + i0);
   }
-  for (int t = 0; t < T; t++) {
+  return DSM_OK;
+}
+
+// T ticks: per segment one evaluation launch over its item list and one LM launch over its slots
+static int tick_ticks(dsm_stream *s, const Advance &a) {
+  dsm_context *ctx = s->ctx;
+  const int nseg = (int)s->tsegs.size();
+  s->tm.used = 0;
+  s->tm.lvl.clear();
+  for (int t = 0; t < a.T; t++) {
     const int buf = (s->parity + t) & 1;
     for (int si = nseg - 1; si >= 0; si--) {
       const Seg &sg = s->tsegs[si];
@@ -1113,32 +1024,31 @@ static int tick_advance(dsm_stream *s) {
       if (s->last_count[si] + s->last_chain[si] == 0) grid = (long long)ns * 16;
       if (grid > s->items_cap[si]) grid = s->items_cap[si];
       float *part = s->d_partials + (size_t)i0 * s->partial_stride;
-      hipEvent_t ea = nullptr, eb = nullptr;
-      if (ctx->timing && !sg.companion) {
-        ea = get_event(ctx, ev_used++);
-        eb = get_event(ctx, ev_used++);
-        s->ev_lvl.push_back(0); // (all levels in one launch: booked under index 0)
-        if (ea) DSM_HIP(hipEventRecord(ea, sg.st));
-      }
-      const TickList next{s->d_items[2 * si + (buf ^ 1)], s->d_segctl + si, buf ^ 1, s->items_cap[si], chain_rounds > 0 ? ns : 0, s->chain_max_n0};
+      hipEvent_t eb = nullptr;
+      const int rc = timed_eval_begin(ctx, sg, 0, s->tm, &eb); // (all levels in one launch: booked under index 0)
+      if (rc) return rc;
+      const TickList next = tick_list(s, si, buf ^ 1, a.chain_rounds);
       const TickChainArgs chain{(const TrackerDev **)s->d_tracker_ptrs + i0, s->d_states + i0, next, s->d_modectl + mode, s->d_pending[mode], s->d_results[mode],
-                                s->d_slot_ticket + i0, chain_rounds, s->chain_flags};
+                                s->d_slot_ticket + i0, a.chain_rounds, s->chain_flags};
       launch_tick_eval(sg.st, mode, (int)grid, s->d_states + i0, part, s->partial_stride, s->d_items[2 * si + buf], s->d_segctl + si, buf, s->items_cap[si], chain, s->chain_possible);
       if (eb) DSM_HIP(hipEventRecord(eb, sg.st));
       launch_tick_lm(sg.st, mode, ns, (const TrackerDev **)s->d_tracker_ptrs + i0, s->d_states + i0, part, s->partial_stride, next, s->d_modectl + mode,
-                     s->d_pending[mode], s->d_results[mode], s->d_slot_ticket + i0, speculate, s->lm_opts);
+                     s->d_pending[mode], s->d_results[mode], s->d_slot_ticket + i0, a.speculate, s->lm_opts);
     }
   }
-  s->parity = (s->parity + T) & 1;
-  s->inflight_parity[par] = s->parity;
-  s->inflight_timed[par] = ctx->timing;
+  s->parity = (s->parity + a.T) & 1;
+  s->inflight_parity[a.par] = s->parity;
+  s->inflight_timed[a.par] = ctx->timing;
   DSM_HIP(hipGetLastError());
-  for (int si = 1; si < nseg; si++) {
-    hipEvent_t ev = s->tsegs[si].companion ? ctx->companion_event : ctx->join_events[si - 1];
-    DSM_HIP(hipEventRecord(ev, s->tsegs[si].st));
-    DSM_HIP(hipStreamWaitEvent(ctx->stream, ev, 0));
-  }
-  // ---- read-back behind the ticks: control blocks and the result rings, into this advance's pinned copies ----
+  return DSM_OK;
+}
+
+// read-back behind the ticks: control blocks and the result rings, into this advance's pinned copies
+static int tick_read_back(dsm_stream *s, const Advance &a) {
+  dsm_context *ctx = s->ctx;
+  const int nseg = (int)s->tsegs.size(), par = a.par;
+  const int rc = join_segments(ctx, s->tsegs);
+  if (rc) return rc;
   DSM_HIP(hipMemcpyAsync(s->h_modectl + par * 2, s->d_modectl, sizeof(TickModeCtl) * 2, hipMemcpyDeviceToHost, ctx->stream));
   DSM_HIP(hipMemcpyAsync(s->h_segctl + par * nseg, s->d_segctl, sizeof(TickSegCtl) * nseg, hipMemcpyDeviceToHost, ctx->stream));
   for (int mode = 0; mode < 2; mode++)
@@ -1146,17 +1056,32 @@ static int tick_advance(dsm_stream *s) {
       DSM_HIP(hipMemcpyAsync(s->h_results[mode] + (size_t)par * s->ring[mode], s->d_results[mode], sizeof(TickResult) * s->ring[mode], hipMemcpyDeviceToHost,
                              ctx->stream));
   DSM_HIP(hipEventRecord(s->ev_end[par], ctx->stream));
+  return DSM_OK;
+}
+
+static int tick_advance(dsm_stream *s) {
+  dsm_context *ctx = s->ctx;
+  DSM_HIP(hipSetDevice(ctx->device));
+  if (!s->partial_stride) return DSM_OK; // nothing was ever submitted
+  int rc;
+  if (!s->tick_ready && (rc = tick_setup(s))) return rc;
+  if (s->collected == s->advances && s->resident[0] + s->resident[1] == 0 && s->waiting[0].empty() && s->waiting[1].empty() &&
+      s->handed[0] == s->seen[0].admitted && s->handed[1] == s->seen[1].admitted)
+    return DSM_OK; // idle
+  if ((rc = bind_streams(ctx, s->tsegs))) return rc;
+  if ((s->advances - s->collected >= 2 || ctx->timing) && (rc = tick_sync(s))) return rc; // (at most one advance behind: the pinned copies are two deep;
+                                                                                          // a timed advance reads its own events alone)
+  Advance a{};
+  a.k = s->advances;
+  a.par = a.k & 1;
+  if ((rc = tick_hand_over(s, a))) return rc;
+  tick_plan(s, a);
+  if ((rc = tick_reserve_and_admit(s, a)) || (rc = tick_ticks(s, a)) || (rc = tick_read_back(s, a))) return rc;
   s->advances++;
-  s->total_ticks += T;
+  s->total_ticks += a.T;
   s->passes++;
   // what was in flight before this advance has finished on the device by now, or finishes while the host is busy here
-  if (ctx->timing || !s->pipelined) return tick_sync(s);
-  while (s->collected < s->advances - 1) {
-    rc = tick_collect(s, s->collected);
-    if (rc) return rc;
-    s->collected++;
-  }
-  return DSM_OK;
+  return tick_sync(s, ctx->timing || !s->pipelined ? s->advances : s->advances - 1);
 }
 
 extern "C" {

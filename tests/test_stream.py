@@ -1,7 +1,9 @@
-"""The streaming form of the batched calls (dsm_stream_*, csrc/stream_capi.hip): problems are admitted as slots free up, advance
-in passes with a bounded number of rounds per level, are carried over when they need more and retire individually.  None of
-that may change a result: every problem's pose, residuals, flags and per-level evaluation counts must equal the batch
-calls' bit for bit, whatever the pool size, the rounds per pass or the stream groups."""
+"""The streaming form of the batched calls (dsm_stream_*, csrc/stream_capi.hip): a pool of slots that problems take as they free
+up and leave individually, advanced by one of two engines -- the tick engine (the default: one LM round of every resident
+problem per tick, admission and retirement on the device, advances pipelined) and the pass engine (a sweep down the pyramid
+with a bounded number of rounds per level; problems that need more are carried into the next pass).  None of that may change
+a result: every problem's pose, residuals, flags and per-level evaluation counts must equal the batch calls' bit for bit,
+whatever the engine, the pool size, the ticks per advance, the rounds per pass or the stream groups."""
 import numpy as np
 import pytest
 
@@ -13,10 +15,10 @@ pytestmark = pytest.mark.gpu
 def _batch_reference(ctx, trks, nl, scales):
     n = len(trks)
     good, poses, affs, last, flow = ctx.track_batch(trks, np.tile(S.IDENTITY_POSE, (n, 1)), np.zeros((n, 2)), nl - 1)
-    ev_t = list(ctx.stats().evals)
+    st_t = ctx.stats()
     err, sc = ctx.optimize_scale_batch(trks, scales, nl - 1)
-    ev_s = list(ctx.stats().evals)
-    return good, poses, affs, last, flow, err, sc, ev_t, ev_s
+    st_s = ctx.stats()
+    return good, poses, affs, last, flow, err, sc, list(st_t.evals), list(st_s.evals), (st_t, st_s)
 
 
 def _stream_run(ctx, trks, nl, scales, track_slots, scale_slots, rounds=None, quantile=None, waves=1, engine=0, ticks=0, pipelined=True, chain=None):  # noqa: PLR0913
@@ -70,12 +72,14 @@ def _stream_run(ctx, trks, nl, scales, track_slots, scale_slots, rounds=None, qu
         res[owner[r.ticket]] = r
     assert len(res) == 2 * n
     sched = st.schedule(0)
+    st.drain()  # (nothing is left to run: the tick engine reads back what is still in flight)
+    sched["stats"] = st.stats()  # (track, scale), cumulative over the stream's life
     st.close()
     return res, passes, sched
 
 
 def _check(res, ref, n, nl):
-    good, poses, affs, last, flow, err, sc, ev_t, ev_s = ref
+    good, poses, affs, last, flow, err, sc, ev_t, ev_s = ref[:9]
     tot_t, tot_s = [0] * 6, [0] * 6
     for i in range(n):
         r = res[("track", i)]
@@ -90,6 +94,24 @@ def _check(res, ref, n, nl):
             tot_t[l] += r.evals[l]
             tot_s[l] += q.evals[l]
     assert tot_t[:nl] == ev_t[:nl] and tot_s[:nl] == ev_s[:nl]  # the same evaluations, level by level
+
+
+def _eval_bytes(sc, l):
+    """SURVEY.md 8d, the compulsory bytes of one evaluation at level l: the template once (16 bytes a point) and the target image
+    once (12 bytes a texel), or the four 12-byte taps of every point where that is less"""
+    n = len(sc.tpl[0][l])
+    return 16 * n + min(48 * n, 12 * (sc.w >> l) * (sc.h >> l))
+
+
+def _check_stats(stats, ref, res, scs, nl):
+    """dsm_stats.algorithmic_bytes (the bench's roofline fraction is computed from it), evals and evals_residual_only of a drained
+    stream, per kind: equal to the batch calls', and the bytes equal to the formula over every problem's evaluation counts"""
+    for mode, kind in enumerate(("track", "scale")):
+        st, bt = stats[mode], ref[9][mode]
+        assert st.algorithmic_bytes == bt.algorithmic_bytes, (kind, st.algorithmic_bytes, bt.algorithmic_bytes)
+        assert list(st.evals)[:nl] == list(bt.evals)[:nl], (kind, list(st.evals), list(bt.evals))
+        assert list(st.evals_residual_only)[:nl] == list(bt.evals_residual_only)[:nl], (kind, list(st.evals_residual_only), list(bt.evals_residual_only))
+        assert st.algorithmic_bytes == sum(res[(kind, i)].evals[l] * _eval_bytes(sc, l) for i, sc in enumerate(scs) for l in range(nl)), kind
 
 
 @pytest.mark.parametrize("streams", [1, 2])
@@ -107,6 +129,7 @@ def test_stream_results_equal_the_batch_calls_bit_for_bit(ctx, streams):
         for slots, sslots, rounds, waves in ((20, 20, None, 1), (7, 5, None, 1), (6, 6, [2] * 6, 2), (5, 3, [1] * 6, 4)):
             res, passes, sched = _stream_run(ctx, trks, nl, scales.copy(), slots, sslots, rounds, None, waves)
             _check(res, ref, len(trks), nl)
+            _check_stats(sched["stats"], ref, res, scs, nl)
             if rounds is not None:
                 assert max(r.passes for r in res.values()) > 1  # problems really were carried
         # the tick engine: every resident problem advances one round per tick, admission and retirement on the device.
@@ -120,6 +143,7 @@ def test_stream_results_equal_the_batch_calls_bit_for_bit(ctx, streams):
                                                       (6, 5, 0, 4, True), (20, 8, 0, 1, False)):
             res, passes, sched = _stream_run(ctx, trks, nl, scales.copy(), slots, sslots, None, None, waves, engine=1, ticks=ticks, pipelined=pipelined)
             _check(res, ref, len(trks), nl)
+            _check_stats(sched["stats"], ref, res, scs, nl)
     finally:
         ctx.set_streams(1)
 
