@@ -193,6 +193,8 @@ SYMBOLS = {
     "dsm_tracker_get_frame": (C.c_int, [_vp, C.c_int, C.c_int, c_float_p]),
     "dsm_tracker_calc_res_pose": (C.c_int, [_vp, C.c_int, c_double_p, c_double_p, C.c_float, c_double_p, c_double_p, c_double_p, c_int_p]),
     "dsm_tracker_calc_res_scale": (C.c_int, [_vp, C.c_int, C.c_float, C.c_float, c_double_p, c_float_p, c_float_p, c_int_p]),
+    "dsm_diag_single_eval": (C.c_int, [_vp, C.c_int, C.c_int, c_double_p, c_double_p, C.c_float, C.c_float, C.c_int, C.c_int, c_double_p, c_double_p,
+                                       c_double_p, c_float_p, c_float_p, c_int_p]),
     "dsm_tracker_track": (C.c_int, [_vp, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
     "dsm_tracker_optimize_scale": (C.c_int, [_vp, c_float_p, C.c_int, c_float_p]),
     "dsm_tracker_optimize_scale_guesses": (C.c_int, [_vp, C.c_int, c_float_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),

@@ -1739,15 +1739,43 @@ int dsm_pose_estimator_estimate(dsm_pose_estimator *pe, int n_pts, const double 
   return DSM_OK;
 }
 
-// single fused evaluation
+// The middle launch of dsm_diag_single_eval's forms 1-3 (form 0 is single_eval's own launch): problem 0's staged evaluation of `nch` chunks
+static int launch_eval_form(dsm_context *ctx, int mode, int lvl, int nch, int form, std::vector<void *> &scratch) {
+  if (form == 1) { // the split pair: full evaluations in one kernel, residual-only ones in the other
+    launch_eval(ctx->stream, mode, lvl, round8(nch > 0 ? nch : 1), 1, ctx->d_tracker_ptrs, ctx->d_states, ctx->d_partials, ctx->partial_stride,
+                nullptr, nullptr, false, /*split_ro=*/true);
+  } else if (form == 2) { // the tick engine's items: this evaluation's chunks as the list of a one-slot segment, the count set here
+    std::vector<unsigned> h(sizeof(TickSegCtl) / sizeof(unsigned) + (nch > 0 ? nch : 1), 0u);
+    TickSegCtl *hseg = (TickSegCtl *)h.data();
+    hseg->count[0] = nch;
+    for (int c = 0; c < nch; c++) h[sizeof(TickSegCtl) / sizeof(unsigned) + c] = (0u << kTickChunkBits) | (unsigned)c;
+    unsigned *d = nullptr;
+    DSM_HIP(hipMalloc(&d, h.size() * sizeof(unsigned)));
+    scratch.push_back(d);
+    DSM_HIP(hipMemcpyAsync(d, h.data(), h.size() * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
+    DSM_HIP(hipStreamSynchronize(ctx->stream)); // (h is pageable and goes out of scope)
+    TickChainArgs none;
+    memset(&none, 0, sizeof none);
+    launch_tick_eval(ctx->stream, mode, nch, ctx->d_states, ctx->d_partials, ctx->partial_stride, d + sizeof(TickSegCtl) / sizeof(unsigned),
+                     (TickSegCtl *)d, /*buf=*/0, /*cap=*/nch, none, /*with_chains=*/false);
+  } else { // the chains' one-chunk form
+    launch_diag_chain_eval(ctx->stream, mode, ctx->d_states, ctx->d_partials);
+  }
+  return DSM_OK;
+}
+
+// single fused evaluation.  form / residual_only: dsm_diag_single_eval alone (every other caller: 0, 0)
 static int single_eval(dsm_tracker *t, int mode, int lvl, const double *pose, const double *aff, float scale,
-                       float cutoff, SingleOut *out) {
+                       float cutoff, SingleOut *out, int form = 0, int residual_only = 0) {
   if (!t) return invalid("null tracker");
   if (lvl < 0 || lvl >= t->nlevels) return invalid("level out of range");
   dsm_context *ctx = t->ctx;
   dsm_tracker *ts[1] = {t};
   int rc = prepare_batch(ctx, 1, ts, mode);
   if (rc) return rc;
+  const int nch = level_chunks(t->desc, lvl);
+  if (form == 2 && nch >= (1 << kTickChunkBits)) return invalid("dsm_diag_single_eval: level too large for an item list");
+  if (form == 3 && nch > 1) return invalid("dsm_diag_single_eval: form 3 wants a level of one chunk under the tracker's chunk table");
   StartInfo &I = ctx->h_start[0];
   memset(&I, 0, sizeof I);
   if (pose) memcpy(I.pose, pose, sizeof I.pose);
@@ -1755,16 +1783,27 @@ static int single_eval(dsm_tracker *t, int mode, int lvl, const double *pose, co
   I.scale = scale;
   I.cutoff = cutoff;
   I.lvl = lvl;
+  I.residual_only = residual_only;
   DSM_HIP(hipMemcpyAsync(ctx->d_start, ctx->h_start, sizeof(StartInfo), hipMemcpyHostToDevice, ctx->stream));
   launch_lm(ctx->stream, mode, LM_OP_SINGLE_PREP, lvl, 1, ctx->d_tracker_ptrs, ctx->d_states, ctx->d_partials,
             ctx->partial_stride, ctx->d_start, nullptr, nullptr);
-  launch_eval(ctx->stream, mode, lvl, round8(level_chunks(t->desc, lvl) > 0 ? level_chunks(t->desc, lvl) : 1), 1, ctx->d_tracker_ptrs,
-              ctx->d_states, ctx->d_partials, ctx->partial_stride, nullptr, nullptr);
+  std::vector<void *> scratch; // device memory of the diagnostic forms, freed once the stream is idle
+  if (form == 0)
+    launch_eval(ctx->stream, mode, lvl, round8(nch > 0 ? nch : 1), 1, ctx->d_tracker_ptrs,
+                ctx->d_states, ctx->d_partials, ctx->partial_stride, nullptr, nullptr);
+  else
+    rc = launch_eval_form(ctx, mode, lvl, nch, form, scratch);
+  if (rc) { // (the prepared state stays RUNNING on a failed launch: harmless, every call prepares its own)
+    for (void *p : scratch) (void)hipFree(p);
+    return rc;
+  }
   launch_lm(ctx->stream, mode, LM_OP_SINGLE_FINISH, lvl, 1, ctx->d_tracker_ptrs, ctx->d_states, ctx->d_partials,
             ctx->partial_stride, nullptr, ctx->d_single, nullptr);
   DSM_HIP(hipGetLastError());
   DSM_HIP(hipMemcpyAsync(ctx->h_single, ctx->d_single, sizeof(SingleOut), hipMemcpyDeviceToHost, ctx->stream));
-  DSM_HIP(hipStreamSynchronize(ctx->stream));
+  const hipError_t sync = hipStreamSynchronize(ctx->stream);
+  for (void *p : scratch) (void)hipFree(p);
+  DSM_HIP(sync);
   *out = ctx->h_single[0];
   return DSM_OK;
 }
@@ -1790,6 +1829,27 @@ int dsm_tracker_calc_res_scale(dsm_tracker *t, int lvl, float scale, float cutof
   if (rs) memcpy(rs, o.rs, sizeof o.rs);
   if (H) *H = o.Hs;
   if (b) *b = o.bs;
+  if (n_warped) *n_warped = o.n_warped;
+  return DSM_OK;
+}
+
+int dsm_diag_single_eval(dsm_tracker *t, int mode, int lvl, const double pose[7], const double aff[2], float scale, float cutoff_th,
+                         int form, int residual_only, double rs[6], double H[64], double b[8], float *Hs, float *bs, int *n_warped) {
+  if (mode < 0 || mode > 1) return invalid("dsm_diag_single_eval: mode is 0 (pose) or 1 (scale)");
+  if (form < 0 || form > 3) return invalid("dsm_diag_single_eval: form is 0 .. 3");
+  if (mode == 0 && (!pose || !aff)) return invalid("dsm_diag_single_eval: null pose/aff");
+  SingleOut o;
+  int rc = single_eval(t, mode, lvl, mode == 0 ? pose : nullptr, mode == 0 ? aff : nullptr, mode == 0 ? 1.0f : scale, cutoff_th, &o, form,
+                       residual_only ? 1 : 0);
+  if (rc) return rc;
+  if (rs) memcpy(rs, o.rs, sizeof o.rs);
+  if (mode == 0) {
+    if (H) memcpy(H, o.H, sizeof o.H);
+    if (b) memcpy(b, o.b, sizeof o.b);
+  } else {
+    if (Hs) *Hs = o.Hs;
+    if (bs) *bs = o.bs;
+  }
   if (n_warped) *n_warped = o.n_warped;
   return DSM_OK;
 }

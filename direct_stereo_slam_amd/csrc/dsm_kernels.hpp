@@ -59,6 +59,7 @@ struct StartInfo { // host -> device, one per problem
   float cutoff; // single evaluation only
   int coarsest;
   int lvl;      // single evaluation only
+  int residual_only; // single evaluation only (dsm_diag_single_eval): EvalIn::residual_only
 };
 
 // mode: 0 = pose (calcResPose + calcGSSSEPose), 1 = scale (calcResScale + calcGSSSEScale)
@@ -165,6 +166,9 @@ int lm_spin_expired();
 // persistent LM loop of the levels whose evaluation is ONE chunk (chain_kernel: the tick engine's chain as a launch of its own, one
 // workgroup per problem, until the problem reaches a level of several chunks or terminates; no speculative candidates)
 void launch_chain(hipStream_t s, int mode, int nprob, const TrackerDev *const *trackers, LMState *states, int *status_out);
+
+// dsm_diag_single_eval: problem 0's staged evaluation (one chunk) in the chains' form, its partial into partials[0 .. 52)
+void launch_diag_chain_eval(hipStream_t s, int mode, const LMState *states, float *partials);
 
 // row A4 / N3: makeCoarseDepthL0 on the device (template_kernels.hip), batched over the keyframes of a call
 struct TplJob {

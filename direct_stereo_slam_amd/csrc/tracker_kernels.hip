@@ -738,7 +738,7 @@ __device__ __forceinline__ void make_eval_cutoff(const TrackerDev &T, EvalIn &e,
 // The complete inputs of an evaluation at `lvl` into the problem state: one thread (a level's first evaluation, a single evaluation
 // of dsm_tracker_calc_res_*).
 __device__ __forceinline__ void make_eval_any(const TrackerDev &T, LMState &S, int mode, int lvl, const double pose[7], const double aff[2],
-                              float scale, float cutoff) {
+                              float scale, float cutoff, bool residual_only = false) {
   EvalIn &e = S.in;
   make_eval_level(T, e, mode, lvl);
   if (mode == 1) {
@@ -747,7 +747,7 @@ __device__ __forceinline__ void make_eval_any(const TrackerDev &T, LMState &S, i
     make_eval_rot(e, mode, pose, true);
     make_eval_aff(T, e, mode, aff, true);
   }
-  make_eval_cutoff(T, e, cutoff, false, true);
+  make_eval_cutoff(T, e, cutoff, residual_only, true);
 }
 
 // lane 0 only
@@ -1796,7 +1796,7 @@ __global__ __launch_bounds__(kLmThreads) void lm_kernel(int mode, int op, int lv
       S.status = ST_RUNNING;
       S.lvl = I.lvl;
       S.spec_valid = 0;
-      make_eval_any(T, S, mode, I.lvl, I.pose, I.aff, I.scale, I.cutoff);
+      make_eval_any(T, S, mode, I.lvl, I.pose, I.aff, I.scale, I.cutoff, I.residual_only != 0);
     }
     return;
   }
@@ -2450,6 +2450,38 @@ void launch_chain(hipStream_t s, int mode, int nprob, const TrackerDev *const *t
     hipLaunchKernelGGL((chain_kernel<1>), dim3(nprob), dim3(kThreads), 0, s, trackers, states, status_out);
   else
     hipLaunchKernelGGL((chain_kernel<2>), dim3(nprob), dim3(kThreads), 0, s, trackers, states, status_out);
+}
+
+// dsm_diag_single_eval, form 3: ONE evaluation in the form the chains run it (chain_kernel above, tick_eval_kernel's chain path) -- the
+// inputs from the LDS copy of the state, the level's single chunk into an LDS partial with the workgroup barrier between the row sums
+// and the final sum -- and the partial copied out to where LM_OP_SINGLE_FINISH reads it.  The same eval_chunk instantiations under the
+// same register budget as the chains'; no state machine.  A level of no chunk writes nothing (as the chains evaluate nothing there).
+template <int MODE>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void diag_chain_eval_kernel(const LMState *__restrict__ states,
+                                                                                                        float *__restrict__ partials) {
+  __shared__ float red[16][kNumSlots];
+  __shared__ __attribute__((aligned(16))) LMState st;
+  __shared__ __attribute__((aligned(16))) float part[kPartialStride];
+  const int tid = threadIdx.x;
+  stage_in(st, states, tid, kThreads);
+  if (tid < kPartialStride) part[tid] = 0.f; // (the scale problem writes 7 of the 52 slots)
+  __syncthreads();
+  const int status = __builtin_amdgcn_readfirstlane(st.status), lvl = __builtin_amdgcn_readfirstlane(st.lvl);
+  EvalConsts c;
+  eval_consts_from_lds(st.in, c);
+  if (status != ST_RUNNING || st.is_scale != MODE || chunks_of(c.n, c.ppt) != 1) return; // workgroup-uniform
+  if (lvl == 0)
+    eval_chunk<MODE, true>(c, 0, tid, true, red, part);
+  else
+    eval_chunk<MODE, false, true, 1>(c, 0, tid, true, red, part);
+  __syncthreads();
+  if (tid < kNumSlots) partials[tid] = part[tid];
+}
+void launch_diag_chain_eval(hipStream_t s, int mode, const LMState *states, float *partials) {
+  if (mode == 0)
+    hipLaunchKernelGGL((diag_chain_eval_kernel<0>), dim3(1), dim3(kThreads), 0, s, states, partials);
+  else
+    hipLaunchKernelGGL((diag_chain_eval_kernel<1>), dim3(1), dim3(kThreads), 0, s, states, partials);
 }
 
 void launch_tick_reserve(hipStream_t s, const TickReserveArgs &a, const LMState *states, TickModeCtl *mcs, long long *admit_idx) {

@@ -597,6 +597,23 @@ class TrackerAndScaler:
         check(self.L.dsm_tracker_calc_res_scale(self.h, lvl, scale, cutoff, _dp(rs), C.byref(H), C.byref(b), C.byref(n)))
         return rs, H.value, b.value, n.value
 
+    def diagEvalPose(self, lvl, pose, aff, cutoff, form=0, residual_only=False):
+        """calcResPose with the evaluation launched in a chosen form of the loop (dsm_diag_single_eval): 0 the direct calls' kernel,
+        1 the split pair, 2 the tick engine's items, 3 the chains' one-chunk form; returns (rs[6], H[8,8], b[8], n_warped)"""
+        pose = np.ascontiguousarray(pose, np.float64)
+        aff = np.ascontiguousarray(aff, np.float64)
+        rs, H, b, n = np.zeros(6), np.zeros(64), np.zeros(8), C.c_int()
+        check(self.L.dsm_diag_single_eval(self.h, 0, lvl, _dp(pose), _dp(aff), 1.0, cutoff, form, int(residual_only), _dp(rs), _dp(H), _dp(b),
+                                          None, None, C.byref(n)))
+        return rs, H.reshape(8, 8), b, n.value
+
+    def diagEvalScale(self, lvl, scale, cutoff, form=0, residual_only=False):
+        """calcResScale likewise; returns (rs[6], h00, h01, n_warped)"""
+        rs, H, b, n = np.zeros(6), C.c_float(), C.c_float(), C.c_int()
+        check(self.L.dsm_diag_single_eval(self.h, 1, lvl, None, None, scale, cutoff, form, int(residual_only), _dp(rs), None, None, C.byref(H),
+                                          C.byref(b), C.byref(n)))
+        return rs, H.value, b.value, n.value
+
     def trackNewestCoarse(self, lastToNew, aff_g2l, coarsestLvl, minResForAbort=None):
         """returns (good, lastToNew_out, aff_g2l_out, lastResiduals) and sets lastFlowIndicators"""
         pose = np.array(lastToNew, np.float64)

@@ -364,6 +364,18 @@ int dsm_tracker_calc_res_pose(dsm_tracker *t, int lvl, const double pose[7], con
 /* replaces calcResScale + calcGSSSEScale (TrackerAndScaler.cpp:1007-1172, 966-1005) */
 int dsm_tracker_calc_res_scale(dsm_tracker *t, int lvl, float scale, float cutoff_th, double rs[6],
                                float *H, float *b, int *n_warped);
+/* test aid (no reference counterpart): ONE evaluation as dsm_tracker_calc_res_pose (mode 0) / _scale (mode 1) runs it -- the same
+ * preparation, the same reduction of the chunk partials, outputs of the same meaning (H, b: mode 0; Hs, bs: mode 1; pose, aff: mode 0;
+ * scale: mode 1) -- with the evaluation itself launched in a chosen form of the evaluation loop:
+ *   0  the evaluation kernel of the direct calls (with residual_only = 0: bit for bit what dsm_tracker_calc_res_* return);
+ *   1  the split pair of the batched schedules: the kernel of the full evaluations, then the kernel of the residual-only ones;
+ *   2  the tick engine's kernel (dsm_stream_*) over an item list of this evaluation's chunks;
+ *   3  the one-chunk form of the chains (dsm_params.persistent_coarse < 0, the tick engine's chains): the partial formed in LDS.  Only for a
+ *      level of at most one chunk under the tracker's chunk table (dsm_reduction_geometry); DSM_ERR_INVALID otherwise.
+ * residual_only != 0: the evaluation that ends an LM loop -- energy, counts and flow indicators; the normal equations are not formed
+ * (H, b, Hs, bs come back as zeros).  A bad mode, form or level is DSM_ERR_INVALID with nothing written.  No production path calls this. */
+int dsm_diag_single_eval(dsm_tracker *t, int mode, int lvl, const double pose[7], const double aff[2], float scale, float cutoff_th,
+                         int form, int residual_only, double rs[6], double H[64], double b[8], float *Hs, float *bs, int *n_warped);
 
 /* replaces TrackerAndScaler::trackNewestCoarse (TrackerAndScaler.cpp:451-638).
  * min_res_for_abort / last_residuals: DSM_MAX_LEVELS doubles (reference: Vec5; NaN = no limit).

@@ -85,6 +85,16 @@ def _common(npt, buf, rs, cutoff):
                 flow64=np.array([np.sum(fT) / (nflow + 0.1), np.sum(fRT) / (nflow + 0.1)]))
 
 
+def residual_ref(npt, lvl, T, aff, cutoff):
+    """the residual side of one pose evaluation alone -- what a residual-only evaluation returns: the integer outputs, E64 and the flow
+    sums of pose_ref without the Jacobians (and the buffers of the usable points, `buf`)"""
+    rs = npt.calc_res_pose(lvl, T, aff, cutoff)
+    B = npt.pose_buf
+    out = _common(npt, B, rs, cutoff)
+    out.update(n4=(len(B["hw"]) + 3) & ~3, idx=B["idx"], n_tpl=len(npt.pc[lvl][0]), Eterms=energy_terms(B), buf=B)
+    return out
+
+
 def pose_ref(npt, lvl, T, aff, cutoff):
     """one pose evaluation of NumpyTracker npt at the 4x4 pose T"""
     rs = npt.calc_res_pose(lvl, T, aff, cutoff)

@@ -3,11 +3,14 @@
       restated in numpy float32 on the oracle's per-point values, lies well inside the reduction part of the bound for every
       chunk table -- so the bound is not tight against the order the device really uses;
   (b) the bound has teeth: a lost or doubled point and an entry off by 100 u A pass the whole-matrix bars of
-      tests/test_parity_tracker.py and fail the per-entry bound."""
+      tests/test_parity_tracker.py and fail the per-entry bound;
+  (c) the residual-only assertions of tests/test_eval_forms_f64.py have teeth: a lost point, a doubled point and a point whose
+      intensity is gathered one column to the right, over the chunk-edge sweep's sizes."""
 import numpy as np
 import pytest
 
 import _gn_f64 as G
+from _gn_checks import sweep_sizes
 from _scenes import make_scene
 from direct_stereo_slam_amd import synth as S
 from oracle import numpy_ref as N
@@ -210,3 +213,104 @@ def test_bound_catches_one_entry_off_by_100_u_A(kitti_65537, pose):
         h = sref["h64"].copy()
         h[e] += 100 * G.U * sref["A"][e]
         assert old_scale_ok(h[0], h[1], float(h_o), float(hb_o)) and not new_scale_ok(h, sref, P), e
+
+
+# ---- (c) the residual-only assertions' teeth ------------------------------------------------------------------------------
+def ro_device(ref, P, Eterms, idx, n_terms, n_sat):
+    """what a residual-only evaluation returns -- (E, numTermsInE, saturated share, padded warped count) -- for usable points at template
+    indices idx with energy terms Eterms, under the device's tree at P points per thread (build_rs: the float of E's double sum plus
+    n_sat x max_energy)"""
+    tree = float(device_tree(Eterms[None, :], idx, ref["n_tpl"], P)[0]) if len(idx) else 0.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(np.float32(tree + n_sat * float(ref["max_energy"]))), n_terms, np.float32(n_sat) / np.float32(n_terms), (len(idx) + 3) & ~3
+
+
+def ro_caught(out, ref, P):
+    """which of test_eval_forms_f64's residual-only assertions (tests/_gn_checks.py common_checks) fails on `out`: 'int', 'E' or None"""
+    E, n_terms, sat_ratio, n4 = out
+    if n_terms != ref["n_terms"] or n4 != ref["n4"] or (ref["n_terms"] > 0 and sat_ratio != ref["sat_ratio"]):
+        return "int"
+    if ref["n_terms"] > 0 and abs(E - ref["E64"]) > min(2e-6 * ref["E64"], G.energy_bound(ref["E64"], P)):
+        return "E"
+    return None
+
+
+def shifted_terms(npt, ref, aff, cutoff):
+    """every usable point's residual taken from the texel one column to the right (Ku + 1): (its energy term, whether the point stays
+    usable -- finite and below the cut-off, so that the integer outputs do not move)"""
+    B = ref["buf"]
+    a, b = N.aff_from_to(npt.ref_exposure, npt.new_exposure, npt.ref_aff, aff)
+    Ku, Kv = npt.fx[0] * B["u"] + npt.cx[0], npt.fy[0] * B["v"] + npt.cy[0]
+    h = N.interp33(npt.new_dIp[0], Ku + np.float32(1), Kv)[:, 0]
+    r = h - (np.float32(a) * B["refc"] + np.float32(b))
+    ar = np.abs(r)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        hw = np.where(ar < npt.huber, np.float32(1), npt.huber / ar).astype(np.float32)
+        return (((hw * r) * r) * (np.float32(2) - hw)).astype(np.float32), np.isfinite(h) & (ar <= np.float32(cutoff))
+
+
+SHIFT_LOW_DECILE_CAUGHT = [1, 2, 3, 4, 5, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 4609, 8193,
+                           16383, 16384, 16385, 20481, 65535, 65536, 65537, 81921]
+
+
+def test_residual_only_assertions_catch_one_wrong_point(built):
+    """The residual-only assertions (integer outputs equal, E within min(2e-6 E64, energy_bound)) against an emulated residual-only
+    evaluation (the device's tree on the oracle's terms) of level 0 of the dense KITTI template, seed 21, at the true pose, cut to the
+    chunk-edge sweep's sizes -- the first n points as the sweep cuts them; where those hold no usable point (n <= 513: the template's
+    first rows leave the image), n points from the first usable point of the template's second half.  Loosest table of each size.
+      * one usable point dropped, one counted twice: caught by the integer outputs at EVERY size;
+      * one usable point's residual taken from the texel one column to the right (what a two-tap gather does when it goes wrong), the
+        point staying usable so that the integer outputs cannot see it: E moves by the difference d of two energy terms, and the bar
+        catches it while d exceeds about 2e-6 E64.  For the point of MEDIAN d among the usable ones that is every size of the sweep, the
+        full 446 992 points included (d = 6.5e-6 E64 there, 3.2 times the bar).  For the point at the LOWEST DECILE of d it is the
+        sizes of SHIFT_LOW_DECILE_CAUGHT: every size up to 81 921, none from 262 143 up.  Largest n caught: 81 921, where d is 0.999 of
+        the bar and the tree's own rounding of E tips it over; 1.24 of the bar at 65 537, 0.35 at 262 143.  At 446 992 points 72 % of the
+        usable points are individually visible to the E bar (asserted below as 0.70 .. 0.75), 91 % at 65 537, all of them up to 2049."""
+    sc = make_scene("kitti", seed=21)
+    npt = numpy_tracker(sc)
+    T, aff, cutoff = T_of(sc.gt_pose), list(sc.gt_aff), 20.0
+    whole = len(sc.tpl[0][0])
+    assert whole == 446992
+    idx_whole = G.residual_ref(npt, 0, T, aff, cutoff)["idx"]
+    mid = int(idx_whole[np.searchsorted(idx_whole, whole // 2)])
+    low_caught, rows = [], []
+    for n in sweep_sizes() + [whole]:
+        for start in (0, mid):
+            npt.set_ref(0.0, 0.0, 1.0, *[[a[0][start:start + n].copy()] + list(a[1:]) for a in sc.tpl])
+            ref = G.residual_ref(npt, 0, T, aff, cutoff)
+            if len(ref["idx"]):
+                break
+        m = len(ref["idx"])
+        assert m > 0 and ref["n_tpl"] == n, n
+        P = max(G.pts_per_thread(n, g) for g in (0, 1, 2))
+        args = (ref["Eterms"], ref["idx"], ref["n_terms"], ref["n_sat"])
+        assert ro_caught(ro_device(ref, P, *args), ref, P) is None, n  # the unmutated evaluation passes
+        k = m // 2
+        keep = np.arange(m) != k
+        assert ro_caught(ro_device(ref, P, ref["Eterms"][keep], ref["idx"][keep], ref["n_terms"] - 1, ref["n_sat"]), ref, P) == "int", ("dropped", n)
+        twice = (np.append(ref["Eterms"], ref["Eterms"][k]), np.append(ref["idx"], n), ref["n_terms"] + 1, ref["n_sat"])  # (the copy in a slot past the list)
+        ref_t = dict(ref, n_tpl=n + 1)
+        assert ro_caught(ro_device(ref_t, P, *twice), ref, P) == "int", ("doubled", n)
+        terms, stays = shifted_terms(npt, ref, aff, cutoff)
+        d = np.abs(terms.astype(np.float64) - ref["Eterms"].astype(np.float64))
+        cand = np.flatnonzero(stays)
+        if len(cand) == 0:  # (n = 1 .. 5: the shifted point leaves the usable set -- the integer outputs see it)
+            low_caught.append(n)
+            continue
+        order = cand[np.argsort(d[cand], kind="stable")]
+        got = {}
+        for name, k in (("median", order[len(order) // 2]), ("low decile", order[len(order) // 10])):
+            Et = ref["Eterms"].copy()
+            Et[k] = terms[k]
+            got[name] = ro_caught(ro_device(ref, P, Et, *args[1:]), ref, P)
+        bar = min(2e-6 * ref["E64"], G.energy_bound(ref["E64"], P))
+        rows.append((n, m, got["median"], got["low decile"], float(d[order[len(order) // 2]] / bar), float(d[order[len(order) // 10]] / bar),
+                     float(np.mean(d[cand] > bar))))
+        assert got["median"] == "E", ("a typical point's shifted gather", n, rows[-1])
+        if got["low decile"] == "E":
+            low_caught.append(n)
+    print("n, usable, median caught, low decile caught, d / bar (median, low decile), share of points with d > bar")
+    for r in rows:
+        print("  ", r)
+    assert low_caught == SHIFT_LOW_DECILE_CAUGHT, low_caught
+    assert 0.70 <= rows[-1][-1] <= 0.75, rows[-1]
