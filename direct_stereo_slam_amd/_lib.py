@@ -121,6 +121,15 @@ class IcpJob(C.Structure):
         ("score", c_float_p), ("ok", c_int_p), ("iterations", c_int_p), ("state", c_int_p), ("corr_counts", c_int_p),
     ]
 
+
+class PoseJob(C.Structure):
+    _fields_ = [
+        ("n_pts", C.c_int), ("xyz", c_double_p), ("ref_colors", C.POINTER(c_float_p)), ("ref_ab_exposure", C.c_float),
+        ("new_dIp", C.POINTER(c_float_p)), ("new_I", C.POINTER(c_float_p)), ("new_ab_exposure", C.c_float), ("new_cam", C.c_float * 4),
+        ("ref_to_new_io", c_double_p), ("pose_error", c_float_p), ("inlier_percent", c_int_p), ("ok", c_int_p),
+    ]
+
+
 # every symbol include/dsm_hotpath.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _pp_f = C.POINTER(c_float_p)
@@ -208,6 +217,9 @@ SYMBOLS = {
     "dsm_pose_estimator_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(_vp)]),
     "dsm_pose_estimator_destroy": (C.c_int, [_vp]),
     "dsm_pose_estimator_estimate": (C.c_int, [_vp, C.c_int, c_double_p, _pp_f, C.c_float, _pp_f, C.c_float, c_float_p, C.c_int, c_double_p, c_float_p, c_int_p]),
+    "dsm_pose_batch_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(_vp)]),
+    "dsm_pose_batch_destroy": (C.c_int, [_vp]),
+    "dsm_pose_estimate_batch": (C.c_int, [_vp, C.c_int, C.POINTER(PoseJob), C.c_int]),
     "dsm_ringdb_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_float, c_float_p, C.c_int64, C.c_int, C.c_int, C.POINTER(_vp)]),
     "dsm_ringdb_destroy": (C.c_int, [_vp]),
     "dsm_ringdb_size": (C.c_int64, [_vp]),

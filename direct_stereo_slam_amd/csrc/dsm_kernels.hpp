@@ -213,6 +213,22 @@ struct PyrJob {
   const void *src; // device-visible address of the caller's pinned image (kernel copy path), else null
 };
 void launch_desc_scatter(hipStream_t s, int n, const TrackerDev *d_src, TrackerDev *const *d_dst);
+// dsm_pose_estimate_batch (pose_batch_kernels.hip): one job's template pack and one job's pyramid import
+struct PosePackJob {
+  const double *xyz;                // n x 3 (the staged arena, or the caller's page-locked array)
+  const float *col[DSM_MAX_LEVELS]; // n each
+  float4 *pts[DSM_MAX_LEVELS];      // n + kTemplatePad entries each
+  int n, pad;
+};
+struct PoseImportJob {
+  const float *in3[DSM_MAX_LEVELS]; // staged (I, dx, dy) texels, 16-byte aligned
+  float *plane[DSM_MAX_LEVELS];     // intensity planes, 16-byte aligned
+  int *bad;                         // [level]{count, smallest index} of the gradient check
+};
+// every level of every job in one launch; max_n: the largest n of the table
+void launch_pose_pack(hipStream_t s, const PosePackJob *d_jobs, int njobs, int nlevels, int max_n);
+// every level of a wave of jobs in one launch; check: count the texels whose gradient channels are not makeImages' (as launch_dip_import)
+void launch_pose_import(hipStream_t s, const PoseImportJob *d_jobs, int njobs, int w, int h, int nlevels, bool check, float tol);
 // raw <- src for every job, rows of row_bytes at pitch `pitch` in src (tight in raw); unit: 16, 4 or 1 bytes per access
 void launch_host_rows_copy(hipStream_t s, const PyrJob *d_jobs, int njobs, int row_bytes, int rows, size_t pitch, int unit, int max_blocks);
 void launch_pyramid_batched(hipStream_t s, int w, int h, int nlevels, const PyrJob *d_jobs, int njobs, bool u8);

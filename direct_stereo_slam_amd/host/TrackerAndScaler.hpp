@@ -437,4 +437,51 @@ private:
   dsm_pose_estimator *pe_ = nullptr;
 };
 
+// One match of PoseEstimatorBatch::estimate: the arguments of PoseEstimator::estimate and its results.
+struct PoseMatch {
+  int n = 0;                                // pts.size()
+  const double *xyz = nullptr;              // n x 3 doubles: pts[i].first
+  const float *const *ref_colors = nullptr; // ref_colors[lvl][i] = pts[i].second[lvl]
+  float ref_ab_exposure = 1.0f;
+  FrameView new_fh;                         // dIp and ab_exposure of the current keyframe ...
+  const float *const *new_I = nullptr;      // ... or, with new_fh.dIp null, its intensity planes per level
+  float new_cam[4] = {0, 0, 0, 0};
+  double ref_to_new[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; // in: the guess, out: the result (row-major 4x4)
+  float pose_error = 0.0f;
+  int inlier_percent = 0;
+  bool ok = false;
+};
+
+// PoseEstimator::estimate of the matches of many sequences in ONE call (dsm_pose_estimate_batch): every match's ref_to_new, pose_error
+// and ok equal those of PoseEstimator::estimate on the same arguments, bit for bit.  One geometry (w, h, pyrLevelsUsed) per object.
+class PoseEstimatorBatch {
+public:
+  PoseEstimatorBatch(dsm_context *ctx, int w, int h, int pyrLevelsUsed, const dsm_params *params = nullptr) {
+    check_abi();
+    check(dsm_pose_batch_create(ctx, w, h, pyrLevelsUsed, params, &pb_), "dsm_pose_batch_create");
+  }
+  ~PoseEstimatorBatch() { dsm_pose_batch_destroy(pb_); }
+  PoseEstimatorBatch(const PoseEstimatorBatch &) = delete;
+  PoseEstimatorBatch &operator=(const PoseEstimatorBatch &) = delete;
+
+  void estimate(std::vector<PoseMatch> &matches, int coarsest_lvl) {
+    if (matches.empty()) return;
+    std::vector<dsm_pose_job> jobs(matches.size());
+    std::vector<int> ok(matches.size(), 0);
+    for (size_t j = 0; j < matches.size(); j++) {
+      PoseMatch &m = matches[j];
+      dsm_pose_job &J = jobs[j];
+      J.n_pts = m.n, J.xyz = m.xyz, J.ref_colors = m.ref_colors, J.ref_ab_exposure = m.ref_ab_exposure;
+      J.new_dIp = m.new_fh.dIp, J.new_I = m.new_I, J.new_ab_exposure = m.new_fh.ab_exposure;
+      for (int k = 0; k < 4; k++) J.new_cam[k] = m.new_cam[k];
+      J.ref_to_new_io = m.ref_to_new, J.pose_error = &m.pose_error, J.inlier_percent = &m.inlier_percent, J.ok = &ok[j];
+    }
+    check(dsm_pose_estimate_batch(pb_, (int)jobs.size(), jobs.data(), coarsest_lvl), "PoseEstimatorBatch::estimate");
+    for (size_t j = 0; j < matches.size(); j++) matches[j].ok = ok[j] != 0;
+  }
+
+private:
+  dsm_pose_batch *pb_ = nullptr;
+};
+
 } // namespace dsm_host

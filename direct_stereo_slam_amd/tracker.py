@@ -692,6 +692,106 @@ class PoseEstimator:
         return bool(ok.value), T.reshape(4, 4), err.value
 
 
+class PoseBatch:
+    """`dso::PoseEstimator::estimate` of many matches in one call (dsm_pose_estimate_batch): one geometry, per job its own points,
+    colours, intrinsics, exposures and guess.  A job is a dict with the keys pts_xyz, ref_colors, ref_ab_exposure, new_ab_exposure,
+    new_cam, ref_to_new and exactly one of new_dIp (the AoS (I,dx,dy) pyramid) / new_I (its intensity planes)."""
+
+    KEYS = ("pts_xyz", "ref_colors", "ref_ab_exposure", "new_ab_exposure", "new_cam", "ref_to_new")
+
+    def __init__(self, ctx, w, h, nlevels, params=None):
+        self.ctx, self.L = ctx, ctx.L
+        self.w, self.h, self.nlevels = w, h, nlevels
+        self.params = params if params is not None else default_params()
+        hnd = C.c_void_p()
+        check(self.L.dsm_pose_batch_create(ctx.h, w, h, nlevels, C.byref(self.params), C.byref(hnd)))
+        self.h_ = hnd
+
+    def close(self):
+        if getattr(self, "h_", None) and getattr(self.ctx, "h", None):
+            self.L.dsm_pose_batch_destroy(self.h_)
+        self.h_ = None
+
+    def __del__(self):
+        self.close()
+
+    @staticmethod
+    def check_jobs(jobs, w, h, nlevels):
+        """what is wrong with a job list, before any library call: ValueError.  Returns the jobs with their arrays in the ABI's types;
+        the same array object passed by several jobs stays one array (the library shares the planes of a shared target pyramid)."""
+        if len(jobs) < 1:
+            raise ValueError("PoseBatch: an empty job list")
+        conv = {}  # id(caller's array) -> converted array
+
+        def as_f32(a):
+            if id(a) not in conv:
+                conv[id(a)] = (a, np.ascontiguousarray(a, np.float32))
+            return conv[id(a)][1]
+
+        out = []
+        for j, job in enumerate(jobs):
+            missing = [k for k in PoseBatch.KEYS if k not in job]
+            if missing:
+                raise ValueError(f"PoseBatch: job {j} lacks {missing}")
+            has_dip, has_i = job.get("new_dIp") is not None, job.get("new_I") is not None
+            if has_dip == has_i:
+                raise ValueError(f"PoseBatch: job {j} needs exactly one of new_dIp and new_I")
+            xyz = np.ascontiguousarray(job["pts_xyz"], np.float64)
+            if xyz.ndim != 2 or xyz.shape[1] != 3 or not 1 <= len(xyz) <= w * h:
+                raise ValueError(f"PoseBatch: job {j}: pts_xyz must be n x 3 with 1 <= n <= w*h")
+            cols = [np.ascontiguousarray(c, np.float32).reshape(-1) for c in job["ref_colors"]]
+            if len(cols) != nlevels or any(len(c) != len(xyz) for c in cols):
+                raise ValueError(f"PoseBatch: job {j}: ref_colors must hold {nlevels} lists of {len(xyz)} colours (one per point and level)")
+            tgt = [as_f32(a) for a in (job["new_dIp"] if has_dip else job["new_I"])]
+            if len(tgt) != nlevels or any(a.size != (w >> l) * (h >> l) * (3 if has_dip else 1) for l, a in enumerate(tgt)):
+                raise ValueError(f"PoseBatch: job {j}: the target pyramid must hold {nlevels} levels of this batch's geometry")
+            cam = np.ascontiguousarray(job["new_cam"], np.float32).reshape(-1)
+            T = np.array(job["ref_to_new"], np.float64).reshape(-1)
+            if len(cam) != 4 or len(T) != 16:
+                raise ValueError(f"PoseBatch: job {j}: new_cam is (fx, fy, cx, cy), ref_to_new a 4 x 4 matrix")
+            out.append(dict(xyz=xyz, cols=cols, tgt=tgt, dip=has_dip, cam=cam, T=T.copy(), ref_exp=float(job["ref_ab_exposure"]),
+                            new_exp=float(job["new_ab_exposure"])))
+        return out
+
+    @staticmethod
+    def build_jobs(js):
+        """the dsm_pose_job array of checked jobs (check_jobs), and what must outlive the call: (array, outputs, keep-alive list);
+        outputs = (T n x 16 holding the guesses, pose_error, inlier_percent, ok)"""
+        n = len(js)
+        arr = (_lib.PoseJob * n)()
+        T = np.stack([j["T"] for j in js])
+        err, inl, ok = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        keep = [js]
+        tables = {}  # one pointer table per target pyramid: jobs that share a pyramid pass the same level pointers
+        for i, j in enumerate(js):
+            cols = _ptr_array(j["cols"])
+            key = tuple(id(a) for a in j["tgt"])
+            if key not in tables:
+                tables[key] = _ptr_array(j["tgt"])
+            keep.append(cols)
+            a = arr[i]
+            a.n_pts, a.xyz, a.ref_colors, a.ref_ab_exposure = len(j["xyz"]), _dp(j["xyz"]), cols, j["ref_exp"]
+            if j["dip"]:
+                a.new_dIp = tables[key]
+            else:
+                a.new_I = tables[key]
+            a.new_ab_exposure = j["new_exp"]
+            a.new_cam[:] = [float(v) for v in j["cam"]]
+            a.ref_to_new_io = _dp(T[i:])
+            a.pose_error = err[i:].ctypes.data_as(c_float_p)
+            a.inlier_percent = inl[i:].ctypes.data_as(c_int_p)
+            a.ok = ok[i:].ctypes.data_as(c_int_p)
+        keep.append(tables)
+        return arr, (T, err, inl, ok), keep
+
+    def estimate_many(self, jobs, coarsest_lvl):
+        """per job (ok, ref_to_new 4x4, pose_error, inlier_percent)"""
+        arr, (T, err, inl, ok), keep = self.build_jobs(self.check_jobs(jobs, self.w, self.h, self.nlevels))
+        check(self.L.dsm_pose_estimate_batch(self.h_, len(arr), arr, coarsest_lvl))
+        del keep
+        return [(bool(ok[i]), T[i].reshape(4, 4).copy(), float(err[i]), int(inl[i])) for i in range(len(arr))]
+
+
 def track_hypotheses(ctx, trk, tries, aff_last_2_l, coarsestLvl, last_coarse_rmse0, reTrackThreshold=1.5):
     """The hypothesis loop of FrontEnd::trackNewCoarse (FrontEnd.cpp:194-247) with the same results as
     the reference's sequential loop, but evaluated as ONE batched launch sequence ("next" row N4).

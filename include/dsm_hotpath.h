@@ -569,6 +569,42 @@ int dsm_pose_estimator_estimate(dsm_pose_estimator *pe, int n_pts, const double 
                                 const float *const *new_dIp, float new_ab_exposure, const float new_cam[4],
                                 int coarsest_lvl, double ref_to_new_io[16], float *pose_error, int *ok);
 
+/* PoseEstimator::estimate of MANY matches in one call (the call site LoopHandler.cpp:274-279 of every sequence a node serves, between
+ * dsm_loop_detect_batch_many and dsm_icp_batch).  A dsm_pose_batch serves one geometry (w, h, nlevels) and one dsm_params; intrinsics,
+ * exposures, point counts and guesses differ per job.  Per job the result -- matrix, pose_error, ok -- equals
+ * dsm_pose_estimator_estimate of that job on a handle of the same w, h, nlevels and params bit for bit, whatever the batch size and the
+ * job's place in it.
+ *   - Footprint: the templates live in an arena of 16 bytes x (n_pts + slack) x nlevels per job (NOT w*h per level), the targets in one
+ *     intensity plane per level and distinct target pyramid (jobs that pass the same level pointers share the planes).  The arenas grow
+ *     on demand and are kept: a repeated call of the same shape allocates nothing.
+ *   - Submission: one page-locked staging buffer with every job's points, colours, pack table and device descriptor goes to the device in
+ *     one copy (xyz / ref_colors arrays that lie in page-locked memory -- dsm_host_alloc -- are read in place instead); one pack launch
+ *     builds every template of every level; new_dIp pyramids are imported in waves of 8 jobs through a bounded staging buffer, one launch
+ *     per wave; new_I planes are copied straight to their place; then ONE mode-2 LM run over all jobs (every scheduling form of
+ *     dsm_params applies) and one read-back.  Host synchronisations: those of the LM run (one per pass), independent of n_jobs.
+ *   - Validation is all or nothing, before any output is written or anything is enqueued: DSM_ERR_INVALID for a NULL pointer,
+ *     n_jobs < 1, n_pts < 1 or > w*h, both or neither of new_dIp / new_I, a NULL level pointer, a non-finite guess or coarsest_lvl out
+ *     of range.  With dsm_params.frame_check a new_dIp whose gradient channels are not makeImages' fails the call with DSM_ERR_INVALID
+ *     naming the job, the level and the texel (as dsm_tracker_upload_frame), and no job's outputs are written. */
+typedef struct dsm_pose_batch dsm_pose_batch;
+typedef struct dsm_pose_job {
+  int n_pts;
+  const double *xyz;              /* n_pts x 3, the matched keyframe's points (LoopFrame::pts_dso) */
+  const float *const *ref_colors; /* [lvl][n_pts] */
+  float ref_ab_exposure;
+  const float *const *new_dIp;    /* the current keyframe's AoS (I,dx,dy) pyramid, as dsm_pose_estimator_estimate, or NULL */
+  const float *const *new_I;      /* ... or its intensity planes per level, as dsm_tracker_upload_intensity; exactly one of the two */
+  float new_ab_exposure;
+  float new_cam[4];               /* per job: makeK(new_cam), PoseEstimator.cpp:306 */
+  double *ref_to_new_io;          /* row-major 4x4: guess in, result out (always written, :466) */
+  float *pose_error;              /* out, may be NULL */
+  int *inlier_percent;            /* out, may be NULL (:486) */
+  int *ok;                        /* out: aff_good && pose_error < RES_THRES && inlier_percent > INNER_PERCENT (:469-505) */
+} dsm_pose_job;
+int dsm_pose_batch_create(dsm_context *ctx, int w, int h, int nlevels, const dsm_params *params, dsm_pose_batch **out);
+int dsm_pose_batch_destroy(dsm_pose_batch *pb);
+int dsm_pose_estimate_batch(dsm_pose_batch *pb, int n_jobs, const dsm_pose_job *jobs, int coarsest_lvl);
+
 /* ---- ring-key database (ScanContext place recognition) ------------------------------- */
 /* replaces the flann::Index built at LoopHandler.cpp:35-39 plus the function-static delay
  * queue of search_ringkey (search_place.h:43-45).  dim=20, margin=LOOP_MARGIN=100,
