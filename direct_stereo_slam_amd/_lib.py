@@ -130,6 +130,23 @@ class PoseJob(C.Structure):
     ]
 
 
+class LmProposeIn(C.Structure):
+    _fields_ = [
+        ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
+        ("lam", C.c_float), ("level_cutoff_repeat", C.c_float), ("iteration", C.c_int),
+        ("Hs", C.c_float), ("bs", C.c_float), ("scale_cur", C.c_float),
+    ]
+
+
+class LmProposeOut(C.Structure):
+    _fields_ = [
+        ("inc", C.c_double * 8), ("inc_norm", C.c_double), ("cand", C.c_double * 7), ("aff_cand", C.c_double * 2),
+        ("M", C.c_float * 9), ("t", C.c_float * 3), ("aff0", C.c_float), ("aff1", C.c_float), ("cutoff", C.c_float),
+        ("max_energy", C.c_float), ("residual_only", C.c_int), ("Ki", C.c_float * 9),
+        ("inc_f", C.c_float), ("scale_cand", C.c_float), ("pad", C.c_int * 2),
+    ]
+
+
 # every symbol include/dsm_hotpath.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _pp_f = C.POINTER(c_float_p)
@@ -204,6 +221,7 @@ SYMBOLS = {
     "dsm_tracker_calc_res_scale": (C.c_int, [_vp, C.c_int, C.c_float, C.c_float, c_double_p, c_float_p, c_float_p, c_int_p]),
     "dsm_diag_single_eval": (C.c_int, [_vp, C.c_int, C.c_int, c_double_p, c_double_p, C.c_float, C.c_float, C.c_int, C.c_int, c_double_p, c_double_p,
                                        c_double_p, c_float_p, c_float_p, c_int_p]),
+    "dsm_diag_lm_propose": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmProposeIn), C.c_int, C.c_int, C.POINTER(LmProposeOut)]),
     "dsm_tracker_track": (C.c_int, [_vp, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
     "dsm_tracker_optimize_scale": (C.c_int, [_vp, c_float_p, C.c_int, c_float_p]),
     "dsm_tracker_optimize_scale_guesses": (C.c_int, [_vp, C.c_int, c_float_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),

@@ -2162,4 +2162,44 @@ int dsm_diag_single_eval(dsm_tracker *t, int mode, int lvl, const double pose[7]
   return DSM_OK;
 }
 
+static_assert(sizeof(dsm_lm_propose_in) == 672 && sizeof(dsm_lm_propose_out) == 264, "mirrored by _lib.py's LmProposeIn / LmProposeOut");
+int dsm_diag_lm_propose(dsm_tracker *t, int mode, int lvl, int n, const dsm_lm_propose_in *in, int spec, int helper,
+                        dsm_lm_propose_out *out) {
+  if (!t || !in || !out) return invalid("dsm_diag_lm_propose: null argument");
+  if (n < 1 || n > 65536) return invalid("dsm_diag_lm_propose: n is 1 .. 65536");
+  if (mode < 0 || mode > 2) return invalid("dsm_diag_lm_propose: mode is 0 (pose), 1 (scale) or 2 (loop-closure pose)");
+  if (lvl < 0 || lvl >= t->nlevels) return invalid("dsm_diag_lm_propose: level out of range");
+  if (!t->have_k) return invalid("dsm_diag_lm_propose: dsm_tracker_make_k first");
+  dsm_context *ctx = t->ctx;
+  DSM_HIP(hipSetDevice(ctx->device));
+  int rc = sync_desc(t);
+  if (rc) return rc;
+  const int expired_before = lm_spin_expired();
+  if (expired_before < 0) return hip_fail(hipGetLastError(), "lm_spin_expired", __FILE__, __LINE__);
+  dsm_lm_propose_in *d_in = nullptr;
+  dsm_lm_propose_out *d_out = nullptr;
+  std::vector<dsm_lm_propose_out> h_out((size_t)n); // (the caller's array is written only by a call that succeeds)
+  hipError_t e = hipMalloc(&d_in, sizeof(dsm_lm_propose_in) * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(dsm_lm_propose_out) * (size_t)n);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, sizeof(dsm_lm_propose_in) * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof(dsm_lm_propose_out) * (size_t)n, ctx->stream);
+  if (e == hipSuccess) {
+    launch_diag_lm_propose(ctx->stream, mode, lvl, t->d_desc, n, d_in, d_out, spec != 0, helper != 0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out, sizeof(dsm_lm_propose_out) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t sync = hipStreamSynchronize(ctx->stream); // (also before the buffers are freed after a failed enqueue)
+  if (e == hipSuccess) e = sync;
+  if (d_in) (void)hipFree(d_in);
+  if (d_out) (void)hipFree(d_out);
+  DSM_HIP(e);
+  const int expired_after = lm_spin_expired();
+  if (expired_after != expired_before) {
+    set_error("dsm_diag_lm_propose: a bounded wait of the LM step's wave hand-shake expired");
+    return DSM_ERR_STATE;
+  }
+  memcpy(out, h_out.data(), sizeof(dsm_lm_propose_out) * (size_t)n);
+  return DSM_OK;
+}
+
 } // extern "C"

@@ -4,6 +4,9 @@
 #pragma once
 #include "dsm_device.hpp"
 
+struct dsm_lm_propose_in; // include/dsm_hotpath.h
+struct dsm_lm_propose_out;
+
 namespace dsm {
 
 // Reduction geometry (part of the documented numerics): a workgroup of 256 threads owns a chunk of 256*P
@@ -169,6 +172,11 @@ void launch_chain(hipStream_t s, int mode, int nprob, const TrackerDev *const *t
 
 // dsm_diag_single_eval: problem 0's staged evaluation (one chunk) in the chains' form, its partial into partials[0 .. 52)
 void launch_diag_chain_eval(hipStream_t s, int mode, const LMState *states, float *partials);
+
+// dsm_diag_lm_propose: propose_pose / propose_scale (and the raw solve) on n caller-supplied systems, one workgroup per problem; the
+// structures are the public ones of include/dsm_hotpath.h
+void launch_diag_lm_propose(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_propose_in *in,
+                            ::dsm_lm_propose_out *out, bool spec, bool helper);
 
 // row A4 / N3: makeCoarseDepthL0 on the device (template_kernels.hip), batched over the keyframes of a call
 struct TplJob {

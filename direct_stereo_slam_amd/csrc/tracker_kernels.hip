@@ -15,6 +15,7 @@
 // (thread-sequential -> 16-lane DPP rows -> 16 rows sequential -> chunks sequential in
 // double): deterministic run to run, equal to the reference's SSE lane order only up to
 // float rounding (quirk Q4 is a CPU artefact, not reproduced).  No float atomics.
+#include "../../include/dsm_hotpath.h"
 #include "dsm_kernels.hpp"
 #include "lm_math.hpp"
 #include "xwg_sync.hpp"
@@ -826,7 +827,8 @@ __device__ __forceinline__ double build_b_elem(const ParamsDev &p, const double 
 // 1-2, another pivot order, 7.7 k.)
 // Rows / columns whose bit is clear in `active` do not take part (the 6- and 7-dim sub-solves): they are ordered last and
 // enter as zero rows, zero columns and a zero right-hand side, which leaves every operation on the active block unchanged
-// (x - 0 * y = x) and yields 0 for them.  stitch: row / column 6 of the system is row / column 7 of H (:521-534).
+// (x - 0 * 0 = x) and yields 0 for them.  The padding rows are KEPT zero by selection, not by arithmetic: 0 - 0 * y is a NaN for a
+// non-finite y, and would reach the active unknowns through L^-T where the checker's smaller system has no such row.  stitch: row / column 6 of the system is row / column 7 of H (:521-534).
 struct LdltScratch {
   double x[8];
   double av[8];
@@ -919,13 +921,13 @@ __device__ __forceinline__ void wave_ldlt_solve8(const double *Hlds, const doubl
         const double temp = du[j] * lane_value_d(a[j], k);
         sacc += a[j] * temp;
       }
-      a[k] = a[k] - sacc;
+      a[k] = act_i ? a[k] - sacc : 0.0; // (a padding row stays zero by selection: 0 - 0 * NaN would not)
     }
     const double akk = lane_value_d(a[k], k);
     const bool valid = fabs(akk) > 0.0;
     if (k == 0 && !valid) all_zero = true;
     const double q = a[k] / akk;
-    a[k] = (i > k && valid) ? q : a[k];
+    a[k] = (i > k && valid && act_i) ? q : a[k];
     du[k] = akk;
     d_own = i == k ? akk : d_own;
   }
@@ -933,7 +935,7 @@ __device__ __forceinline__ void wave_ldlt_solve8(const double *Hlds, const doubl
 #pragma unroll
   for (int j = 0; j < 7; j++) {
     const double yj = lane_value_d(y, j);
-    y = i > j ? y - a[j] * yj : y;
+    y = (i > j && act_i) ? y - a[j] * yj : y;
   }
   {
     const double tol = 1.0 / 1.7976931348623157e308; // Eigen: 1 / NumTraits<double>::highest()
@@ -1034,13 +1036,11 @@ __device__ __forceinline__ void finish_track(const TrackerDev &T, LMState &S) {
   S.status = status;
 }
 
-// whole wave: solve + propose for the pose problem (:505-554) from the H, b of the problem state (LDS).
-// spec: the proposal is the speculative one (S.spec_*).  hp: this wave's helper (lm_help_wave), or null.
-__device__ __forceinline__ void propose_pose(const TrackerDev &T, LMState &S, float lambda, int lane, LdltScratch &scr, bool spec = false,
-                                             LmHelp *hp = nullptr) {
+// the unknowns of the pose solve under the affine modes (wave_ldlt_solve8's `active`, `stitch`)
+__device__ __forceinline__ void lm_solve_unknowns(const TrackerDev &T, unsigned &active, bool &stitch) {
   const float modeA = T.p.affine_opt_mode_a, modeB = T.p.affine_opt_mode_b;
-  unsigned active = 0xFFu;
-  bool stitch = false;
+  active = 0xFFu;
+  stitch = false;
   if (modeA < 0 && modeB < 0) { // :511-515 fix a, b
     active = 0x3Fu;
   } else if (!(modeA < 0) && modeB < 0) { // :516-520 fix b
@@ -1049,6 +1049,15 @@ __device__ __forceinline__ void propose_pose(const TrackerDev &T, LMState &S, fl
     stitch = true;
     active = 0x7Fu;
   }
+}
+
+// whole wave: solve + propose for the pose problem (:505-554) from the H, b of the problem state (LDS).
+// spec: the proposal is the speculative one (S.spec_*).  hp: this wave's helper (lm_help_wave), or null.
+__device__ __forceinline__ void propose_pose(const TrackerDev &T, LMState &S, float lambda, int lane, LdltScratch &scr, bool spec = false,
+                                             LmHelp *hp = nullptr) {
+  unsigned active;
+  bool stitch;
+  lm_solve_unknowns(T, active, stitch);
   double inc[8];
   wave_ldlt_solve8(S.H, S.b, lambda, active, stitch, lane, scr, inc);
   // From here on every lane computes the same (wave-uniform) values; lane 0 stores them.  The two
@@ -2482,6 +2491,78 @@ void launch_diag_chain_eval(hipStream_t s, int mode, const LMState *states, floa
     hipLaunchKernelGGL((diag_chain_eval_kernel<0>), dim3(1), dim3(kThreads), 0, s, states, partials);
   else
     hipLaunchKernelGGL((diag_chain_eval_kernel<1>), dim3(1), dim3(kThreads), 0, s, states, partials);
+}
+
+// dsm_diag_lm_propose: the proposing half of an LM step on caller-supplied systems, one workgroup per problem.  A zeroed LMState in
+// LDS takes the level part of both candidates' blocks (as begin_level leaves them) and the caller's fields; wave 0 then runs the
+// production propose_pose / propose_scale unchanged -- with wave 2 as its helper where asked for, as in lm_step_block -- after one
+// extra call of the solve that exposes the raw increment.  No state machine, no partials.
+__global__ __launch_bounds__(kLmThreads) void diag_lm_propose_kernel(int mode, int lvl, const TrackerDev *__restrict__ Tg, int n,
+                                                                     const ::dsm_lm_propose_in *__restrict__ in,
+                                                                     ::dsm_lm_propose_out *__restrict__ out, int spec, int helper) {
+  __shared__ LmShared sh;
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  if (prob >= n) return; // workgroup-uniform
+  if (tid < kLmT16) ((uint4 *)&sh.trk)[tid] = ((const uint4 *)Tg)[tid];
+  for (int i = tid; i < kLmS16; i += kLmThreads) ((uint4 *)&sh.st)[i] = uint4{0, 0, 0, 0};
+  if (tid == 0) sh.help.cmd = 0, sh.help.done = 0;
+  __syncthreads();
+  const TrackerDev &T = sh.trk;
+  LMState &S = sh.st;
+  const ::dsm_lm_propose_in &I = in[prob];
+  const float lambda = I.lambda;
+  if (tid < 64) S.H[tid] = I.H[tid];
+  if (tid < 8) S.b[tid] = I.b[tid];
+  if (tid == 0) {
+    S.status = ST_RUNNING;
+    S.lvl = lvl;
+    S.phase = PH_INIT;
+    S.is_scale = mode;
+    S.iteration = I.iteration;
+    S.lambda = lambda;
+    S.level_cutoff_repeat = I.level_cutoff_repeat;
+    for (int i = 0; i < 7; i++) S.cur[i] = I.cur[i];
+    S.aff_cur[0] = I.aff_cur[0], S.aff_cur[1] = I.aff_cur[1];
+    S.Hs = I.Hs, S.bs = I.bs, S.scale_cur = I.scale_cur;
+    make_eval_level(T, S.in, mode, lvl);
+    make_eval_level(T, S.spec_in, mode, lvl);
+  }
+  __syncthreads();
+  const bool helped = mode != 1 && helper != 0;
+  if (helped && tid >= 128 && tid < 192) lm_help_wave(T, S, sh.help, tid - 128);
+  if (tid >= 64) return; // wave 0 carries on
+  const int lane = tid;
+  double inc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (mode != 1) {
+    unsigned active;
+    bool stitch;
+    lm_solve_unknowns(T, active, stitch);
+    wave_ldlt_solve8(S.H, S.b, lambda, active, stitch, lane, sh.ldlt, inc);
+    propose_pose(T, S, lambda, lane, sh.ldlt, spec != 0, helped ? &sh.help : nullptr);
+  } else if (lane == 0) {
+    propose_scale(T, S, lambda, spec != 0);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  if (lane != 0) return;
+  const EvalIn &e = spec ? S.spec_in : S.in;
+  ::dsm_lm_propose_out &O = out[prob];
+  for (int i = 0; i < 8; i++) O.inc[i] = inc[i];
+  O.inc_norm = spec ? S.spec_inc_norm : S.inc_norm;
+  for (int i = 0; i < 7; i++) O.cand[i] = spec ? S.spec_cand[i] : S.cand[i];
+  for (int i = 0; i < 2; i++) O.aff_cand[i] = spec ? S.spec_aff_cand[i] : S.aff_cand[i];
+  for (int i = 0; i < 9; i++) O.M[i] = e.M[i], O.Ki[i] = e.Ki[i];
+  for (int i = 0; i < 3; i++) O.t[i] = e.t[i];
+  O.aff0 = e.aff0, O.aff1 = e.aff1, O.cutoff = e.cutoff, O.max_energy = e.max_energy;
+  O.residual_only = e.residual_only;
+  O.inc_f = spec ? S.spec_inc_f : S.inc_f;
+  O.scale_cand = spec ? S.spec_scale_cand : S.scale_cand;
+  O.pad[0] = O.pad[1] = 0;
+}
+void launch_diag_lm_propose(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_propose_in *in,
+                            ::dsm_lm_propose_out *out, bool spec, bool helper) {
+  hipLaunchKernelGGL(diag_lm_propose_kernel, dim3(n), dim3(kLmThreads), 0, s, mode, lvl, tracker, n, in, out, spec ? 1 : 0, helper ? 1 : 0);
 }
 
 void launch_tick_reserve(hipStream_t s, const TickReserveArgs &a, const LMState *states, TickModeCtl *mcs, long long *admit_idx) {

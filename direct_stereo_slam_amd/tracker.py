@@ -11,7 +11,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import MAX_LEVELS, Params, Stats, c_double_p, c_float_p, c_int_p, check
+from ._lib import MAX_LEVELS, LmProposeIn, LmProposeOut, Params, Stats, c_double_p, c_float_p, c_int_p, check
+
+# numpy record layouts of dsm_lm_propose_in / dsm_lm_propose_out (the field names of _lib.LmProposeIn / LmProposeOut)
+LM_PROPOSE_IN = np.dtype(LmProposeIn)
+LM_PROPOSE_OUT = np.dtype(LmProposeOut)
 
 
 def _fp(a):
@@ -613,6 +617,15 @@ class TrackerAndScaler:
         check(self.L.dsm_diag_single_eval(self.h, 1, lvl, None, None, scale, cutoff, form, int(residual_only), _dp(rs), None, None, C.byref(H),
                                           C.byref(b), C.byref(n)))
         return rs, H.value, b.value, n.value
+
+    def diagLmPropose(self, mode, lvl, problems, spec=False, helper=False):
+        """the proposing half of an LM step on caller-supplied systems (dsm_diag_lm_propose).  problems: a numpy array of
+        LM_PROPOSE_IN records; returns an array of LM_PROPOSE_OUT records, one per problem"""
+        problems = np.ascontiguousarray(problems, LM_PROPOSE_IN)
+        out = np.zeros(len(problems), LM_PROPOSE_OUT)
+        check(self.L.dsm_diag_lm_propose(self.h, mode, lvl, len(problems), problems.ctypes.data_as(C.POINTER(LmProposeIn)), int(spec), int(helper),
+                                         out.ctypes.data_as(C.POINTER(LmProposeOut))))
+        return out
 
     def trackNewestCoarse(self, lastToNew, aff_g2l, coarsestLvl, minResForAbort=None):
         """returns (good, lastToNew_out, aff_g2l_out, lastResiduals) and sets lastFlowIndicators"""

@@ -377,6 +377,38 @@ int dsm_tracker_calc_res_scale(dsm_tracker *t, int lvl, float scale, float cutof
 int dsm_diag_single_eval(dsm_tracker *t, int mode, int lvl, const double pose[7], const double aff[2], float scale, float cutoff_th,
                          int form, int residual_only, double rs[6], double H[64], double b[8], float *Hs, float *bs, int *n_warped);
 
+/* test aid (no reference counterpart): the second half of a Levenberg-Marquardt round -- the step that turns H, b and lambda into the
+ * next candidate (TrackerAndScaler.cpp:505-554 pose, :897-913 scale) -- run by the production device code on caller-supplied
+ * systems, n problems in one launch (one workgroup each).  The tracker supplies what the step reads of it: the parameters, K^-1 of
+ * level lvl (dsm_tracker_make_k must have been called), the reference affine and the exposures; no template or frame is needed.
+ * mode: 0 pose, 2 loop-closure pose (M = R instead of R K^-1, reference affine (0, 0)), 1 stereo scale.
+ * spec != 0: the proposal is staged as the speculative candidate (consumed one iteration later: the iteration bound is tested at
+ * iteration + 2).  helper != 0 (modes 0, 2): a second wave forms the affine part and the cut-off of the candidate's evaluation, as in
+ * the production step.  DSM_ERR_INVALID with nothing written for a NULL pointer, n < 1 or n > 65536, a bad mode or level, or a tracker
+ * without makeK; DSM_ERR_STATE (outputs not written) when a bounded wait of the wave hand-shake expired during the call.
+ * No production path calls this. */
+typedef struct dsm_lm_propose_in {
+  double H[64], b[8];       /* modes 0, 2: the normal equations, row-major; only the lower triangle of H is read */
+  double cur[7], aff_cur[2]; /* modes 0, 2: the current pose {qx,qy,qz,qw,tx,ty,tz} and affine pair */
+  float lambda;
+  float level_cutoff_repeat; /* cut-off of the candidate's evaluation = coarse_cutoff_th * level_cutoff_repeat */
+  int iteration;             /* iterations of the level already consumed */
+  float Hs, bs, scale_cur;   /* mode 1 */
+} dsm_lm_propose_in;
+typedef struct dsm_lm_propose_out {
+  double inc[8];   /* modes 0, 2: the solve's raw increment (before extrapolation and SCALE_*) */
+  double inc_norm; /* |inc| after extrapolation (:588) */
+  double cand[7], aff_cand[2];
+  /* the candidate's part of the inputs of its evaluation */
+  float M[9], t[3], aff0, aff1, cutoff, max_energy;
+  int residual_only;
+  float Ki[9];     /* K^-1 of the level, as the evaluation reads it */
+  float inc_f, scale_cand; /* mode 1 */
+  int pad[2];
+} dsm_lm_propose_out;
+int dsm_diag_lm_propose(dsm_tracker *t, int mode, int lvl, int n, const dsm_lm_propose_in *in, int spec, int helper,
+                        dsm_lm_propose_out *out);
+
 /* replaces TrackerAndScaler::trackNewestCoarse (TrackerAndScaler.cpp:451-638).
  * min_res_for_abort / last_residuals: DSM_MAX_LEVELS doubles (reference: Vec5; NaN = no limit).
  * flow_out = lastFlowIndicators.  *good = the reference's bool return value. */
