@@ -156,6 +156,8 @@ _pp_d = C.POINTER(c_double_p)
 ALLREDUCE_MIN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 MERGE_ALGOS = {"allreduce_min": 0, "allgather": 1}
+# DSM_RINGKEY_FORM_* of include/dsm_hotpath.h, in the enum's order (dsm_ringdb_scan_plan)
+RINGKEY_FORMS = ("FEWQ4_1", "FEWQ4_2", "FEWQ_4", "FEWQ_8", "TILE_1", "TILE_2", "TILE_ANYDIM", "MANY4", "MANY_ANYDIM")
 SYMBOLS = {
     "dsm_last_error": (C.c_char_p, []),
     "dsm_abi_version": (C.c_int, []),
@@ -248,6 +250,7 @@ SYMBOLS = {
     "dsm_ringdb_knn_packed": (C.c_int, [_vp, c_float_p, C.c_int, _vp]),
     "dsm_ringdb_knn_packed_dev": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "dsm_ringdb_knn_packed_host": (C.c_int, [_vp, c_float_p, C.c_int, c_int64_p]),
+    "dsm_ringdb_scan_plan": (C.c_int, [_vp, C.c_int, C.c_int, c_int_p, c_int_p, C.POINTER(C.c_longlong)]),
     "dsm_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
     "dsm_comm_create": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.POINTER(_vp)]),
     "dsm_comm_destroy": (C.c_int, [_vp]),

@@ -261,6 +261,9 @@ void launch_ringkey_knn(hipStream_t s, const float *keysT, int64_t cap, int64_t 
                         int nq, unsigned long long *d_scratch, int n_slices,
                         unsigned long long *d_packed_out);
 int ringkey_num_slices(int64_t n_local, int nq, int dim);
+// the form (DSM_RINGKEY_FORM_*, include/dsm_hotpath.h) that launch_ringkey_knn takes for nq queries, and the keys of one slice of a form
+int ringkey_scan_form(int dim, int nq);
+long long ringkey_slice_keys(int64_t n_local, int n_slices, int form);
 void launch_ringkey_insert(hipStream_t s, float *keysT, int64_t cap, int64_t pos, int dim,
                            const float *d_key, int nkeys);
 // many indexes in one call (dsm_ringdb_query_then_enqueue_many, dsm_loop_detect_batch_many): query q scans its own index
@@ -276,8 +279,10 @@ struct RingKeyInsertDesc {
   long long cap, pos;
 };
 int ringkey_many_slices(int64_t n_local);
+// the form that launch_ringkey_knn_many takes (four: every capacity of the call is a multiple of four)
+int ringkey_many_form(int dim, bool four);
 // one scan over all nq queries (each over its own index, d_queries nq x dim) into d_scratch (n_slices = the largest count of the call),
-// then ringkey_merge_kernel into d_packed_out (nq x k).  four: dim 20 and every capacity a multiple of four (16-byte plane loads)
+// then ringkey_merge_kernel into d_packed_out (nq x k).  four: every capacity a multiple of four (16-byte plane loads; ringkey_many_form)
 void launch_ringkey_knn_many(hipStream_t s, const RingKeyScanDesc *d_descs, int dim, int k, bool four, const float *d_queries, int nq,
                              int n_slices, unsigned long long *d_scratch, unsigned long long *d_packed_out);
 // one launch appending nkeys keys (nkeys x dim) to their indexes

@@ -18,6 +18,8 @@ static int rdb_reserve(dsm_ringdb *db, int64_t need_local) {
   if (need_local <= db->cap) return DSM_OK;
   int64_t ncap = db->cap > 0 ? db->cap : 1024;
   while (ncap < need_local) ncap *= 2;
+  // the scans with four keys per thread (DSM_RINGKEY_FORM_FEWQ4_*, MANY4) load 16 bytes per plane at slots that are multiples of four
+  if (ncap & 3) return invalid("ring-key index: the capacity must be a multiple of four");
   float *nk = nullptr;
   DSM_HIP(hipMalloc(&nk, sizeof(float) * (size_t)ncap * db->dim));
   hipError_t e = hipSuccess;
@@ -211,7 +213,7 @@ int ringdb_many_prepare(dsm_context *ctx, int n, dsm_ringdb *const *dbs, int dim
   std::fill(jobs.begin(), jobs.end(), 0);
   std::vector<int> filled(nu, 0);
   P.n_slices = 1;
-  P.four = dim == 20;
+  P.four = true;
   for (int j = 0; j < n; j++) {
     const int u = P.slot_of[j];
     dsm_ringdb *db = P.uniq[u];
@@ -373,6 +375,16 @@ int dsm_ringdb_knn_packed_host(dsm_ringdb *db, const float *queries, int nq, int
   int rc = dsm_ringdb_knn_packed(db, queries, nq, db->d_out);
   if (rc) return rc;
   DSM_HIP(hipMemcpy(packed_out, db->d_out, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return DSM_OK;
+}
+
+int dsm_ringdb_scan_plan(dsm_ringdb *db, int nq, int many, int *form_out, int *n_slices_out, long long *keys_per_slice_out) {
+  if (!db || !form_out || !n_slices_out || !keys_per_slice_out || (!many && nq < 1)) return invalid("dsm_ringdb_scan_plan: bad argument");
+  const int form = many ? ringkey_many_form(db->dim, db->cap % 4 == 0) : ringkey_scan_form(db->dim, nq);
+  const int n_slices = many ? ringkey_many_slices(db->n_local) : ringkey_num_slices(db->n_local, nq, db->dim);
+  *form_out = form;
+  *n_slices_out = n_slices;
+  *keys_per_slice_out = ringkey_slice_keys(db->n_local, n_slices, form);
   return DSM_OK;
 }
 

@@ -54,7 +54,7 @@ void ringdb_forget_comm(dsm_ringdb *db);
 // index matured earlier in the call (ringdb_finish_query).
 struct RingManyPlan {
   int n = 0, dim = 0, k = 0, n_slices = 1, n_matured = 0;
-  bool four = false;                       // dim 20 and every capacity a multiple of four: ringkey_knn_many4_kernel
+  bool four = false;                       // every capacity a multiple of four (ringkey_many_form: dim 20 then takes ringkey_knn_many4_kernel)
   std::vector<dsm_ringdb *> uniq;          // the call's distinct indexes, in order of first appearance
   std::vector<int> slot_of;                // per query: its index's position in uniq
   std::vector<int> mat_off, mat_count;     // per distinct index: its matured keys' first row in `matured`, and their number

@@ -10,6 +10,7 @@
 //
 // HBM layout: dimension-major planes keysT[j * capacity + i] (i = local slot of this shard), so the
 // tile loads are fully coalesced; global index = i * shard_count + shard_rank.
+#include "../../include/dsm_hotpath.h"
 #include "dsm_kernels.hpp"
 
 namespace dsm {
@@ -18,6 +19,13 @@ constexpr int kRkThreads = 256;
 constexpr int kRkTile = 128;
 // "no candidate": larger than every packed candidate both as uint64 and as int64 (dist2 >= 0 keeps bit 63 clear)
 constexpr unsigned long long kNoCand = 0x7FFFFFFFFFFFFFFFull;
+
+// keys per slice (the last slice may hold fewer).  four: the forms with four consecutive keys per thread, whose slices start on
+// 16-byte boundaries of the planes.  The kernels and dsm_ringdb_scan_plan share this one copy.
+__host__ __device__ __forceinline__ long long ringkey_slice_len(long long n_local, int n_slices, bool four) {
+  const long long per = (n_local + n_slices - 1) / n_slices;
+  return four ? (per + 3) & ~3ll : per;
+}
 
 template <int K>
 __device__ __forceinline__ void topk_insert(unsigned long long (&t)[K], unsigned long long c) {
@@ -61,7 +69,7 @@ __global__ __launch_bounds__(kRkThreads) void ringkey_knn_kernel(const float *__
 #pragma unroll
   for (int i = 0; i < QPT; i++) q[i] = (blockIdx.x * QPT + i) * kRkThreads + threadIdx.x;
   const int slice = blockIdx.y;
-  const long long per = (n_local + n_slices - 1) / n_slices;
+  const long long per = ringkey_slice_len(n_local, n_slices, false);
   const long long k0 = (long long)slice * per;
   const long long k1 = k0 + per < n_local ? k0 + per : n_local;
 
@@ -150,7 +158,7 @@ __global__ __launch_bounds__(kRkThreads) void ringkey_knn_fewq_kernel(const floa
   __shared__ unsigned long long wtop[kRkThreads / 64][QG][K];
   const int slice = blockIdx.x, q0 = blockIdx.y * QG;
   const int nqg = nq - q0 < QG ? nq - q0 : QG;
-  const long long per = (n_local + n_slices - 1) / n_slices;
+  const long long per = ringkey_slice_len(n_local, n_slices, false);
   const long long k0 = (long long)slice * per;
   const long long k1 = k0 + per < n_local ? k0 + per : n_local;
   for (int e = threadIdx.x; e < QG * DIM; e += kRkThreads) {
@@ -234,7 +242,7 @@ __global__ __launch_bounds__(kRkThreads) void ringkey_knn_fewq4_kernel(const flo
   __shared__ unsigned long long wtop[kRkThreads / 64][QG][K];
   const int slice = blockIdx.x, q0 = blockIdx.y * QG;
   const int nqg = nq - q0 < QG ? nq - q0 : QG;
-  const long long per = (((n_local + n_slices - 1) / n_slices) + 3) & ~3ll; // slices start on 16-byte boundaries of the planes
+  const long long per = ringkey_slice_len(n_local, n_slices, true);
   const long long k0 = (long long)slice * per;
   const long long k1 = k0 + per < n_local ? k0 + per : n_local;
   for (int e = threadIdx.x; e < QG * DIM; e += kRkThreads) {
@@ -402,7 +410,7 @@ __global__ __launch_bounds__(kRkThreads) void ringkey_knn_many4_kernel(const Rin
     if (threadIdx.x < K) out[threadIdx.x] = kNoCand;
     return;
   }
-  const long long per = (((d.n_local + d.n_slices - 1) / d.n_slices) + 3) & ~3ll; // slices start on 16-byte boundaries of the planes
+  const long long per = ringkey_slice_len(d.n_local, d.n_slices, true);
   const long long k0 = (long long)slice * per;
   const long long k1 = k0 + per < d.n_local ? k0 + per : d.n_local;
   float qv[DIM];
@@ -445,7 +453,7 @@ __global__ __launch_bounds__(kRkThreads) void ringkey_knn_many_kernel(const Ring
     if (threadIdx.x < K) out[threadIdx.x] = kNoCand;
     return;
   }
-  const long long per = (d.n_local + d.n_slices - 1) / d.n_slices;
+  const long long per = ringkey_slice_len(d.n_local, d.n_slices, false);
   const long long k0 = (long long)slice * per;
   const long long k1 = k0 + per < d.n_local ? k0 + per : d.n_local;
   if (threadIdx.x < dim) qs[threadIdx.x] = queries[(size_t)q * dim + threadIdx.x];
@@ -508,41 +516,49 @@ int ringkey_num_slices(int64_t n_local, int nq, int dim) {
   return (int)s;
 }
 
+// THE dispatch rule of the single-index scan: launch_knn_k switches on it and dsm_ringdb_scan_plan reports it.  The forms with four
+// keys per thread load 16 bytes per plane, which needs a capacity that is a multiple of four: rdb_reserve refuses any other.
+int ringkey_scan_form(int dim, int nq) {
+  if (ringkey_use_fewq(dim, nq)) {
+    if (nq == 1) return DSM_RINGKEY_FORM_FEWQ4_1;
+    if (nq == 2) return DSM_RINGKEY_FORM_FEWQ4_2;
+    // (groups of four / eight queries with four keys per thread: 408 us against 274 for eight queries over 10^7 keys -- registers)
+    return nq <= 4 ? DSM_RINGKEY_FORM_FEWQ_4 : DSM_RINGKEY_FORM_FEWQ_8;
+  }
+  if (dim != 20) return DSM_RINGKEY_FORM_TILE_ANYDIM;
+  return nq >= kRkTwoPerThread ? DSM_RINGKEY_FORM_TILE_2 : DSM_RINGKEY_FORM_TILE_1;
+}
+
+long long ringkey_slice_keys(int64_t n_local, int n_slices, int form) {
+  return ringkey_slice_len(n_local, n_slices, form == DSM_RINGKEY_FORM_FEWQ4_1 || form == DSM_RINGKEY_FORM_FEWQ4_2 || form == DSM_RINGKEY_FORM_MANY4);
+}
+
 template <int K>
 static void launch_knn_k(hipStream_t s, const float *keysT, int64_t cap, int64_t n_local, int dim, float thres,
                          int shard_rank, int shard_count, const float *d_queries, int nq,
                          unsigned long long *d_scratch, int n_slices, unsigned long long *d_packed_out) {
   dim3 grid((nq + kRkThreads - 1) / kRkThreads, n_slices), block(kRkThreads);
-  if (ringkey_use_fewq(dim, nq)) {
-#define DSM_FEWQ(QG)                                                                                                   \
-  hipLaunchKernelGGL((ringkey_knn_fewq_kernel<20, K, QG>), dim3(n_slices, (nq + QG - 1) / QG), block, 0, s, keysT, (long long)cap,       \
+#define DSM_FEWQ(KERNEL, QG)                                                                                           \
+  hipLaunchKernelGGL((KERNEL<20, K, QG>), dim3(n_slices, (nq + QG - 1) / QG), block, 0, s, keysT, (long long)cap,      \
                      (long long)n_local, thres, shard_rank, shard_count, d_queries, nq, n_slices, d_scratch)
-#define DSM_FEWQ4(QG)                                                                                                  \
-  hipLaunchKernelGGL((ringkey_knn_fewq4_kernel<20, K, QG>), dim3(n_slices, (nq + QG - 1) / QG), block, 0, s, keysT, (long long)cap,      \
-                     (long long)n_local, thres, shard_rank, shard_count, d_queries, nq, n_slices, d_scratch)
-    if (nq == 1 && (cap & 3) == 0)
-      DSM_FEWQ4(1);
-    else if (nq == 2 && (cap & 3) == 0)
-      DSM_FEWQ4(2);
-    else if (nq == 1) // (groups of four / eight queries with four keys per thread: 408 us against 274 for eight queries over 10^7 keys -- registers)
-      DSM_FEWQ(1);
-    else if (nq == 2)
-      DSM_FEWQ(2);
-    else if (nq <= 4)
-      DSM_FEWQ(4);
-    else
-      DSM_FEWQ(kRkQG);
-#undef DSM_FEWQ
-#undef DSM_FEWQ4
-  } else if (dim == 20 && nq >= kRkTwoPerThread)
+  switch (ringkey_scan_form(dim, nq)) {
+  case DSM_RINGKEY_FORM_FEWQ4_1: DSM_FEWQ(ringkey_knn_fewq4_kernel, 1); break;
+  case DSM_RINGKEY_FORM_FEWQ4_2: DSM_FEWQ(ringkey_knn_fewq4_kernel, 2); break;
+  case DSM_RINGKEY_FORM_FEWQ_4: DSM_FEWQ(ringkey_knn_fewq_kernel, 4); break;
+  case DSM_RINGKEY_FORM_FEWQ_8: DSM_FEWQ(ringkey_knn_fewq_kernel, kRkQG); break;
+  case DSM_RINGKEY_FORM_TILE_2:
     hipLaunchKernelGGL((ringkey_knn_kernel<20, K, 2>), dim3((nq + 2 * kRkThreads - 1) / (2 * kRkThreads), n_slices), block, 0, s, keysT,
                        (long long)cap, (long long)n_local, dim, thres, shard_rank, shard_count, d_queries, nq, n_slices, d_scratch);
-  else if (dim == 20)
+    break;
+  case DSM_RINGKEY_FORM_TILE_1:
     hipLaunchKernelGGL((ringkey_knn_kernel<20, K>), grid, block, 0, s, keysT, (long long)cap, (long long)n_local, dim,
                        thres, shard_rank, shard_count, d_queries, nq, n_slices, d_scratch);
-  else
+    break;
+  default: // DSM_RINGKEY_FORM_TILE_ANYDIM
     hipLaunchKernelGGL((ringkey_knn_kernel<0, K>), grid, block, 0, s, keysT, (long long)cap, (long long)n_local, dim,
                        thres, shard_rank, shard_count, d_queries, nq, n_slices, d_scratch);
+  }
+#undef DSM_FEWQ
   hipLaunchKernelGGL((ringkey_merge_kernel<K>), dim3(nq), dim3(64), 0, s, d_scratch, nq, n_slices, d_packed_out);
 }
 
@@ -570,13 +586,20 @@ int ringkey_many_slices(int64_t n_local) {
   return (int)(s < 1 ? 1 : s);
 }
 
+// THE dispatch rule of the many-index scan (launch_knn_many_k switches on it, dsm_ringdb_scan_plan reports it).  four: every capacity
+// of the call is a multiple of four
+int ringkey_many_form(int dim, bool four) { return four && dim == 20 ? DSM_RINGKEY_FORM_MANY4 : DSM_RINGKEY_FORM_MANY_ANYDIM; }
+
 template <int K>
 static void launch_knn_many_k(hipStream_t s, const RingKeyScanDesc *d_descs, int dim, bool four, const float *d_queries, int nq,
                               int n_slices, unsigned long long *d_scratch, unsigned long long *d_packed_out) {
-  if (four && dim == 20)
+  switch (ringkey_many_form(dim, four)) {
+  case DSM_RINGKEY_FORM_MANY4:
     hipLaunchKernelGGL((ringkey_knn_many4_kernel<20, K>), dim3(n_slices, nq), dim3(kRkThreads), 0, s, d_descs, d_queries, nq, d_scratch);
-  else
+    break;
+  default: // DSM_RINGKEY_FORM_MANY_ANYDIM
     hipLaunchKernelGGL((ringkey_knn_many_kernel<K>), dim3(n_slices, nq), dim3(kRkThreads), 0, s, d_descs, d_queries, dim, nq, d_scratch);
+  }
   hipLaunchKernelGGL((ringkey_merge_kernel<K>), dim3(nq), dim3(64), 0, s, d_scratch, nq, n_slices, d_packed_out);
 }
 

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import ALLGATHER_FN, ALLREDUCE_MIN_FN, MERGE_ALGOS, NO_CANDIDATE, c_float_p, c_int64_p, c_int_p, check
+from ._lib import ALLGATHER_FN, ALLREDUCE_MIN_FN, MERGE_ALGOS, NO_CANDIDATE, RINGKEY_FORMS, c_float_p, c_int64_p, c_int_p, check
 
 
 def _fp(a):
@@ -172,6 +172,13 @@ class RingKeyDB:
         out = np.zeros((q.shape[0], self.k), np.int64)
         check(self.L.dsm_ringdb_knn_packed_host(self.h, _fp(q), q.shape[0], out.ctypes.data_as(c_int64_p)))
         return out
+
+    def scan_plan(self, nq=1, many=False):
+        """dsm_ringdb_scan_plan (host only, launches nothing): (form name -- one of _lib.RINGKEY_FORMS --, slices, keys per slice) of a
+        scan of nq queries over the index as it stands; many: of this index inside query_then_enqueue_many (nq is not used)"""
+        form, n_slices, per = C.c_int(), C.c_int(), C.c_longlong()
+        check(self.L.dsm_ringdb_scan_plan(self.h, nq, int(bool(many)), C.byref(form), C.byref(n_slices), C.byref(per)))
+        return RINGKEY_FORMS[form.value], n_slices.value, per.value
 
     def knn_packed_device(self, d_queries_ptr, nq, d_out_ptr):
         """queries / output are raw device pointers (e.g. torch tensors' data_ptr()); asynchronous on

@@ -679,6 +679,25 @@ int dsm_ringdb_knn_packed(dsm_ringdb *db, const float *queries, int nq, void *d_
 int dsm_ringdb_knn_packed_dev(dsm_ringdb *db, const void *d_queries, int nq, void *d_packed_out);
 /* same, result copied to host memory (nq*k int64) */
 int dsm_ringdb_knn_packed_host(dsm_ringdb *db, const float *queries, int nq, int64_t *packed_out);
+/* Which scan would run?  Host only, launches nothing: the form that a scan of nq queries over the index as it stands takes
+ * (many = 0: dsm_ringdb_knn_packed* / dsm_ringdb_query_then_enqueue; many != 0: this index as one of
+ * dsm_ringdb_query_then_enqueue_many's, where nq is not used), the number of slices its local entries are cut into and the keys of
+ * one slice (the last may hold fewer).  The launches switch on the same rule, so the answer cannot drift from what runs; tests
+ * use it to prove that they reach every form, a second key tile (more than 128 keys per slice of a DSM_RINGKEY_FORM_TILE_* scan)
+ * and a thread's second iteration (more than 1024 keys per slice of the FEWQ4 / MANY4 forms).  Every form returns the same bits. */
+enum {
+  DSM_RINGKEY_FORM_FEWQ4_1 = 0,     /* dim 20, 1 query: a thread per four keys */
+  DSM_RINGKEY_FORM_FEWQ4_2 = 1,     /* dim 20, 2 queries: a thread per four keys */
+  DSM_RINGKEY_FORM_FEWQ_4 = 2,      /* dim 20, 3-4 queries: a thread per key, one query group of four */
+  DSM_RINGKEY_FORM_FEWQ_8 = 3,      /* dim 20, 5-32 queries: a thread per key, query groups of eight */
+  DSM_RINGKEY_FORM_TILE_1 = 4,      /* dim 20, 33-511 queries: a thread per query, key tiles of 128 through LDS */
+  DSM_RINGKEY_FORM_TILE_2 = 5,      /* dim 20, from 512 queries: two queries per thread */
+  DSM_RINGKEY_FORM_TILE_ANYDIM = 6, /* any other dimension: a thread per query, flann::L2's tail loop */
+  DSM_RINGKEY_FORM_MANY4 = 7,       /* many indexes, dim 20: a thread per four keys */
+  DSM_RINGKEY_FORM_MANY_ANYDIM = 8, /* many indexes, any other dimension: a thread per key */
+  DSM_RINGKEY_FORM_COUNT = 9
+};
+int dsm_ringdb_scan_plan(dsm_ringdb *db, int nq, int many, int *form_out, int *n_slices_out, long long *keys_per_slice_out);
 
 /* ---- sharded ring-key database across the GPUs of a node -------- */
 /* The index of LoopHandler.cpp:35-39 split `ordinal mod G` over G processes (one per GPU); search_ringkey's k-NN
