@@ -342,9 +342,11 @@ int dsm_make_coarse_depth_l0(int w0, int h0, int nl, int npts, const float *pu, 
     bak[l].assign((size_t)w[l] * h[l], 0.f);
   }
   for (int k = 0; k < npts; k++) { // :149-164
-    const int u = pu[k] + 0.5f;
-    const int v = pv[k] + 0.5f;
-    if (u < 0 || v < 0 || u >= w[0] || v >= h[0]) return DSM_ERR_INVALID; // the reference would write out of bounds
+    const float fu = pu[k] + 0.5f, fv = pv[k] + 0.5f;
+    // accepted: finite and truncating into [0, w) x [0, h), i.e. -1 < f < size; tested before the conversion, which is undefined for a
+    // NaN and for values outside int (every comparison is false for a NaN)
+    if (!(fu > -1.0f && fu < (float)w[0] && fv > -1.0f && fv < (float)h[0])) return DSM_ERR_INVALID; // the reference would write out of bounds
+    const int u = (int)fu, v = (int)fv;
     idepth[0][u + w[0] * v] += pidepth[k] * pweight[k];
     wsum[0][u + w[0] * v] += pweight[k];
   }

@@ -48,13 +48,15 @@ __global__ void tpl_splat_link_kernel(const TplJob *__restrict__ jobs, int w, in
   const TplView V = tpl_view(J, w, h, px_total);
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= J.npts) return;
-  const int u = (int)(V.pu[k] + 0.5f); // :151-152
-  const int v = (int)(V.pv[k] + 0.5f);
-  if (u < 0 || v < 0 || u >= w || v >= h) { // the reference would write out of bounds
+  const float fu = V.pu[k] + 0.5f, fv = V.pv[k] + 0.5f; // :151-152
+  // accepted: fu and fv finite and truncating (toward zero) into [0, w) x [0, h), i.e. -1 < f < size.  Tested on the floats, every
+  // comparison false for a NaN: the float -> int conversion of a NaN or of a value outside int is not defined (here it gave 0 for NaN).
+  if (!(fu > -1.0f && fu < (float)w && fv > -1.0f && fv < (float)h)) { // the reference would write out of bounds
     atomicOr(J.d_n + nlevels, 1);
     V.next[k] = -2;
     return;
   }
+  const int u = (int)fu, v = (int)fv;
   V.next[k] = atomicExch(&V.head[u + w * v], k);
 }
 

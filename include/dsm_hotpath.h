@@ -233,7 +233,11 @@ int dsm_tracker_set_ref(dsm_tracker *t, int ref_frame_id, double ref_aff_a, doub
  * and emitted (row-major, the reference's order) straight into this tracker's template; the keyframe's
  * (I,dx,dy) pyramid is the one already resident in `frame_owner`'s `slot` (the tracker that tracked the frame
  * which became the keyframe; may be `t` itself).  Result identical to dsm_make_coarse_depth_l0 +
- * dsm_tracker_set_ref, without the host loops and the template upload.  n_out (may be NULL): pc_n per level. */
+ * dsm_tracker_set_ref, without the host loops and the template upload.  n_out (may be NULL): pc_n per level.
+ * COORDINATES: a point is accepted exactly when pu + 0.5f and pv + 0.5f (float) are finite and truncate toward zero into
+ * [0, w) x [0, h), i.e. -1 < pu + 0.5f < w and -1 < pv + 0.5f < h; so -1.4 lands on pixel 0, and NaN, +-inf, 1e20, -1.6 and w - 0.5
+ * are refused.  One refused point fails the whole call with DSM_ERR_INVALID (the reference would write out of bounds, :160) and
+ * leaves the tracker without a reference. */
 int dsm_tracker_set_ref_from_points(dsm_tracker *t, dsm_tracker *frame_owner, int slot, int ref_frame_id,
                                     double ref_aff_a, double ref_aff_b, float ref_exposure, int npts,
                                     const float *pu, const float *pv, const float *pidepth, const float *pweight,
@@ -859,7 +863,9 @@ int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_itera
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.
  * Outputs: n_out[lvl] and the four template lists (capacity w_l*h_l each) -- exactly the arguments of
- * dsm_tracker_set_ref.  Host side in this round (row A4 / N3). */
+ * dsm_tracker_set_ref.  Host side in this round (row A4 / N3).
+ * COORDINATES: as dsm_tracker_set_ref_from_points -- a point is accepted exactly when pu + 0.5f and pv + 0.5f are finite and
+ * truncate toward zero into [0, w) x [0, h); anything else returns DSM_ERR_INVALID (outputs then unspecified). */
 int dsm_make_coarse_depth_l0(int w, int h, int nlevels, int npts, const float *pu, const float *pv,
                              const float *pidepth, const float *pweight, const float *const *ref_dIp,
                              int *n_out, float *const *pc_u, float *const *pc_v, float *const *pc_idepth,
