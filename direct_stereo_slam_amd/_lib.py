@@ -130,6 +130,15 @@ class PoseJob(C.Structure):
     ]
 
 
+class ActivationJob(C.Structure):
+    _fields_ = [
+        ("map", C.c_void_p), ("n_hosts", C.c_int), ("krki", c_float_p), ("kt", c_float_p),
+        ("n_seeds", C.c_int), ("seed_host", c_int_p), ("seed_u", c_float_p), ("seed_v", c_float_p), ("seed_idepth", c_float_p),
+        ("n_cand", C.c_int), ("cand_host", c_int_p), ("cand_u", c_float_p), ("cand_v", c_float_p), ("cand_idepth", c_float_p),
+        ("cand_type", c_float_p), ("min_act_dist", C.c_float), ("decision_out", C.POINTER(C.c_ubyte)), ("n_activated_out", c_int_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -266,6 +275,13 @@ SYMBOLS = {
     "dsm_loop_detect_batch": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(LoopJob), C.c_double, C.c_int, C.c_int, c_int_p, c_int_p]),
     "dsm_loop_detect_batch_many": (C.c_int, [_vp, C.c_int, C.POINTER(LoopJob), C.POINTER(_vp), C.c_double, C.c_int, C.c_int, c_int_p, c_int_p]),
     "dsm_icp_batch": (C.c_int, [_vp, C.c_int, C.POINTER(IcpJob), C.c_int, C.c_double, C.c_double, C.c_double]),
+    "dsm_distmap_create": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "dsm_distmap_destroy": (C.c_int, [_vp]),
+    "dsm_distmap_get": (C.c_int, [_vp, c_float_p]),
+    "dsm_distmap_add": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "dsm_distmaps_make": (C.c_int, [_vp, C.c_int, C.POINTER(ActivationJob)]),
+    "dsm_activate_points_batch": (C.c_int, [_vp, C.c_int, C.POINTER(ActivationJob)]),
+    "dsm_activate_points_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(ActivationJob), c_float_p]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

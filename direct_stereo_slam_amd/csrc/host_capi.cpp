@@ -561,3 +561,103 @@ int dsm_pinhole_undistort_map(const double calib[4], int w_in, int h_in, int out
 }
 
 } // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// CoarseDistanceMap + the activation walk of FrontEnd::activatePointsMT as the reference runs them: one sequential loop, the list
+// BFS of growDistBFS (TrackerAndScaler.cpp:1235-1324) on a float map.  D1-D6: DESIGN.md section 12.
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct HostDistMap {
+  int w1, h1;
+  std::vector<float> map;
+  std::vector<int> l1, l2; // bfs_list1_ / bfs_list2_ as cell indices
+  // growDistBFS (:1235-1324): the list in l1 holds bfs_num cells
+  void grow(int bfs_num) {
+    static const int DX[8] = {1, -1, 0, 0, 1, -1, -1, 1}, DY[8] = {0, 0, 1, -1, 1, 1, -1, -1};
+    for (int k = 1; k < 40 && bfs_num > 0; k++) { // (an empty list stays empty: the remaining levels do nothing)
+      const int bfs_num2 = bfs_num;
+      std::swap(l1, l2);
+      bfs_num = 0;
+      const int nd = (k % 2 == 0) ? 4 : 8;
+      for (int i = 0; i < bfs_num2; i++) {
+        const int x = l2[i] % w1, y = l2[i] / w1;
+        if (x == 0 || y == 0 || x == w1 - 1 || y == h1 - 1) continue;
+        for (int d = 0; d < nd; d++) {
+          const int idx = (x + DX[d]) + (y + DY[d]) * w1;
+          if (map[idx] > k) {
+            map[idx] = (float)k;
+            if ((size_t)bfs_num == l1.size()) l1.push_back(idx); else l1[bfs_num] = idx;
+            bfs_num++;
+          }
+        }
+      }
+    }
+  }
+  void push_first(int idx, int at) {
+    if ((size_t)at == l1.size()) l1.push_back(idx); else l1[at] = idx;
+  }
+};
+
+// ptp = KRKi (u, v, 1) + Kt idepth (:1218, FrontEnd.cpp:432-433), then the bounds test; returns the cell or -1
+inline int project_l1(const float *M, const float *T, float u, float v, float id, int w1, int h1, float *p0_out) {
+  const float p0 = ((M[0] * u + M[1] * v) + M[2]) + T[0] * id;
+  const float p1 = ((M[3] * u + M[4] * v) + M[5]) + T[1] * id;
+  const float p2 = ((M[6] * u + M[7] * v) + M[8]) + T[2] * id;
+  const float qu = p0 / p2 + 0.5f, qv = p1 / p2 + 0.5f;
+  *p0_out = p0;
+  if (!(qu >= 1.0f && qv >= 1.0f && qu < (float)w1 && qv < (float)h1)) return -1;
+  return (int)qu + w1 * (int)qv;
+}
+} // namespace
+
+extern "C" int dsm_activate_points_host(int w, int h, const dsm_activation_job *job, float *map_out) {
+  auto fail = [](const char *msg) {
+    dsm::set_error(msg);
+    return (int)DSM_ERR_INVALID;
+  };
+  if (w < 2 || h < 2 || !job) return fail("dsm_activate_points_host: bad argument");
+  const dsm_activation_job &J = *job;
+  if (J.n_hosts < 0 || J.n_seeds < 0 || J.n_cand < 0 || (J.n_hosts && (!J.krki || !J.kt)) ||
+      (J.n_seeds && (!J.seed_host || !J.seed_u || !J.seed_v || !J.seed_idepth)) ||
+      (J.n_cand && (!J.cand_host || !J.cand_u || !J.cand_v || !J.cand_idepth || !J.cand_type || !J.decision_out)))
+    return fail("dsm_activate_points_host: negative count or NULL array");
+  for (int i = 0; i < J.n_seeds; i++)
+    if (J.seed_host[i] < 0 || J.seed_host[i] >= J.n_hosts) return fail("dsm_activate_points_host: seed_host outside [0, n_hosts)");
+  for (int i = 0; i < J.n_cand; i++)
+    if (J.cand_host[i] < 0 || J.cand_host[i] >= J.n_hosts) return fail("dsm_activate_points_host: cand_host outside [0, n_hosts)");
+  HostDistMap D;
+  D.w1 = w >> 1, D.h1 = h >> 1;
+  D.map.assign((size_t)D.w1 * D.h1, 1000.0f); // :1202-1203
+  int num_items = 0;
+  float p0;
+  for (int i = 0; i < J.n_seeds; i++) { // :1216-1226
+    const int hst = J.seed_host[i];
+    const int c = project_l1(J.krki + 9 * hst, J.kt + 3 * hst, J.seed_u[i], J.seed_v[i], J.seed_idepth[i], D.w1, D.h1, &p0);
+    if (c < 0) continue;
+    D.map[c] = 0;
+    D.push_first(c, num_items++);
+  }
+  D.grow(num_items);
+  int n_act = 0;
+  for (int i = 0; i < J.n_cand; i++) { // FrontEnd.cpp:431-449
+    const int hst = J.cand_host[i];
+    const int c = project_l1(J.krki + 9 * hst, J.kt + 3 * hst, J.cand_u[i], J.cand_v[i], J.cand_idepth[i], D.w1, D.h1, &p0);
+    if (c < 0) {
+      J.decision_out[i] = 2;
+      continue;
+    }
+    const float dist = D.map[c] + (p0 - floorf(p0));
+    if (dist >= J.min_act_dist * J.cand_type[i]) {
+      D.map[c] = 0; // addIntoDistFinal (:1326-1332)
+      D.push_first(c, 0);
+      D.grow(1);
+      J.decision_out[i] = 1;
+      n_act++;
+    } else {
+      J.decision_out[i] = 0;
+    }
+  }
+  if (J.n_activated_out) *J.n_activated_out = n_act;
+  if (map_out) memcpy(map_out, D.map.data(), sizeof(float) * D.map.size());
+  return DSM_OK;
+}

@@ -4,6 +4,7 @@
 // :992-998, :1032) keep their shape.  Header-only, plain C++11, no Eigen/Sophus/DSO needed:
 // the DSO types are reduced to the fields this path actually reads.  INTEGRATION.md shows the
 // three-line conversions from the real dso::FrameHessian / Sophus::SE3 / dso::AffLight.
+// The second class of that header, dso::CoarseDistanceMap (TrackerAndScaler.h:139-170), is host/CoarseDistanceMap.hpp.
 #pragma once
 #include <cmath>
 #include <stdexcept>

@@ -55,6 +55,7 @@ typedef struct dsm_tracker dsm_tracker; /* one TrackerAndScaler instance */
 typedef struct dsm_ringdb dsm_ringdb;   /* ring-key database + delay queue */
 typedef struct dsm_comm dsm_comm;       /* communicator of the sharded ring-key database: one rank per GPU (RCCL) */
 typedef struct dsm_pose_estimator dsm_pose_estimator; /* loop-closure direct alignment (PoseEstimator) */
+typedef struct dsm_distmap dsm_distmap; /* one CoarseDistanceMap: the level-1 distance map of a window */
 
 /* Runtime parameters.  These are DSO globals / literals in the reference; the values
  * written by dsm_params_default() are the upstream DSO defaults as used by the
@@ -858,6 +859,58 @@ typedef struct dsm_icp_job {
 } dsm_icp_job;
 int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_iterations, double transformation_epsilon, double max_corr_dist,
                   double score_thres);
+
+/* ---- CoarseDistanceMap and the activation walk -------------------------------------------------------------
+ * replaces dso::CoarseDistanceMap (TrackerAndScaler.h:139-170, TrackerAndScaler.cpp:1174-1362) and the distance-map part of
+ * FrontEnd::activatePointsMT (FrontEnd.cpp:371-451), for the windows of many sequences in one call.  The map has
+ * w1 x h1 = (w >> 1) x (h >> 1) cells (makeK, :1349-1350) holding 0 .. 39 or 1000.  Everything is integer-exact; the float32
+ * projection is evaluated as ((m0 u + m1 v) + m2) + kt idepth per component, without contraction. */
+
+/* replaces CoarseDistanceMap(ww, hh) (:1174-1187) and its destructor (:1189-1195); a fresh map holds 1000 everywhere */
+int dsm_distmap_create(dsm_context *ctx, int w, int h, dsm_distmap **map_out);
+int dsm_distmap_destroy(dsm_distmap *map);
+/* reads fwdWarpedIDDistFinal (FrontEnd.cpp:439): w1 * h1 floats, row-major */
+int dsm_distmap_get(dsm_distmap *map, float *out);
+/* replaces CoarseDistanceMap::addIntoDistFinal (:1326-1332): the cell becomes 0 unconditionally, then growDistBFS(1) (:1235-1324) runs
+ * from it on the map as it stands.  DSM_ERR_INVALID outside [0, w1) x [0, h1) (the reference would write out of bounds). */
+int dsm_distmap_add(dsm_distmap *map, int u, int v);
+
+/* One window.  hosts: the frames of the window other than the newest, each with KRKi = K[1] R Ki[0] (row-major 3x3) and Kt = K[1] t
+ * of host-to-newest (:1212-1214, FrontEnd.cpp:387-392).  seeds: the active points of those frames (ph->u, ph->v, ph->idepth_scaled,
+ * :1216-1226).  candidates: the immature points that passed the canActivate filter (FrontEnd.cpp:400-429), in the reference's order,
+ * with idepth = 0.5f * (idepth_max + idepth_min) formed by the caller (:433) and type = my_type (:442). */
+typedef struct dsm_activation_job {
+  dsm_distmap *map;
+  int n_hosts;
+  const float *krki; /* n_hosts * 9, row-major */
+  const float *kt;   /* n_hosts * 3 */
+  int n_seeds;
+  const int *seed_host;
+  const float *seed_u, *seed_v, *seed_idepth;
+  int n_cand;
+  const int *cand_host;
+  const float *cand_u, *cand_v, *cand_idepth, *cand_type;
+  float min_act_dist;           /* current_min_act_dist_ (FrontEnd.cpp:442) */
+  unsigned char *decision_out;  /* n_cand: 0 keep, 1 activate, 2 out of bounds (the reference deletes the point, :446-449) */
+  int *n_activated_out;         /* may be NULL */
+} dsm_activation_job;
+
+/* replaces CoarseDistanceMap::makeDistanceMap (:1197-1230) for every job: the map is reset to 1000, every seed whose projection
+ * (qu, qv) = (ptp0 / ptp2 + 0.5f, ptp1 / ptp2 + 0.5f) satisfies qu >= 1 && qv >= 1 && qu < w1 && qv < h1 (NaN and +-inf fail) sets
+ * cell ((int)qu, (int)qv) to 0, then growDistBFS: level k = 1 .. 39 writes k into the neighbours (8 for odd k, 4 for even k) that
+ * hold more than k, and a cell on the map's border is never expanded.  The cand_* fields are ignored. */
+int dsm_distmaps_make(dsm_context *ctx, int n_jobs, const dsm_activation_job *jobs);
+/* dsm_distmaps_make, then the walk of FrontEnd.cpp:431-449 per job: a candidate outside the bounds above gets decision 2; otherwise
+ * dist = map[cell] + (ptp0 - floorf(ptp0)), it is activated (1) iff dist >= min_act_dist * type and then added to the map
+ * (dsm_distmap_add) before the next candidate is looked at; otherwise 0.  One launch sequence and one host wait for all jobs; a
+ * job's map and decisions do not depend on the other jobs of the call.  One geometry per call (as dsm_set_refs_from_points), a
+ * map in one job only, n_seeds == 0 and n_cand == 0 are valid.  Validation is all or nothing, before anything is enqueued:
+ * DSM_ERR_INVALID for NULL arrays, negative counts, mixed geometries, a map twice, or a host index outside [0, n_hosts). */
+int dsm_activate_points_batch(dsm_context *ctx, int n_jobs, const dsm_activation_job *jobs);
+/* The same as one plain sequential loop on the host (the reference's list BFS, :1235-1324): job->map is ignored, (w, h) is the
+ * level-0 size, map_out (w1 * h1 floats, may be NULL) receives the final map.  The CPU baseline of tools/activation_timing.py and
+ * a checker that needs no device, like dsm_make_coarse_depth_l0 beside the device template builder. */
+int dsm_activate_points_host(int w, int h, const dsm_activation_job *job, float *map_out);
 
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
