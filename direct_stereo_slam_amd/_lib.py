@@ -139,6 +139,17 @@ class ActivationJob(C.Structure):
     ]
 
 
+class ImmatureJob(C.Structure):
+    _fields_ = [
+        ("window", C.c_void_p), ("cam", C.c_float * 4), ("cam_inv", C.c_float * 2), ("n_frames", C.c_int), ("frame_ids", c_int_p),
+        ("pre_R", c_float_p), ("pre_t", c_float_p), ("pre_aff", c_float_p),
+        ("n_pts", C.c_int), ("host", c_int_p), ("u", c_float_p), ("v", c_float_p), ("idepth_min", c_float_p), ("idepth_max", c_float_p),
+        ("energy_th", c_float_p), ("color", c_float_p), ("weights", c_float_p), ("min_obs", C.c_int),
+        ("status", C.POINTER(C.c_ubyte)), ("idepth_out", c_float_p), ("res_state", C.POINTER(C.c_ubyte)),
+        ("hdd_out", c_float_p), ("bd_out", c_float_p), ("energy_out", c_float_p), ("iterations_out", c_int_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -282,6 +293,14 @@ SYMBOLS = {
     "dsm_distmaps_make": (C.c_int, [_vp, C.c_int, C.POINTER(ActivationJob)]),
     "dsm_activate_points_batch": (C.c_int, [_vp, C.c_int, C.POINTER(ActivationJob)]),
     "dsm_activate_points_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(ActivationJob), c_float_p]),
+    "dsm_window_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "dsm_window_destroy": (C.c_int, [_vp]),
+    "dsm_window_put_host": (C.c_int, [_vp, C.c_int, c_float_p]),
+    "dsm_window_put_from_tracker": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
+    "dsm_window_drop": (C.c_int, [_vp, C.c_int]),
+    "dsm_window_get": (C.c_int, [_vp, C.c_int, c_float_p]),
+    "dsm_optimize_immature_points_batch": (C.c_int, [_vp, C.c_int, C.POINTER(ImmatureJob), C.c_float, C.c_float, C.c_int]),
+    "dsm_optimize_immature_points_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(ImmatureJob), C.POINTER(c_float_p), C.c_float, C.c_float, C.c_int]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

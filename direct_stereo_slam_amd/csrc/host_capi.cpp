@@ -661,3 +661,139 @@ extern "C" int dsm_activate_points_host(int w, int h, const dsm_activation_job *
   if (map_out) memcpy(map_out, D.map.data(), sizeof(float) * D.map.size());
   return DSM_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// FrontEnd::optimizeImmaturePoint (dso_helpers/FrontEndOptPoint.cpp:35-138) as the reference runs it: one sequential loop over the
+// points of a window, ImmaturePoint::linearizeResidual per residual with the accumulators passed by reference.  M1-M8, U1-U9:
+// DESIGN.md section 13.  The pattern pixel itself is imm::tap (immature_math.hpp), shared with the device kernel.
+// ---------------------------------------------------------------------------------------------
+#include "immature_math.hpp"
+
+namespace {
+struct ImmTmpRes { // ImmaturePointTemporaryResidual
+  int state_state, state_NewState;
+  float state_energy, state_NewEnergy;
+  int target;
+};
+
+struct ImmPoint {
+  const dsm_immature_job *J;
+  dsm::imm::Cam C;
+  const float *const *frame_I;
+  int i; // the point
+  float huber;
+  // ImmaturePoint::linearizeResidual (UPSTREAM-DSO), U1-U9
+  float linearize(float slack, ImmTmpRes &res, float &Hdd, float &bd, float idepth) const {
+    using namespace dsm::imm;
+    if (res.state_state == RES_OOB) { // U1
+      res.state_NewState = RES_OOB;
+      return res.state_energy;
+    }
+    const int nf = J->n_frames, pair = J->host[i] * nf + res.target;
+    float energyLeft = 0;
+    for (int idx = 0; idx < 8; idx++) {
+      int dx, dy;
+      pattern(idx, dx, dy);
+      float tE, tH, tb;
+      if (!tap(C, frame_I[res.target], J->pre_R + 9 * pair, J->pre_t + 3 * pair, J->pre_aff + 2 * pair, J->u[i], J->v[i], dx, dy, idepth,
+               J->color[8 * i + idx], J->weights[8 * i + idx], huber, tE, tH, tb)) { // U4 / U6: the earlier pixels' terms stay in Hdd / bd
+        res.state_NewState = RES_OOB;
+        return res.state_energy;
+      }
+      energyLeft += tE;
+      Hdd += tH;
+      bd += tb;
+    }
+    const float lim = J->energy_th[i] * slack; // U9
+    if (energyLeft > lim) {
+      energyLeft = lim;
+      res.state_NewState = RES_OUTLIER;
+    } else {
+      res.state_NewState = RES_IN;
+    }
+    res.state_NewEnergy = energyLeft;
+    return energyLeft;
+  }
+};
+} // namespace
+
+extern "C" int dsm_optimize_immature_points_host(int w, int h, const dsm_immature_job *job, const float *const *frame_I, float huber_th,
+                                                 float min_idepth_h_act, int gn_iterations) {
+  using namespace dsm::imm;
+  auto fail = [](const char *msg) {
+    dsm::set_error(msg);
+    return (int)DSM_ERR_INVALID;
+  };
+  if (w < 8 || h < 8 || !job || !frame_I) return fail("dsm_optimize_immature_points_host: bad argument");
+  const dsm_immature_job &J = *job;
+  if (gn_iterations < 0 || gn_iterations > DSM_IMMATURE_GN_ITERATIONS_LIMIT || !std::isfinite(huber_th) || !std::isfinite(min_idepth_h_act))
+    return fail("dsm_optimize_immature_points_host: gn_iterations outside [0, 16], or a non-finite threshold");
+  if (J.n_frames < 1 || J.n_frames > DSM_IMMATURE_MAX_FRAMES || J.n_pts < 0 || !J.frame_ids || !J.pre_R || !J.pre_t || !J.pre_aff)
+    return fail("dsm_optimize_immature_points_host: n_frames outside [1, 9], a negative count or a NULL array");
+  if (J.n_pts && (!J.host || !J.u || !J.v || !J.idepth_min || !J.idepth_max || !J.energy_th || !J.color || !J.weights || !J.status ||
+                  !J.idepth_out || !J.res_state))
+    return fail("dsm_optimize_immature_points_host: NULL array");
+  for (int f = 0; f < J.n_frames; f++)
+    if (!frame_I[f]) return fail("dsm_optimize_immature_points_host: NULL frame");
+  for (int i = 0; i < J.n_pts; i++)
+    if (J.host[i] < 0 || J.host[i] >= J.n_frames) return fail("dsm_optimize_immature_points_host: host outside [0, n_frames)");
+  ImmPoint P;
+  P.J = job, P.frame_I = frame_I, P.huber = huber_th;
+  P.C = Cam{J.cam[0], J.cam[1], J.cam[2], J.cam[3], J.cam_inv[0], J.cam_inv[1], w, h};
+  const int nf = J.n_frames;
+  for (int i = 0; i < J.n_pts; i++) {
+    P.i = i;
+    ImmTmpRes residuals[DSM_IMMATURE_MAX_FRAMES];
+    int nres = 0;
+    for (int f = 0; f < nf; f++) // :38-46
+      if (f != J.host[i]) residuals[nres++] = ImmTmpRes{RES_IN, RES_OUTLIER, 0.f, 0.f, f};
+    float lastEnergy = 0, lastHdd = 0, lastbd = 0;
+    float currentIdepth = (J.idepth_max[i] + J.idepth_min[i]) * 0.5f; // M1
+    int status = -1, iterations = 0;
+    for (int k = 0; k < nres; k++) { // M2
+      lastEnergy += P.linearize(1000, residuals[k], lastHdd, lastbd, currentIdepth);
+      residuals[k].state_state = residuals[k].state_NewState;
+      residuals[k].state_energy = residuals[k].state_NewEnergy;
+    }
+    if (!std::isfinite(lastEnergy) || lastHdd < min_idepth_h_act) status = 0; // :63-68
+    float lambda = 0.1;
+    for (int iteration = 0; status < 0 && iteration < gn_iterations; iteration++) {
+      float H = lastHdd;
+      H *= 1 + lambda;
+      float step = (1.0 / H) * lastbd; // M3: quotient and product in double
+      float newIdepth = currentIdepth - step;
+      float newHdd = 0, newbd = 0, newEnergy = 0;
+      for (int k = 0; k < nres; k++) newEnergy += P.linearize(1, residuals[k], newHdd, newbd, newIdepth);
+      iterations++;
+      if (!std::isfinite(lastEnergy) || newHdd < min_idepth_h_act) { // M4: lastEnergy, not newEnergy (:90)
+        status = 0;
+        break;
+      }
+      if (newEnergy < lastEnergy) {
+        currentIdepth = newIdepth, lastHdd = newHdd, lastbd = newbd, lastEnergy = newEnergy;
+        for (int k = 0; k < nres; k++) {
+          residuals[k].state_state = residuals[k].state_NewState;
+          residuals[k].state_energy = residuals[k].state_NewEnergy;
+        }
+        lambda *= 0.5;
+      } else {
+        lambda *= 5;
+      }
+      if (fabsf(step) < 0.0001 * currentIdepth) break; // M5: in double, currentIdepth already updated
+    }
+    if (status < 0) {
+      int numGoodRes = 0;
+      for (int k = 0; k < nres; k++) numGoodRes += residuals[k].state_state == RES_IN;
+      status = (!std::isfinite(currentIdepth) || numGoodRes < J.min_obs) ? 2 : 1; // :121-138
+    }
+    J.status[i] = (unsigned char)status;
+    J.idepth_out[i] = currentIdepth;
+    J.res_state[(size_t)i * nf + J.host[i]] = DSM_RES_HOST;
+    for (int k = 0; k < nres; k++) J.res_state[(size_t)i * nf + residuals[k].target] = (unsigned char)residuals[k].state_state;
+    if (J.hdd_out) J.hdd_out[i] = lastHdd;
+    if (J.bd_out) J.bd_out[i] = lastbd;
+    if (J.energy_out) J.energy_out[i] = lastEnergy;
+    if (J.iterations_out) J.iterations_out[i] = iterations;
+  }
+  return DSM_OK;
+}

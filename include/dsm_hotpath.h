@@ -56,6 +56,7 @@ typedef struct dsm_ringdb dsm_ringdb;   /* ring-key database + delay queue */
 typedef struct dsm_comm dsm_comm;       /* communicator of the sharded ring-key database: one rank per GPU (RCCL) */
 typedef struct dsm_pose_estimator dsm_pose_estimator; /* loop-closure direct alignment (PoseEstimator) */
 typedef struct dsm_distmap dsm_distmap; /* one CoarseDistanceMap: the level-1 distance map of a window */
+typedef struct dsm_window dsm_window;   /* the level-0 intensity planes of the keyframes of one window (frame_hessians_) */
 
 /* Runtime parameters.  These are DSO globals / literals in the reference; the values
  * written by dsm_params_default() are the upstream DSO defaults as used by the
@@ -911,6 +912,78 @@ int dsm_activate_points_batch(dsm_context *ctx, int n_jobs, const dsm_activation
  * level-0 size, map_out (w1 * h1 floats, may be NULL) receives the final map.  The CPU baseline of tools/activation_timing.py and
  * a checker that needs no device, like dsm_make_coarse_depth_l0 beside the device template builder. */
 int dsm_activate_points_host(int w, int h, const dsm_activation_job *job, float *map_out);
+
+/* ---- Optimisation of the selected immature points --------------------------------------------------------------
+ * replaces the second half of FrontEnd::activatePointsMT (FrontEnd.cpp:458-468): FrontEnd::optimizeImmaturePoint
+ * (dso_helpers/FrontEndOptPoint.cpp:35-138) for every selected point of the windows of many sequences in one call.  Everything is
+ * float32 without contraction except the LM step and the convergence test, which are double as in the reference (M3, M5). */
+#define DSM_IMMATURE_HUBER_TH 9.0f            /* setting_huberTH */
+#define DSM_IMMATURE_MIN_IDEPTH_H_ACT 100.0f  /* setting_minIdepthH_act */
+#define DSM_IMMATURE_GN_ITERATIONS 3          /* setting_GNItsOnPointActivation */
+#define DSM_IMMATURE_GN_ITERATIONS_LIMIT 16   /* largest gn_iterations accepted */
+#define DSM_WINDOW_MAX_FRAMES 16              /* largest capacity of a dsm_window */
+#define DSM_IMMATURE_MAX_FRAMES 9             /* largest n_frames of a job: at most 8 residuals per point */
+/* residual states (dsm_immature_job.res_state): ResState IN / OOB / OUTLIER, and the mark of the host's own column */
+#define DSM_RES_IN 0
+#define DSM_RES_OOB 1
+#define DSM_RES_OUTLIER 2
+#define DSM_RES_HOST 255
+
+/* The keyframe images of one window on the device: level-0 intensity planes only (gradients are formed where they are
+ * interpolated), w * h floats per frame, all memory allocated at creation.  capacity in [1, DSM_WINDOW_MAX_FRAMES]. */
+int dsm_window_create(dsm_context *ctx, int w, int h, int capacity, dsm_window **win_out);
+int dsm_window_destroy(dsm_window *win);
+/* a new frame from w * h host intensities (pageable or from dsm_host_alloc, as dsm_tracker_upload_intensity); returns when the
+ * caller's buffer is free.  DSM_ERR_INVALID for a frame id already in the store or a full store. */
+int dsm_window_put_host(dsm_window *win, int frame_id, const float *I);
+/* a new frame as a device-side copy of level 0 of the frame resident in `slot` (DSM_SLOT_NEW_LEFT / _RIGHT) of `owner`: the frame
+ * that has just become a keyframe.  DSM_ERR_INVALID as above, for a tracker of another context or geometry, or an empty slot. */
+int dsm_window_put_from_tracker(dsm_window *win, int frame_id, dsm_tracker *owner, int slot);
+/* marginalisation: the frame's place is free again.  DSM_ERR_INVALID for an id not in the store. */
+int dsm_window_drop(dsm_window *win, int frame_id);
+/* reads a frame back (w * h floats); for tests */
+int dsm_window_get(dsm_window *win, int frame_id, float *out);
+
+/* One window.  frame_ids: frame_hessians_ in order; pre_*: FrameFramePrecalc::PRE_RTll / PRE_tTll / PRE_aff_mode of every
+ * [host][target] pair in float32, formed by the caller (the exp of the affine model stays on the host); the diagonal is not read.
+ * A point is an ImmaturePoint that dsm_activate_points_batch selected: host (an index into frame_ids), u, v, idepth_min, idepth_max,
+ * energyTH, color[8], weights[8]. */
+typedef struct dsm_immature_job {
+  dsm_window *window;       /* ignored by dsm_optimize_immature_points_host */
+  float cam[4];             /* fxl, fyl, cxl, cyl */
+  float cam_inv[2];         /* fxli, fyli */
+  int n_frames;             /* 1 .. DSM_IMMATURE_MAX_FRAMES */
+  const int *frame_ids;     /* n_frames */
+  const float *pre_R;       /* n_frames * n_frames * 9, [host][target], row-major 3x3 */
+  const float *pre_t;       /* n_frames * n_frames * 3 */
+  const float *pre_aff;     /* n_frames * n_frames * 2 */
+  int n_pts;
+  const int *host;          /* n_pts */
+  const float *u, *v, *idepth_min, *idepth_max, *energy_th; /* n_pts each */
+  const float *color;       /* n_pts * 8 */
+  const float *weights;     /* n_pts * 8 */
+  int min_obs;              /* the reference passes 1 (FrontEnd.cpp:336) */
+  unsigned char *status;    /* n_pts: 0 = `return 0` (the point stays immature), 1 = activated, 2 = (PointHessian*)-1 (delete the point) */
+  float *idepth_out;        /* n_pts: currentIdepth at the exit taken */
+  unsigned char *res_state; /* n_pts * n_frames: DSM_RES_* of the residual against each frame at the exit taken, DSM_RES_HOST in the
+                               host's own column; the caller builds the PointFrameResiduals and lastResiduals from it (:154-173) */
+  float *hdd_out, *bd_out, *energy_out; /* optional (NULL): lastHdd, lastbd, lastEnergy at the exit taken */
+  int *iterations_out;      /* optional (NULL): trial evaluations run (0 .. gn_iterations) */
+} dsm_immature_job;
+
+/* FrontEndOptPoint.cpp:37-138 for every point of every job, as written down in DESIGN.md section 13 (M1-M8, U1-U9): one staged copy,
+ * one launch, one host wait for the whole batch; nothing is allocated once the context's arena has grown to the batch size; a job's
+ * results do not depend on the other jobs of the call.  A window may serve several jobs; one geometry per call; n_pts == 0 is valid;
+ * a point whose window holds its host frame only has no residuals, Hdd = 0, and gets status 0.  PointHessian's own energyTH
+ * finiteness test (:141) reads caller data only and stays with the caller.  Validation is all or nothing, before anything is
+ * enqueued: DSM_ERR_INVALID for NULL arrays or negative counts, n_frames outside [1, 9], a host index outside [0, n_frames), a frame
+ * id that is not in the window, mixed geometries, gn_iterations outside [0, 16], non-finite huber_th or min_idepth_h_act. */
+int dsm_optimize_immature_points_batch(dsm_context *ctx, int n_jobs, const dsm_immature_job *jobs, float huber_th, float min_idepth_h_act,
+                                       int gn_iterations);
+/* The same for one job as one plain sequential loop on the host: job->window is ignored, frame_I[i] is the w * h level-0 intensity
+ * plane of frame_ids[i].  The CPU baseline of tools/point_optimisation_timing.py and a checker that needs no device. */
+int dsm_optimize_immature_points_host(int w, int h, const dsm_immature_job *job, const float *const *frame_I, float huber_th,
+                                      float min_idepth_h_act, int gn_iterations);
 
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
