@@ -150,6 +150,25 @@ class ImmatureJob(C.Structure):
     ]
 
 
+class TraceParams(C.Structure):
+    _fields_ = [
+        ("max_pix_search", C.c_float), ("slack_interval", C.c_float), ("stepsize", C.c_float), ("min_improvement", C.c_float),
+        ("min_test_radius", C.c_int), ("gn_iterations", C.c_int), ("gn_threshold", C.c_float), ("extra_slack_on_th", C.c_float),
+        ("huber_th", C.c_float),
+    ]
+
+
+class TraceJob(C.Structure):
+    _fields_ = [
+        ("target_tracker", C.c_void_p), ("target_slot", C.c_int), ("target_window", C.c_void_p), ("target_frame_id", C.c_int),
+        ("n_hosts", C.c_int), ("krki", c_float_p), ("kt", c_float_p), ("aff", c_float_p),
+        ("n_pts", C.c_int), ("host", c_int_p), ("u", c_float_p), ("v", c_float_p), ("energy_th", c_float_p), ("grad_h", c_float_p),
+        ("color", c_float_p), ("weights", c_float_p),
+        ("status", C.POINTER(C.c_ubyte)), ("idepth_min", c_float_p), ("idepth_max", c_float_p), ("quality", c_float_p),
+        ("trace_uv", c_float_p), ("trace_interval", c_float_p), ("steps_out", c_int_p), ("counts_out", c_int_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -301,6 +320,9 @@ SYMBOLS = {
     "dsm_window_get": (C.c_int, [_vp, C.c_int, c_float_p]),
     "dsm_optimize_immature_points_batch": (C.c_int, [_vp, C.c_int, C.POINTER(ImmatureJob), C.c_float, C.c_float, C.c_int]),
     "dsm_optimize_immature_points_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(ImmatureJob), C.POINTER(c_float_p), C.c_float, C.c_float, C.c_int]),
+    "dsm_trace_params_default": (C.c_int, [C.POINTER(TraceParams)]),
+    "dsm_trace_points_batch": (C.c_int, [_vp, C.c_int, C.POINTER(TraceJob), C.POINTER(TraceParams)]),
+    "dsm_trace_points_host": (C.c_int, [C.c_int, C.c_int, c_float_p, C.POINTER(TraceJob), C.POINTER(TraceParams)]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

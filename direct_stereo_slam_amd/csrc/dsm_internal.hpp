@@ -126,8 +126,26 @@ struct dsm_undistorter {
   dsm::UndistortTables tab{}; // device pointers + sizes (dsm_kernels.hpp)
 };
 
+// dsm_window_create (immature_kernels.hip): the level-0 intensity planes of a window's keyframes; also a target of trace_kernels.hip
+struct dsm_window {
+  dsm_context *ctx = nullptr;
+  int w = 0, h = 0, capacity = 0;
+  float *d_planes = nullptr; // capacity planes of w * h floats
+  int ids[DSM_WINDOW_MAX_FRAMES] = {};
+  bool used[DSM_WINDOW_MAX_FRAMES] = {};
+  int find(int id) const {
+    for (int i = 0; i < capacity; i++)
+      if (used[i] && ids[i] == id) return i;
+    return -1;
+  }
+  float *plane(int i) const { return d_planes + (size_t)i * w * h; }
+};
+
 namespace dsm {
 int invalid(const char *msg); // set_error + DSM_ERR_INVALID
+// host_capi.cpp: what dsm_trace_points_batch and dsm_trace_points_host refuse in the settings / in the arrays of a job (NULL: nothing)
+const char *trace_params_error(const dsm_trace_params *p);
+const char *trace_job_error(const dsm_trace_job &J);
 int ensure_batch_capacity(dsm_context *ctx, int nprob, int partial_stride);
 int ensure_stage(dsm_context *ctx, size_t floats);
 int sync_desc(dsm_tracker *t);

@@ -797,3 +797,112 @@ extern "C" int dsm_optimize_immature_points_host(int w, int h, const dsm_immatur
   }
   return DSM_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The loop of FrontEnd::traceNewCoarse (FrontEnd.cpp:276-327) as the reference runs it: one sequential loop over the immature points,
+// ImmaturePoint::traceOn per point.  T1-T16: DESIGN.md section 14.  The per-sample arithmetic is trace_math.hpp, shared with the device
+// kernel; the sums over the pattern are plain loops in pattern order.
+// ---------------------------------------------------------------------------------------------
+#include "trace_math.hpp"
+
+namespace dsm {
+// the rules of dsm_trace_points_batch / _host for the settings; NULL when they hold
+const char *trace_params_error(const dsm_trace_params *p) {
+  if (!p) return "no parameters";
+  if (p->gn_iterations < 0 || p->gn_iterations > 16) return "gn_iterations outside [0, 16]";
+  if (!std::isfinite(p->stepsize) || !(p->stepsize > 0)) return "a non-finite or non-positive stepsize";
+  if (!std::isfinite(p->max_pix_search) || !std::isfinite(p->slack_interval) || !std::isfinite(p->min_improvement) ||
+      !std::isfinite(p->gn_threshold) || !std::isfinite(p->extra_slack_on_th) || !std::isfinite(p->huber_th))
+    return "a non-finite parameter";
+  if (p->min_test_radius < 0) return "a negative min_test_radius";
+  return nullptr;
+}
+// ... and for the arrays of one job
+const char *trace_job_error(const dsm_trace_job &J) {
+  if (J.n_hosts < 0 || J.n_hosts > DSM_TRACE_MAX_HOSTS || J.n_pts < 0) return "n_hosts outside [0, 16] or a negative count";
+  if (J.n_hosts && (!J.krki || !J.kt || !J.aff)) return "NULL host array";
+  if (J.n_pts && (!J.host || !J.u || !J.v || !J.energy_th || !J.grad_h || !J.color || !J.weights || !J.status || !J.idepth_min ||
+                  !J.idepth_max || !J.quality || !J.trace_uv || !J.trace_interval))
+    return "NULL point array";
+  for (int i = 0; i < J.n_pts; i++) {
+    if (J.host[i] < 0 || J.host[i] >= J.n_hosts) return "host outside [0, n_hosts)";
+    if (J.status[i] > DSM_IPS_UNINITIALIZED) return "a status byte above 5";
+  }
+  return nullptr;
+}
+} // namespace dsm
+
+extern "C" int dsm_trace_params_default(dsm_trace_params *p) {
+  if (!p) return DSM_ERR_INVALID;
+  p->max_pix_search = 0.027f, p->slack_interval = 1.5f, p->stepsize = 1.0f, p->min_improvement = 2.0f;
+  p->min_test_radius = 2, p->gn_iterations = 3;
+  p->gn_threshold = 0.1f, p->extra_slack_on_th = 1.2f, p->huber_th = 9.0f;
+  return DSM_OK;
+}
+
+extern "C" int dsm_trace_points_host(int w, int h, const float *target_I, const dsm_trace_job *job, const dsm_trace_params *params) {
+  using namespace dsm::trc;
+  auto fail = [](const char *msg) {
+    dsm::set_error(std::string("dsm_trace_points_host: ") + msg);
+    return (int)DSM_ERR_INVALID;
+  };
+  if (w < 8 || h < 8 || !target_I || !job) return fail("bad argument");
+  if (const char *e = dsm::trace_params_error(params)) return fail(e);
+  if (const char *e = dsm::trace_job_error(*job)) return fail(e);
+  const dsm_trace_job &J = *job;
+  const dsm_trace_params &S = *params;
+  int counts[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < J.n_pts; i++) {
+    const float *R = J.krki + 9 * J.host[i], *t = J.kt + 3 * J.host[i], *aff = J.aff + 2 * J.host[i];
+    const float *color = J.color + 8 * i, *wt = J.weights + 8 * i;
+    const int entered = J.status[i];
+    Point P{entered, J.idepth_min[i], J.idepth_max[i], J.quality[i], J.trace_uv[2 * i], J.trace_uv[2 * i + 1], J.trace_interval[i]};
+    Line L;
+    int steps = 0;
+    if (geometry(w, h, R, t, J.u[i], J.v[i], J.grad_h + 4 * i, S, P, L)) {
+      steps = L.numSteps;
+      float rx[8], ry[8], errors[DSM_TRACE_MAX_STEPS + 1];
+      for (int k = 0; k < 8; k++) rotated_pattern(R, k, rx[k], ry[k]);
+      float ptx = L.ptx, pty = L.pty, bestU = 0, bestV = 0, bestEnergy = 1e10f;
+      int bestIdx = -1;
+      for (int s = 0; s < steps; s++) { // T9
+        float energy = 0;
+        for (int k = 0; k < 8; k++) {
+          const float x = ptx + rx[k], y = pty + ry[k];
+          const bool ok = guard(x, y, w, h);
+          energy += search_term(ok, ok ? interp_I(load4(target_I, w, x, y), x, y) : 0.f, aff, color[k], S.huber_th);
+        }
+        errors[s] = energy;
+        if (energy < bestEnergy) bestU = ptx, bestV = pty, bestEnergy = energy, bestIdx = s;
+        ptx += L.dx;
+        pty += L.dy;
+      }
+      float secondBest = 1e10f; // T10
+      for (int s = 0; s < steps; s++)
+        if (outside_radius(s, bestIdx, test_radius(S)) && errors[s] < secondBest) secondBest = errors[s];
+      quality_update(P, secondBest, bestEnergy, steps);
+      GN g{bestU, bestV, bestU, bestV, 0.f, bestEnergy}; // T11
+      if (S.gn_iterations > 0) g.bestEnergy = 1e5f;
+      for (int it = 0; it < S.gn_iterations; it++) {
+        float H = 1, b = 0, E = 0;
+        for (int k = 0; k < 8; k++) {
+          const float x = g.bestU + rx[k], y = g.bestV + ry[k];
+          const bool ok = guard(x, y, w, h);
+          float hI = 0, gx = 0, gy = 0, tH, tb, tE;
+          if (ok) interp_Ig(load12(target_I, w, x, y), x, y, hI, gx, gy);
+          if (gn_terms(ok, hI, gx, gy, aff, color[k], wt[k], S.huber_th, L.dx, L.dy, tH, tb, tE)) H += tH, b += tb;
+          E += tE;
+        }
+        if (gn_update(g, H, b, E, L.dx, L.dy, S.gn_threshold)) break;
+      }
+      finish(P, L, g, t, J.energy_th[i], S, entered);
+    }
+    J.status[i] = (unsigned char)P.status;
+    J.idepth_min[i] = P.idepth_min, J.idepth_max[i] = P.idepth_max, J.quality[i] = P.quality;
+    J.trace_uv[2 * i] = P.uv0, J.trace_uv[2 * i + 1] = P.uv1, J.trace_interval[i] = P.interval;
+    if (J.steps_out) J.steps_out[i] = steps;
+    counts[P.status]++;
+  }
+  if (J.counts_out) memcpy(J.counts_out, counts, sizeof counts); // T16
+  return DSM_OK;
+}

@@ -24,20 +24,6 @@
 
 using namespace dsm;
 
-struct dsm_window {
-  dsm_context *ctx = nullptr;
-  int w = 0, h = 0, capacity = 0;
-  float *d_planes = nullptr; // capacity planes of w * h floats
-  int ids[DSM_WINDOW_MAX_FRAMES] = {};
-  bool used[DSM_WINDOW_MAX_FRAMES] = {};
-  int find(int id) const {
-    for (int i = 0; i < capacity; i++)
-      if (used[i] && ids[i] == id) return i;
-    return -1;
-  }
-  float *plane(int i) const { return d_planes + (size_t)i * w * h; }
-};
-
 namespace {
 
 constexpr int kWavesPerBlock = 4;

@@ -985,6 +985,74 @@ int dsm_optimize_immature_points_batch(dsm_context *ctx, int n_jobs, const dsm_i
 int dsm_optimize_immature_points_host(int w, int h, const dsm_immature_job *job, const float *const *frame_I, float huber_th,
                                       float min_idepth_h_act, int gn_iterations);
 
+/* ---- Tracing the immature points against the new frame -------------------------------------------------------
+ * replaces the loop of FrontEnd::traceNewCoarse (FrontEnd.cpp:276-327), which runs on every frame (:717, :730) over every immature
+ * point of every frame of the window: ImmaturePoint::traceOn (UPSTREAM-DSO, parity unpinned) as the rules T1-T16 of DESIGN.md section
+ * 14 state it, for the points of many sequences in one call.  Everything is float32 without contraction. */
+/* ImmaturePointStatus, in the upstream enum's order (lastTraceStatus) */
+#define DSM_IPS_GOOD 0
+#define DSM_IPS_OOB 1
+#define DSM_IPS_OUTLIER 2
+#define DSM_IPS_SKIPPED 3
+#define DSM_IPS_BADCONDITION 4
+#define DSM_IPS_UNINITIALIZED 5
+#define DSM_TRACE_MAX_HOSTS 16 /* largest n_hosts of a job */
+#define DSM_TRACE_MAX_STEPS 99 /* the cap of the line search (T7) */
+
+/* the settings traceOn reads; dsm_trace_params_default fills the upstream defaults */
+typedef struct dsm_trace_params {
+  float max_pix_search;    /* 0.027f  setting_maxPixSearch (times w + h) */
+  float slack_interval;    /* 1.5f    setting_trace_slackInterval */
+  float stepsize;          /* 1.0f    setting_trace_stepsize */
+  float min_improvement;   /* 2.0f    setting_trace_minImprovementFactor */
+  int min_test_radius;     /* 2       setting_minTraceTestRadius */
+  int gn_iterations;       /* 3       setting_trace_GNIterations, 0 .. 16 */
+  float gn_threshold;      /* 0.1f    setting_trace_GNThreshold */
+  float extra_slack_on_th; /* 1.2f    setting_trace_extraSlackOnTH */
+  float huber_th;          /* 9.0f    setting_huberTH */
+} dsm_trace_params;
+
+/* The immature points of one sequence against its new frame.  The new frame is level 0 of `target_slot` of `target_tracker` if
+ * that is non-NULL (FrontEnd.cpp:717, :730: the frame just tracked), else frame `target_frame_id` of `target_window`; exactly one
+ * of the two is given.  hosts: frame_hessians_ in order, with K R K^-1 and K t of host-to-new (:292-293) and
+ * fromToVecExposure(host, new) cast to float (:295-297; the exp stays on the host).  The last seven arrays are the fields traceOn
+ * reads and writes, updated in place. */
+typedef struct dsm_trace_job {
+  dsm_tracker *target_tracker;
+  int target_slot;
+  dsm_window *target_window;
+  int target_frame_id;
+  int n_hosts;       /* 0 .. DSM_TRACE_MAX_HOSTS */
+  const float *krki; /* n_hosts * 9, row-major */
+  const float *kt;   /* n_hosts * 3 */
+  const float *aff;  /* n_hosts * 2 */
+  int n_pts;
+  const int *host;                  /* n_pts: index into the hosts */
+  const float *u, *v, *energy_th;   /* n_pts each */
+  const float *grad_h;              /* n_pts * 4: gradH, row-major */
+  const float *color, *weights;     /* n_pts * 8 each */
+  unsigned char *status;            /* n_pts, in/out: lastTraceStatus (DSM_IPS_*) */
+  float *idepth_min, *idepth_max, *quality; /* n_pts each, in/out */
+  float *trace_uv;                  /* n_pts * 2, in/out: lastTraceUV */
+  float *trace_interval;            /* n_pts, in/out: lastTracePixelInterval */
+  int *steps_out;                   /* optional (NULL), n_pts: numSteps searched, 0 if the search was not reached */
+  int *counts_out;                  /* optional (NULL), 6: points per status after the call (:302-313) */
+} dsm_trace_job;
+
+/* the upstream defaults listed above */
+int dsm_trace_params_default(dsm_trace_params *p);
+/* FrontEnd.cpp:276-327 for every job: one staged copy through the context's page-locked arena, one launch, one host wait for the whole
+ * batch; nothing is allocated once the arena has grown to the batch size; a job's results do not depend on the other jobs of the
+ * call; one geometry per call; n_pts == 0 and n_hosts == 0 (then n_pts == 0) are valid.  Validation is all or nothing, before
+ * anything is enqueued: DSM_ERR_INVALID for NULL arrays or negative counts, n_hosts above DSM_TRACE_MAX_HOSTS, a host index outside
+ * [0, n_hosts), a status byte above 5, an empty or unknown target (an empty slot, an id not in the window, both or neither of
+ * tracker and window), a tracker or window of another context, mixed geometries, gn_iterations outside [0, 16], a non-finite or
+ * non-positive stepsize, any other non-finite parameter, a negative min_test_radius. */
+int dsm_trace_points_batch(dsm_context *ctx, int n_jobs, const dsm_trace_job *jobs, const dsm_trace_params *params);
+/* The same for one job as one plain sequential loop on the host plane target_I (w * h floats); the target fields of the job are
+ * ignored.  The CPU baseline of tools/trace_timing.py and a checker that needs no device. */
+int dsm_trace_points_host(int w, int h, const float *target_I, const dsm_trace_job *job, const dsm_trace_params *params);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.
