@@ -22,8 +22,7 @@
 #include <cstring>
 #include <vector>
 
-#include "dsm_internal.hpp"
-#include "ringdb_internal.hpp"
+#include "call_arena.hpp"
 
 using namespace dsm;
 
@@ -51,8 +50,6 @@ struct DmJob {
   int out_off;                                                    // first candidate of the job in cell / frac / thr / decision
   float min_act;
 };
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 __global__ __launch_bounds__(kThreads) void distmap_fill_kernel(const DmJob *jobs, int bytes16) {
   const int o = (blockIdx.x * kThreads + threadIdx.x) * 16;
@@ -248,56 +245,45 @@ int run_batch(dsm_context *ctx, int n_jobs, const dsm_activation_job *jobs, bool
   int rc = check_jobs(ctx, n_jobs, jobs, with_cand, &items, &cands);
   if (rc) return rc;
   const int w1 = jobs[0].map->w1, h1 = jobs[0].map->h1, bytes16 = (int)jobs[0].map->bytes16;
-  // arena (dsm::loop_arena_grow): staged [job table | krki, kt, host, u, v, idepth, type of every job], device-only [cell | frac | thr],
-  // read back [decision | n_activated]
-  const size_t b_jobs = align256(sizeof(DmJob) * n_jobs);
+  // staged [job table | krki, kt, host, u, v, idepth, type of every job], device-only [cell | frac | thr], read back [decision | n_activated]
   size_t words = 0;
   for (int j = 0; j < n_jobs; j++)
     words += 12 * (size_t)jobs[j].n_hosts + 4 * ((size_t)jobs[j].n_seeds + (with_cand ? jobs[j].n_cand : 0)) + (with_cand ? jobs[j].n_cand : 0);
-  const size_t in_bytes = b_jobs + align256(4 * words);
-  const size_t b_c4 = align256(4 * std::max<size_t>(1, cands)), work_bytes = 3 * b_c4;
-  const size_t b_dec = align256(std::max<size_t>(1, cands)), out_bytes = b_dec + align256(sizeof(int) * n_jobs);
-  DSM_HIP(hipSetDevice(ctx->device));
-  rc = loop_arena_grow(ctx, in_bytes + work_bytes + out_bytes, in_bytes + out_bytes);
-  if (rc) return rc;
-  unsigned char *d = (unsigned char *)ctx->loop_dev, *h = (unsigned char *)ctx->loop_pin;
-  DmJob *hj = (DmJob *)h;
-  float *hs = (float *)(h + b_jobs);
-  size_t o = 0, oc = 0;
+  CallArena A;
+  const size_t o_jobs = A.in.take(sizeof(DmJob) * n_jobs), o_stage = A.in.take(4 * words), b_c4 = 4 * std::max<size_t>(1, cands);
+  const size_t o_cell = A.work.take(b_c4), o_frac = A.work.take(b_c4), o_thr = A.work.take(b_c4);
+  const size_t o_dec = A.out.take(std::max<size_t>(1, cands)), o_nact = A.out.take(sizeof(int) * n_jobs);
+  if ((rc = A.bind(ctx))) return rc;
+  DmJob *hj = A.host_in<DmJob>(o_jobs);
+  WordPacker W{A.host_in<float>(o_stage)};
+  size_t oc = 0;
   int max_items = 0;
   for (int j = 0; j < n_jobs; j++) {
     const dsm_activation_job &J = jobs[j];
     const int ns = J.n_seeds, nc = with_cand ? J.n_cand : 0, n = ns + nc;
     DmJob &D = hj[j];
     D.map = J.map->d_map, D.n_seeds = ns, D.n_cand = nc, D.out_off = (int)oc, D.min_act = J.min_act_dist;
-    auto put = [&](int *off, const void *a, const void *b, size_t na, size_t nb) { // two host arrays, back to back
-      *off = (int)o;
-      if (na) memcpy(hs + o, a, 4 * na);
-      if (nb) memcpy(hs + o + na, b, 4 * nb);
-      o += na + nb;
-    };
-    put(&D.off_krki, J.krki, nullptr, 9 * (size_t)J.n_hosts, 0);
-    put(&D.off_kt, J.kt, nullptr, 3 * (size_t)J.n_hosts, 0);
-    put(&D.off_host, J.seed_host, J.cand_host, ns, nc);
-    put(&D.off_u, J.seed_u, J.cand_u, ns, nc);
-    put(&D.off_v, J.seed_v, J.cand_v, ns, nc);
-    put(&D.off_id, J.seed_idepth, J.cand_idepth, ns, nc);
-    put(&D.off_type, J.cand_type, nullptr, nc, 0);
+    W.put(&D.off_krki, J.krki, 9 * (size_t)J.n_hosts);
+    W.put(&D.off_kt, J.kt, 3 * (size_t)J.n_hosts);
+    W.put2(&D.off_host, J.seed_host, ns, J.cand_host, nc);
+    W.put2(&D.off_u, J.seed_u, ns, J.cand_u, nc);
+    W.put2(&D.off_v, J.seed_v, ns, J.cand_v, nc);
+    W.put2(&D.off_id, J.seed_idepth, ns, J.cand_idepth, nc);
+    W.put(&D.off_type, J.cand_type, nc);
     oc += nc;
     max_items = std::max(max_items, n);
   }
-  const DmJob *dj = (const DmJob *)d;
-  const float *d_stage = (const float *)(d + b_jobs);
-  int *d_cell = (int *)(d + in_bytes);
-  float *d_frac = (float *)(d + in_bytes + b_c4), *d_thr = (float *)(d + in_bytes + 2 * b_c4);
-  unsigned char *d_dec = d + in_bytes + work_bytes;
-  int *d_nact = (int *)(d + in_bytes + work_bytes + b_dec);
+  const DmJob *dj = A.dev_in<const DmJob>(o_jobs);
+  int *d_cell = A.dev_work<int>(o_cell);
+  float *d_frac = A.dev_work<float>(o_frac), *d_thr = A.dev_work<float>(o_thr);
+  unsigned char *d_dec = A.dev_out<unsigned char>(o_dec);
+  int *d_nact = A.dev_out<int>(o_nact);
   hipStream_t st = ctx->stream;
-  DSM_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
+  if ((rc = A.upload())) return rc;
   hipLaunchKernelGGL(distmap_fill_kernel, dim3((bytes16 / 16 + kThreads - 1) / kThreads, n_jobs), dim3(kThreads), 0, st, dj, bytes16);
   if (max_items)
-    hipLaunchKernelGGL(distmap_project_kernel, dim3((max_items + kThreads - 1) / kThreads, n_jobs), dim3(kThreads), 0, st, dj, d_stage, d_cell,
-                       d_frac, d_thr, w1, h1, with_cand ? 1 : 0);
+    hipLaunchKernelGGL(distmap_project_kernel, dim3((max_items + kThreads - 1) / kThreads, n_jobs), dim3(kThreads), 0, st, dj,
+                       A.dev_in<const float>(o_stage), d_cell, d_frac, d_thr, w1, h1, with_cand ? 1 : 0);
   for (int k = 1; k < kLevels; k++)
     hipLaunchKernelGGL(distmap_dilate_kernel, dim3((w1 * h1 + kThreads - 1) / kThreads, n_jobs), dim3(kThreads), 0, st, dj, w1, h1, k);
   if (with_cand) {
@@ -309,11 +295,10 @@ int run_batch(dsm_context *ctx, int n_jobs, const dsm_activation_job *jobs, bool
                          (const float *)d_thr, d_dec, d_nact, w1, h1, bytes16);
   }
   DSM_HIP(hipGetLastError());
-  if (with_cand) DSM_HIP(hipMemcpyAsync(h + in_bytes, d_dec, out_bytes, hipMemcpyDeviceToHost, st));
-  DSM_HIP(hipStreamSynchronize(st));
+  if ((rc = A.fetch(with_cand ? A.out.used : 0))) return rc; // (no candidates: the maps are made, nothing comes back)
   if (with_cand) {
-    const unsigned char *h_dec = h + in_bytes;
-    const int *h_nact = (const int *)(h + in_bytes + b_dec);
+    const unsigned char *h_dec = A.host_out<unsigned char>(o_dec);
+    const int *h_nact = A.host_out<int>(o_nact);
     for (int j = 0; j < n_jobs; j++) {
       if (jobs[j].n_cand) memcpy(jobs[j].decision_out, h_dec + hj[j].out_off, jobs[j].n_cand);
       if (jobs[j].n_activated_out) *jobs[j].n_activated_out = h_nact[j];

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 
+#include "call_arena.hpp"
 #include "dsm_internal.hpp"
 #include <algorithm>
 #include <utility>
@@ -39,6 +40,13 @@ int ensure_stage(dsm_context *ctx, size_t floats) {
   if (rc) return rc;
   ctx->stage_floats = floats;
   return DSM_OK;
+}
+
+const void *pinned_device_pointer(const void *p) {
+  hipPointerAttribute_t a{};
+  if (hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer) return a.devicePointer;
+  (void)hipGetLastError(); // (pageable memory is reported as an error by some runtimes)
+  return nullptr;
 }
 
 int ensure_batch_capacity(dsm_context *ctx, int nprob, int partial_stride) {
@@ -325,8 +333,7 @@ int dsm_context_destroy(dsm_context *ctx) {
   hipHostFree(ctx->h_status);
   hipFree(ctx->d_stage);
   if (ctx->h_tpl_stage) hipHostFree(ctx->h_tpl_stage);
-  hipFree(ctx->loop_dev);
-  if (ctx->loop_pin) hipHostFree(ctx->loop_pin);
+  CallArena::release(ctx);
   if (ctx->h_tpl_counts) hipHostFree(ctx->h_tpl_counts);
   for (hipEvent_t ev : ctx->ev_pool) hipEventDestroy(ev);
   for (hipEvent_t ev : ctx->join_events) hipEventDestroy(ev);
@@ -1787,13 +1794,6 @@ struct dsm_pose_batch {
 namespace {
 constexpr int kPoseImportWave = 8; // pyramids staged at a time: 12 B x sum of pixels each, whatever the batch size
 size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-// the device-visible address of a caller's array if it lies in page-locked memory, else null
-const void *pinned_device_pointer(const void *p) {
-  hipPointerAttribute_t a{};
-  if (hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer) return a.devicePointer;
-  (void)hipGetLastError(); // (pageable memory is reported as an error by some runtimes)
-  return nullptr;
-}
 struct PosePyramid { // a distinct target pyramid of a call
   bool dip;
   const float *const *lv;

@@ -74,9 +74,10 @@ struct dsm_context {
   // staging for host->device template / frame uploads
   float *d_stage = nullptr;
   size_t stage_floats = 0;
-  // dsm_loop_descriptors_batch / dsm_loop_detect_batch: device arena and its page-locked mirror (grown on demand)
-  void *loop_dev = nullptr, *loop_pin = nullptr;
-  size_t loop_dev_bytes = 0, loop_pin_bytes = 0;
+  // the staging arena of the batched calls (loop chain, ring-key search of many indexes, ICP, distance map, immature points, trace):
+  // device buffer and page-locked mirror, owned and laid out by call_arena.hpp alone
+  void *arena_dev = nullptr, *arena_pin = nullptr;
+  size_t arena_dev_bytes = 0, arena_pin_bytes = 0;
   // dsm_set_refs_from_points: page-locked mirror of the jobs' points and job table, and of their counts
   float *h_tpl_stage = nullptr;
   size_t tpl_stage_floats = 0;
@@ -148,6 +149,8 @@ const char *trace_params_error(const dsm_trace_params *p);
 const char *trace_job_error(const dsm_trace_job &J);
 int ensure_batch_capacity(dsm_context *ctx, int nprob, int partial_stride);
 int ensure_stage(dsm_context *ctx, size_t floats);
+// the device-visible address of a caller's array if it lies in page-locked memory, else null
+const void *pinned_device_pointer(const void *p);
 int sync_desc(dsm_tracker *t);
 int sync_descs(dsm_context *ctx, dsm_tracker *const *ts, int n);
 int check_ready(dsm_tracker *t, int mode);

@@ -18,8 +18,8 @@
 #include <cstring>
 #include <vector>
 
+#include "call_arena.hpp"
 #include "icp_internal.hpp"
-#include "ringdb_internal.hpp"
 
 using namespace dsm;
 
@@ -243,8 +243,6 @@ bool finite16(const double *m) {
   return true;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 } // namespace
 
 extern "C" {
@@ -285,36 +283,29 @@ int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_itera
     for (int s0 = 0; s0 < J.n_src; s0 += kIcpThreads)
       for (int t0 = 0; t0 < J.n_tgt; t0 += per) blocks.push_back(IcpNnBlock{j, s0, t0, std::min(J.n_tgt, t0 + per)});
   }
-  // arena (the loop chain's, dsm::loop_arena_grow): staged [jobs | blocks | source xyz | target xyz], device-only [orig | work | target |
-  // keys], read back [states]
-  const size_t b_jobs = align256(sizeof(IcpJobDev) * n_jobs), b_blocks = align256(sizeof(IcpNnBlock) * std::max<size_t>(1, blocks.size()));
-  const size_t b_src = align256(sizeof(double) * 3 * (size_t)tot_src), b_tgt = align256(sizeof(double) * 3 * (size_t)tot_tgt);
-  const size_t in_bytes = b_jobs + b_blocks + b_src + b_tgt;
-  const size_t b_f4s = align256(sizeof(float4) * (size_t)std::max(1ll, tot_src)), b_f4t = align256(sizeof(float4) * (size_t)std::max(1ll, tot_tgt));
-  const size_t b_keys = align256(sizeof(unsigned long long) * (size_t)std::max(1ll, tot_src));
-  const size_t work_bytes = 2 * b_f4s + b_f4t + b_keys;
-  const size_t out_bytes = align256(sizeof(IcpState) * n_jobs);
-  // the context's device before the arena may grow: a thread that drives contexts on several GPUs may have another one selected
-  DSM_HIP(hipSetDevice(ctx->device));
-  int rc = loop_arena_grow(ctx, in_bytes + work_bytes + out_bytes, in_bytes + out_bytes);
+  // staged [jobs | blocks | source xyz | target xyz], device-only [orig | work | target | keys], read back [states]
+  CallArena A;
+  const size_t o_jobs = A.in.take(sizeof(IcpJobDev) * n_jobs), o_blocks = A.in.take(sizeof(IcpNnBlock) * std::max<size_t>(1, blocks.size()));
+  const size_t o_src = A.in.take(sizeof(double) * 3 * (size_t)tot_src), o_tgt = A.in.take(sizeof(double) * 3 * (size_t)tot_tgt);
+  const size_t b_f4s = sizeof(float4) * (size_t)std::max(1ll, tot_src), b_f4t = sizeof(float4) * (size_t)std::max(1ll, tot_tgt);
+  const size_t o_orig = A.work.take(b_f4s), o_work = A.work.take(b_f4s), o_tgt4 = A.work.take(b_f4t);
+  const size_t o_keys = A.work.take(sizeof(unsigned long long) * (size_t)std::max(1ll, tot_src)), o_states = A.out.take(sizeof(IcpState) * n_jobs);
+  int rc = A.bind(ctx);
   if (rc) return rc;
-  unsigned char *d = (unsigned char *)ctx->loop_dev, *h = (unsigned char *)ctx->loop_pin;
-  memcpy(h, hj.data(), sizeof(IcpJobDev) * n_jobs);
-  if (!blocks.empty()) memcpy(h + b_jobs, blocks.data(), sizeof(IcpNnBlock) * blocks.size());
+  memcpy(A.host_in<IcpJobDev>(o_jobs), hj.data(), sizeof(IcpJobDev) * n_jobs);
+  if (!blocks.empty()) memcpy(A.host_in<IcpNnBlock>(o_blocks), blocks.data(), sizeof(IcpNnBlock) * blocks.size());
   for (int j = 0; j < n_jobs; j++) {
-    if (jobs[j].n_src) memcpy(h + b_jobs + b_blocks + sizeof(double) * 3 * hj[j].off_src, jobs[j].src_xyz, sizeof(double) * 3 * jobs[j].n_src);
-    if (jobs[j].n_tgt)
-      memcpy(h + b_jobs + b_blocks + b_src + sizeof(double) * 3 * hj[j].off_tgt, jobs[j].tgt_xyz, sizeof(double) * 3 * jobs[j].n_tgt);
+    if (jobs[j].n_src) memcpy(A.host_in<double>(o_src) + 3 * hj[j].off_src, jobs[j].src_xyz, sizeof(double) * 3 * jobs[j].n_src);
+    if (jobs[j].n_tgt) memcpy(A.host_in<double>(o_tgt) + 3 * hj[j].off_tgt, jobs[j].tgt_xyz, sizeof(double) * 3 * jobs[j].n_tgt);
   }
-  const IcpJobDev *dj = (const IcpJobDev *)d;
-  const IcpNnBlock *db = (const IcpNnBlock *)(d + b_jobs);
-  const double *d_src = (const double *)(d + b_jobs + b_blocks), *d_tgt = (const double *)(d + b_jobs + b_blocks + b_src);
-  float4 *orig = (float4 *)(d + in_bytes), *work = (float4 *)(d + in_bytes + b_f4s), *tgt = (float4 *)(d + in_bytes + 2 * b_f4s);
-  unsigned long long *keys = (unsigned long long *)(d + in_bytes + 2 * b_f4s + b_f4t);
-  IcpState *d_states = (IcpState *)(d + in_bytes + work_bytes);
-  const IcpState *h_states = (const IcpState *)(h + in_bytes);
+  const IcpJobDev *dj = A.dev_in<const IcpJobDev>(o_jobs);
+  const IcpNnBlock *db = A.dev_in<const IcpNnBlock>(o_blocks);
+  const double *d_src = A.dev_in<const double>(o_src), *d_tgt = A.dev_in<const double>(o_tgt);
+  float4 *orig = A.dev_work<float4>(o_orig), *work = A.dev_work<float4>(o_work), *tgt = A.dev_work<float4>(o_tgt4);
+  unsigned long long *keys = A.dev_work<unsigned long long>(o_keys);
+  IcpState *d_states = A.dev_out<IcpState>(o_states);
   hipStream_t st = ctx->stream;
-  DSM_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
+  if ((rc = A.upload())) return rc;
   const int nb = (int)blocks.size();
   const double max_dist2 = max_corr_dist * max_corr_dist;
   hipLaunchKernelGGL(icp_prep_kernel, dim3(n_jobs), dim3(kIcpThreads), 0, st, dj, d_src, d_tgt, orig, work, tgt, keys, d_states);
@@ -332,8 +323,8 @@ int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_itera
     hipLaunchKernelGGL(icp_fitness_kernel, dim3(n_jobs), dim3(kIcpThreads), 0, st, dj, d_states, (const unsigned long long *)keys);
   }
   DSM_HIP(hipGetLastError());
-  DSM_HIP(hipMemcpyAsync(h + in_bytes, d_states, sizeof(IcpState) * n_jobs, hipMemcpyDeviceToHost, st));
-  DSM_HIP(hipStreamSynchronize(st));
+  if ((rc = A.fetch(sizeof(IcpState) * n_jobs))) return rc;
+  const IcpState *h_states = A.host_out<IcpState>(o_states);
   for (int j = 0; j < n_jobs; j++) {
     dsm_icp_job &J = jobs[j];
     const IcpState &S = h_states[j];

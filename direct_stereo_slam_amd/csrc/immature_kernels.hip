@@ -18,9 +18,8 @@
 #include <cstring>
 #include <vector>
 
-#include "dsm_internal.hpp"
+#include "call_arena.hpp"
 #include "immature_math.hpp"
-#include "ringdb_internal.hpp"
 
 using namespace dsm;
 
@@ -37,8 +36,6 @@ struct ImJob {
   int off_R, off_t, off_aff, off_host, off_u, off_v, off_idmin, off_idmax, off_eth, off_color, off_wt; // 4-byte words into the staged inputs
   int out_off;                                                                                          // first point of the job in the output
 };
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ float lane_value(float x, int lane) { // x of a wave-uniform lane
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), __builtin_amdgcn_readfirstlane(lane)));
@@ -303,19 +300,16 @@ int dsm_optimize_immature_points_batch(dsm_context *ctx, int n_jobs, const dsm_i
   int rc = check_jobs(ctx, n_jobs, jobs, huber_th, min_idepth_h_act, gn_iterations, &pts);
   if (rc) return rc;
   if (pts == 0) return DSM_OK;
-  // arena (dsm::loop_arena_grow): staged [job table | pre_R, pre_t, pre_aff, host, u, v, idepth_min, idepth_max, energy_th, color,
-  // weights of every job], read back [kOutWords words per point]
-  const size_t b_jobs = align256(sizeof(ImJob) * n_jobs);
+  // staged [job table | pre_R, pre_t, pre_aff, host, u, v, idepth_min, idepth_max, energy_th, color, weights of every job], read back
+  // [kOutWords words per point]
   size_t words = 0;
   for (int j = 0; j < n_jobs; j++) words += 14 * (size_t)jobs[j].n_frames * jobs[j].n_frames + 22 * (size_t)jobs[j].n_pts;
-  const size_t in_bytes = b_jobs + align256(4 * words), out_bytes = align256(4 * kOutWords * pts);
-  DSM_HIP(hipSetDevice(ctx->device));
-  rc = loop_arena_grow(ctx, in_bytes + out_bytes, in_bytes + out_bytes);
-  if (rc) return rc;
-  unsigned char *d = (unsigned char *)ctx->loop_dev, *hp = (unsigned char *)ctx->loop_pin;
-  ImJob *hj = (ImJob *)hp;
-  float *hs = (float *)(hp + b_jobs);
-  size_t o = 0, op = 0;
+  CallArena A;
+  const size_t o_jobs = A.in.take(sizeof(ImJob) * n_jobs), o_stage = A.in.take(4 * words), o_out = A.out.take(4 * kOutWords * pts);
+  if ((rc = A.bind(ctx))) return rc;
+  ImJob *hj = A.host_in<ImJob>(o_jobs);
+  WordPacker W{A.host_in<float>(o_stage)};
+  size_t op = 0;
   int max_pts = 0;
   for (int j = 0; j < n_jobs; j++) {
     const dsm_immature_job &J = jobs[j];
@@ -325,36 +319,27 @@ int dsm_optimize_immature_points_batch(dsm_context *ctx, int n_jobs, const dsm_i
     for (size_t f = 0; f < nf; f++) D.plane[f] = J.window->plane(J.window->find(J.frame_ids[f]));
     D.fx = J.cam[0], D.fy = J.cam[1], D.cx = J.cam[2], D.cy = J.cam[3], D.fxi = J.cam_inv[0], D.fyi = J.cam_inv[1];
     D.n_frames = J.n_frames, D.n_pts = J.n_pts, D.min_obs = J.min_obs, D.out_off = (int)op;
-    auto put = [&](int *off, const void *a, size_t na) {
-      *off = (int)o;
-      if (na) memcpy(hs + o, a, 4 * na);
-      o += na;
-    };
-    put(&D.off_R, J.pre_R, 9 * nf * nf);
-    put(&D.off_t, J.pre_t, 3 * nf * nf);
-    put(&D.off_aff, J.pre_aff, 2 * nf * nf);
-    put(&D.off_host, J.host, n);
-    put(&D.off_u, J.u, n);
-    put(&D.off_v, J.v, n);
-    put(&D.off_idmin, J.idepth_min, n);
-    put(&D.off_idmax, J.idepth_max, n);
-    put(&D.off_eth, J.energy_th, n);
-    put(&D.off_color, J.color, 8 * n);
-    put(&D.off_wt, J.weights, 8 * n);
+    W.put(&D.off_R, J.pre_R, 9 * nf * nf);
+    W.put(&D.off_t, J.pre_t, 3 * nf * nf);
+    W.put(&D.off_aff, J.pre_aff, 2 * nf * nf);
+    W.put(&D.off_host, J.host, n);
+    W.put(&D.off_u, J.u, n);
+    W.put(&D.off_v, J.v, n);
+    W.put(&D.off_idmin, J.idepth_min, n);
+    W.put(&D.off_idmax, J.idepth_max, n);
+    W.put(&D.off_eth, J.energy_th, n);
+    W.put(&D.off_color, J.color, 8 * n);
+    W.put(&D.off_wt, J.weights, 8 * n);
     op += n;
     max_pts = std::max(max_pts, J.n_pts);
   }
-  const ImJob *dj = (const ImJob *)d;
-  const float *d_stage = (const float *)(d + b_jobs);
-  unsigned *d_out = (unsigned *)(d + in_bytes);
-  hipStream_t st = ctx->stream;
-  DSM_HIP(hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(immature_kernel, dim3((max_pts + kWavesPerBlock - 1) / kWavesPerBlock, n_jobs), dim3(64 * kWavesPerBlock), 0, st, dj, d_stage,
-                     d_out, jobs[0].window->w, jobs[0].window->h, huber_th, min_idepth_h_act, gn_iterations);
+  if ((rc = A.upload())) return rc;
+  hipLaunchKernelGGL(immature_kernel, dim3((max_pts + kWavesPerBlock - 1) / kWavesPerBlock, n_jobs), dim3(64 * kWavesPerBlock), 0, ctx->stream,
+                     A.dev_in<const ImJob>(o_jobs), A.dev_in<const float>(o_stage), A.dev_out<unsigned>(o_out), jobs[0].window->w,
+                     jobs[0].window->h, huber_th, min_idepth_h_act, gn_iterations);
   DSM_HIP(hipGetLastError());
-  DSM_HIP(hipMemcpyAsync(hp + in_bytes, d_out, 4 * kOutWords * pts, hipMemcpyDeviceToHost, st));
-  DSM_HIP(hipStreamSynchronize(st));
-  const unsigned *ho = (const unsigned *)(hp + in_bytes);
+  if ((rc = A.fetch(4 * kOutWords * pts))) return rc;
+  const unsigned *ho = A.host_out<unsigned>(o_out);
   for (int j = 0; j < n_jobs; j++) {
     const dsm_immature_job &J = jobs[j];
     const int nf = J.n_frames;

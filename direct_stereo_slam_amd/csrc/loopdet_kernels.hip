@@ -25,7 +25,7 @@
 #include <functional>
 #include <vector>
 
-#include "dsm_internal.hpp"
+#include "call_arena.hpp"
 #include "loopdet_internal.hpp"
 #include "ringdb_internal.hpp"
 
@@ -357,51 +357,22 @@ __global__ void sc_pca_kernel(JobDev *jobs, int n_jobs) {
 // ---- host side: ONE enqueue and ONE read-back per call -------------------------------------------------------------------------------
 // Round 4's form allocated thirteen device buffers per job and freed them at the end (hipFree synchronises), staged its inputs from
 // pageable memory job by job, synchronised three times and copied every small output back on its own: 0.9 ms of host time for ONE
-// keyframe around ~60 us of kernels.  Now: a device arena and a page-locked mirror that live in the context (grown on demand), the
-// inputs of all jobs packed into one host->device copy, the outputs of all jobs packed into one device->host copy, and -- for
-// dsm_loop_detect_batch -- the ring keys handed to the ring-key search ON THE DEVICE between the two.
+// keyframe around ~60 us of kernels.  Now: the context's staging arena (call_arena.hpp), the inputs of all jobs packed into one
+// host->device copy, the outputs of all jobs packed into one device->host copy, and -- for dsm_loop_detect_batch -- the ring keys handed
+// to the ring-key search ON THE DEVICE between the two.
 namespace {
-
-struct Arena { // linear sub-allocation of a region that is laid out identically on the device and in the pinned mirror
-  size_t used = 0;
-  size_t take(size_t bytes) {
-    const size_t o = used;
-    used = (used + bytes + 255) & ~(size_t)255;
-    return o;
-  }
-};
 
 struct LoopPlan {
   int n_jobs = 0, nbins = 0, num_r = 0, nblocks = 0;
   long long cells = 0;
   std::vector<JobDev> hj;
-  // offsets (bytes) into the input region (pinned + device), the work region (device only), the output region (device + pinned)
+  dsm::CallArena A; // bound by loop_enqueue; the offsets below lie in its regions
   std::vector<size_t> in_xyz, in_ptkf, in_ids, out_small, out_sig_idx, out_sig_val, out_sel, out_sph;
-  size_t in_tab = 0, in_extra = 0, in_bytes = 0, work_bytes = 0, out_bytes = 0, out_keys = 0, out_cand = 0;
+  size_t in_tab = 0, in_extra = 0, out_keys = 0, out_cand = 0;
   bool any_sc = false;
 };
 // per job "small" outputs: [n_out, n_sig, pad, pad][tfm 16 doubles] -- ring keys of all jobs are one contiguous array (out_keys)
 constexpr size_t kSmallBytes = 16 + 16 * sizeof(double);
-
-} // namespace
-
-int dsm::loop_arena_grow(dsm_context *ctx, size_t dev_bytes, size_t pin_bytes) {
-  if (dev_bytes > ctx->loop_dev_bytes) {
-    if (ctx->loop_dev) DSM_HIP(hipFree(ctx->loop_dev));
-    ctx->loop_dev = nullptr, ctx->loop_dev_bytes = 0;
-    DSM_HIP(hipMalloc(&ctx->loop_dev, dev_bytes + dev_bytes / 2));
-    ctx->loop_dev_bytes = dev_bytes + dev_bytes / 2;
-  }
-  if (pin_bytes > ctx->loop_pin_bytes) {
-    if (ctx->loop_pin) DSM_HIP(hipHostFree(ctx->loop_pin));
-    ctx->loop_pin = nullptr, ctx->loop_pin_bytes = 0;
-    DSM_HIP(hipHostMalloc(&ctx->loop_pin, pin_bytes + pin_bytes / 2, hipHostMallocDefault));
-    ctx->loop_pin_bytes = pin_bytes + pin_bytes / 2;
-  }
-  return DSM_OK;
-}
-
-namespace {
 
 int check_jobs(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double lidar_range, int num_s, int num_r, long long *cells_out) {
   if (!ctx || n_jobs < 1 || !jobs || !(lidar_range > 0) || num_s < 1 || num_r < 1 || num_s > kLdThreads || num_r > kLdThreads)
@@ -436,13 +407,13 @@ int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double 
   int rc = check_jobs(ctx, n_jobs, jobs, lidar_range, num_s, num_r, &cells);
   if (rc) return rc;
   const long long vs0 = (long long)std::floor(2 * lidar_range * 1.0) + 1, vs1 = (long long)std::floor(2 * lidar_range * 2.0) + 1;
-  DSM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   P.n_jobs = n_jobs, P.nbins = num_s * num_r, P.num_r = num_r, P.cells = cells, P.nblocks = (int)((cells + kLdThreads - 1) / kLdThreads);
   P.hj.assign(n_jobs, JobDev());
   P.in_xyz.resize(n_jobs), P.in_ptkf.resize(n_jobs), P.in_ids.resize(n_jobs), P.out_small.resize(n_jobs), P.out_sig_idx.resize(n_jobs), P.out_sig_val.resize(n_jobs);
   P.out_sel.resize(n_jobs), P.out_sph.resize(n_jobs);
-  Arena in, work, out;
+  CallArena &A = P.A;
+  CallArena::Region &in = A.in, &work = A.work, &out = A.out;
   std::vector<size_t> w_gy(n_jobs), w_gi(n_jobs), w_bc(n_jobs), w_mom(n_jobs), w_bins(n_jobs), w_sel(n_jobs), w_sph(n_jobs);
   int max_pts = 1;
   for (int j = 0; j < n_jobs; j++) {
@@ -478,12 +449,7 @@ int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double 
   P.out_keys = out.take(sizeof(float) * (size_t)num_r * n_jobs);
   P.out_cand = out.take(X.out_bytes);
   const size_t w_extra = work.take(X.work_bytes);
-  P.in_bytes = in.used, P.work_bytes = work.used, P.out_bytes = out.used;
-  // device arena: [in | work | out]; pinned mirror: [in | out]
-  rc = loop_arena_grow(ctx, P.in_bytes + P.work_bytes + P.out_bytes, P.in_bytes + P.out_bytes);
-  if (rc) return rc;
-  unsigned char *d_in = (unsigned char *)ctx->loop_dev, *d_work = d_in + P.in_bytes, *d_out = d_work + P.work_bytes;
-  unsigned char *h_in = (unsigned char *)ctx->loop_pin;
+  if ((rc = A.bind(ctx))) return rc;
   bool any_direct = false, any_staged = false;
   for (int j = 0; j < n_jobs; j++) {
     const dsm_loop_job &J = jobs[j];
@@ -496,46 +462,38 @@ int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double 
     std::vector<std::pair<int, int>> ids;
     for (int k = 0; k < J.n_kf; k++) ids.push_back(std::make_pair(J.kf_ids[k], J.kf_keep[k] ? 1 : 0));
     std::sort(ids.begin(), ids.end());
-    int *h_ids = (int *)(h_in + P.in_ids[j]);
+    int *h_ids = A.host_in<int>(P.in_ids[j]);
     for (int k = 0; k < J.n_kf; k++) h_ids[2 * k] = ids[k].first, h_ids[2 * k + 1] = ids[k].second;
     // the cloud: straight from the caller's buffers where both are page-locked (dsm_host_alloc / hipHostMalloc / hipHostRegister: a node
     // that keeps its window's clouds there), else through the pinned mirror (a host copy of 28 bytes per point)
-    const void *dev_xyz = nullptr, *dev_kf = nullptr;
-    if (J.n_pts) {
-      hipPointerAttribute_t ax, ak;
-      if (hipPointerGetAttributes(&ax, J.pt_xyz) == hipSuccess && ax.type == hipMemoryTypeHost && ax.devicePointer &&
-          hipPointerGetAttributes(&ak, J.pt_kf_id) == hipSuccess && ak.type == hipMemoryTypeHost && ak.devicePointer)
-        dev_xyz = ax.devicePointer, dev_kf = ak.devicePointer;
-      else
-        (void)hipGetLastError(); // (pageable memory is reported as an error by some runtimes)
-    }
-    if (dev_xyz) {
+    const void *dev_xyz = J.n_pts ? pinned_device_pointer(J.pt_xyz) : nullptr, *dev_kf = dev_xyz ? pinned_device_pointer(J.pt_kf_id) : nullptr;
+    if (dev_kf) {
       D.xyz_src = (const double *)dev_xyz, D.pt_kf_src = (const int *)dev_kf;
       any_direct = true;
     } else if (J.n_pts) {
-      memcpy(h_in + P.in_ptkf[j], J.pt_kf_id, sizeof(int) * (size_t)J.n_pts);
-      memcpy(h_in + P.in_xyz[j], J.pt_xyz, sizeof(double) * 3 * (size_t)J.n_pts);
+      memcpy(A.host_in<int>(P.in_ptkf[j]), J.pt_kf_id, sizeof(int) * (size_t)J.n_pts);
+      memcpy(A.host_in<double>(P.in_xyz[j]), J.pt_xyz, sizeof(double) * 3 * (size_t)J.n_pts);
       any_staged = true;
     }
-    D.xyz = (const double *)(d_in + P.in_xyz[j]), D.pt_kf = (const int *)(d_in + P.in_ptkf[j]);
-    D.ids = (const int *)(d_in + P.in_ids[j]), D.n_ids = J.n_kf;
-    D.grid_y = (unsigned long long *)(d_work + w_gy[j]), D.grid_idx = (int *)(d_work + w_gi[j]), D.block_count = (int *)(d_work + w_bc[j]);
-    D.moments = (double *)(d_work + w_mom[j]), D.bins = (unsigned long long *)(d_work + w_bins[j]);
-    D.sel_idx = (int *)(J.sel_idx ? d_out + P.out_sel[j] : d_work + w_sel[j]);
-    D.sph = (double *)(J.sel_idx ? d_out + P.out_sph[j] : d_work + w_sph[j]);
-    D.n_out = (int *)(d_out + P.out_small[j]);
+    D.xyz = A.dev_in<const double>(P.in_xyz[j]), D.pt_kf = A.dev_in<const int>(P.in_ptkf[j]);
+    D.ids = A.dev_in<const int>(P.in_ids[j]), D.n_ids = J.n_kf;
+    D.grid_y = A.dev_work<unsigned long long>(w_gy[j]), D.grid_idx = A.dev_work<int>(w_gi[j]), D.block_count = A.dev_work<int>(w_bc[j]);
+    D.moments = A.dev_work<double>(w_mom[j]), D.bins = A.dev_work<unsigned long long>(w_bins[j]);
+    D.sel_idx = J.sel_idx ? A.dev_out<int>(P.out_sel[j]) : A.dev_work<int>(w_sel[j]);
+    D.sph = J.sel_idx ? A.dev_out<double>(P.out_sph[j]) : A.dev_work<double>(w_sph[j]);
+    D.n_out = A.dev_out<int>(P.out_small[j]);
     D.n_sig = D.n_out + 1;
-    D.tfm_out = (double *)(d_out + P.out_small[j] + 16);
-    D.ringkey = J.ringkey ? (float *)(d_out + P.out_keys) + (size_t)j * num_r : nullptr;
-    D.sig_idx = (int *)(d_out + P.out_sig_idx[j]), D.sig_val = (double *)(d_out + P.out_sig_val[j]);
+    D.tfm_out = A.dev_out<double>(P.out_small[j] + 16);
+    D.ringkey = J.ringkey ? A.dev_out<float>(P.out_keys) + (size_t)j * num_r : nullptr;
+    D.sig_idx = A.dev_out<int>(P.out_sig_idx[j]), D.sig_val = A.dev_out<double>(P.out_sig_val[j]);
   }
-  memcpy(h_in + P.in_tab, P.hj.data(), sizeof(JobDev) * (size_t)n_jobs);
-  if (X.fill) X.fill(h_in + P.in_extra);
-  DSM_HIP(hipMemcpyAsync(d_in, h_in, any_staged ? P.in_bytes : in_small_bytes, hipMemcpyHostToDevice, st));
-  JobDev *dj = (JobDev *)(d_in + P.in_tab);
+  memcpy(A.host_in<JobDev>(P.in_tab), P.hj.data(), sizeof(JobDev) * (size_t)n_jobs);
+  if (X.fill) X.fill(A.host_in<unsigned char>(P.in_extra));
+  if ((rc = A.upload(any_staged ? in.used : in_small_bytes))) return rc;
+  JobDev *dj = A.dev_in<JobDev>(P.in_tab);
   if (any_direct) hipLaunchKernelGGL(loop_gather_kernel, dim3(64, n_jobs), dim3(kLdThreads), 0, st, dj);
   // a job without a descriptor leaves its key slot untouched: zero the key array so that the search sees defined values
-  DSM_HIP(hipMemsetAsync(d_out + P.out_keys, 0, sizeof(float) * (size_t)num_r * n_jobs, st));
+  DSM_HIP(hipMemsetAsync(A.dev_out<float>(P.out_keys), 0, sizeof(float) * (size_t)num_r * n_jobs, st));
   // ---- generate_spherical_points: all jobs side by side (blockIdx.y = job)
   const int gx_cells = (int)std::min<long long>(P.nblocks, 4096), gx_pts = std::min((max_pts + kLdThreads - 1) / kLdThreads, 1024);
   hipLaunchKernelGGL(voxel_clear_kernel, dim3(gx_cells, n_jobs), dim3(kLdThreads), 0, st, dj, cells);
@@ -554,41 +512,39 @@ int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double 
     hipLaunchKernelGGL(sc_finish_kernel, dim3(n_jobs), dim3(kLdThreads), sizeof(double) * num_s, st, dj, lidar_range, num_s, num_r);
   }
   DSM_HIP(hipGetLastError());
-  if (d_keys) *d_keys = (float *)(d_out + P.out_keys);
-  X.d_in = d_in + P.in_extra, X.d_work = d_work + w_extra, X.d_out = d_out + P.out_cand;
+  if (d_keys) *d_keys = A.dev_out<float>(P.out_keys);
+  X.d_in = A.dev_in<unsigned char>(P.in_extra), X.d_work = A.dev_work<unsigned char>(w_extra), X.d_out = A.dev_out<unsigned char>(P.out_cand);
   return DSM_OK;
 }
 
 // the ONE read-back and the scatter into the caller's arrays; h_extra: where the caller's own results arrived
-int loop_finish(dsm_context *ctx, const dsm_loop_job *jobs, const LoopPlan &P, const void **h_extra) {
-  hipStream_t st = ctx->stream;
-  unsigned char *d_out = (unsigned char *)ctx->loop_dev + P.in_bytes + P.work_bytes;
-  unsigned char *h_out = (unsigned char *)ctx->loop_pin + P.in_bytes;
-  DSM_HIP(hipMemcpyAsync(h_out, d_out, P.out_bytes, hipMemcpyDeviceToHost, st));
-  DSM_HIP(hipStreamSynchronize(st));
-  if (h_extra) *h_extra = h_out + P.out_cand;
+int loop_finish(const dsm_loop_job *jobs, const LoopPlan &P, const void **h_extra) {
+  const CallArena &A = P.A;
+  const int rc = A.fetch(A.out.used);
+  if (rc) return rc;
+  if (h_extra) *h_extra = A.host_out<void>(P.out_cand);
   // A job that asks for a descriptor and whose cloud came out empty fails the WHOLE call before anything is written to the caller's
   // arrays (and, in dsm_loop_detect_batch, before any key is enqueued): a batch is all or nothing, unlike the sequential calls it
   // otherwise equals, which would have failed at that keyframe with the earlier ones already through
   for (int j = 0; j < P.n_jobs; j++)
-    if (jobs[j].ringkey && ((const int *)(h_out + P.out_small[j]))[0] < 1)
+    if (jobs[j].ringkey && A.host_out<int>(P.out_small[j])[0] < 1)
       return invalid("dsm_loop_descriptors_batch: ScanContext of an empty point set (no output of the call was written)");
   for (int j = 0; j < P.n_jobs; j++) {
     const dsm_loop_job &J = jobs[j];
-    const int *small = (const int *)(h_out + P.out_small[j]);
+    const int *small = A.host_out<int>(P.out_small[j]);
     const int n_out = small[0], n_sig = small[1];
     *J.n_out = n_out;
     if (J.sel_idx && n_out > 0) {
-      memcpy(J.sel_idx, h_out + P.out_sel[j], sizeof(int) * (size_t)n_out);
-      memcpy(J.pts_spherical, h_out + P.out_sph[j], sizeof(double) * 3 * (size_t)n_out);
+      memcpy(J.sel_idx, A.host_out<int>(P.out_sel[j]), sizeof(int) * (size_t)n_out);
+      memcpy(J.pts_spherical, A.host_out<double>(P.out_sph[j]), sizeof(double) * 3 * (size_t)n_out);
     }
     if (!J.ringkey) continue;
-    memcpy(J.tfm_pca_rig, h_out + P.out_small[j] + 16, sizeof(double) * 16);
+    memcpy(J.tfm_pca_rig, A.host_out<double>(P.out_small[j] + 16), sizeof(double) * 16);
     *J.n_sig = n_sig;
-    memcpy(J.ringkey, (const float *)(h_out + P.out_keys) + (size_t)j * P.num_r, sizeof(float) * (size_t)P.num_r);
+    memcpy(J.ringkey, A.host_out<float>(P.out_keys) + (size_t)j * P.num_r, sizeof(float) * (size_t)P.num_r);
     if (n_sig > 0) {
-      memcpy(J.sig_idx, h_out + P.out_sig_idx[j], sizeof(int) * (size_t)n_sig);
-      memcpy(J.sig_val, h_out + P.out_sig_val[j], sizeof(double) * (size_t)n_sig);
+      memcpy(J.sig_idx, A.host_out<int>(P.out_sig_idx[j]), sizeof(int) * (size_t)n_sig);
+      memcpy(J.sig_val, A.host_out<double>(P.out_sig_val[j]), sizeof(double) * (size_t)n_sig);
     }
   }
   return DSM_OK;
@@ -603,7 +559,7 @@ int dsm_loop_descriptors_batch(dsm_context *ctx, int n_jobs, const dsm_loop_job 
   LoopExtra X;
   int rc = loop_enqueue(ctx, n_jobs, jobs, lidar_range, num_s, num_r, X, P, nullptr);
   if (rc) return rc;
-  return loop_finish(ctx, jobs, P, nullptr);
+  return loop_finish(jobs, P, nullptr);
 }
 
 // The per-keyframe loop chain of LoopHandler (LoopHandler.cpp:186 generate_spherical_points, :236 ScanContext::generate, :247
@@ -634,7 +590,7 @@ int dsm_loop_detect_batch(dsm_context *ctx, dsm_ringdb *db, int n_jobs, const ds
   const bool search = db->size_global > k; // `ringkeys->size() > FLANN_NN`, search_place.h:29 (the index as it stands before the batch)
   if (search && (rc = dsm::ringdb_knn_device(db, d_keys, n_jobs, (unsigned long long *)X.d_out))) return rc;
   const void *h_cand_v = nullptr;
-  rc = loop_finish(ctx, jobs, P, &h_cand_v);
+  rc = loop_finish(jobs, P, &h_cand_v);
   if (rc) return rc;
   const unsigned long long *h_cand = (const unsigned long long *)h_cand_v;
   if (!search) {
@@ -687,7 +643,7 @@ int dsm_loop_detect_batch_many(dsm_context *ctx, int n_jobs, const dsm_loop_job 
   if (rc) return rc;
   const void *h_cand = nullptr;
   // (an empty filtered cloud fails here, before any output or index changes: the inserted planes lie beyond every index's size)
-  rc = loop_finish(ctx, jobs, P, &h_cand);
+  rc = loop_finish(jobs, P, &h_cand);
   if (rc) return rc;
   std::vector<const float *> keys(n_jobs);
   for (int j = 0; j < n_jobs; j++) keys[j] = jobs[j].ringkey;

@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "dsm_internal.hpp"
+#include "call_arena.hpp"
 #include <string>
 
 #include "ringdb_internal.hpp"
@@ -151,8 +151,6 @@ void ringdb_queue_push(dsm_ringdb *db, const float *key, std::vector<float> *mat
   db->queue_idx++;
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int ringdb_many_prepare(dsm_context *ctx, int n, dsm_ringdb *const *dbs, int dim, const char *who, RingManyPlan &P) {
   const std::string w(who);
   if (n < 1 || !dbs) return invalid((w + ": bad argument").c_str());
@@ -229,8 +227,10 @@ int ringdb_many_prepare(dsm_context *ctx, int n, dsm_ringdb *const *dbs, int dim
     if (D.n_slices > P.n_slices) P.n_slices = D.n_slices;
     if (db->cap % 4) P.four = false; // rdb_reserve keeps capacities at 1024 * 2^m: checked, not assumed
   }
-  P.off_ins = align256(sizeof(RingKeyScanDesc) * (size_t)n);
-  P.off_keys = P.off_ins + align256(sizeof(RingKeyInsertDesc) * (size_t)P.n_matured);
+  CallArena::Region staged;
+  staged.take(sizeof(RingKeyScanDesc) * (size_t)n);
+  P.off_ins = staged.take(sizeof(RingKeyInsertDesc) * (size_t)P.n_matured);
+  P.off_keys = staged.used;
   P.staged_bytes = P.off_keys + sizeof(float) * P.matured.size();
   return DSM_OK;
 }
@@ -452,25 +452,22 @@ int dsm_ringdb_query_then_enqueue_many(int n, dsm_ringdb *const *dbs, const floa
   int rc = ringdb_many_prepare(nullptr, n, dbs, -1, "dsm_ringdb_query_then_enqueue_many", P);
   if (rc) return rc;
   dsm_context *ctx = P.uniq[0]->ctx;
-  hipStream_t st = ctx->stream;
-  // the context's loop-chain arena: device [queries | staged | scratch | candidates], page-locked mirror [queries | staged | candidates]
-  const size_t q_bytes = align256(sizeof(float) * (size_t)n * P.dim), in_bytes = q_bytes + align256(P.staged_bytes);
-  const size_t sc_bytes = align256(sizeof(unsigned long long) * ringdb_many_scratch_words(P)), pk_bytes = sizeof(unsigned long long) * (size_t)n * P.k;
-  rc = loop_arena_grow(ctx, in_bytes + sc_bytes + pk_bytes, in_bytes + pk_bytes);
+  // device [queries | staged | scratch | candidates], page-locked mirror [queries | staged | candidates]
+  CallArena A;
+  const size_t o_q = A.in.take(sizeof(float) * (size_t)n * P.dim), o_staged = A.in.take(P.staged_bytes);
+  const size_t o_scratch = A.work.take(sizeof(unsigned long long) * ringdb_many_scratch_words(P));
+  const size_t pk_bytes = sizeof(unsigned long long) * (size_t)n * P.k, o_packed = A.out.take(pk_bytes);
+  if ((rc = A.bind(ctx))) return rc;
+  memcpy(A.host_in<float>(o_q), keys, sizeof(float) * (size_t)n * P.dim);
+  ringdb_many_stage(P, A.host_in<unsigned char>(o_staged));
+  if ((rc = A.upload())) return rc;
+  rc = ringdb_many_launch(ctx->stream, P, A.dev_in<unsigned char>(o_staged), A.dev_in<float>(o_q), A.dev_work<unsigned long long>(o_scratch),
+                          A.dev_out<unsigned long long>(o_packed));
   if (rc) return rc;
-  unsigned char *d_in = (unsigned char *)ctx->loop_dev, *h_in = (unsigned char *)ctx->loop_pin;
-  unsigned long long *d_scratch = (unsigned long long *)(d_in + in_bytes), *d_packed = (unsigned long long *)(d_in + in_bytes + sc_bytes);
-  const unsigned long long *h_packed = (const unsigned long long *)(h_in + in_bytes);
-  memcpy(h_in, keys, sizeof(float) * (size_t)n * P.dim);
-  ringdb_many_stage(P, h_in + q_bytes);
-  DSM_HIP(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, st));
-  rc = ringdb_many_launch(st, P, d_in + q_bytes, (const float *)d_in, d_scratch, d_packed);
-  if (rc) return rc;
-  DSM_HIP(hipMemcpyAsync((void *)h_packed, d_packed, pk_bytes, hipMemcpyDeviceToHost, st));
-  DSM_HIP(hipStreamSynchronize(st));
+  if ((rc = A.fetch(pk_bytes))) return rc;
   std::vector<const float *> kp(n);
   for (int j = 0; j < n; j++) kp[j] = keys + (size_t)j * P.dim;
-  ringdb_many_finish(P, dbs, kp.data(), h_packed, cand_out, ncand_out);
+  ringdb_many_finish(P, dbs, kp.data(), A.host_out<unsigned long long>(o_packed), cand_out, ncand_out);
   return DSM_OK;
 }
 

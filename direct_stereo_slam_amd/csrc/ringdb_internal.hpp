@@ -86,6 +86,4 @@ int ringdb_finish_query(const dsm_ringdb *db, const float *key, const unsigned l
 // the delay-queue half of search_ringkey on the host copy of the queue (search_place.h:41-56): the key that leaves the queue is
 // appended to `matured` (not to the index)
 void ringdb_queue_push(dsm_ringdb *db, const float *key, std::vector<float> *matured);
-// dsm_loop_descriptors_batch's device arena and page-locked mirror in the context (loopdet_kernels.hip), grown on demand
-int loop_arena_grow(dsm_context *ctx, size_t dev_bytes, size_t pin_bytes);
 } // namespace dsm

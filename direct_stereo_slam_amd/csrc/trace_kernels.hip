@@ -16,8 +16,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "dsm_internal.hpp"
-#include "ringdb_internal.hpp"
+#include "call_arena.hpp"
 #include "trace_math.hpp"
 
 using namespace dsm;
@@ -38,8 +37,6 @@ struct TrJob {
       off_interval; // 4-byte words into the staged inputs
   int out_off;      // first point of the job in the output
 };
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // lanes of one wave only: what the lanes of a point wrote to LDS is read by the other lanes of the same point
 __device__ __forceinline__ void wave_lds_sync() {
@@ -216,16 +213,13 @@ extern "C" int dsm_trace_points_batch(dsm_context *ctx, int n_jobs, const dsm_tr
   int rc = check_jobs(ctx, n_jobs, jobs, params, &w, &h, &pts, &words);
   if (rc) return rc;
   if (pts) {
-    // arena (dsm::loop_arena_grow): staged [job table | krki, kt, aff, then the point arrays of every job], read back [kOutWords per point]
-    const size_t b_jobs = align256(sizeof(TrJob) * n_jobs);
-    const size_t in_bytes = b_jobs + align256(4 * words), out_bytes = align256(4 * kOutWords * pts);
-    DSM_HIP(hipSetDevice(ctx->device));
-    rc = loop_arena_grow(ctx, in_bytes + out_bytes, in_bytes + out_bytes);
-    if (rc) return rc;
-    unsigned char *d = (unsigned char *)ctx->loop_dev, *hp = (unsigned char *)ctx->loop_pin;
-    TrJob *hj = (TrJob *)hp;
-    float *hs = (float *)(hp + b_jobs);
-    size_t o = 0, op = 0;
+    // staged [job table | krki, kt, aff, then the point arrays of every job], read back [kOutWords per point]
+    CallArena A;
+    const size_t o_jobs = A.in.take(sizeof(TrJob) * n_jobs), o_stage = A.in.take(4 * words), o_out = A.out.take(4 * kOutWords * pts);
+    if ((rc = A.bind(ctx))) return rc;
+    TrJob *hj = A.host_in<TrJob>(o_jobs);
+    WordPacker W{A.host_in<float>(o_stage)};
+    size_t op = 0;
     int max_pts = 0;
     for (int j = 0; j < n_jobs; j++) {
       const dsm_trace_job &J = jobs[j];
@@ -233,43 +227,32 @@ extern "C" int dsm_trace_points_batch(dsm_context *ctx, int n_jobs, const dsm_tr
       TrJob &D = hj[j];
       memset(&D, 0, sizeof D);
       D.plane = target_plane(J), D.n_hosts = J.n_hosts, D.n_pts = J.n_pts, D.out_off = (int)op;
-      auto put = [&](int *off, const void *a, size_t na) {
-        *off = (int)o;
-        if (na) memcpy(hs + o, a, 4 * na);
-        o += na;
-      };
-      put(&D.off_R, J.krki, 9 * nh);
-      put(&D.off_t, J.kt, 3 * nh);
-      put(&D.off_aff, J.aff, 2 * nh);
-      put(&D.off_host, J.host, n);
-      put(&D.off_u, J.u, n);
-      put(&D.off_v, J.v, n);
-      put(&D.off_eth, J.energy_th, n);
-      put(&D.off_G, J.grad_h, 4 * n);
-      put(&D.off_color, J.color, 8 * n);
-      put(&D.off_wt, J.weights, 8 * n);
-      D.off_status = (int)o;
-      for (size_t i = 0; i < n; i++) ((int *)hs)[o + i] = J.status[i];
-      o += n;
-      put(&D.off_idmin, J.idepth_min, n);
-      put(&D.off_idmax, J.idepth_max, n);
-      put(&D.off_quality, J.quality, n);
-      put(&D.off_uv, J.trace_uv, 2 * n);
-      put(&D.off_interval, J.trace_interval, n);
+      W.put(&D.off_R, J.krki, 9 * nh);
+      W.put(&D.off_t, J.kt, 3 * nh);
+      W.put(&D.off_aff, J.aff, 2 * nh);
+      W.put(&D.off_host, J.host, n);
+      W.put(&D.off_u, J.u, n);
+      W.put(&D.off_v, J.v, n);
+      W.put(&D.off_eth, J.energy_th, n);
+      W.put(&D.off_G, J.grad_h, 4 * n);
+      W.put(&D.off_color, J.color, 8 * n);
+      W.put(&D.off_wt, J.weights, 8 * n);
+      int *status = (int *)W.reserve(&D.off_status, n);
+      for (size_t i = 0; i < n; i++) status[i] = J.status[i];
+      W.put(&D.off_idmin, J.idepth_min, n);
+      W.put(&D.off_idmax, J.idepth_max, n);
+      W.put(&D.off_quality, J.quality, n);
+      W.put(&D.off_uv, J.trace_uv, 2 * n);
+      W.put(&D.off_interval, J.trace_interval, n);
       op += n;
       max_pts = std::max(max_pts, J.n_pts);
     }
-    const TrJob *dj = (const TrJob *)d;
-    const float *d_stage = (const float *)(d + b_jobs);
-    unsigned *d_out = (unsigned *)(d + in_bytes);
-    hipStream_t st = ctx->stream;
-    DSM_HIP(hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(trace_kernel, dim3((max_pts + kPointsPerBlock - 1) / kPointsPerBlock, n_jobs), dim3(64 * kWavesPerBlock), 0, st, dj, d_stage,
-                       d_out, w, h, *params);
+    if ((rc = A.upload())) return rc;
+    hipLaunchKernelGGL(trace_kernel, dim3((max_pts + kPointsPerBlock - 1) / kPointsPerBlock, n_jobs), dim3(64 * kWavesPerBlock), 0, ctx->stream,
+                       A.dev_in<const TrJob>(o_jobs), A.dev_in<const float>(o_stage), A.dev_out<unsigned>(o_out), w, h, *params);
     DSM_HIP(hipGetLastError());
-    DSM_HIP(hipMemcpyAsync(hp + in_bytes, d_out, 4 * kOutWords * pts, hipMemcpyDeviceToHost, st));
-    DSM_HIP(hipStreamSynchronize(st));
-    const unsigned *ho = (const unsigned *)(hp + in_bytes);
+    if ((rc = A.fetch(4 * kOutWords * pts))) return rc;
+    const unsigned *ho = A.host_out<unsigned>(o_out);
     for (int j = 0; j < n_jobs; j++) {
       const dsm_trace_job &J = jobs[j];
       for (int i = 0; i < J.n_pts; i++) {
