@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "call_arena.hpp"
+#include "point_math.hpp"
 
 using namespace dsm;
 
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void distmap_fill_kernel(const DmJob *job
   *reinterpret_cast<uint4 *>(jobs[blockIdx.y].map + o) = make_uint4(~0u, ~0u, ~0u, ~0u);
 }
 
-// D2 / D6: ptp = KRKi (u, v, 1) + Kt idepth, each component ((m0 u + m1 v) + m2) + kt idepth (-ffp-contract=off)
+// D2 / D6: ptp = KRKi (u, v, 1) + Kt idepth (point_math.hpp, shared with the host form)
 __global__ __launch_bounds__(kThreads) void distmap_project_kernel(const DmJob *jobs, const float *stage, int *cell, float *frac, float *thr,
                                                                    int w1, int h1, int with_cand) {
   const DmJob J = jobs[blockIdx.y];
@@ -66,10 +67,8 @@ __global__ __launch_bounds__(kThreads) void distmap_project_kernel(const DmJob *
   const int hst = reinterpret_cast<const int *>(stage)[J.off_host + i];
   const float *M = stage + J.off_krki + 9 * hst, *T = stage + J.off_kt + 3 * hst;
   const float u = stage[J.off_u + i], v = stage[J.off_v + i], id = stage[J.off_id + i];
-  const float p0 = ((M[0] * u + M[1] * v) + M[2]) + T[0] * id;
-  const float p1 = ((M[3] * u + M[4] * v) + M[5]) + T[1] * id;
-  const float p2 = ((M[6] * u + M[7] * v) + M[8]) + T[2] * id;
-  const float qu = p0 / p2 + 0.5f, qv = p1 / p2 + 0.5f;
+  const pt::Vec3 p = pt::add_translation(pt::rotate_uv1(M, u, v), T, id);
+  const float qu = p.x / p.z + 0.5f, qv = p.y / p.z + 0.5f;
   const bool ok = qu >= 1.0f && qv >= 1.0f && qu < (float)w1 && qv < (float)h1; // NaN and +-inf fail
   const int c = ok ? (int)qu + w1 * (int)qv : -1;
   if (i < J.n_seeds) {
@@ -77,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void distmap_project_kernel(const DmJob *
   } else {
     const int o = J.out_off + (i - J.n_seeds);
     cell[o] = c;
-    frac[o] = p0 - floorf(p0);                                // FrontEnd.cpp:440: the unnormalised ptp[0]
+    frac[o] = p.x - floorf(p.x);                              // FrontEnd.cpp:440: the unnormalised ptp[0]
     thr[o] = J.min_act * stage[J.off_type + (i - J.n_seeds)]; // :442
   }
 }
@@ -215,27 +214,23 @@ __global__ __launch_bounds__(64) void distmap_add_kernel(unsigned char *map, int
 // all-or-nothing validation of a batch: nothing is enqueued before every job has passed
 int check_jobs(dsm_context *ctx, int n_jobs, const dsm_activation_job *jobs, bool with_cand, size_t *items_out,
                size_t *cands_out) {
-  if (!ctx || n_jobs < 1 || !jobs) return invalid("dsm_activate_points_batch / dsm_distmaps_make: bad argument");
+  auto bad = [with_cand](const char *msg) {
+    return invalid((std::string(with_cand ? "dsm_activate_points_batch: " : "dsm_distmaps_make: ") + msg).c_str());
+  };
+  if (!ctx || n_jobs < 1 || !jobs) return bad("bad argument");
   size_t items = 0, cands = 0;
   std::vector<const dsm_distmap *> seen;
   for (int j = 0; j < n_jobs; j++) {
     const dsm_activation_job &J = jobs[j];
     const int nc = with_cand ? J.n_cand : 0;
-    if (!J.map || J.map->ctx != ctx) return invalid("distance map job: no map, or a map of another context");
-    if (J.map->w != jobs[0].map->w || J.map->h != jobs[0].map->h) return invalid("distance map jobs: one geometry per call");
-    if (std::find(seen.begin(), seen.end(), J.map) != seen.end()) return invalid("distance map jobs: a map may appear in one job only");
+    if (!J.map || J.map->ctx != ctx) return bad("no map, or a map of another context");
+    if (J.map->w != jobs[0].map->w || J.map->h != jobs[0].map->h) return bad("one geometry per call");
+    if (std::find(seen.begin(), seen.end(), J.map) != seen.end()) return bad("a map may appear in one job only");
     seen.push_back(J.map);
-    if (J.n_hosts < 0 || J.n_seeds < 0 || nc < 0 || (J.n_hosts && (!J.krki || !J.kt)) ||
-        (J.n_seeds && (!J.seed_host || !J.seed_u || !J.seed_v || !J.seed_idepth)) ||
-        (nc && (!J.cand_host || !J.cand_u || !J.cand_v || !J.cand_idepth || !J.cand_type || !J.decision_out)))
-      return invalid("distance map job: negative count or NULL array");
-    for (int i = 0; i < J.n_seeds; i++)
-      if (J.seed_host[i] < 0 || J.seed_host[i] >= J.n_hosts) return invalid("distance map job: seed_host outside [0, n_hosts)");
-    for (int i = 0; i < nc; i++)
-      if (J.cand_host[i] < 0 || J.cand_host[i] >= J.n_hosts) return invalid("distance map job: cand_host outside [0, n_hosts)");
+    if (const char *e = activation_job_error(J, with_cand)) return bad(e);
     items += (size_t)J.n_seeds + nc + 12 * (size_t)J.n_hosts, cands += nc;
   }
-  if (items > kMaxItems) return invalid("distance map jobs: too many points in one call");
+  if (items > kMaxItems) return bad("too many points in one call");
   *items_out = items, *cands_out = cands;
   return DSM_OK;
 }

@@ -144,7 +144,10 @@ struct dsm_window {
 
 namespace dsm {
 int invalid(const char *msg); // set_error + DSM_ERR_INVALID
-// host_capi.cpp: what dsm_trace_points_batch and dsm_trace_points_host refuse in the settings / in the arrays of a job (NULL: nothing)
+// points_host.cpp: what both forms of a point call (dsm_*_batch and dsm_*_host) refuse in the settings / in the arrays of a job (NULL: nothing)
+const char *activation_job_error(const dsm_activation_job &J, bool with_cand);
+const char *immature_settings_error(float huber_th, float min_idepth_h_act, int gn_iterations);
+const char *immature_job_error(const dsm_immature_job &J);
 const char *trace_params_error(const dsm_trace_params *p);
 const char *trace_job_error(const dsm_trace_job &J);
 int ensure_batch_capacity(dsm_context *ctx, int nprob, int partial_stride);

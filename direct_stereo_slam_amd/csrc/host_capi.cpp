@@ -1,12 +1,16 @@
 // host_capi.cpp -- the pieces of the path that SURVEY.md section 8a keeps on the host by design:
 // search_sc (<= 3 candidates per query, src/loop_closure/loop_detection/search_place.h:59-84) and the replay of the hypothesis
-// loop of FrontEnd::trackNewCoarse (dsm_hypotheses_resolve).
+// loop of FrontEnd::trackNewCoarse (dsm_hypotheses_resolve).  (The host forms of the three point calls: points_host.cpp.)
 // Plain C++; no device code.
 #include "../../include/dsm_hotpath.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
+#include <vector>
+
+#include "loopdet_internal.hpp"
 
 extern "C" {
 
@@ -114,15 +118,6 @@ int dsm_hypotheses_resolve(int n_tries, const double *tries, const double aff_la
 // ---------------------------------------------------------------------------------------------
 // ScanContext::generate, ScanContext.cpp:78-141 (+ align_points_PCA :19-66)
 // ---------------------------------------------------------------------------------------------
-#include <cmath>
-#include <cstring>
-#include <vector>
-
-#include "loopdet_internal.hpp"
-
-namespace dsm {
-
-} // namespace dsm
 using dsm::eig3_sym;
 
 extern "C" {
@@ -415,8 +410,6 @@ int dsm_make_coarse_depth_l0(int w0, int h0, int nl, int npts, const float *pu, 
 // UPSTREAM-DSO Undistort (src/util/Undistort.cpp): readFromFile's remap for the Pinhole model, makeOptimalK_crop and
 // UndistortPinhole::distortCoordinates.  Quirks U1-U7: DESIGN.md section 9.
 // ---------------------------------------------------------------------------------------------
-#include <string>
-
 namespace dsm {
 void set_error(const std::string &msg);
 }
@@ -561,348 +554,3 @@ int dsm_pinhole_undistort_map(const double calib[4], int w_in, int h_in, int out
 }
 
 } // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// CoarseDistanceMap + the activation walk of FrontEnd::activatePointsMT as the reference runs them: one sequential loop, the list
-// BFS of growDistBFS (TrackerAndScaler.cpp:1235-1324) on a float map.  D1-D6: DESIGN.md section 12.
-// ---------------------------------------------------------------------------------------------
-namespace {
-struct HostDistMap {
-  int w1, h1;
-  std::vector<float> map;
-  std::vector<int> l1, l2; // bfs_list1_ / bfs_list2_ as cell indices
-  // growDistBFS (:1235-1324): the list in l1 holds bfs_num cells
-  void grow(int bfs_num) {
-    static const int DX[8] = {1, -1, 0, 0, 1, -1, -1, 1}, DY[8] = {0, 0, 1, -1, 1, 1, -1, -1};
-    for (int k = 1; k < 40 && bfs_num > 0; k++) { // (an empty list stays empty: the remaining levels do nothing)
-      const int bfs_num2 = bfs_num;
-      std::swap(l1, l2);
-      bfs_num = 0;
-      const int nd = (k % 2 == 0) ? 4 : 8;
-      for (int i = 0; i < bfs_num2; i++) {
-        const int x = l2[i] % w1, y = l2[i] / w1;
-        if (x == 0 || y == 0 || x == w1 - 1 || y == h1 - 1) continue;
-        for (int d = 0; d < nd; d++) {
-          const int idx = (x + DX[d]) + (y + DY[d]) * w1;
-          if (map[idx] > k) {
-            map[idx] = (float)k;
-            if ((size_t)bfs_num == l1.size()) l1.push_back(idx); else l1[bfs_num] = idx;
-            bfs_num++;
-          }
-        }
-      }
-    }
-  }
-  void push_first(int idx, int at) {
-    if ((size_t)at == l1.size()) l1.push_back(idx); else l1[at] = idx;
-  }
-};
-
-// ptp = KRKi (u, v, 1) + Kt idepth (:1218, FrontEnd.cpp:432-433), then the bounds test; returns the cell or -1
-inline int project_l1(const float *M, const float *T, float u, float v, float id, int w1, int h1, float *p0_out) {
-  const float p0 = ((M[0] * u + M[1] * v) + M[2]) + T[0] * id;
-  const float p1 = ((M[3] * u + M[4] * v) + M[5]) + T[1] * id;
-  const float p2 = ((M[6] * u + M[7] * v) + M[8]) + T[2] * id;
-  const float qu = p0 / p2 + 0.5f, qv = p1 / p2 + 0.5f;
-  *p0_out = p0;
-  if (!(qu >= 1.0f && qv >= 1.0f && qu < (float)w1 && qv < (float)h1)) return -1;
-  return (int)qu + w1 * (int)qv;
-}
-} // namespace
-
-extern "C" int dsm_activate_points_host(int w, int h, const dsm_activation_job *job, float *map_out) {
-  auto fail = [](const char *msg) {
-    dsm::set_error(msg);
-    return (int)DSM_ERR_INVALID;
-  };
-  if (w < 2 || h < 2 || !job) return fail("dsm_activate_points_host: bad argument");
-  const dsm_activation_job &J = *job;
-  if (J.n_hosts < 0 || J.n_seeds < 0 || J.n_cand < 0 || (J.n_hosts && (!J.krki || !J.kt)) ||
-      (J.n_seeds && (!J.seed_host || !J.seed_u || !J.seed_v || !J.seed_idepth)) ||
-      (J.n_cand && (!J.cand_host || !J.cand_u || !J.cand_v || !J.cand_idepth || !J.cand_type || !J.decision_out)))
-    return fail("dsm_activate_points_host: negative count or NULL array");
-  for (int i = 0; i < J.n_seeds; i++)
-    if (J.seed_host[i] < 0 || J.seed_host[i] >= J.n_hosts) return fail("dsm_activate_points_host: seed_host outside [0, n_hosts)");
-  for (int i = 0; i < J.n_cand; i++)
-    if (J.cand_host[i] < 0 || J.cand_host[i] >= J.n_hosts) return fail("dsm_activate_points_host: cand_host outside [0, n_hosts)");
-  HostDistMap D;
-  D.w1 = w >> 1, D.h1 = h >> 1;
-  D.map.assign((size_t)D.w1 * D.h1, 1000.0f); // :1202-1203
-  int num_items = 0;
-  float p0;
-  for (int i = 0; i < J.n_seeds; i++) { // :1216-1226
-    const int hst = J.seed_host[i];
-    const int c = project_l1(J.krki + 9 * hst, J.kt + 3 * hst, J.seed_u[i], J.seed_v[i], J.seed_idepth[i], D.w1, D.h1, &p0);
-    if (c < 0) continue;
-    D.map[c] = 0;
-    D.push_first(c, num_items++);
-  }
-  D.grow(num_items);
-  int n_act = 0;
-  for (int i = 0; i < J.n_cand; i++) { // FrontEnd.cpp:431-449
-    const int hst = J.cand_host[i];
-    const int c = project_l1(J.krki + 9 * hst, J.kt + 3 * hst, J.cand_u[i], J.cand_v[i], J.cand_idepth[i], D.w1, D.h1, &p0);
-    if (c < 0) {
-      J.decision_out[i] = 2;
-      continue;
-    }
-    const float dist = D.map[c] + (p0 - floorf(p0));
-    if (dist >= J.min_act_dist * J.cand_type[i]) {
-      D.map[c] = 0; // addIntoDistFinal (:1326-1332)
-      D.push_first(c, 0);
-      D.grow(1);
-      J.decision_out[i] = 1;
-      n_act++;
-    } else {
-      J.decision_out[i] = 0;
-    }
-  }
-  if (J.n_activated_out) *J.n_activated_out = n_act;
-  if (map_out) memcpy(map_out, D.map.data(), sizeof(float) * D.map.size());
-  return DSM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// FrontEnd::optimizeImmaturePoint (dso_helpers/FrontEndOptPoint.cpp:35-138) as the reference runs it: one sequential loop over the
-// points of a window, ImmaturePoint::linearizeResidual per residual with the accumulators passed by reference.  M1-M8, U1-U9:
-// DESIGN.md section 13.  The pattern pixel itself is imm::tap (immature_math.hpp), shared with the device kernel.
-// ---------------------------------------------------------------------------------------------
-#include "immature_math.hpp"
-
-namespace {
-struct ImmTmpRes { // ImmaturePointTemporaryResidual
-  int state_state, state_NewState;
-  float state_energy, state_NewEnergy;
-  int target;
-};
-
-struct ImmPoint {
-  const dsm_immature_job *J;
-  dsm::imm::Cam C;
-  const float *const *frame_I;
-  int i; // the point
-  float huber;
-  // ImmaturePoint::linearizeResidual (UPSTREAM-DSO), U1-U9
-  float linearize(float slack, ImmTmpRes &res, float &Hdd, float &bd, float idepth) const {
-    using namespace dsm::imm;
-    if (res.state_state == RES_OOB) { // U1
-      res.state_NewState = RES_OOB;
-      return res.state_energy;
-    }
-    const int nf = J->n_frames, pair = J->host[i] * nf + res.target;
-    float energyLeft = 0;
-    for (int idx = 0; idx < 8; idx++) {
-      int dx, dy;
-      pattern(idx, dx, dy);
-      float tE, tH, tb;
-      if (!tap(C, frame_I[res.target], J->pre_R + 9 * pair, J->pre_t + 3 * pair, J->pre_aff + 2 * pair, J->u[i], J->v[i], dx, dy, idepth,
-               J->color[8 * i + idx], J->weights[8 * i + idx], huber, tE, tH, tb)) { // U4 / U6: the earlier pixels' terms stay in Hdd / bd
-        res.state_NewState = RES_OOB;
-        return res.state_energy;
-      }
-      energyLeft += tE;
-      Hdd += tH;
-      bd += tb;
-    }
-    const float lim = J->energy_th[i] * slack; // U9
-    if (energyLeft > lim) {
-      energyLeft = lim;
-      res.state_NewState = RES_OUTLIER;
-    } else {
-      res.state_NewState = RES_IN;
-    }
-    res.state_NewEnergy = energyLeft;
-    return energyLeft;
-  }
-};
-} // namespace
-
-extern "C" int dsm_optimize_immature_points_host(int w, int h, const dsm_immature_job *job, const float *const *frame_I, float huber_th,
-                                                 float min_idepth_h_act, int gn_iterations) {
-  using namespace dsm::imm;
-  auto fail = [](const char *msg) {
-    dsm::set_error(msg);
-    return (int)DSM_ERR_INVALID;
-  };
-  if (w < 8 || h < 8 || !job || !frame_I) return fail("dsm_optimize_immature_points_host: bad argument");
-  const dsm_immature_job &J = *job;
-  if (gn_iterations < 0 || gn_iterations > DSM_IMMATURE_GN_ITERATIONS_LIMIT || !std::isfinite(huber_th) || !std::isfinite(min_idepth_h_act))
-    return fail("dsm_optimize_immature_points_host: gn_iterations outside [0, 16], or a non-finite threshold");
-  if (J.n_frames < 1 || J.n_frames > DSM_IMMATURE_MAX_FRAMES || J.n_pts < 0 || !J.frame_ids || !J.pre_R || !J.pre_t || !J.pre_aff)
-    return fail("dsm_optimize_immature_points_host: n_frames outside [1, 9], a negative count or a NULL array");
-  if (J.n_pts && (!J.host || !J.u || !J.v || !J.idepth_min || !J.idepth_max || !J.energy_th || !J.color || !J.weights || !J.status ||
-                  !J.idepth_out || !J.res_state))
-    return fail("dsm_optimize_immature_points_host: NULL array");
-  for (int f = 0; f < J.n_frames; f++)
-    if (!frame_I[f]) return fail("dsm_optimize_immature_points_host: NULL frame");
-  for (int i = 0; i < J.n_pts; i++)
-    if (J.host[i] < 0 || J.host[i] >= J.n_frames) return fail("dsm_optimize_immature_points_host: host outside [0, n_frames)");
-  ImmPoint P;
-  P.J = job, P.frame_I = frame_I, P.huber = huber_th;
-  P.C = Cam{J.cam[0], J.cam[1], J.cam[2], J.cam[3], J.cam_inv[0], J.cam_inv[1], w, h};
-  const int nf = J.n_frames;
-  for (int i = 0; i < J.n_pts; i++) {
-    P.i = i;
-    ImmTmpRes residuals[DSM_IMMATURE_MAX_FRAMES];
-    int nres = 0;
-    for (int f = 0; f < nf; f++) // :38-46
-      if (f != J.host[i]) residuals[nres++] = ImmTmpRes{RES_IN, RES_OUTLIER, 0.f, 0.f, f};
-    float lastEnergy = 0, lastHdd = 0, lastbd = 0;
-    float currentIdepth = (J.idepth_max[i] + J.idepth_min[i]) * 0.5f; // M1
-    int status = -1, iterations = 0;
-    for (int k = 0; k < nres; k++) { // M2
-      lastEnergy += P.linearize(1000, residuals[k], lastHdd, lastbd, currentIdepth);
-      residuals[k].state_state = residuals[k].state_NewState;
-      residuals[k].state_energy = residuals[k].state_NewEnergy;
-    }
-    if (!std::isfinite(lastEnergy) || lastHdd < min_idepth_h_act) status = 0; // :63-68
-    float lambda = 0.1;
-    for (int iteration = 0; status < 0 && iteration < gn_iterations; iteration++) {
-      float H = lastHdd;
-      H *= 1 + lambda;
-      float step = (1.0 / H) * lastbd; // M3: quotient and product in double
-      float newIdepth = currentIdepth - step;
-      float newHdd = 0, newbd = 0, newEnergy = 0;
-      for (int k = 0; k < nres; k++) newEnergy += P.linearize(1, residuals[k], newHdd, newbd, newIdepth);
-      iterations++;
-      if (!std::isfinite(lastEnergy) || newHdd < min_idepth_h_act) { // M4: lastEnergy, not newEnergy (:90)
-        status = 0;
-        break;
-      }
-      if (newEnergy < lastEnergy) {
-        currentIdepth = newIdepth, lastHdd = newHdd, lastbd = newbd, lastEnergy = newEnergy;
-        for (int k = 0; k < nres; k++) {
-          residuals[k].state_state = residuals[k].state_NewState;
-          residuals[k].state_energy = residuals[k].state_NewEnergy;
-        }
-        lambda *= 0.5;
-      } else {
-        lambda *= 5;
-      }
-      if (fabsf(step) < 0.0001 * currentIdepth) break; // M5: in double, currentIdepth already updated
-    }
-    if (status < 0) {
-      int numGoodRes = 0;
-      for (int k = 0; k < nres; k++) numGoodRes += residuals[k].state_state == RES_IN;
-      status = (!std::isfinite(currentIdepth) || numGoodRes < J.min_obs) ? 2 : 1; // :121-138
-    }
-    J.status[i] = (unsigned char)status;
-    J.idepth_out[i] = currentIdepth;
-    J.res_state[(size_t)i * nf + J.host[i]] = DSM_RES_HOST;
-    for (int k = 0; k < nres; k++) J.res_state[(size_t)i * nf + residuals[k].target] = (unsigned char)residuals[k].state_state;
-    if (J.hdd_out) J.hdd_out[i] = lastHdd;
-    if (J.bd_out) J.bd_out[i] = lastbd;
-    if (J.energy_out) J.energy_out[i] = lastEnergy;
-    if (J.iterations_out) J.iterations_out[i] = iterations;
-  }
-  return DSM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// The loop of FrontEnd::traceNewCoarse (FrontEnd.cpp:276-327) as the reference runs it: one sequential loop over the immature points,
-// ImmaturePoint::traceOn per point.  T1-T16: DESIGN.md section 14.  The per-sample arithmetic is trace_math.hpp, shared with the device
-// kernel; the sums over the pattern are plain loops in pattern order.
-// ---------------------------------------------------------------------------------------------
-#include "trace_math.hpp"
-
-namespace dsm {
-// the rules of dsm_trace_points_batch / _host for the settings; NULL when they hold
-const char *trace_params_error(const dsm_trace_params *p) {
-  if (!p) return "no parameters";
-  if (p->gn_iterations < 0 || p->gn_iterations > 16) return "gn_iterations outside [0, 16]";
-  if (!std::isfinite(p->stepsize) || !(p->stepsize > 0)) return "a non-finite or non-positive stepsize";
-  if (!std::isfinite(p->max_pix_search) || !std::isfinite(p->slack_interval) || !std::isfinite(p->min_improvement) ||
-      !std::isfinite(p->gn_threshold) || !std::isfinite(p->extra_slack_on_th) || !std::isfinite(p->huber_th))
-    return "a non-finite parameter";
-  if (p->min_test_radius < 0) return "a negative min_test_radius";
-  return nullptr;
-}
-// ... and for the arrays of one job
-const char *trace_job_error(const dsm_trace_job &J) {
-  if (J.n_hosts < 0 || J.n_hosts > DSM_TRACE_MAX_HOSTS || J.n_pts < 0) return "n_hosts outside [0, 16] or a negative count";
-  if (J.n_hosts && (!J.krki || !J.kt || !J.aff)) return "NULL host array";
-  if (J.n_pts && (!J.host || !J.u || !J.v || !J.energy_th || !J.grad_h || !J.color || !J.weights || !J.status || !J.idepth_min ||
-                  !J.idepth_max || !J.quality || !J.trace_uv || !J.trace_interval))
-    return "NULL point array";
-  for (int i = 0; i < J.n_pts; i++) {
-    if (J.host[i] < 0 || J.host[i] >= J.n_hosts) return "host outside [0, n_hosts)";
-    if (J.status[i] > DSM_IPS_UNINITIALIZED) return "a status byte above 5";
-  }
-  return nullptr;
-}
-} // namespace dsm
-
-extern "C" int dsm_trace_params_default(dsm_trace_params *p) {
-  if (!p) return DSM_ERR_INVALID;
-  p->max_pix_search = 0.027f, p->slack_interval = 1.5f, p->stepsize = 1.0f, p->min_improvement = 2.0f;
-  p->min_test_radius = 2, p->gn_iterations = 3;
-  p->gn_threshold = 0.1f, p->extra_slack_on_th = 1.2f, p->huber_th = 9.0f;
-  return DSM_OK;
-}
-
-extern "C" int dsm_trace_points_host(int w, int h, const float *target_I, const dsm_trace_job *job, const dsm_trace_params *params) {
-  using namespace dsm::trc;
-  auto fail = [](const char *msg) {
-    dsm::set_error(std::string("dsm_trace_points_host: ") + msg);
-    return (int)DSM_ERR_INVALID;
-  };
-  if (w < 8 || h < 8 || !target_I || !job) return fail("bad argument");
-  if (const char *e = dsm::trace_params_error(params)) return fail(e);
-  if (const char *e = dsm::trace_job_error(*job)) return fail(e);
-  const dsm_trace_job &J = *job;
-  const dsm_trace_params &S = *params;
-  int counts[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < J.n_pts; i++) {
-    const float *R = J.krki + 9 * J.host[i], *t = J.kt + 3 * J.host[i], *aff = J.aff + 2 * J.host[i];
-    const float *color = J.color + 8 * i, *wt = J.weights + 8 * i;
-    const int entered = J.status[i];
-    Point P{entered, J.idepth_min[i], J.idepth_max[i], J.quality[i], J.trace_uv[2 * i], J.trace_uv[2 * i + 1], J.trace_interval[i]};
-    Line L;
-    int steps = 0;
-    if (geometry(w, h, R, t, J.u[i], J.v[i], J.grad_h + 4 * i, S, P, L)) {
-      steps = L.numSteps;
-      float rx[8], ry[8], errors[DSM_TRACE_MAX_STEPS + 1];
-      for (int k = 0; k < 8; k++) rotated_pattern(R, k, rx[k], ry[k]);
-      float ptx = L.ptx, pty = L.pty, bestU = 0, bestV = 0, bestEnergy = 1e10f;
-      int bestIdx = -1;
-      for (int s = 0; s < steps; s++) { // T9
-        float energy = 0;
-        for (int k = 0; k < 8; k++) {
-          const float x = ptx + rx[k], y = pty + ry[k];
-          const bool ok = guard(x, y, w, h);
-          energy += search_term(ok, ok ? interp_I(load4(target_I, w, x, y), x, y) : 0.f, aff, color[k], S.huber_th);
-        }
-        errors[s] = energy;
-        if (energy < bestEnergy) bestU = ptx, bestV = pty, bestEnergy = energy, bestIdx = s;
-        ptx += L.dx;
-        pty += L.dy;
-      }
-      float secondBest = 1e10f; // T10
-      for (int s = 0; s < steps; s++)
-        if (outside_radius(s, bestIdx, test_radius(S)) && errors[s] < secondBest) secondBest = errors[s];
-      quality_update(P, secondBest, bestEnergy, steps);
-      GN g{bestU, bestV, bestU, bestV, 0.f, bestEnergy}; // T11
-      if (S.gn_iterations > 0) g.bestEnergy = 1e5f;
-      for (int it = 0; it < S.gn_iterations; it++) {
-        float H = 1, b = 0, E = 0;
-        for (int k = 0; k < 8; k++) {
-          const float x = g.bestU + rx[k], y = g.bestV + ry[k];
-          const bool ok = guard(x, y, w, h);
-          float hI = 0, gx = 0, gy = 0, tH, tb, tE;
-          if (ok) interp_Ig(load12(target_I, w, x, y), x, y, hI, gx, gy);
-          if (gn_terms(ok, hI, gx, gy, aff, color[k], wt[k], S.huber_th, L.dx, L.dy, tH, tb, tE)) H += tH, b += tb;
-          E += tE;
-        }
-        if (gn_update(g, H, b, E, L.dx, L.dy, S.gn_threshold)) break;
-      }
-      finish(P, L, g, t, J.energy_th[i], S, entered);
-    }
-    J.status[i] = (unsigned char)P.status;
-    J.idepth_min[i] = P.idepth_min, J.idepth_max[i] = P.idepth_max, J.quality[i] = P.quality;
-    J.trace_uv[2 * i] = P.uv0, J.trace_uv[2 * i + 1] = P.uv1, J.trace_interval[i] = P.interval;
-    if (J.steps_out) J.steps_out[i] = steps;
-    counts[P.status]++;
-  }
-  if (J.counts_out) memcpy(J.counts_out, counts, sizeof counts); // T16
-  return DSM_OK;
-}

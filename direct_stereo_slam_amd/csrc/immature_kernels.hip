@@ -125,43 +125,19 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void immature_kernel(const ImJ
   P.aff[0] = stage[J.off_aff + 2 * pair], P.aff[1] = stage[J.off_aff + 2 * pair + 1];
   P.u = stage[J.off_u + pt], P.v = stage[J.off_v + pt], P.energy_th = stage[J.off_eth + pt];
   P.color = stage[J.off_color + 8 * pt + (lane & 7)], P.wt = stage[J.off_wt + 8 * pt + (lane & 7)];
-  imm::pattern(lane & 7, P.dx, P.dy);
+  pt::pattern(lane & 7, P.dx, P.dy);
 
   LaneRes res{imm::RES_IN, imm::RES_OUTLIER, 0.f, 0.f};
-  float lastHdd = 0.f, lastbd = 0.f;
-  float currentIdepth = uniform((stage[J.off_idmax + pt] + stage[J.off_idmin + pt]) * 0.5f); // M1
-  float lastEnergy = uniform(evaluate(P, res, 1000.f, currentIdepth, lastHdd, lastbd));   // M2
-  lastHdd = uniform(lastHdd), lastbd = uniform(lastbd);
+  float Hdd = 0.f, bd = 0.f;
+  const float start = uniform(imm::lm_start(stage[J.off_idmin + pt], stage[J.off_idmax + pt])); // M1
+  const float energy = uniform(evaluate(P, res, 1000.f, start, Hdd, bd));                       // M2
   res.state = res.new_state, res.energy = res.new_energy;
-  int status = -1, iterations = 0;
-  if (!__builtin_isfinite(lastEnergy) || lastHdd < min_h) status = 0; // :63-68
-  float lambda = 0.1f;
-  for (int iteration = 0; status < 0 && iteration < gn_its; iteration++) {
-    float H = lastHdd;
-    H *= 1 + lambda;
-    const float step = (float)((1.0 / (double)H) * (double)lastbd); // M3
-    const float newIdepth = currentIdepth - step;
-    float newHdd = 0.f, newbd = 0.f;
-    const float newEnergy = uniform(evaluate(P, res, 1.f, newIdepth, newHdd, newbd));
-    newHdd = uniform(newHdd), newbd = uniform(newbd);
-    iterations++;
-    if (!__builtin_isfinite(lastEnergy) || newHdd < min_h) { // M4
-      status = 0;
-      break;
-    }
-    if (newEnergy < lastEnergy) {
-      currentIdepth = newIdepth, lastHdd = newHdd, lastbd = newbd, lastEnergy = newEnergy;
-      res.state = res.new_state, res.energy = res.new_energy;
-      lambda *= 0.5f;
-    } else {
-      lambda *= 5.f;
-    }
-    if ((double)__builtin_fabsf(step) < 0.0001 * (double)currentIdepth) break; // M5
+  imm::LM lm = imm::lm_begin(start, energy, uniform(Hdd), uniform(bd), min_h);
+  while (!lm.done && lm.iterations < gn_its) {
+    const float newEnergy = uniform(evaluate(P, res, 1.f, imm::lm_propose(lm), Hdd, bd));
+    if (imm::lm_trial(lm, newEnergy, uniform(Hdd), uniform(bd), min_h)) res.state = res.new_state, res.energy = res.new_energy;
   }
-  if (status < 0) {
-    const int good = __popcll(__ballot(P.act && (lane & 7) == 0 && res.state == imm::RES_IN));
-    status = (!__builtin_isfinite(currentIdepth) || good < J.min_obs) ? 2 : 1; // :121-138
-  }
+  imm::lm_finish(lm, __popcll(__ballot(P.act && (lane & 7) == 0 && res.state == imm::RES_IN)), J.min_obs);
   unsigned st[3] = {0u, 0u, 0u};
   for (int f = 0; f < nf; f++) {
     const int rr = f < host ? f : f - 1;
@@ -170,11 +146,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void immature_kernel(const ImJ
   }
   unsigned word;
   switch (lane) {
-  case 0: word = __float_as_uint(currentIdepth); break;
-  case 1: word = __float_as_uint(lastHdd); break;
-  case 2: word = __float_as_uint(lastbd); break;
-  case 3: word = __float_as_uint(lastEnergy); break;
-  case 4: word = (unsigned)status | ((unsigned)iterations << 8); break;
+  case 0: word = __float_as_uint(lm.idepth); break;
+  case 1: word = __float_as_uint(lm.Hdd); break;
+  case 2: word = __float_as_uint(lm.bd); break;
+  case 3: word = __float_as_uint(lm.energy); break;
+  case 4: word = (unsigned)lm.status | ((unsigned)lm.iterations << 8); break;
   case 5: word = st[0]; break;
   case 6: word = st[1]; break;
   default: word = st[2]; break;
@@ -185,26 +161,20 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void immature_kernel(const ImJ
 // all-or-nothing validation of a batch: nothing is enqueued before every job has passed
 int check_jobs(dsm_context *ctx, int n_jobs, const dsm_immature_job *jobs, float huber_th, float min_idepth_h_act, int gn_iterations,
                size_t *pts_out) {
-  if (!ctx || n_jobs < 1 || !jobs) return invalid("dsm_optimize_immature_points_batch: bad argument");
-  if (gn_iterations < 0 || gn_iterations > DSM_IMMATURE_GN_ITERATIONS_LIMIT || !std::isfinite(huber_th) || !std::isfinite(min_idepth_h_act))
-    return invalid("dsm_optimize_immature_points_batch: gn_iterations outside [0, 16], or a non-finite threshold");
+  auto bad = [](const char *msg) { return invalid((std::string("dsm_optimize_immature_points_batch: ") + msg).c_str()); };
+  if (!ctx || n_jobs < 1 || !jobs) return bad("bad argument");
+  if (const char *e = immature_settings_error(huber_th, min_idepth_h_act, gn_iterations)) return bad(e);
   size_t pts = 0;
   for (int j = 0; j < n_jobs; j++) {
     const dsm_immature_job &J = jobs[j];
-    if (!J.window || J.window->ctx != ctx) return invalid("immature job: no window, or a window of another context");
-    if (J.window->w != jobs[0].window->w || J.window->h != jobs[0].window->h) return invalid("immature jobs: one geometry per call");
-    if (J.n_frames < 1 || J.n_frames > DSM_IMMATURE_MAX_FRAMES || J.n_pts < 0 || !J.frame_ids || !J.pre_R || !J.pre_t || !J.pre_aff)
-      return invalid("immature job: n_frames outside [1, 9], a negative count or a NULL array");
-    if (J.n_pts && (!J.host || !J.u || !J.v || !J.idepth_min || !J.idepth_max || !J.energy_th || !J.color || !J.weights || !J.status ||
-                    !J.idepth_out || !J.res_state))
-      return invalid("immature job: NULL array");
+    if (!J.window || J.window->ctx != ctx) return bad("no window, or a window of another context");
+    if (J.window->w != jobs[0].window->w || J.window->h != jobs[0].window->h) return bad("one geometry per call");
+    if (const char *e = immature_job_error(J)) return bad(e);
     for (int f = 0; f < J.n_frames; f++)
-      if (J.window->find(J.frame_ids[f]) < 0) return invalid("immature job: a frame id that is not in the window");
-    for (int i = 0; i < J.n_pts; i++)
-      if (J.host[i] < 0 || J.host[i] >= J.n_frames) return invalid("immature job: host outside [0, n_frames)");
+      if (J.window->find(J.frame_ids[f]) < 0) return bad("a frame id that is not in the window");
     pts += (size_t)J.n_pts;
   }
-  if (pts > kMaxPoints) return invalid("immature jobs: too many points in one call");
+  if (pts > kMaxPoints) return bad("too many points in one call");
   *pts_out = pts;
   return DSM_OK;
 }

@@ -8,10 +8,10 @@
 //                 come from the chain of float additions before any texel is back, so their sixteen texel loads are in flight
 //                 together; lanes of points that are finished or never searched are masked.  The refinement (T11) runs the eight
 //                 points of the wave at once.
-// Bit parity with the sequential float sums: a lane computes its pixel's term (trace_math.hpp, shared with the host form) and the
-// eight lanes of a point add the eight terms as one chain in lane order = pattern order (__shfl, width 8), so every lane of the point
-// holds the same sum.  errors[] (T10) sits in LDS, 100 floats per point; only lanes of the same wave exchange data through it, and no
-// wave waits for another.  Loops are bounded by 99 steps, gn_iterations and 8.
+// Bit parity with the sequential float sums: a lane computes its pixel's term (trace_math.hpp and point_math.hpp, shared with the
+// host form) and the eight lanes of a point add the eight terms as one chain in lane order = pattern order (__shfl, width 8), so
+// every lane of the point holds the same sum.  errors[] (T10) sits in LDS, 100 floats per point; only lanes of the same wave
+// exchange data through it, and no wave waits for another.  Loops are bounded by 99 steps, gn_iterations and 8.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void trace_kernel(const TrJob 
   const int entered = stage_i[J.off_status + pt];
   trc::Point P{have ? entered : DSM_IPS_OOB, stage[J.off_idmin + pt], stage[J.off_idmax + pt], stage[J.off_quality + pt],
                stage[J.off_uv + 2 * pt], stage[J.off_uv + 2 * pt + 1], stage[J.off_interval + pt]};
-  trc::Line L{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0};
+  trc::Line L{};
   const bool run = trc::geometry(w, h, R, t, u, v, G, S, P, L); // T1-T7, the same in the eight lanes of a point
   const int ns = run ? L.numSteps : 0;
   float rx, ry;
@@ -90,20 +90,20 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void trace_kernel(const TrJob 
   for (int s0 = 0; __ballot(s0 < ns) != 0ull; s0 += kStepsPerTrip) {
     float px[kStepsPerTrip], py[kStepsPerTrip], x[kStepsPerTrip], y[kStepsPerTrip];
     bool ok[kStepsPerTrip];
-    trc::Tex4 T[kStepsPerTrip];
+    pt::Tex4 T[kStepsPerTrip];
 #pragma unroll
     for (int j = 0; j < kStepsPerTrip; j++) { // the positions are the chain of additions; all loads of the trip are issued here
       px[j] = ptx, py[j] = pty;
       x[j] = ptx + rx, y[j] = pty + ry;
       ok[j] = s0 + j < ns && trc::guard(x[j], y[j], w, h); // T8: no load leaves the plane
-      T[j] = trc::Tex4{0.f, 0.f, 0.f, 0.f};
-      if (ok[j]) T[j] = trc::load4(I, w, x[j], y[j]);
+      T[j] = pt::Tex4{0.f, 0.f, 0.f, 0.f};
+      if (ok[j]) T[j] = pt::load4(I, w, x[j], y[j]);
       ptx += L.dx;
       pty += L.dy;
     }
 #pragma unroll
     for (int j = 0; j < kStepsPerTrip; j++) {
-      const float term = trc::search_term(ok[j], trc::interp_I(T[j], x[j], y[j]), aff, color, S.huber_th);
+      const float term = trc::search_term(ok[j], pt::interp_I(T[j], x[j], y[j]), aff, color, S.huber_th);
       const float energy = chain8(0.f, term);
       if (s0 + j < ns) {
         if (k == 0) my_errs[s0 + j] = energy;
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void trace_kernel(const TrJob 
     const float x = g.bestU + rx, y = g.bestV + ry;
     const bool ok = live && trc::guard(x, y, w, h);
     float hI = 0.f, gx = 0.f, gy = 0.f, tH, tb, tE;
-    if (ok) trc::interp_Ig(trc::load12(I, w, x, y), x, y, hI, gx, gy);
+    if (ok) pt::interp_Ig(pt::load12(I, w, x, y), x, y, hI, gx, gy);
     const bool fin = trc::gn_terms(ok, hI, gx, gy, aff, color, wt, S.huber_th, L.dx, L.dy, tH, tb, tE);
     const unsigned counted = (unsigned)(__ballot(fin) >> (lane & 56)) & 0xffu; // the pixels of this point that reach H and b
     float H = 1.f, b = 0.f, E = 0.f;

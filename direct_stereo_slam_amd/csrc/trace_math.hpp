@@ -1,11 +1,11 @@
 // trace_math.hpp -- ImmaturePoint::traceOn as DESIGN.md section 14 states it (T1-T16): the arithmetic the device kernel
-// (trace_kernels.hip) and the host form (host_capi.cpp) share, so that both evaluate the same expression tree.  float32 throughout,
+// (trace_kernels.hip) and the host form (points_host.cpp) share, so that both evaluate the same expression tree.  float32 throughout,
 // no contraction (-ffp-contract=off), no fmaf; division and sqrtf correctly rounded.  The sums over the eight pattern pixels are the
 // callers': the host form adds in a loop, the kernel along the lanes of a point, both in pattern order.
 #pragma once
 
 #include "../../include/dsm_hotpath.h"
-#include "immature_math.hpp"
+#include "point_math.hpp"
 
 namespace dsm {
 namespace trc {
@@ -18,10 +18,10 @@ struct Point {
 
 // what T2-T7 leave for the search, the refinement and the new interval
 struct Line {
-  float pr0, pr1, pr2; // K R K^-1 (u, v, 1)
-  float dx, dy;        // the unit step along the epipolar line
-  float err;           // errorInPixel
-  float ptx, pty;      // the first position of the search
+  pt::Vec3 pr;    // K R K^-1 (u, v, 1)
+  float dx, dy;   // the unit step along the epipolar line
+  float err;      // errorInPixel
+  float ptx, pty; // the first position of the search
   int numSteps;
 };
 
@@ -29,20 +29,18 @@ struct GN {
   float bestU, bestV, uBak, vBak, stepBack, bestEnergy;
 };
 
-DSM_IMM_HD bool inside(float u, float v, int w, int h) { return u > 4 && v > 4 && u < (float)(w - 5) && v < (float)(h - 5); } // T2
-DSM_IMM_HD void oob_exit(Point &P) { P.uv0 = -1, P.uv1 = -1, P.interval = 0, P.status = DSM_IPS_OOB; }
+DSM_HD bool inside(float u, float v, int w, int h) { return u > 4 && v > 4 && u < (float)(w - 5) && v < (float)(h - 5); } // T2
+DSM_HD void oob_exit(Point &P) { P.uv0 = -1, P.uv1 = -1, P.interval = 0, P.status = DSM_IPS_OOB; }
 
 // T1-T7 for the point (u, v) of a host with K R K^-1 = R (row-major), K t = t and gradH = G.  True: the search runs on L.  False: the
 // rule that returned has written P (T1: nothing).
-DSM_IMM_HD bool geometry(int w, int h, const float *R, const float *t, float u, float v, const float *G, const dsm_trace_params &S, Point &P,
-                         Line &L) {
+DSM_HD bool geometry(int w, int h, const float *R, const float *t, float u, float v, const float *G, const dsm_trace_params &S, Point &P,
+                     Line &L) {
   if (P.status == DSM_IPS_OOB) return false; // T1
   const float maxPix = (float)(w + h) * S.max_pix_search; // T2
-  L.pr0 = (R[0] * u + R[1] * v) + R[2];
-  L.pr1 = (R[3] * u + R[4] * v) + R[5];
-  L.pr2 = (R[6] * u + R[7] * v) + R[8];
-  const float m0 = L.pr0 + t[0] * P.idepth_min, m1 = L.pr1 + t[1] * P.idepth_min, m2 = L.pr2 + t[2] * P.idepth_min;
-  const float uMin = m0 / m2, vMin = m1 / m2;
+  L.pr = pt::rotate_uv1(R, u, v);
+  const pt::Vec3 m = pt::add_translation(L.pr, t, P.idepth_min);
+  const float m2 = m.z, uMin = m.x / m2, vMin = m.y / m2;
   if (!inside(uMin, vMin, w, h)) {
     oob_exit(P);
     return false;
@@ -50,8 +48,8 @@ DSM_IMM_HD bool geometry(int w, int h, const float *R, const float *t, float u, 
   const bool bounded = __builtin_isfinite(P.idepth_max);
   float dist, uMax, vMax;
   if (bounded) { // T3
-    const float x0 = L.pr0 + t[0] * P.idepth_max, x1 = L.pr1 + t[1] * P.idepth_max, x2 = L.pr2 + t[2] * P.idepth_max;
-    uMax = x0 / x2, vMax = x1 / x2;
+    const pt::Vec3 x = pt::add_translation(L.pr, t, P.idepth_max);
+    uMax = x.x / x.z, vMax = x.y / x.z;
     if (!inside(uMax, vMax, w, h)) {
       oob_exit(P);
       return false;
@@ -63,8 +61,8 @@ DSM_IMM_HD bool geometry(int w, int h, const float *R, const float *t, float u, 
     }
   } else { // T4
     dist = maxPix;
-    const float x0 = L.pr0 + t[0] * 0.01f, x1 = L.pr1 + t[1] * 0.01f, x2 = L.pr2 + t[2] * 0.01f;
-    uMax = x0 / x2, vMax = x1 / x2;
+    const pt::Vec3 x = pt::add_translation(L.pr, t, 0.01f);
+    uMax = x.x / x.z, vMax = x.y / x.z;
     const float dx = uMax - uMin, dy = vMax - vMin;
     const float d = 1.0f / __builtin_sqrtf(dx * dx + dy * dy);
     uMax = uMin + (dist * dx) * d;
@@ -104,56 +102,18 @@ DSM_IMM_HD bool geometry(int w, int h, const float *R, const float *t, float u, 
 }
 
 // the rotated pattern pixel of T7
-DSM_IMM_HD void rotated_pattern(const float *R, int k, float &rx, float &ry) {
+DSM_HD void rotated_pattern(const float *R, int k, float &rx, float &ry) {
   int px, py;
-  imm::pattern(k, px, py);
+  pt::pattern(k, px, py);
   rx = R[0] * (float)px + R[1] * (float)py;
   ry = R[3] * (float)px + R[4] * (float)py;
 }
 
 // T8: samples outside this box count as non-finite; inside it the twelve texels of a sample lie in the plane
-DSM_IMM_HD bool guard(float x, float y, int w, int h) { return x >= 1 && y >= 1 && x < (float)(w - 2) && y < (float)(h - 2); }
-
-struct Tex4 { // the four texels of an intensity sample
-  float b1, b2, c1, c2;
-};
-struct Tex12 { // ... and the eight more of its gradients (rows iy - 1 .. iy + 2, as immature_math.hpp names them)
-  float a0, a1, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1;
-};
-
-DSM_IMM_HD Tex4 load4(const float *I, int w, float x, float y) { // under guard(x, y)
-  const float *p = I + ((long long)(int)y * w + (int)x);
-  return Tex4{p[0], p[1], p[w], p[w + 1]};
-}
-DSM_IMM_HD Tex12 load12(const float *I, int w, float x, float y) { // under guard(x, y)
-  const float *p = I + ((long long)(int)y * w + (int)x);
-  return Tex12{p[-w], p[-w + 1], p[-1], p[0], p[1], p[2], p[w - 1], p[w], p[w + 1], p[w + 2], p[2 * w], p[2 * w + 1]};
-}
-
-// U6, channel 0
-DSM_IMM_HD float interp_I(const Tex4 &T, float x, float y) {
-  const int ix = (int)x, iy = (int)y;
-  const float fdx = x - ix, fdy = y - iy, dxdy = fdx * fdy;
-  const float w11 = dxdy, w01 = fdy - dxdy, w10 = fdx - dxdy, w00 = 1 - fdx - fdy + dxdy;
-  return ((w11 * T.c2 + w01 * T.c1) + w10 * T.b2) + w00 * T.b1;
-}
-// U6, all three channels
-DSM_IMM_HD void interp_Ig(const Tex12 &T, float x, float y, float &hI, float &hx, float &hy) {
-  using imm::grad_fix;
-  const int ix = (int)x, iy = (int)y;
-  const float fdx = x - ix, fdy = y - iy, dxdy = fdx * fdy;
-  const float w11 = dxdy, w01 = fdy - dxdy, w10 = fdx - dxdy, w00 = 1 - fdx - fdy + dxdy;
-  hI = ((w11 * T.c2 + w01 * T.c1) + w10 * T.b2) + w00 * T.b1;
-  const float gx00 = grad_fix(0.5f * (T.b2 - T.b0)), gx10 = grad_fix(0.5f * (T.b3 - T.b1)), gx01 = grad_fix(0.5f * (T.c2 - T.c0)),
-              gx11 = grad_fix(0.5f * (T.c3 - T.c1));
-  const float gy00 = grad_fix(0.5f * (T.c1 - T.a0)), gy10 = grad_fix(0.5f * (T.c2 - T.a1)), gy01 = grad_fix(0.5f * (T.d0 - T.b1)),
-              gy11 = grad_fix(0.5f * (T.d1 - T.b2));
-  hx = ((w11 * gx11 + w01 * gx01) + w10 * gx10) + w00 * gx00;
-  hy = ((w11 * gy11 + w01 * gy01) + w10 * gy10) + w00 * gy00;
-}
+DSM_HD bool guard(float x, float y, int w, int h) { return x >= 1 && y >= 1 && x < (float)(w - 2) && y < (float)(h - 2); }
 
 // T9: one pixel's term of a step's energy; `ok`: the sample passed the guard, hI is its intensity
-DSM_IMM_HD float search_term(bool ok, float hI, const float *aff, float color, float huber) {
+DSM_HD float search_term(bool ok, float hI, const float *aff, float color, float huber) {
   if (!ok || !__builtin_isfinite(hI)) return 1e5f;
   const float r = hI - (aff[0] * color + aff[1]);
   const float ar = __builtin_fabsf(r);
@@ -162,8 +122,8 @@ DSM_IMM_HD float search_term(bool ok, float hI, const float *aff, float color, f
 }
 
 // T11: one pixel's terms of an iteration.  False: the sample is non-finite, tE = 1e5f and nothing goes into H and b.
-DSM_IMM_HD bool gn_terms(bool ok, float hI, float gx, float gy, const float *aff, float color, float wt, float huber, float dx, float dy,
-                         float &tH, float &tb, float &tE) {
+DSM_HD bool gn_terms(bool ok, float hI, float gx, float gy, const float *aff, float color, float wt, float huber, float dx, float dy,
+                     float &tH, float &tb, float &tE) {
   tH = 0.f, tb = 0.f;
   if (!ok || !__builtin_isfinite(hI)) {
     tE = 1e5f;
@@ -180,15 +140,15 @@ DSM_IMM_HD bool gn_terms(bool ok, float hI, float gx, float gy, const float *aff
 }
 
 // T10: steps i < bestIdx - radius || i > bestIdx + radius count; a radius above the 99 steps excludes them all, whatever its size
-DSM_IMM_HD int test_radius(const dsm_trace_params &S) { return S.min_test_radius > 100 ? 100 : S.min_test_radius; }
-DSM_IMM_HD bool outside_radius(int i, int bestIdx, int radius) { return i < bestIdx - radius || i > bestIdx + radius; }
-DSM_IMM_HD void quality_update(Point &P, float secondBest, float bestEnergy, int numSteps) {
+DSM_HD int test_radius(const dsm_trace_params &S) { return S.min_test_radius > 100 ? 100 : S.min_test_radius; }
+DSM_HD bool outside_radius(int i, int bestIdx, int radius) { return i < bestIdx - radius || i > bestIdx + radius; }
+DSM_HD void quality_update(Point &P, float secondBest, float bestEnergy, int numSteps) {
   const float q = secondBest / bestEnergy;
   if (q < P.quality || numSteps > 10) P.quality = q;
 }
 
 // T11: the end of an iteration, given its sums.  True: the loop ends.
-DSM_IMM_HD bool gn_update(GN &g, float H, float b, float E, float dx, float dy, float gn_threshold) {
+DSM_HD bool gn_update(GN &g, float H, float b, float E, float dx, float dy, float gn_threshold) {
   if (E > g.bestEnergy) {
     g.stepBack *= 0.5f;
     g.bestU = g.uBak + g.stepBack * dx;
@@ -207,7 +167,7 @@ DSM_IMM_HD bool gn_update(GN &g, float H, float b, float E, float dx, float dy, 
 }
 
 // T12-T15; `entered`: the status the point came with
-DSM_IMM_HD void finish(Point &P, const Line &L, const GN &g, const float *t, float energy_th, const dsm_trace_params &S, int entered) {
+DSM_HD void finish(Point &P, const Line &L, const GN &g, const float *t, float energy_th, const dsm_trace_params &S, int entered) {
   if (!(g.bestEnergy < energy_th * S.extra_slack_on_th)) { // T12
     P.uv0 = -1, P.uv1 = -1, P.interval = 0;
     P.status = entered == DSM_IPS_OUTLIER ? DSM_IPS_OOB : DSM_IPS_OUTLIER;
@@ -215,11 +175,11 @@ DSM_IMM_HD void finish(Point &P, const Line &L, const GN &g, const float *t, flo
   }
   float lo, hi; // T13
   if (L.dx * L.dx > L.dy * L.dy) {
-    lo = (L.pr2 * (g.bestU - L.err * L.dx) - L.pr0) / (t[0] - t[2] * (g.bestU - L.err * L.dx));
-    hi = (L.pr2 * (g.bestU + L.err * L.dx) - L.pr0) / (t[0] - t[2] * (g.bestU + L.err * L.dx));
+    lo = (L.pr.z * (g.bestU - L.err * L.dx) - L.pr.x) / (t[0] - t[2] * (g.bestU - L.err * L.dx));
+    hi = (L.pr.z * (g.bestU + L.err * L.dx) - L.pr.x) / (t[0] - t[2] * (g.bestU + L.err * L.dx));
   } else {
-    lo = (L.pr2 * (g.bestV - L.err * L.dy) - L.pr1) / (t[1] - t[2] * (g.bestV - L.err * L.dy));
-    hi = (L.pr2 * (g.bestV + L.err * L.dy) - L.pr1) / (t[1] - t[2] * (g.bestV + L.err * L.dy));
+    lo = (L.pr.z * (g.bestV - L.err * L.dy) - L.pr.y) / (t[1] - t[2] * (g.bestV - L.err * L.dy));
+    hi = (L.pr.z * (g.bestV + L.err * L.dy) - L.pr.y) / (t[1] - t[2] * (g.bestV + L.err * L.dy));
   }
   if (lo > hi) {
     const float s = lo;

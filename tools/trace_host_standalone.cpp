@@ -4,7 +4,7 @@
 // given as the second argument) and prints one JSON line: the statuses as a digit string, the steps summed and the FNV-1a hash of the
 // traced floats (NaNs made canonical), which tests/_trace_ref.py can reproduce.  Build, from the repository root:
 //   hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       tools/trace_host_standalone.cpp direct_stereo_slam_amd/csrc/host_capi.cpp -o trace_host_standalone
+//       tools/trace_host_standalone.cpp direct_stereo_slam_amd/csrc/points_host.cpp -o trace_host_standalone
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
