@@ -1727,14 +1727,11 @@ int dsm_pose_estimator_destroy(dsm_pose_estimator *pe) {
   return DSM_OK;
 }
 
-int dsm_pose_estimator_estimate(dsm_pose_estimator *pe, int n_pts, const double *xyz, const float *const *ref_colors,
-                                float ref_ab_exposure, const float *const *new_dIp, float new_ab_exposure,
-                                const float new_cam[4], int coarsest_lvl, double ref_to_new_io[16], float *pose_error,
-                                int *ok) {
-  if (!pe || n_pts < 1 || !xyz || !ref_colors || !new_dIp || !new_cam || !ref_to_new_io)
-    return invalid("dsm_pose_estimator_estimate: bad argument");
+// The loading half of PoseEstimator::estimate (:306-319), shared by dsm_pose_estimator_estimate and dsm_diag_pose_estimator_eval:
+// makeK(new_cam), the points narrowed to float, the reference with affine (0, 0), the new frame's pyramid
+static int pose_estimator_load(dsm_pose_estimator *pe, int n_pts, const double *xyz, const float *const *ref_colors, float ref_ab_exposure,
+                               const float *const *new_dIp, float new_ab_exposure, const float new_cam[4]) {
   dsm_tracker *t = pe->t;
-  if (n_pts > t->w * t->h) return invalid("dsm_pose_estimator_estimate: more points than pixels");
   int rc = dsm_tracker_make_k(t, new_cam[0], new_cam[1], new_cam[2], new_cam[3]); // makeK(new_cam), :306
   if (rc) return rc;
   pe->x.resize(n_pts), pe->y.resize(n_pts), pe->z.resize(n_pts);
@@ -1752,7 +1749,18 @@ int dsm_pose_estimator_estimate(dsm_pose_estimator *pe, int n_pts, const double 
   // the float4 template slot holds (x, y, z, refColor[lvl]); ref_aff_g2l_ = (0,0) (:317)
   rc = dsm_tracker_set_ref(t, 0, 0.0, 0.0, ref_ab_exposure, n, px, py, pz, ref_colors);
   if (rc) return rc;
-  rc = dsm_tracker_upload_frame(t, DSM_SLOT_NEW_LEFT, new_dIp, new_ab_exposure);
+  return dsm_tracker_upload_frame(t, DSM_SLOT_NEW_LEFT, new_dIp, new_ab_exposure);
+}
+
+int dsm_pose_estimator_estimate(dsm_pose_estimator *pe, int n_pts, const double *xyz, const float *const *ref_colors,
+                                float ref_ab_exposure, const float *const *new_dIp, float new_ab_exposure,
+                                const float new_cam[4], int coarsest_lvl, double ref_to_new_io[16], float *pose_error,
+                                int *ok) {
+  if (!pe || n_pts < 1 || !xyz || !ref_colors || !new_dIp || !new_cam || !ref_to_new_io)
+    return invalid("dsm_pose_estimator_estimate: bad argument");
+  dsm_tracker *t = pe->t;
+  if (n_pts > t->w * t->h) return invalid("dsm_pose_estimator_estimate: more points than pixels");
+  int rc = pose_estimator_load(pe, n_pts, xyz, ref_colors, ref_ab_exposure, new_dIp, new_ab_exposure, new_cam);
   if (rc) return rc;
   dsm_context *ctx = t->ctx;
   dsm_tracker *ts[1] = {t};
@@ -2158,6 +2166,31 @@ int dsm_diag_single_eval(dsm_tracker *t, int mode, int lvl, const double pose[7]
     if (Hs) *Hs = o.Hs;
     if (bs) *bs = o.bs;
   }
+  if (n_warped) *n_warped = o.n_warped;
+  return DSM_OK;
+}
+
+int dsm_diag_pose_estimator_eval(dsm_pose_estimator *pe, int n_pts, const double *xyz, const float *const *ref_colors,
+                                 float ref_ab_exposure, const float *const *new_dIp, float new_ab_exposure, const float new_cam[4],
+                                 int lvl, const double pose[7], const double aff[2], float cutoff_th, int form, int residual_only,
+                                 double rs[6], double H[64], double b[8], int *n_warped) {
+  if (!pe || n_pts < 1 || !xyz || !ref_colors || !new_dIp || !new_cam || !pose || !aff)
+    return invalid("dsm_diag_pose_estimator_eval: bad argument");
+  dsm_tracker *t = pe->t;
+  if (n_pts > t->w * t->h) return invalid("dsm_diag_pose_estimator_eval: more points than pixels");
+  if (lvl < 0 || lvl >= t->nlevels) return invalid("dsm_diag_pose_estimator_eval: level out of range");
+  if (form != 0 && form != 1 && form != 3)
+    return invalid("dsm_diag_pose_estimator_eval: form is 0, 1 or 3 (the tick engine has no loop-closure instantiation)");
+  if (form == 3 && num_chunks(n_pts, t->desc.p.geometry) > 1) // (every level holds n_pts points: refused before anything is uploaded)
+    return invalid("dsm_diag_pose_estimator_eval: form 3 wants n_pts of at most one chunk under the estimator's chunk table");
+  int rc = pose_estimator_load(pe, n_pts, xyz, ref_colors, ref_ab_exposure, new_dIp, new_ab_exposure, new_cam);
+  if (rc) return rc;
+  SingleOut o;
+  rc = single_eval(t, 2, lvl, pose, aff, 1.0f, cutoff_th, &o, form, residual_only ? 1 : 0);
+  if (rc) return rc;
+  if (rs) memcpy(rs, o.rs, sizeof o.rs);
+  if (H) memcpy(H, o.H, sizeof o.H);
+  if (b) memcpy(b, o.b, sizeof o.b);
   if (n_warped) *n_warped = o.n_warped;
   return DSM_OK;
 }

@@ -2461,7 +2461,7 @@ void launch_chain(hipStream_t s, int mode, int nprob, const TrackerDev *const *t
     hipLaunchKernelGGL((chain_kernel<2>), dim3(nprob), dim3(kThreads), 0, s, trackers, states, status_out);
 }
 
-// dsm_diag_single_eval, form 3: ONE evaluation in the form the chains run it (chain_kernel above, tick_eval_kernel's chain path) -- the
+// dsm_diag_single_eval / dsm_diag_pose_estimator_eval, form 3: ONE evaluation in the form the chains run it (chain_kernel above, tick_eval_kernel's chain path) -- the
 // inputs from the LDS copy of the state, the level's single chunk into an LDS partial with the workgroup barrier between the row sums
 // and the final sum -- and the partial copied out to where LM_OP_SINGLE_FINISH reads it.  The same eval_chunk instantiations under the
 // same register budget as the chains'; no state machine.  A level of no chunk writes nothing (as the chains evaluate nothing there).
@@ -2489,8 +2489,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
 void launch_diag_chain_eval(hipStream_t s, int mode, const LMState *states, float *partials) {
   if (mode == 0)
     hipLaunchKernelGGL((diag_chain_eval_kernel<0>), dim3(1), dim3(kThreads), 0, s, states, partials);
-  else
+  else if (mode == 1)
     hipLaunchKernelGGL((diag_chain_eval_kernel<1>), dim3(1), dim3(kThreads), 0, s, states, partials);
+  else
+    hipLaunchKernelGGL((diag_chain_eval_kernel<2>), dim3(1), dim3(kThreads), 0, s, states, partials);
 }
 
 // dsm_diag_lm_propose: the proposing half of an LM step on caller-supplied systems, one workgroup per problem.  A zeroed LMState in

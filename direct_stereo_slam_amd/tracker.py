@@ -704,6 +704,24 @@ class PoseEstimator:
                                                  new_ab_exposure, _fp(cam), coarsest_lvl, _dp(T), C.byref(err), C.byref(ok)))
         return bool(ok.value), T.reshape(4, 4), err.value
 
+    def load_args(self, pts_xyz, ref_colors, ref_ab_exposure, new_dIp, new_ab_exposure, new_cam):
+        """the inputs of an evaluation as diagEval takes them, converted once (a sweep evaluates the same inputs many times).  Test aid."""
+        xyz = np.ascontiguousarray(pts_xyz, np.float64).reshape(-1, 3)
+        cols = [np.ascontiguousarray(c, np.float32) for c in ref_colors]
+        dIp = [np.ascontiguousarray(a, np.float32) for a in new_dIp]
+        cam = np.ascontiguousarray(new_cam, np.float32)
+        return (xyz, cols, dIp, cam), (len(xyz), _dp(xyz), _ptr_array(cols), ref_ab_exposure, _ptr_array(dIp), new_ab_exposure, _fp(cam))
+
+    def diagEval(self, inputs, lvl, pose, aff, cutoff, form=0, residual_only=False):
+        """ONE evaluation of the loop-closure alignment in a chosen form of the loop (dsm_diag_pose_estimator_eval: 0 the direct
+        kernel, 1 the split pair, 3 the chains' one-chunk form) on `inputs` = load_args(...): (rs, H[8,8], b, n_warped).  Test aid."""
+        pose = np.ascontiguousarray(pose, np.float64)
+        aff = np.ascontiguousarray(aff, np.float64)
+        rs, H, b, n = np.zeros(6), np.zeros(64), np.zeros(8), C.c_int()
+        check(self.L.dsm_diag_pose_estimator_eval(self.h, *inputs[1], lvl, _dp(pose), _dp(aff), cutoff, form, int(residual_only), _dp(rs),
+                                                  _dp(H), _dp(b), C.byref(n)))
+        return rs, H.reshape(8, 8), b, n.value
+
 
 class PoseBatch:
     """`dso::PoseEstimator::estimate` of many matches in one call (dsm_pose_estimate_batch): one geometry, per job its own points,

@@ -382,6 +382,22 @@ int dsm_tracker_calc_res_scale(dsm_tracker *t, int lvl, float scale, float cutof
  * (H, b, Hs, bs come back as zeros).  A bad mode, form or level is DSM_ERR_INVALID with nothing written.  No production path calls this. */
 int dsm_diag_single_eval(dsm_tracker *t, int mode, int lvl, const double pose[7], const double aff[2], float scale, float cutoff_th,
                          int form, int residual_only, double rs[6], double H[64], double b[8], float *Hs, float *bs, int *n_warped);
+/* test aid (no reference counterpart): ONE evaluation of the loop-closure alignment (mode 2: PoseEstimator::calcRes + calcGSSSE,
+ * PoseEstimator.cpp:84-296) at level lvl, pose {qx,qy,qz,qw,tx,ty,tz} and affine pair aff.  The inputs are those of
+ * dsm_pose_estimator_estimate and are loaded by the same function (makeK(new_cam), the points narrowed to float, the reference with
+ * affine (0, 0), the new frame's pyramid); the evaluation then runs as dsm_diag_single_eval runs one -- the direct calls' preparation
+ * and reduction, outputs of dsm_tracker_calc_res_pose's meaning -- launched in form
+ *   0  the evaluation kernel the estimator's LM run launches per step (eval_kernel<2, LVL0, false, 0>);
+ *   1  the split pair: the kernel of the full evaluations, then the kernel of the residual-only ones;
+ *   3  the chains' one-chunk form (chain_kernel<2>'s two instantiations of the loop under its register budget), for a level of at
+ *      most one chunk under the estimator's chunk table; DSM_ERR_INVALID otherwise.
+ * Form 2 (the tick engine) has no loop-closure instantiation and no caller: DSM_ERR_INVALID.  residual_only != 0: energy, counts and
+ * flow indicators; H and b come back as zeros.  DSM_ERR_INVALID with nothing written for a NULL pe, xyz, ref_colors, new_dIp,
+ * new_cam, pose or aff, n_pts < 1 or > w*h, a bad level or form.  rs, H, b, n_warped may be NULL.  No production path calls this. */
+int dsm_diag_pose_estimator_eval(dsm_pose_estimator *pe, int n_pts, const double *xyz, const float *const *ref_colors,
+                                 float ref_ab_exposure, const float *const *new_dIp, float new_ab_exposure, const float new_cam[4],
+                                 int lvl, const double pose[7], const double aff[2], float cutoff_th, int form, int residual_only,
+                                 double rs[6], double H[64], double b[8], int *n_warped);
 
 /* test aid (no reference counterpart): the second half of a Levenberg-Marquardt round -- the step that turns H, b and lambda into the
  * next candidate (TrackerAndScaler.cpp:505-554 pose, :897-913 scale) -- run by the production device code on caller-supplied

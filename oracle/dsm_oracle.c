@@ -1426,13 +1426,10 @@ static void pe_calc_gs(orc_pose_estimator *e, int lvl, const double aff[2], doub
   }
 }
 
-/* PoseEstimator::estimate, :298-506.  Returns the reference's bool. */
-int orc_pe_estimate(orc_pose_estimator *e, int n, const double *xyz, const float *const *colors, float ref_ab_exposure,
-                    const float *const *new_dIp, float new_ab_exposure, const float new_cam[4], int coarsest_lvl,
-                    double ref_to_new_io[16], float *pose_error, int *inlier_percent_out) {
-  const int *maxIterations = e->p.max_iterations;
-  const float lambdaExtrapolationLimit = e->p.lambda_extrapolation_limit;
-  const float cutoff0 = e->p.coarse_cutoff_th;
+/* the head of PoseEstimator::estimate (:306-319): makeK(new_cam) :62-82, the points and their colours, the new frame's pyramid and
+ * the two exposures -- what calcRes / calcGSSSE read.  The pointers are borrowed. */
+void orc_pe_load(orc_pose_estimator *e, int n, const double *xyz, const float *const *colors, float ref_ab_exposure,
+                 const float *const *new_dIp, float new_ab_exposure, const float new_cam[4]) {
   e->fx[0] = new_cam[0], e->fy[0] = new_cam[1], e->cx[0] = new_cam[2], e->cy[0] = new_cam[3]; /* makeK :62-82 */
   for (int l = 1; l < e->nlevels; l++) {
     e->fx[l] = e->fx[l - 1] * 0.5;
@@ -1442,6 +1439,22 @@ int orc_pe_estimate(orc_pose_estimator *e, int n, const double *xyz, const float
   }
   e->n = n, e->xyz = xyz, e->colors = colors, e->dIp = new_dIp;
   e->ref_exposure = ref_ab_exposure, e->new_exposure = new_ab_exposure;
+}
+/* one calcRes / calcGSSSE of the loaded inputs (calcGSSSE consumes the buffers of the last calcRes) */
+void orc_pe_calc_res(orc_pose_estimator *e, int lvl, const double pose[7], const double aff[2], float cutoff_th, double rs[6]) {
+  pe_calc_res(e, lvl, pose, aff, cutoff_th, rs);
+}
+void orc_pe_calc_gs(orc_pose_estimator *e, int lvl, const double aff[2], double H[64], double b[8]) { pe_calc_gs(e, lvl, aff, H, b); }
+int orc_pe_warped_n(orc_pose_estimator *e) { return e->bn; }
+
+/* PoseEstimator::estimate, :298-506.  Returns the reference's bool. */
+int orc_pe_estimate(orc_pose_estimator *e, int n, const double *xyz, const float *const *colors, float ref_ab_exposure,
+                    const float *const *new_dIp, float new_ab_exposure, const float new_cam[4], int coarsest_lvl,
+                    double ref_to_new_io[16], float *pose_error, int *inlier_percent_out) {
+  const int *maxIterations = e->p.max_iterations;
+  const float lambdaExtrapolationLimit = e->p.lambda_extrapolation_limit;
+  const float cutoff0 = e->p.coarse_cutoff_th;
+  orc_pe_load(e, n, xyz, colors, ref_ab_exposure, new_dIp, new_ab_exposure, new_cam);
   int lastInners[ORC_MAX_LEVELS] = {0};
   double lastResiduals[ORC_MAX_LEVELS];
   for (int i = 0; i < ORC_MAX_LEVELS; i++) lastResiduals[i] = NAN;

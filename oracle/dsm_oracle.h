@@ -98,6 +98,14 @@ int orc_pe_estimate(orc_pose_estimator *e, int n, const double *xyz, const float
                     float ref_ab_exposure, const float *const *new_dIp, float new_ab_exposure,
                     const float new_cam[4], int coarsest_lvl, double ref_to_new_io[16], float *pose_error,
                     int *inlier_percent_out);
+/* single evaluations of the same calcRes / calcGSSSE (test access, as orc_calc_res_pose / orc_calc_gs_pose / orc_pose_warped_n):
+ * orc_pe_load does what the head of estimate does (makeK :62-82, points, colours, pyramid, exposures; the pointers are borrowed and at
+ * most w * h points fit the buffers, :41-50), orc_pe_calc_gs consumes the buffers of the last orc_pe_calc_res. */
+void orc_pe_load(orc_pose_estimator *e, int n, const double *xyz, const float *const *colors, float ref_ab_exposure,
+                 const float *const *new_dIp, float new_ab_exposure, const float new_cam[4]);
+void orc_pe_calc_res(orc_pose_estimator *e, int lvl, const double pose[7], const double aff[2], float cutoff_th, double rs[6]);
+void orc_pe_calc_gs(orc_pose_estimator *e, int lvl, const double aff[2], double H[64], double b[8]);
+int orc_pe_warped_n(orc_pose_estimator *e);
 
 /* Sophus restatements exposed for property tests */
 void orc_se3_exp(const double xi[6], double pose_out[7]);

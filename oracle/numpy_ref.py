@@ -171,6 +171,73 @@ def ldlt_solve(A, b):
     return x
 
 
+def _pad4(a):
+    """zero entries up to a multiple of 4 (they count in n: quirk Q3)"""
+    a = _f(a)
+    return np.concatenate([a, np.zeros((-len(a)) % 4, np.float32)])
+
+
+def _residuals(img, wl, hl, u, v, new_id, Ku, Kv, col, huber, cutoff, aff, flow, flow_terms):
+    """the second half of a residual pass, the same text in calcResPose :786-851, calcResScale :1102-1172 and PoseEstimator::calcRes
+    (PoseEstimator.cpp:233-295): the bounds test, the gather, the residual with its Huber weight, the energy in point order, the
+    buffers of the usable points and the Vec6"""
+    with np.errstate(invalid="ignore"):
+        inb = (Ku > 2) & (Kv > 2) & (Ku < f32(wl - 3)) & (Kv < f32(hl - 3)) & (new_id > 0)  # :786 / :1102
+    idx = np.nonzero(inb)[0]
+    hit = interp33(img, Ku[idx], Kv[idx])  # :790 / :1106
+    fin = np.isfinite(hit[:, 0])
+    idx, hit = idx[fin], hit[fin]
+    refc = col[idx]
+    if aff is not None:
+        residual = hit[:, 0] - (f32(aff[0]) * refc + f32(aff[1]))  # :793
+    else:
+        residual = hit[:, 0] - refc  # :1109
+    ar = np.abs(residual)
+    with np.errstate(divide="ignore"):
+        hw = np.where(ar < huber, f32(1), huber / ar).astype(np.float32)  # :794-795
+    sat = ar > cutoff  # :797
+    max_energy = f32(f32(f32(2) * huber) * cutoff) - f32(huber * huber)  # :726-728
+    terms = np.where(sat, max_energy, ((hw * residual) * residual) * (f32(2) - hw)).astype(np.float32)  # :800 / :809
+    E = seq_sum(terms)
+    n_terms, n_sat = len(idx), int(sat.sum())
+    keep = ~sat
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rs = np.array([E, n_terms, float(flow[0]) / (float(flow[2]) + 0.1), 0.0, float(flow[1]) / (float(flow[2]) + 0.1),
+                       f32(n_sat) / f32(n_terms) if n_terms else np.nan])  # :843-851
+    buf = dict(idx=idx[keep], u=u[idx][keep], v=v[idx][keep], new_id=new_id[idx][keep], dx=hit[keep, 1], dy=hit[keep, 2],
+               residual=residual[keep], hw=hw[keep], refc=refc[keep], flow_terms=flow_terms)
+    return rs, buf
+
+
+def _pose_vectors(B, fxl, fyl, a, b0):
+    """the per-point vectors handed to Accumulator9::updateSSE_eighted -- the same text in calcGSSSEPose :658-678 and
+    PoseEstimator::calcGSSSE (PoseEstimator.cpp:101-120) -- on the buffers B of a residual pass, padded to a multiple of 4"""
+    pad = _pad4
+    dx, dy = pad(B["dx"]) * fxl, pad(B["dy"]) * fyl  # :658-659
+    u, v, idp = pad(B["u"]), pad(B["v"]), pad(B["new_id"])
+    zero, one = f32(0), f32(1)
+    J = [idp * dx, idp * dy, zero - idp * (u * dx + v * dy), zero - ((u * v) * dx + dy * (one + v * v)),
+         (u * v) * dy + dx * (one + u * u), u * dy - v * dx, a * (b0 - pad(B["refc"])), np.full(len(u), -1, np.float32),
+         pad(B["residual"])]  # :664-678
+    return J, pad(B["hw"])
+
+
+def _normal_equations(J, wgt, scales):
+    """acc.finish(), 1 / n and the SCALE_* factors (:681-696 / PoseEstimator.cpp:123-138) of the nine vectors J and the weights"""
+    n = len(wgt)
+    Hf = np.zeros((9, 9), np.float32)
+    for r in range(9):
+        Jw = J[r] * wgt
+        for c in range(r, 9):
+            Hf[r, c] = Hf[c, r] = lane_accumulate(Jw * J[c]) if n else f32(0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        invn = f32(1.0) / f32(n)
+        H = Hf[:8, :8].astype(np.float64) * float(invn)  # :682-683
+        b = Hf[:8, 8].astype(np.float64) * float(invn)
+    H = (H * scales[None, :]) * scales[:, None]  # :685-692
+    return H, b * scales, n
+
+
 class NumpyTracker:
     """TrackerAndScaler (TrackerAndScaler.h:34-137) in numpy; parameter names follow dsm_params / orc_params"""
 
@@ -247,38 +314,12 @@ class NumpyTracker:
             flow[0] = seq_sum(flow_terms[0])
             flow[1] = seq_sum(flow_terms[1])
             flow[2] = seq_sum(np.full(len(xs), 2, np.float32))
-        with np.errstate(invalid="ignore"):
-            inb = (Ku > 2) & (Kv > 2) & (Ku < f32(wl - 3)) & (Kv < f32(hl - 3)) & (new_id > 0)  # :786 / :1102
-        idx = np.nonzero(inb)[0]
-        hit = interp33(img, Ku[idx], Kv[idx])  # :790 / :1106
-        fin = np.isfinite(hit[:, 0])
-        idx, hit = idx[fin], hit[fin]
-        refc = col[idx]
-        if aff is not None:
-            residual = hit[:, 0] - (f32(aff[0]) * refc + f32(aff[1]))  # :793
-        else:
-            residual = hit[:, 0] - refc  # :1109
-        ar = np.abs(residual)
-        with np.errstate(divide="ignore"):
-            hw = np.where(ar < self.huber, f32(1), self.huber / ar).astype(np.float32)  # :794-795
-        sat = ar > cutoff  # :797
-        max_energy = f32(f32(f32(2) * self.huber) * cutoff) - f32(self.huber * self.huber)  # :726-728
-        terms = np.where(sat, max_energy, ((hw * residual) * residual) * (f32(2) - hw)).astype(np.float32)  # :800 / :809
-        E = seq_sum(terms)
-        n_terms, n_sat = len(idx), int(sat.sum())
-        keep = ~sat
         self.res_evals[lvl] += 1
-        with np.errstate(invalid="ignore", divide="ignore"):
-            rs = np.array([E, n_terms, float(flow[0]) / (float(flow[2]) + 0.1), 0.0, float(flow[1]) / (float(flow[2]) + 0.1),
-                           f32(n_sat) / f32(n_terms) if n_terms else np.nan])  # :843-851
-        buf = dict(idx=idx[keep], u=u[idx][keep], v=v[idx][keep], new_id=new_id[idx][keep], dx=hit[keep, 1], dy=hit[keep, 2],
-                   residual=residual[keep], hw=hw[keep], refc=refc[keep], flow_terms=flow_terms)
-        return rs, buf
+        return _residuals(img, wl, hl, u, v, new_id, Ku, Kv, col, self.huber, cutoff, aff, flow, flow_terms)
 
     @staticmethod
     def _pad4(a):  # :824-834: zero entries up to a multiple of 4 (they count in n: quirk Q3)
-        a = _f(a)
-        return np.concatenate([a, np.zeros((-len(a)) % 4, np.float32)])
+        return _pad4(a)
 
     def calc_res_pose(self, lvl, T, aff, cutoff):
         R = T[:3, :3].astype(np.float32)
@@ -293,33 +334,11 @@ class NumpyTracker:
     def pose_jacobian(self, lvl, aff):
         """calcGSSSEPose's per-point vectors (:658-678) on the buffers of the last calc_res_pose, padded with zero entries to a
         multiple of 4 (quirk Q3): J = the 8 tangent entries and the residual (9 float32 arrays), and the Huber weights"""
-        B = self.pose_buf
-        fxl, fyl = self.fx[lvl], self.fy[lvl]
         a = f32(aff_from_to(self.ref_exposure, self.new_exposure, self.ref_aff, aff)[0])
-        b0 = f32(self.ref_aff[1])
-        pad = self._pad4
-        dx, dy = pad(B["dx"]) * fxl, pad(B["dy"]) * fyl  # :658-659
-        u, v, idp = pad(B["u"]), pad(B["v"]), pad(B["new_id"])
-        zero, one = f32(0), f32(1)
-        J = [idp * dx, idp * dy, zero - idp * (u * dx + v * dy), zero - ((u * v) * dx + dy * (one + v * v)),
-             (u * v) * dy + dx * (one + u * u), u * dy - v * dx, a * (b0 - pad(B["refc"])), np.full(len(u), -1, np.float32),
-             pad(B["residual"])]  # :664-678
-        return J, pad(B["hw"])
+        return _pose_vectors(self.pose_buf, self.fx[lvl], self.fy[lvl], a, f32(self.ref_aff[1]))
 
     def calc_gs_pose(self, lvl, aff):  # calcGSSSEPose :640-697
-        J, wgt = self.pose_jacobian(lvl, aff)
-        n = len(wgt)
-        Hf = np.zeros((9, 9), np.float32)
-        for r in range(9):
-            Jw = J[r] * wgt
-            for c in range(r, 9):
-                Hf[r, c] = Hf[c, r] = lane_accumulate(Jw * J[c]) if n else f32(0)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            invn = f32(1.0) / f32(n)
-            H = Hf[:8, :8].astype(np.float64) * float(invn)  # :682-683
-            b = Hf[:8, 8].astype(np.float64) * float(invn)
-        H = (H * self.scales[None, :]) * self.scales[:, None]  # :685-692
-        return H, b * self.scales, n
+        return _normal_equations(*self.pose_jacobian(lvl, aff), self.scales)
 
     def calc_res_scale(self, lvl, scale, cutoff):
         R10 = self.T10[:3, :3].astype(np.float32)
@@ -478,3 +497,77 @@ class NumpyTracker:
                 have_repeated = True
             lvl -= 1
         return last[0], float(cur)  # :954, :963
+
+
+class NumpyPoseEstimator:
+    """PoseEstimator (src/loop_closure/pose_estimation/PoseEstimator.h:34-83) in numpy: one calcRes (PoseEstimator.cpp:141-296) and
+    calcGSSSE (:84-139) on loaded inputs.  Written from that text; what it shares with TrackerAndScaler.cpp word for word (the bounds
+    test onwards, the vectors of the accumulator) is shared with NumpyTracker above."""
+
+    def __init__(self, w, h, nlevels, huber=9.0, scale_xi_rot=1.0, scale_xi_trans=0.5, scale_a=10.0, scale_b=1000.0):
+        self.nl = nlevels
+        self.w = [w >> l for l in range(nlevels)]
+        self.h = [h >> l for l in range(nlevels)]
+        self.huber = f32(huber)
+        self.scales = np.array([scale_xi_rot] * 3 + [scale_xi_trans] * 3 + [scale_a, scale_b], np.float64)  # :127-138
+        self.ref_aff = (0.0, 0.0)  # ref_aff_g2l_ = AffLight(0, 0), :317
+
+    def load(self, xyz, colors, ref_ab_exposure, new_dIp, new_ab_exposure, new_cam):
+        """the head of estimate: makeK(new_cam) :62-82 / :306, pts_ :183-185, the exposures and the new frame"""
+        fx, fy, cx, cy = new_cam
+        self.fx, self.fy, self.cx, self.cy = [f32(fx)], [f32(fy)], [f32(cx)], [f32(cy)]
+        for l in range(1, self.nl):  # :72-77: float storage, double arithmetic in the expressions with 0.5
+            self.fx.append(f32(float(self.fx[l - 1]) * 0.5))
+            self.fy.append(f32(float(self.fy[l - 1]) * 0.5))
+            self.cx.append(f32((float(self.cx[0]) + 0.5) / (1 << l) - 0.5))
+            self.cy.append(f32((float(self.cy[0]) + 0.5) / (1 << l) - 0.5))
+        with np.errstate(over="ignore"):
+            self.xyz = np.asarray(xyz, np.float64).reshape(-1, 3).astype(np.float32)  # `float x = pts_[i].first(0)` :184-186
+        self.colors = [_f(c) for c in colors]  # pts_[i].second[lvl]
+        self.new_dIp = [_f(a) for a in new_dIp]
+        self.ref_exposure, self.new_exposure = ref_ab_exposure, new_ab_exposure
+
+    def _aff(self, aff):
+        return aff_from_to(self.ref_exposure, self.new_exposure, self.ref_aff, aff)  # :158-161 / :91-92
+
+    def calc_res(self, lvl, T, aff, cutoff):
+        R = T[:3, :3].astype(np.float32)  # :156
+        t = T[:3, 3].astype(np.float32)   # :157
+        fx, fy, cx, cy = self.fx[lvl], self.fy[lvl], self.cx[lvl], self.cy[lvl]
+        x, y, z = self.xyz[:, 0], self.xyz[:, 1], self.xyz[:, 2]
+        one = f32(1)
+
+        def proj(p):
+            return fx * (p[0] / p[2]) + cx, fy * (p[1] / p[2]) + cy
+
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            Ku0, Kv0 = proj((x, y, z))  # :187-190
+            pt = [((R[r, 0] * x + R[r, 1] * y) + R[r, 2] * z) + t[r] for r in range(3)]  # :192
+            u, v = pt[0] / pt[2], pt[1] / pt[2]
+            Ku, Kv = fx * u + cx, fy * v + cy
+            new_id = one / pt[2]  # :197
+            flow = np.zeros(3, np.float32)
+            flow_terms = (np.zeros(0, np.float32), np.zeros(0, np.float32))
+            if lvl == 0:  # :199-231: every 32nd point
+                s = slice(0, None, 32)
+                xs, ys, k0, l0 = x[s], y[s], Ku0[s], Kv0[s]
+                KuT, KvT = proj((xs + t[0], ys + t[1], one + t[2]))    # Vec3f(x, y, 1) + t
+                KuT2, KvT2 = proj((xs - t[0], ys - t[1], one - t[2]))  # Vec3f(x, y, 1) - t
+                Ku3, Kv3 = proj([((R[r, 0] * xs + R[r, 1] * ys) + R[r, 2]) - t[r] for r in range(3)])  # R * Vec3f(x, y, 1) - t
+                sq = lambda a, b: (a - k0) * (a - k0) + (b - l0) * (b - l0)
+                flow_terms = (np.stack([sq(KuT, KvT), sq(KuT2, KvT2)], 1).ravel(), np.stack([sq(Ku[s], Kv[s]), sq(Ku3, Kv3)], 1).ravel())
+                flow[0] = seq_sum(flow_terms[0])
+                flow[1] = seq_sum(flow_terms[1])
+                flow[2] = seq_sum(np.full(len(xs), 2, np.float32))
+        self.warp = dict(pt2=pt[2], Ku=Ku, Kv=Kv)  # (for tests that place points by their warped depth)
+        rs, self.buf = _residuals(self.new_dIp[lvl], self.w[lvl], self.h[lvl], u, v, new_id, Ku, Kv, self.colors[lvl], self.huber,
+                                  f32(cutoff), self._aff(aff), flow, flow_terms)
+        return rs
+
+    def jacobian(self, lvl, aff):
+        """calcGSSSE's nine per-point vectors (:101-120) on the buffers of the last calc_res, padded to a multiple of 4, and the
+        weights; b0 = ref_aff_g2l_.b = 0 (:90)"""
+        return _pose_vectors(self.buf, self.fx[lvl], self.fy[lvl], f32(self._aff(aff)[0]), f32(self.ref_aff[1]))
+
+    def calc_gs(self, lvl, aff):
+        return _normal_equations(*self.jacobian(lvl, aff), self.scales)

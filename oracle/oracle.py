@@ -87,6 +87,14 @@ def lib(native=False):
     L.orc_pe_estimate.argtypes = [vp, C.c_int, c_double_p, pp, C.c_float, pp, C.c_float, c_float_p, C.c_int, c_double_p,
                                   c_float_p, c_int_p]
     L.orc_pe_estimate.restype = C.c_int
+    L.orc_pe_load.argtypes = [vp, C.c_int, c_double_p, pp, C.c_float, pp, C.c_float, c_float_p]
+    L.orc_pe_load.restype = None
+    L.orc_pe_calc_res.argtypes = [vp, C.c_int, c_double_p, c_double_p, C.c_float, c_double_p]
+    L.orc_pe_calc_res.restype = None
+    L.orc_pe_calc_gs.argtypes = [vp, C.c_int, c_double_p, c_double_p, c_double_p]
+    L.orc_pe_calc_gs.restype = None
+    L.orc_pe_warped_n.argtypes = [vp]
+    L.orc_pe_warped_n.restype = C.c_int
     L.orc_se3_exp.argtypes = [c_double_p, c_double_p]
     L.orc_se3_mul.argtypes = [c_double_p, c_double_p, c_double_p]
     L.orc_quat_to_rot.argtypes = [c_double_p, c_double_p]
@@ -301,6 +309,7 @@ class OraclePoseEstimator:
         self.L = lib(native)
         self.params = params if params is not None else default_params(native)
         self.nlevels = nlevels
+        self.capacity = w * h  # the warped buffers hold w * h entries (PoseEstimator.cpp:41-50)
         self.h_ = self.L.orc_pe_create(w, h, nlevels, C.byref(self.params))
 
     def __del__(self):
@@ -318,3 +327,30 @@ class OraclePoseEstimator:
         ok = self.L.orc_pe_estimate(self.h_, len(xyz), _dp(xyz), _ptr_array(colors), ref_ab_exposure, _ptr_array(new_dIp),
                                     new_ab_exposure, _fp(cam), coarsest_lvl, _dp(T), C.byref(err), C.byref(inl))
         return bool(ok), T.reshape(4, 4), err.value, inl.value
+
+    def load(self, xyz, colors, ref_ab_exposure, new_dIp, new_ab_exposure, new_cam):
+        """the head of estimate (:306-319): makeK, the points and their colours, the new frame's pyramid, the exposures"""
+        xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        if len(xyz) > self.capacity:
+            raise ValueError("more points than level-0 pixels")
+        colors = [np.ascontiguousarray(c, np.float32) for c in colors]
+        new_dIp = [np.ascontiguousarray(a, np.float32) for a in new_dIp]
+        cam = np.ascontiguousarray(new_cam, np.float32)
+        self._keep = (xyz, colors, new_dIp, _ptr_array(colors), _ptr_array(new_dIp))  # borrowed pointers, as in the reference
+        self.L.orc_pe_load(self.h_, len(xyz), _dp(xyz), self._keep[3], ref_ab_exposure, self._keep[4], new_ab_exposure, _fp(cam))
+
+    def calc_res(self, lvl, pose, aff, cutoff):
+        pose = np.ascontiguousarray(pose, np.float64)
+        aff = np.ascontiguousarray(aff, np.float64)
+        rs = np.zeros(6)
+        self.L.orc_pe_calc_res(self.h_, lvl, _dp(pose), _dp(aff), cutoff, _dp(rs))
+        return rs
+
+    def calc_gs(self, lvl, aff):
+        aff = np.ascontiguousarray(aff, np.float64)
+        H, b = np.zeros(64), np.zeros(8)
+        self.L.orc_pe_calc_gs(self.h_, lvl, _dp(aff), _dp(H), _dp(b))
+        return H.reshape(8, 8), b
+
+    def warped_n(self):
+        return self.L.orc_pe_warped_n(self.h_)

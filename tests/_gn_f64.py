@@ -31,6 +31,22 @@ The bound, u = 2^-24, P = points per thread of the level (dsm_kernels.hpp pts_pe
       F_ij = sum over points of w (K_HUBER |J_i J_j| + K_FORM (Jt_i |J_j| + |J_i| Jt_j)).
   The scale problem's J0 differs by the gradients only (its other operations are the oracle's): the same F with
   Jt0 = Dx |deno xno| + Dy |deno yno|.
+* The loop-closure evaluation (MODE == 2, PoseEstimator.cpp:84-296; `pose2_ref` on oracle/numpy_ref.NumpyPoseEstimator) goes through the
+  same stage_b, the same tree and the same LM_OP_SINGLE_FINISH, so P, K_TREE and K_HUBER are unchanged and F has the same form with
+  Jt built from |new_id|, |u|, |v| of the mode-2 buffers.  K_FORM is re-derived from eval_chunk_impl's MODE == 2 text:
+  - the warp pt = ((R0 x + R1 y) + R2 z) + t is the oracle's operation sequence (no contraction); u and v are the IEEE quotients bit
+    for bit on both paths of stage_a (they decide the integer outputs, which are asserted equal), so they add nothing;
+  - the gradients and J0..J5 are stage_b's, as above: 10 + 7;
+  - new_idepth is r1 ITSELF, r1 = fma(fma(-pt2, r0, 1), r0, r0) with r0 = rcp(pt2) (1 + e0), |e0| <= 2^-23: the inner fma returns
+    -e0 up to 2^-47, so r1 = (1 - e0^2) / pt2 rounded once: <= u (+ 2^-46), against the oracle's correctly rounded 1 / pt2 (u): 2 u
+    |new_idepth| where modes 0 / 1 have 4 u (no product with id).  A wave with a lane outside 2^-33 <= |pt2| < 2^32 takes the IEEE
+    division: the oracle's bits.  No operand of this is subnormal inside the range (|r1| in (2^-32, 2^33]);
+  - J6 = a (0 - refColor): b0 is forced to 0 on the device (make_eval_level) and is ref_aff_g2l_.b = 0 in the reference, 0 - refColor
+    is exact and the one product is the same operation on both sides; J7 = -1 and the residual hit - (a refColor + b) likewise: Jt = 0.
+  So K_FORM2 = 10 + 2 + 7 = 19 for mode 2: a smaller constant than 21 because the quotient loses its product, and the one used.
+  The flow pass of mode 2 (shifts against (Ku0, Kv0), translation-only points (x, y, 1), divisions by z, 1 +- t2 and p3z) is the
+  oracle's operation sequence term by term, so its bound is the tree's, as below; a term that is not finite on one side is the same
+  non-finite value on the other.
 * Flow indicators: one point per thread (two adds), the tree, the float of the double sum: u K_TREE sum / (N + 0.1), all
   terms >= 0.
 """
@@ -42,6 +58,7 @@ U = 2.0 ** -24
 K_TREE = 24
 K_HUBER = 4
 K_FORM = 21
+K_FORM2 = 19
 THREADS = 256
 
 
@@ -95,21 +112,16 @@ def residual_ref(npt, lvl, T, aff, cutoff):
     return out
 
 
-def pose_ref(npt, lvl, T, aff, cutoff):
-    """one pose evaluation of NumpyTracker npt at the 4x4 pose T"""
-    rs = npt.calc_res_pose(lvl, T, aff, cutoff)
-    B = npt.pose_buf
-    J, w = npt.pose_jacobian(lvl, aff)
+def _pose_sums(out, B, J, w, fx, fy, cx, cy, img, scales, k_form):
+    """the exact sums, their absolute scales and the formation terms of one pose-like evaluation (modes 0 and 2) from the float32
+    per-point vectors J (9 x n4) and weights w of the buffers B; (fx, fy, cx, cy) and img: the level's camera and target"""
     n4 = len(w)
-    out = _common(npt, B, rs, cutoff)
-    out.update(n4=n4, idx=B["idx"], n_tpl=len(npt.pc[lvl][0]), Eterms=energy_terms(B))
     Jd = np.array(J, np.float64)  # (9, n4)
     Wd = np.asarray(w, np.float64)
     Ja = np.abs(Jd)
     # Jt: J's formulas on absolute values, the interpolated gradients replaced by their scale (see the module docstring)
-    fx, fy, cx, cy = npt.fx[lvl], npt.fy[lvl], npt.cx[lvl], npt.cy[lvl]
-    Ku, Kv = fx * B["u"] + cx, fy * B["v"] + cy  # the same float32 operations as NumpyTracker._warp
-    G = _abs_interp(npt.new_dIp[lvl], Ku, Kv)
+    Ku, Kv = fx * B["u"] + cx, fy * B["v"] + cy  # the same float32 operations as the restatement's warp
+    G = _abs_interp(img, Ku, Kv)
     Dx, Dy = _pad(G[:, 1] * float(fx), n4), _pad(G[:, 2] * float(fy), n4)
     u, v, nid = (np.abs(_pad(B[k], n4)) for k in ("u", "v", "new_id"))
     Jt = np.zeros_like(Jd)
@@ -118,16 +130,46 @@ def pose_ref(npt, lvl, T, aff, cutoff):
     Jt[3] = (u * v) * Dx + Dy * (1 + v * v)
     Jt[4] = (u * v) * Dy + Dx * (1 + u * u)
     Jt[5] = u * Dy + v * Dx
-    S9 = (Jd * Wd) @ Jd.T
-    A9 = (Ja * Wd) @ Ja.T
-    C9 = (Jt * Wd) @ Ja.T
-    F9 = K_HUBER * A9 + K_FORM * (C9 + C9.T)
+    with np.errstate(invalid="ignore", over="ignore"):
+        S9 = (Jd * Wd) @ Jd.T
+        A9 = (Ja * Wd) @ Ja.T
+        C9 = (Jt * Wd) @ Ja.T
+    F9 = K_HUBER * A9 + k_form * (C9 + C9.T)
     invn = float(np.float32(1.0) / np.float32(n4)) if n4 else 0.0
-    s = npt.scales
+    s = scales
     sc = lambda M: (M[:8, :8] * invn * s[None, :]) * s[:, None]
     scb = lambda M: M[:8, 8] * invn * s
     out.update(H64=sc(S9), b64=scb(S9), A=sc(A9), Ab=scb(A9), F=sc(F9), Fb=scb(F9), products=(Jd, Wd))
     return out
+
+
+def pose_ref(npt, lvl, T, aff, cutoff):
+    """one pose evaluation of NumpyTracker npt at the 4x4 pose T"""
+    rs = npt.calc_res_pose(lvl, T, aff, cutoff)
+    B = npt.pose_buf
+    J, w = npt.pose_jacobian(lvl, aff)
+    out = _common(npt, B, rs, cutoff)
+    out.update(n4=len(w), idx=B["idx"], n_tpl=len(npt.pc[lvl][0]), Eterms=energy_terms(B))
+    return _pose_sums(out, B, J, w, npt.fx[lvl], npt.fy[lvl], npt.cx[lvl], npt.cy[lvl], npt.new_dIp[lvl], npt.scales, K_FORM)
+
+
+def residual2_ref(npe, lvl, T, aff, cutoff):
+    """residual_ref for the loop-closure evaluation (mode 2) of NumpyPoseEstimator npe"""
+    rs = npe.calc_res(lvl, T, aff, cutoff)
+    B = npe.buf
+    out = _common(npe, B, rs, cutoff)
+    out.update(n4=(len(B["hw"]) + 3) & ~3, idx=B["idx"], n_tpl=len(npe.xyz), Eterms=energy_terms(B), buf=B)
+    return out
+
+
+def pose2_ref(npe, lvl, T, aff, cutoff):
+    """pose_ref for the loop-closure evaluation (mode 2): PoseEstimator::calcRes + calcGSSSE of NumpyPoseEstimator npe"""
+    rs = npe.calc_res(lvl, T, aff, cutoff)
+    B = npe.buf
+    J, w = npe.jacobian(lvl, aff)
+    out = _common(npe, B, rs, cutoff)
+    out.update(n4=len(w), idx=B["idx"], n_tpl=len(npe.xyz), Eterms=energy_terms(B), buf=B)
+    return _pose_sums(out, B, J, w, npe.fx[lvl], npe.fy[lvl], npe.cx[lvl], npe.cy[lvl], npe.new_dIp[lvl], npe.scales, K_FORM2)
 
 
 def scale_ref(npt, lvl, scale, cutoff):

@@ -1,5 +1,5 @@
-"""Loop-closure pose jobs for the batched estimator's tests: the loop_inputs / gt_matrix recipe of tests/test_pose_estimator.py
-(LoopHandler.cpp:166-181) and the job lists built from it.  Expected values come from oracle.OraclePoseEstimator."""
+"""Loop-closure pose inputs for the estimators' tests: the loop_inputs / gt_matrix recipe (LoopHandler.cpp:166-181), the one copy
+that tests/test_pose_estimator.py, the mode-2 evaluation tests and the golden generator share, and the job lists built from it.  Expected values come from oracle.OraclePoseEstimator."""
 import numpy as np
 
 from direct_stereo_slam_amd import synth as S

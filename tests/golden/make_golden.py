@@ -121,7 +121,7 @@ def tracker_small_fixture():
 
 def pose_estimator_fixture():
     """PoseEstimator::estimate (PoseEstimator.cpp:84-506) on 1500 loop-closure points of a 308x92 keyframe pair"""
-    from test_pose_estimator import gt_matrix, loop_inputs
+    from _pose_jobs import gt_matrix, loop_inputs
 
     sc = make_scene("small", seed=2026, a=0.01, b=2.0)
     xyz, cols = loop_inputs(sc, n=1500, seed=3)

@@ -86,3 +86,33 @@ def test_fixed_affine_modes_and_abort(built):
     good_o = orc.track(S.IDENTITY_POSE, [0, 0], sc.nl - 1, mr)[0]
     good_n = npt.track(S.IDENTITY_POSE, [0, 0], sc.nl - 1, mr)[0]
     assert good_o is False and good_n is False and npt.res_evals == orc.eval_counts()[0][:sc.nl]
+
+
+@pytest.mark.parametrize("size,seed,aff_gt,exposures", [("tiny", 81, (0.0, 0.0), (1.0, 1.0)), ("small", 82, (0.0, 0.0), (1.0, 1.0)),
+                                                        ("small", 83, (0.05, 4.0), (0.8, 1.3))])
+def test_pose_estimator_single_evaluations_bit_identical(built, size, seed, aff_gt, exposures):
+    """PoseEstimator::calcRes / calcGSSSE (PoseEstimator.cpp:84-296): the C oracle's pe_calc_res / pe_calc_gs and NumpyPoseEstimator on
+    every level, at the identity, the ground truth and three times its motion, cut-offs 20 and 5: rs, H, b and the padded count.  The
+    third case: a frame rendered with a brightness change, exposures != 1 (AffLight::fromToVecExposure at work)"""
+    import _pose_eval as PE
+    from _gn_checks import motion_3x
+    from oracle import oracle as O
+
+    inp = PE.scene_inputs(size, seed, 1500, aff=aff_gt, ref_exposure=exposures[0], new_exposure=exposures[1])
+    sc = inp.sc
+    orc, npe = O.OraclePoseEstimator(sc.w, sc.h, sc.nl), PE.numpy_estimator(inp)
+    orc.load(*inp.args())
+    seen = 0
+    for lvl in range(sc.nl):
+        for pose, aff in [(S.IDENTITY_POSE, [0.0, 0.0]), (sc.gt_pose, list(aff_gt)), (motion_3x(sc.gt_pose), list(aff_gt))]:
+            for cutoff in (20.0, 5.0):
+                rs_o = orc.calc_res(lvl, pose, aff, cutoff)
+                H_o, b_o = orc.calc_gs(lvl, aff)
+                rs_n = npe.calc_res(lvl, N.pose_to_matrix(np.asarray(pose, float)), aff, cutoff)
+                H_n, b_n, n_n = npe.calc_gs(lvl, aff)
+                assert n_n == orc.warped_n()
+                np.testing.assert_array_equal(rs_n, rs_o)
+                np.testing.assert_array_equal(H_n, H_o)
+                np.testing.assert_array_equal(b_n, b_o)
+                seen += n_n
+    assert seen > 0

@@ -4,41 +4,10 @@ kernels in mode 2) against the oracle."""
 import numpy as np
 import pytest
 
-from direct_stereo_slam_amd import synth as S
 from oracle import oracle as O
 
+from _pose_jobs import gt_matrix, loop_inputs
 from _scenes import make_scene
-
-
-def bilinear(img, x, y):
-    ix, iy = np.floor(x).astype(int), np.floor(y).astype(int)
-    dx, dy = (x - ix).astype(np.float32), (y - iy).astype(np.float32)
-    return (dx * dy * img[iy + 1, ix + 1] + (dy - dx * dy) * img[iy + 1, ix] + (dx - dx * dy) * img[iy, ix + 1]
-            + (1 - dx - dy + dx * dy) * img[iy, ix]).astype(np.float32)
-
-
-def loop_inputs(sc, n=1500, seed=0):
-    """what LoopHandler::publishKeyframes stores per keyframe (LoopHandler.cpp:166-181): 3-D points in the
-    keyframe and their reference intensity on every pyramid level"""
-    rng = np.random.default_rng(seed)
-    fx, fy, cx, cy = sc.K
-    u = rng.uniform(4, sc.w - 5, n)
-    v = rng.uniform(4, sc.h - 5, n)
-    idl0 = sc.scene.idepth(sc.K, sc.w, sc.h)
-    idp = bilinear(idl0, u, v).astype(np.float64)
-    xyz = np.stack([(u - cx) / fx / idp, (v - cy) / fy / idp, 1 / idp], 1)
-    cols = []
-    for l in range(sc.nl):
-        ul, vl = (u + 0.5) / (1 << l) - 0.5, (v + 0.5) / (1 << l) - 0.5
-        cols.append(bilinear(sc.ref_p[l][..., 0], np.clip(ul, 0, (sc.w >> l) - 2), np.clip(vl, 0, (sc.h >> l) - 2)))
-    return xyz, cols
-
-
-def gt_matrix(sc):
-    T = np.eye(4)
-    T[:3, :3] = S.quat_to_rot(sc.gt_pose[:4])
-    T[:3, 3] = sc.gt_pose[4:]
-    return T
 
 
 def test_oracle_pose_estimator_recovers_ground_truth():
