@@ -265,6 +265,8 @@ SYMBOLS = {
     "dsm_diag_pose_estimator_eval": (C.c_int, [_vp, C.c_int, c_double_p, _pp_f, C.c_float, _pp_f, C.c_float, c_float_p, C.c_int, c_double_p, c_double_p,
                                                C.c_float, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
     "dsm_diag_lm_propose": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmProposeIn), C.c_int, C.c_int, C.POINTER(LmProposeOut)]),
+    "dsm_diag_icp_stages": (C.c_int, [_vp, C.c_int, C.POINTER(IcpJob), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
+                                      c_float_p, C.POINTER(C.c_uint64), _vp]),
     "dsm_tracker_track": (C.c_int, [_vp, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
     "dsm_tracker_optimize_scale": (C.c_int, [_vp, c_float_p, C.c_int, c_float_p]),
     "dsm_tracker_optimize_scale_guesses": (C.c_int, [_vp, C.c_int, c_float_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),

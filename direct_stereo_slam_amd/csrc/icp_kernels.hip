@@ -1,6 +1,6 @@
 // icp_kernels.hip -- the ICP fallback of loop closure (icp.h:44-71, called at LoopHandler.cpp:284-288 when direct alignment rejects a
 // ScanContext match) on the device, batched over independent matches: PCL's IterativeClosestPoint<PointXYZ, PointXYZ> with the
-// reference's settings, restated as the quirks P1-P9 / deviations D1-D4 of DESIGN.md section 10.
+// reference's settings, restated as the quirks P1-P9 / deviations D1-D5 of DESIGN.md section 10.
 //
 // One call = one launch sequence and one read-back:
 //   icp_prep_kernel      (one workgroup per job)  P1: both clouds to float, the guess applied in double; state reset
@@ -13,9 +13,12 @@
 //                        float increment, the convergence tests, final = inc * final, the working cloud moved; keys reset
 //   icp_fitness_prep_kernel + icp_nn_kernel + icp_fitness_kernel  P9: the original source moved by `final`, unbounded search, mean
 // A job whose state is final leaves every later launch at its first instruction: no host round trip per iteration.
+// The sequence is written once (icp_launch): dsm_icp_batch runs it to its end, the test aid dsm_diag_icp_stages stops inside it.
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "call_arena.hpp"
@@ -243,33 +246,48 @@ bool finite16(const double *m) {
   return true;
 }
 
-} // namespace
-
-extern "C" {
-
-// replaces icp() (src/loop_closure/pose_estimation/icp.h:44-71) for a batch of independent matches
-int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_iterations, double transformation_epsilon, double max_corr_dist,
-                  double score_thres) {
-  // all-or-nothing validation: nothing is written before every job has passed
-  if (!ctx || n_jobs < 1 || !jobs || max_iterations < 1 || max_iterations > kIcpIterationsLimit || !std::isfinite(transformation_epsilon) ||
-      !std::isfinite(max_corr_dist) || max_corr_dist < 0 || std::isnan(score_thres))
-    return invalid("dsm_icp_batch: bad argument");
+// what one launch sequence leaves bound in the context's arena: the device-only clouds and keys, and the states (read back by fetch)
+struct IcpRun {
+  CallArena A;
   long long tot_src = 0, tot_tgt = 0;
+  float4 *orig = nullptr, *work = nullptr, *tgt = nullptr;
+  unsigned long long *keys = nullptr;
+  size_t o_states = 0;
+};
+
+// all-or-nothing validation of a call (`who`: "dsm_icp_batch: " ...); outputs: the job's result pointers are required
+int icp_validate(const char *who, dsm_context *ctx, int n_jobs, const dsm_icp_job *jobs, int max_iterations, double transformation_epsilon,
+                 double max_corr_dist, bool outputs) {
+  const std::string w(who);
+  if (!ctx || n_jobs < 1 || !jobs || max_iterations < 1 || max_iterations > kIcpIterationsLimit || !std::isfinite(transformation_epsilon) ||
+      !std::isfinite(max_corr_dist) || max_corr_dist < 0)
+    return invalid((w + "bad argument").c_str());
   for (int j = 0; j < n_jobs; j++) {
     const dsm_icp_job &J = jobs[j];
     if (J.n_src < 0 || J.n_tgt < 0 || J.n_src > DSM_ICP_MAX_POINTS || J.n_tgt > DSM_ICP_MAX_POINTS || (J.n_src && !J.src_xyz) ||
-        (J.n_tgt && !J.tgt_xyz) || !J.tfm_target_source || !J.score || !J.ok || !J.iterations || !J.state)
-      return invalid("dsm_icp_batch: bad job");
-    if (!finite16(J.tfm_target_source)) return invalid("dsm_icp_batch: non-finite guess");
-    tot_src += J.n_src, tot_tgt += J.n_tgt;
+        (J.n_tgt && !J.tgt_xyz) || !J.tfm_target_source || (outputs && (!J.score || !J.ok || !J.iterations || !J.state)))
+      return invalid((w + "bad job").c_str());
+    if (!finite16(J.tfm_target_source)) return invalid((w + "non-finite guess").c_str());
   }
+  return DSM_OK;
+}
+
+// The launch sequence of one call, from the block table to the last kernel of `stop_stage` (DSM_ICP_STAGE_*; the searches and steps of
+// the iterations are told apart by `stop_iteration`, 0-based).  dsm_icp_batch runs it to its end under the production slice rule
+// (force_slices = 0); dsm_diag_icp_stages stops inside it and may force the number of target slices a job is cut into.  Nothing is
+// read back here: the caller fetches the states, or copies the device buffers of `run` out, on the context's stream.
+int icp_launch(dsm_context *ctx, int n_jobs, const dsm_icp_job *jobs, int max_iterations, double transformation_epsilon, double max_corr_dist,
+               int force_slices, int stop_stage, int stop_iteration, IcpRun &run) {
+  long long tot_src = 0, tot_tgt = 0;
+  for (int j = 0; j < n_jobs; j++) tot_src += jobs[j].n_src, tot_tgt += jobs[j].n_tgt;
+  run.tot_src = tot_src, run.tot_tgt = tot_tgt;
   // the call's blocks of the search: as many target slices per job as bring the call to about 2048 workgroups, at least one tile each
   std::vector<IcpJobDev> hj(n_jobs);
   std::vector<IcpNnBlock> blocks;
   long long src_blocks = 0;
   for (int j = 0; j < n_jobs; j++)
     if (jobs[j].n_src && jobs[j].n_tgt) src_blocks += (jobs[j].n_src + kIcpThreads - 1) / kIcpThreads;
-  const long long want_slices = src_blocks ? (2048 + src_blocks - 1) / src_blocks : 1;
+  const long long want_slices = force_slices > 0 ? force_slices : src_blocks ? (2048 + src_blocks - 1) / src_blocks : 1;
   long long os = 0, ot = 0;
   for (int j = 0; j < n_jobs; j++) {
     const dsm_icp_job &J = jobs[j];
@@ -284,7 +302,7 @@ int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_itera
       for (int t0 = 0; t0 < J.n_tgt; t0 += per) blocks.push_back(IcpNnBlock{j, s0, t0, std::min(J.n_tgt, t0 + per)});
   }
   // staged [jobs | blocks | source xyz | target xyz], device-only [orig | work | target | keys], read back [states]
-  CallArena A;
+  CallArena &A = run.A;
   const size_t o_jobs = A.in.take(sizeof(IcpJobDev) * n_jobs), o_blocks = A.in.take(sizeof(IcpNnBlock) * std::max<size_t>(1, blocks.size()));
   const size_t o_src = A.in.take(sizeof(double) * 3 * (size_t)tot_src), o_tgt = A.in.take(sizeof(double) * 3 * (size_t)tot_tgt);
   const size_t b_f4s = sizeof(float4) * (size_t)std::max(1ll, tot_src), b_f4t = sizeof(float4) * (size_t)std::max(1ll, tot_tgt);
@@ -304,27 +322,58 @@ int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_itera
   float4 *orig = A.dev_work<float4>(o_orig), *work = A.dev_work<float4>(o_work), *tgt = A.dev_work<float4>(o_tgt4);
   unsigned long long *keys = A.dev_work<unsigned long long>(o_keys);
   IcpState *d_states = A.dev_out<IcpState>(o_states);
+  run.orig = orig, run.work = work, run.tgt = tgt, run.keys = keys, run.o_states = o_states;
   hipStream_t st = ctx->stream;
   if ((rc = A.upload())) return rc;
   const int nb = (int)blocks.size();
   const double max_dist2 = max_corr_dist * max_corr_dist;
+  const auto stops = [&](int stage, int it) { return stop_stage == stage && (it < 0 || it == stop_iteration); };
   hipLaunchKernelGGL(icp_prep_kernel, dim3(n_jobs), dim3(kIcpThreads), 0, st, dj, d_src, d_tgt, orig, work, tgt, keys, d_states);
-  for (int it = 0; it < max_iterations && nb; it++) {
+  bool stopped = stops(DSM_ICP_STAGE_PREP, -1);
+  for (int it = 0; it < max_iterations && nb && !stopped; it++) {
     hipLaunchKernelGGL(icp_nn_kernel, dim3(nb), dim3(kIcpThreads), 0, st, db, dj, (const IcpState *)d_states, (const float4 *)work,
                        (const float4 *)tgt, keys, 0);
+    if ((stopped = stops(DSM_ICP_STAGE_SEARCH, it))) break;
     hipLaunchKernelGGL(icp_step_kernel, dim3(n_jobs), dim3(kIcpThreads), 0, st, dj, d_states, work, (const float4 *)tgt, keys,
                        max_iterations, transformation_epsilon, max_dist2);
+    stopped = stops(DSM_ICP_STAGE_STEP, it);
   }
-  if (nb) {
+  if (nb && !stopped) {
     hipLaunchKernelGGL(icp_fitness_prep_kernel, dim3(n_jobs), dim3(kIcpThreads), 0, st, dj, (const IcpState *)d_states, (const float4 *)orig,
                        work, keys);
+    stopped = stops(DSM_ICP_STAGE_FITNESS_PREP, -1);
+  }
+  if (nb && !stopped) {
     hipLaunchKernelGGL(icp_nn_kernel, dim3(nb), dim3(kIcpThreads), 0, st, db, dj, (const IcpState *)d_states, (const float4 *)work,
                        (const float4 *)tgt, keys, 1);
-    hipLaunchKernelGGL(icp_fitness_kernel, dim3(n_jobs), dim3(kIcpThreads), 0, st, dj, d_states, (const unsigned long long *)keys);
+    stopped = stops(DSM_ICP_STAGE_FITNESS_SEARCH, -1);
   }
+  if (nb && !stopped)
+    hipLaunchKernelGGL(icp_fitness_kernel, dim3(n_jobs), dim3(kIcpThreads), 0, st, dj, d_states, (const unsigned long long *)keys);
   DSM_HIP(hipGetLastError());
-  if ((rc = A.fetch(sizeof(IcpState) * n_jobs))) return rc;
-  const IcpState *h_states = A.host_out<IcpState>(o_states);
+  return DSM_OK;
+}
+
+// the public mirror of the per-job state is the state itself
+static_assert(sizeof(dsm_icp_state) == sizeof(IcpState) && offsetof(dsm_icp_state, prev_mse) == offsetof(IcpState, prev_mse) &&
+                  offsetof(dsm_icp_state, fitness) == offsetof(IcpState, fitness) && offsetof(dsm_icp_state, state) == offsetof(IcpState, state) &&
+                  offsetof(dsm_icp_state, searches) == offsetof(IcpState, searches) && offsetof(dsm_icp_state, corr) == offsetof(IcpState, corr),
+              "dsm_icp_state (include/dsm_hotpath.h) mirrors IcpState");
+
+} // namespace
+
+extern "C" {
+
+// replaces icp() (src/loop_closure/pose_estimation/icp.h:44-71) for a batch of independent matches
+int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_iterations, double transformation_epsilon, double max_corr_dist,
+                  double score_thres) {
+  if (std::isnan(score_thres)) return invalid("dsm_icp_batch: bad argument");
+  int rc = icp_validate("dsm_icp_batch: ", ctx, n_jobs, jobs, max_iterations, transformation_epsilon, max_corr_dist, true);
+  if (rc) return rc;
+  IcpRun run;
+  if ((rc = icp_launch(ctx, n_jobs, jobs, max_iterations, transformation_epsilon, max_corr_dist, 0, DSM_ICP_STAGE_FITNESS, 0, run))) return rc;
+  if ((rc = run.A.fetch(sizeof(IcpState) * n_jobs))) return rc;
+  const IcpState *h_states = run.A.host_out<IcpState>(run.o_states);
   for (int j = 0; j < n_jobs; j++) {
     dsm_icp_job &J = jobs[j];
     const IcpState &S = h_states[j];
@@ -347,6 +396,31 @@ int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_itera
     *J.score = (float)S.fitness; // P9
     *J.ok = (double)*J.score < score_thres ? 1 : 0;
   }
+  return DSM_OK;
+}
+
+
+// test aid: the same launch sequence stopped after a stage, the device's buffers copied out (include/dsm_hotpath.h)
+int dsm_diag_icp_stages(dsm_context *ctx, int n_jobs, const dsm_icp_job *jobs, int max_iterations, double transformation_epsilon,
+                        double max_corr_dist, int want_slices, int stop_stage, int stop_iteration, float *orig_xyzw, float *work_xyzw,
+                        float *target_xyzw, unsigned long long *keys, dsm_icp_state *states) {
+  int rc = icp_validate("dsm_diag_icp_stages: ", ctx, n_jobs, jobs, max_iterations, transformation_epsilon, max_corr_dist, false);
+  if (rc) return rc;
+  const bool per_iteration = stop_stage == DSM_ICP_STAGE_SEARCH || stop_stage == DSM_ICP_STAGE_STEP;
+  if (want_slices < 0 || stop_stage < DSM_ICP_STAGE_PREP || stop_stage > DSM_ICP_STAGE_FITNESS ||
+      (per_iteration && (stop_iteration < 0 || stop_iteration >= max_iterations)))
+    return invalid("dsm_diag_icp_stages: bad want_slices, stage or iteration");
+  IcpRun run;
+  if ((rc = icp_launch(ctx, n_jobs, jobs, max_iterations, transformation_epsilon, max_corr_dist, want_slices, stop_stage, stop_iteration, run)))
+    return rc;
+  hipStream_t st = ctx->stream;
+  const size_t b_src = sizeof(float4) * (size_t)run.tot_src, b_tgt = sizeof(float4) * (size_t)run.tot_tgt;
+  if (orig_xyzw && b_src) DSM_HIP(hipMemcpyAsync(orig_xyzw, run.orig, b_src, hipMemcpyDeviceToHost, st));
+  if (work_xyzw && b_src) DSM_HIP(hipMemcpyAsync(work_xyzw, run.work, b_src, hipMemcpyDeviceToHost, st));
+  if (target_xyzw && b_tgt) DSM_HIP(hipMemcpyAsync(target_xyzw, run.tgt, b_tgt, hipMemcpyDeviceToHost, st));
+  if (keys && run.tot_src) DSM_HIP(hipMemcpyAsync(keys, run.keys, sizeof(unsigned long long) * (size_t)run.tot_src, hipMemcpyDeviceToHost, st));
+  if ((rc = run.A.fetch(sizeof(IcpState) * n_jobs))) return rc; // drains the stream: the copies above have landed
+  if (states) memcpy(states, run.A.host_out<IcpState>(run.o_states), sizeof(IcpState) * n_jobs);
   return DSM_OK;
 }
 

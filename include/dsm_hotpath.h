@@ -833,7 +833,7 @@ int dsm_loop_detect_batch_many(dsm_context *ctx, int n_jobs, const dsm_loop_job 
 /* The ICP fallback of loop closure: replaces icp() (src/loop_closure/pose_estimation/icp.h:44-71), which LoopHandler::run calls when direct
  * alignment rejects a ScanContext match (LoopHandler.cpp:284-288) -- PCL's IterativeClosestPoint<PointXYZ, PointXYZ> with the settings of
  * icp.h:58-61 -- batched over independent matches (of one sequence or of several).  Semantics: DESIGN.md section 10, quirks P1-P9 and
- * deviations D1-D4; in short, per job:
+ * deviations D1-D5; in short, per job:
  *   - the source (matched keyframe's pts_spherical) is moved by the guess tfm_target_source in double and rounded to float, the target
  *     (current keyframe's pts_spherical) rounded to float;
  *   - up to max_iterations rounds of: exact nearest target of every source point, pairs kept within max_corr_dist, Umeyama (no scale)
@@ -843,10 +843,10 @@ int dsm_loop_detect_batch_many(dsm_context *ctx, int n_jobs, const dsm_loop_job 
  *   - an empty source or target (D3) leaves tfm_target_source unchanged: score = +inf, ok = 0, iterations = 0, state = EMPTY.
  * The RANSAC threshold of icp.h:61 has no effect in PCL (no rejector is installed): it is not a parameter (P7).
  * One launch sequence and one read-back for the whole batch; a job's results do not depend on the other jobs of the call.  Points are
- * expected finite.  Validation is all or nothing, before any output is written: DSM_ERR_INVALID for NULL pointers, negative sizes or more
- * than DSM_ICP_MAX_POINTS points, max_iterations outside [1, DSM_ICP_ITERATIONS_LIMIT], a non-finite or negative max_corr_dist, a
- * non-finite transformation_epsilon, a NaN score_thres or a non-finite guess.  The steady state allocates nothing (the loop chain's
- * device arena and page-locked mirror of the context). */
+ * expected finite; they are not validated, and D5 says what a non-finite coordinate does.  Validation is all or nothing, before any
+ * output is written: DSM_ERR_INVALID for NULL pointers, negative sizes or more than DSM_ICP_MAX_POINTS points, max_iterations outside
+ * [1, DSM_ICP_ITERATIONS_LIMIT], a non-finite or negative max_corr_dist, a non-finite transformation_epsilon, a NaN score_thres or a
+ * non-finite guess.  The steady state allocates nothing (the loop chain's device arena and page-locked mirror of the context). */
 #define DSM_ICP_MAX_ITERATIONS 5                /* icp.h:58 setMaximumIterations */
 #define DSM_ICP_TRANSFORMATION_EPSILON 0.01     /* icp.h:59 setTransformationEpsilon */
 #define DSM_ICP_MAX_CORRESPONDENCE_DISTANCE 2.0 /* icp.h:60 setMaxCorrespondenceDistance */
@@ -876,6 +876,39 @@ typedef struct dsm_icp_job {
 } dsm_icp_job;
 int dsm_icp_batch(dsm_context *ctx, int n_jobs, dsm_icp_job *jobs, int max_iterations, double transformation_epsilon, double max_corr_dist,
                   double score_thres);
+
+/* test aid (no reference counterpart): dsm_icp_batch's own launch sequence -- the same block table, arena layout, staging and kernels,
+ * one function serves both -- stopped after a stage, with what the device holds there copied out.  Stages in launch order:
+ * prep (P1); search and step (P2; P3-P6) of iteration stop_iteration (0-based, < max_iterations); fitness prep, fitness search and
+ * fitness (P9); DSM_ICP_STAGE_FITNESS is the whole sequence.  A batch none of whose jobs has points runs the prep alone.
+ * want_slices: the number of target slices a job's search is cut into (at least one 256-point tile each, so at most that many
+ * tiles); 0 = the production rule (about 2048 workgroups per call), under which the states after DSM_ICP_STAGE_FITNESS are bit for bit
+ * what dsm_icp_batch unpacks.  Of a job only the inputs are read (n_src, src_xyz, n_tgt, tgt_xyz, tfm_target_source); nothing of it is
+ * written.  Outputs, each optional (NULL), the jobs back to back in call order: orig / work (the guess-moved source and the working
+ * cloud) and target as float x, y, z, 0 per point; keys, one per source point: (float bits of dist2 << 32) | target index,
+ * DSM_ICP_NO_KEY where the point has no neighbour (yet); states, one per job.  DSM_ERR_INVALID with nothing written for what
+ * dsm_icp_batch refuses of these arguments, want_slices < 0, an unknown stage or an iteration outside [0, max_iterations).
+ * No production path calls this. */
+#define DSM_ICP_STAGE_PREP 0
+#define DSM_ICP_STAGE_SEARCH 1
+#define DSM_ICP_STAGE_STEP 2
+#define DSM_ICP_STAGE_FITNESS_PREP 3
+#define DSM_ICP_STAGE_FITNESS_SEARCH 4
+#define DSM_ICP_STAGE_FITNESS 5
+#define DSM_ICP_NO_KEY 0xFFFFFFFFFFFFFFFFull
+typedef struct dsm_icp_state {  /* what the device keeps per job between the launches of a call */
+  float final_tf[16];           /* PCL's final_transformation_, row-major */
+  double prev_mse;              /* mean dist2 of the last iteration that went on (DBL_MAX before the first) */
+  double fitness;               /* getFitnessScore() before its cast to float (+inf until the fitness stage) */
+  int state;                    /* DSM_ICP_STATE_*, 0 while iterating */
+  int iterations;               /* increments applied */
+  int searches;                 /* correspondence searches evaluated: iterations, plus the one that found fewer than 3 pairs */
+  int pad;
+  int corr[DSM_ICP_ITERATIONS_LIMIT]; /* pairs kept by each search, -1 past the last */
+} dsm_icp_state;
+int dsm_diag_icp_stages(dsm_context *ctx, int n_jobs, const dsm_icp_job *jobs, int max_iterations, double transformation_epsilon,
+                        double max_corr_dist, int want_slices, int stop_stage, int stop_iteration, float *orig_xyzw, float *work_xyzw,
+                        float *target_xyzw, unsigned long long *keys, dsm_icp_state *states);
 
 /* ---- CoarseDistanceMap and the activation walk -------------------------------------------------------------
  * replaces dso::CoarseDistanceMap (TrackerAndScaler.h:139-170, TrackerAndScaler.cpp:1174-1362) and the distance-map part of

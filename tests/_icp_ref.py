@@ -1,8 +1,12 @@
-"""Test infrastructure: a numpy restatement of the ICP fallback's contract (P1-P9, D1-D3), the checker the device
+"""Test infrastructure: a numpy restatement of the ICP fallback's contract (P1-P9, D1-D5), the checker the device
 (dsm_icp_batch) is compared against.  Per-point arithmetic is float32 with the stated operation orders (a numpy float32 operation is one
 IEEE operation, so distances, correspondences and counts can match the device bit for bit); the moments are float64 (D1) and the SVD is
 numpy's (the device runs its own Jacobi SVD: the float increments agree to rounding).  Sums that the contract orders by source index
-(the MSE of P6 and the fitness of P9) are summed in that order here; the device sums them in a fixed tree order (D4)."""
+(the MSE of P6 and the fitness of P9) are summed in that order here; the device sums them in a fixed tree order (D4).
+For the stage-by-stage tests (tests/test_icp_stages.py): exact_step and exact_mean are the correctly rounded sums the device's step and
+fitness are bounded against, block_sum_order restates the device's own order of a sum."""
+import math
+
 import numpy as np
 
 ITERATIONS, TRANSFORM, ABS_MSE, NO_CORRESPONDENCES, EMPTY = 1, 2, 3, 5, 6
@@ -29,18 +33,26 @@ def transform_float(T, p):
 
 def nearest(src, tgt, chunk=256):
     """P2 / P9: exact nearest target of every source point by ((dx dx) + dy dy) + dz dz in float32 (d = source - target); argmin keeps
-    the first minimum, i.e. the smallest target index of a tie (D2).  Returns (index int64, dist2 float32)."""
+    the first minimum, i.e. the smallest target index of a tie (D2).  D5: a distance that is not finite (NaN or +inf) is never a
+    minimum; a source point without a finite distance has index -1 and distance NaN (no key).
+    Returns (index int64, dist2 float32)."""
     idx = np.empty(len(src), np.int64)
     dist = np.empty(len(src), np.float32)
+    tgt_finite = bool(np.isfinite(tgt).all())
     for a in range(0, len(src), chunk):
         s = src[a:a + chunk]
-        dx = s[:, 0:1] - tgt[None, :, 0]
-        dy = s[:, 1:2] - tgt[None, :, 1]
-        dz = s[:, 2:3] - tgt[None, :, 2]
-        d = (dx * dx + dy * dy) + dz * dz
+        with np.errstate(over="ignore", invalid="ignore"):
+            dx = s[:, 0:1] - tgt[None, :, 0]
+            dy = s[:, 1:2] - tgt[None, :, 1]
+            dz = s[:, 2:3] - tgt[None, :, 2]
+            d = (dx * dx + dy * dy) + dz * dz
+        if not (tgt_finite and np.isfinite(s).all()):  # finite points give a finite or a +inf (overflowed) distance, never a NaN
+            d = np.where(np.isnan(d), np.float32(np.inf), d)
         i = np.argmin(d, axis=1)
-        idx[a:a + chunk] = i
-        dist[a:a + chunk] = d[np.arange(len(s)), i]
+        di = d[np.arange(len(s)), i]
+        none = ~np.isfinite(di)
+        idx[a:a + chunk] = np.where(none, -1, i)
+        dist[a:a + chunk] = np.where(none, np.float32(np.nan), di)
     return idx, dist
 
 
@@ -65,8 +77,54 @@ def ordered_sum(x):
     return float(np.cumsum(x)[-1]) if len(x) else 0.0
 
 
-def icp(src, tgt, tfm, max_iterations=5, eps=0.01, max_corr_dist=2.0, score_thres=1.5):
-    """icp.h:44-71 with PCL's semantics as restated in P1-P9: returns dict(ok, tfm, score, iterations, state, corr_counts)"""
+def exact_step(work, target, idx, keep):
+    """P4 without D1's order: the increment of the kept pairs (work[i], target[idx[i]]) from correctly rounded sums -- the means are
+    math.fsum of the float coordinates as doubles over n, Sigma is math.fsum of the products of the coordinates centred on those means
+    over n -- then numpy's SVD and the determinant fix.  Returns (R, t) in double."""
+    s = np.asarray(work, np.float64)[keep]
+    d = np.asarray(target, np.float64)[np.asarray(idx)[keep]]
+    n = len(s)
+    sm = np.array([math.fsum(s[:, c]) for c in range(3)]) / n
+    dm = np.array([math.fsum(d[:, c]) for c in range(3)]) / n
+    sc, dc = s - sm, d - dm
+    sigma = np.array([[math.fsum(dc[:, r] * sc[:, c]) for c in range(3)] for r in range(3)]) / n
+    U, _, Vt = np.linalg.svd(sigma)
+    S = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2] = -1.0
+    Rm = U @ np.diag(S) @ Vt
+    return Rm, dm - Rm @ sm
+
+
+def exact_mean(d):
+    """P6 / P9 without D4's order: math.fsum of the float distances as doubles, over their number"""
+    d = np.asarray(d, np.float64)
+    return math.fsum(d) / len(d)
+
+
+def block_sum_order(x, lanes=256):
+    """D1 / D4: the sum of one double per source point in the device's order -- lane t of 256 adds x[t], x[t + 256], ... in turn from
+    0.0 (a point that is not a kept pair is passed as 0.0: the lane skips it), then the halving tree red[t] += red[t + s] for
+    s = 128, 64, .. 1.  Every operation is one IEEE double addition, as on the device."""
+    x = np.asarray(x, np.float64).ravel()
+    rows = -(-len(x) // lanes)
+    padded = np.zeros(rows * lanes)
+    padded[:len(x)] = x
+    red = np.zeros(lanes)
+    for row in padded.reshape(rows, lanes):
+        red = red + row
+    s = lanes // 2
+    while s > 0:
+        red[:s] = red[:s] + red[s:2 * s]
+        s //= 2
+    return float(red[0])
+
+
+def icp(src, tgt, tfm, max_iterations=5, eps=0.01, max_corr_dist=2.0, score_thres=1.5, trace=None, search=None):
+    """icp.h:44-71 with PCL's semantics as restated in P1-P9: returns dict(ok, tfm, score, iterations, state, corr_counts).
+    trace: a list that receives dict(work, final, inc) after every increment (the iterated cloud and both float matrices);
+    search: a stand-in for `nearest` (tests of the tests: what a wrong search does to the result)"""
+    search = nearest if search is None else search
     guess = np.asarray(tfm, np.float64).reshape(4, 4)
     src = np.asarray(src, np.float64).reshape(-1, 3)
     tgt = np.asarray(tgt, np.float64).reshape(-1, 3)
@@ -80,7 +138,7 @@ def icp(src, tgt, tfm, max_iterations=5, eps=0.01, max_corr_dist=2.0, score_thre
     it, state, counts = 0, 0, []
     max_d2 = max_corr_dist * max_corr_dist
     while state == 0:
-        idx, d = nearest(work, target)
+        idx, d = search(work, target)
         keep = d.astype(np.float64) <= max_d2
         n = int(keep.sum())
         counts.append(n)
@@ -98,6 +156,8 @@ def icp(src, tgt, tfm, max_iterations=5, eps=0.01, max_corr_dist=2.0, score_thre
                 F[r, c] = ((inc[r, 0] * final[0, c] + inc[r, 1] * final[1, c]) + inc[r, 2] * final[2, c]) + inc[r, 3] * final[3, c]
         final = F
         it += 1
+        if trace is not None:
+            trace.append(dict(work=work.copy(), final=final.copy(), inc=inc.copy()))
         cos_angle = 0.5 * float(((inc[0, 0] + inc[1, 1]) + inc[2, 2]) - np.float32(1))
         tr2 = (inc[0, 3] * inc[0, 3] + inc[1, 3] * inc[1, 3]) + inc[2, 3] * inc[2, 3]
         if it >= max_iterations:  # P6, in PCL's order
@@ -113,7 +173,7 @@ def icp(src, tgt, tfm, max_iterations=5, eps=0.01, max_corr_dist=2.0, score_thre
     for r in range(4):
         for c in range(4):
             out[r, c] = ((Fd[r, 0] * guess[0, c] + Fd[r, 1] * guess[1, c]) + Fd[r, 2] * guess[2, c]) + Fd[r, 3] * guess[3, c]
-    _, dfit = nearest(transform_float(final, orig), target)  # P9: the original source, no distance limit
+    _, dfit = search(transform_float(final, orig), target)  # P9: the original source, no distance limit
     score = np.float32(ordered_sum(dfit) / len(dfit))
     return dict(ok=bool(float(score) < score_thres), tfm=out, score=score, iterations=it, state=state, corr_counts=counts)
 

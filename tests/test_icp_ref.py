@@ -1,5 +1,5 @@
 """CPU: the ICP fallback's interface (dsm_icp_batch) is exported and bound, the numpy checker (tests/_icp_ref.py) behaves as the contract
-P1-P9 says, the device's Umeyama step (csrc/icp_internal.hpp, built for the host) equals the checker's, and the C++ adaptor compiles."""
+P1-P9 says and its exact sums are exact, the device's Umeyama step (csrc/icp_internal.hpp, built for the host) equals the checker's, and the C++ adaptor compiles."""
 import ctypes as C
 import os
 import re
@@ -18,6 +18,7 @@ def test_icp_symbols_exported_and_bound(built):
 
     L = _lib.load()
     assert hasattr(L, "dsm_icp_batch") and "dsm_icp_batch" in _lib.SYMBOLS
+    assert hasattr(L, "dsm_diag_icp_stages") and "dsm_diag_icp_stages" in _lib.SYMBOLS
     assert [f[0] for f in _lib.IcpJob._fields_] == ["n_src", "src_xyz", "n_tgt", "tgt_xyz", "tfm_target_source", "score", "ok", "iterations",
                                                     "state", "corr_counts"]
     hdr = open(os.path.join(ROOT, "include", "dsm_hotpath.h")).read()
@@ -29,6 +30,14 @@ def test_icp_symbols_exported_and_bound(built):
     assert int(consts["DSM_ICP_ITERATIONS_LIMIT"]) == icp.ITERATIONS_LIMIT
     for name, value in (("ITERATIONS", 1), ("TRANSFORM", 2), ("ABS_MSE", 3), ("NO_CORRESPONDENCES", 5), ("EMPTY", 6)):
         assert int(consts["DSM_ICP_STATE_" + name]) == value == getattr(R, name)
+    # the test aid's stages, "no key" value and state record are the header's
+    for k, name in enumerate(("PREP", "SEARCH", "STEP", "FITNESS_PREP", "FITNESS_SEARCH", "FITNESS")):
+        assert int(consts["DSM_ICP_STAGE_" + name]) == k == getattr(icp, "STAGE_" + name)
+    assert int(consts["DSM_ICP_NO_KEY"].rstrip("ul"), 16) == icp.NO_KEY
+    body = hdr[hdr.index("typedef struct dsm_icp_state {"):hdr.index("} dsm_icp_state;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    assert re.findall(r"(?:float|double|int) (\w+)", body) == list(icp.STATE_DTYPE.names)
+    assert icp.STATE_DTYPE.itemsize == 16 * 4 + 2 * 8 + 4 * 4 + 4 * icp.ITERATIONS_LIMIT
 
 
 def test_checker_recovers_rigid_motion():
@@ -168,6 +177,36 @@ def test_checker_breaks_exact_ties_by_the_smallest_index():
         np.testing.assert_array_equal(idx, lower)
     a, b = R.icp(src, tgt, np.eye(4)), R.icp(src, tgt_swapped, np.eye(4))
     assert np.abs(a["tfm"][:3, 3] - b["tfm"][:3, 3]).max() > 0.1  # the tie-break decides the result
+
+
+def test_exact_sums_and_the_device_sum_order():
+    """exact_mean / exact_step are correctly rounded sums; block_sum_order is 256 strided chains and the halving tree, literally"""
+    import math
+    from fractions import Fraction
+
+    rng = np.random.default_rng(4)
+    d = (rng.random(1000) * 4).astype(np.float32)
+    exact = sum(Fraction(float(v)) for v in d) / 1000
+    assert R.exact_mean(d) == float(exact)
+    for n in (1, 255, 256, 257, 1000):
+        x = rng.normal(0, 1e3, n)
+        red = [0.0] * 256
+        for i in range(n):  # lane i % 256 adds its points in index order
+            red[i % 256] += float(x[i])
+        s = 128
+        while s:
+            for t in range(s):
+                red[t] += red[t + s]
+            s //= 2
+        assert R.block_sum_order(x) == red[0] and abs(red[0] - math.fsum(x)) <= 1e-9
+    src, tgt, _ = R.scene(5, 400)
+    work, target = R.transform_double(src, np.eye(4)), R.transform_double(tgt, np.eye(4))
+    idx, dist = R.nearest(work, target)
+    keep = dist <= 4.0
+    Rx, tx = R.exact_step(work, target, idx, keep)
+    Rm, tm = R.umeyama(work[keep], target[idx[keep]])
+    np.testing.assert_allclose(Rx, Rm, rtol=0, atol=1e-13)
+    np.testing.assert_allclose(tx, tm, rtol=0, atol=1e-12)
 
 
 def test_adaptor_header_compiles_without_a_gpu(tmp_path):
