@@ -294,7 +294,9 @@ int dsm_generate_spherical_points(int n_kf, const int *kf_ids, const double *kf_
     const double *g = pt_xyz + 3 * (size_t)i;
     double p[3];
     for (int r = 0; r < 3; r++) p[r] = ((cur_cw[r * 4 + 0] * g[0] + cur_cw[r * 4 + 1] * g[1]) + cur_cw[r * 4 + 2] * g[2]) + cur_cw[r * 4 + 3] * 1.0;
-    if (std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) >= lidar_range) continue;
+    // :59-60 as `!(norm < range)`: the same decision for every finite point; a NaN norm (a non-finite coordinate, or 0 * inf above) is
+    // dropped instead of reaching floor and the 64-bit cast, whose result is then undefined (the device form: voxel_of)
+    if (!(std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) < lidar_range)) continue;
     const long long xi = (long long)std::floor((p[0] + lidar_range) * steps[0]), yi = (long long)std::floor((p[1] + lidar_range) * steps[1]),
                     zi = (long long)std::floor((p[2] + lidar_range) * steps[2]);
     Cell c;

@@ -99,7 +99,9 @@ __device__ __forceinline__ long long voxel_of(const JobDev &J, int i, double lid
     if (!kept) return -1;
   }
   to_camera(J.cw, J.xyz + 3 * (size_t)i, p);
-  if (sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) >= lidar_range) return -1;
+  // :59-60.  `!(norm < range)`, not `norm >= range`: the same decision for every finite point, and a NaN norm (a non-finite coordinate,
+  // or 0 * inf in to_camera) is dropped here instead of reaching floor and the 64-bit cast below, whose result is then undefined
+  if (!(sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) < lidar_range)) return -1;
   const long long xi = (long long)floor((p[0] + lidar_range) * 1.0), yi = (long long)floor((p[1] + lidar_range) * 2.0),
                   zi = (long long)floor((p[2] + lidar_range) * 1.0); // steps 1/RES_X, 1/RES_Y, 1/RES_Z (:23-25,:44)
   return xi + yi * vs0 + zi * vs0 * vs1;
@@ -207,6 +209,7 @@ constexpr int kMomTile = 1024; // points per LDS tile
 static_assert(kCovLanes == kLdThreads, "one covariance partial per thread");
 __global__ __launch_bounds__(kLdThreads) void sc_moments_kernel(const JobDev *jobs) {
   const JobDev &J = jobs[blockIdx.x];
+  if (!J.ringkey) return; // a job without descriptor outputs (uniform per workgroup, before any barrier)
   const int n = *J.n_out, t = threadIdx.x;
   __shared__ double tile[2][3 * kMomTile];
   __shared__ double mean[3];
@@ -254,11 +257,12 @@ __global__ __launch_bounds__(kLdThreads) void sc_moments_kernel(const JobDev *jo
 __global__ void sc_clear_kernel(const JobDev *jobs, int nbins, double lidar_range) {
   const JobDev &J = jobs[blockIdx.y];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nbins) J.bins[i] = ordered_key(-lidar_range - 1.0); // :93-94
+  if (J.ringkey && i < nbins) J.bins[i] = ordered_key(-lidar_range - 1.0); // :93-94
 }
 // :96-119
 __global__ void sc_bin_kernel(const JobDev *jobs, double lidar_range, int num_s, int num_r) {
   const JobDev &J = jobs[blockIdx.y];
+  if (!J.ringkey) return;
   const int n = *J.n_out;
   const double *V = J.V;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -279,6 +283,7 @@ __global__ void sc_bin_kernel(const JobDev *jobs, double lidar_range, int num_s,
 // :122-141 by one workgroup per job: ring key, signature in ascending bin order, per-sector norms summed in ring order
 __global__ void sc_finish_kernel(const JobDev *jobs, double lidar_range, int num_s, int num_r) {
   const JobDev &J = jobs[blockIdx.x];
+  if (!J.ringkey) return; // (uniform per workgroup, before any barrier)
   const int t = threadIdx.x, nbins = num_s * num_r;
   extern __shared__ double sh_norm[]; // num_s
   const unsigned long long thres = ordered_key(-lidar_range);
@@ -333,6 +338,8 @@ __global__ void sc_finish_kernel(const JobDev *jobs, double lidar_range, int num
 
 } // namespace
 
+// A job without descriptor outputs (ringkey == NULL) in a batch that has some is skipped by EVERY sc_* kernel: its key slot keeps the zeros
+// of loop_enqueue's memset, its bins, moments and signature region are never touched.
 // ScanContext::generate, between the halves (ScanContext.cpp:41-64): 3 x 3 eigen-decomposition of the covariance (the host
 // form's cyclic Jacobi, same operations in the same order: loopdet_internal.hpp), centroid, eigenvectors and tfm_pca_rig
 // of every job -- one thread per job, on the device since round 3 (the moments used to travel to the host and back).
@@ -492,7 +499,7 @@ int loop_enqueue(dsm_context *ctx, int n_jobs, const dsm_loop_job *jobs, double 
   if ((rc = A.upload(any_staged ? in.used : in_small_bytes))) return rc;
   JobDev *dj = A.dev_in<JobDev>(P.in_tab);
   if (any_direct) hipLaunchKernelGGL(loop_gather_kernel, dim3(64, n_jobs), dim3(kLdThreads), 0, st, dj);
-  // a job without a descriptor leaves its key slot untouched: zero the key array so that the search sees defined values
+  // a job without a descriptor leaves its key slot untouched (every sc_* kernel skips it): zero the key array so that the search sees defined values
   DSM_HIP(hipMemsetAsync(A.dev_out<float>(P.out_keys), 0, sizeof(float) * (size_t)num_r * n_jobs, st));
   // ---- generate_spherical_points: all jobs side by side (blockIdx.y = job)
   const int gx_cells = (int)std::min<long long>(P.nblocks, 4096), gx_pts = std::min((max_pts + kLdThreads - 1) / kLdThreads, 1024);

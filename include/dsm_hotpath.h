@@ -772,7 +772,8 @@ int dsm_scancontext_generate(const double *pts, int n, double lidar_range, int n
  * matrix of the current keyframe's camera<-world pose; pt_kf_id / pt_xyz: the nearby points with the keyframe that owns each.
  * Outputs: kf_keep[n_kf] (0: the reference erases that keyframe, :33-41), *n_out selected points, sel_idx (their indices in the
  * input list: the reference's updated pts_nearby) and pts_spherical (n_out x 3, current camera frame).  Per 1 x 0.5 x 1 m voxel the
- * highest point (smallest y) is kept (:64-76).  Order of the output: ascending voxel index -- the reference emits its
+ * highest point (smallest y) is kept (:64-76).  A point whose norm in the current camera frame is not < lidar_range is dropped: the
+ * reference's `>=` test for every finite point, and a non-finite point as well (it never reaches the voxel index).  Order of the output: ascending voxel index -- the reference emits its
  * unordered_map in implementation-defined order.  Host side (tens of thousands of points per keyframe). */
 int dsm_generate_spherical_points(int n_kf, const int *kf_ids, const double *kf_pose_wc, const double *cur_cw,
                                   double lidar_range, int n_pts, const int *pt_kf_id, const double *pt_xyz, int *kf_keep,
@@ -802,7 +803,8 @@ typedef struct dsm_loop_job {
   int *n_out;                 /* out */
   int *sel_idx;               /* out: capacity n_pts; NULL (together with pts_spherical): the selected points stay on the device */
   double *pts_spherical;      /* out: capacity n_pts x 3 */
-  float *ringkey;             /* out: num_r floats, or NULL to stop after the point filter */
+  float *ringkey;             /* out: num_r floats, or NULL to stop after the point filter (job by job: one batch may hold both kinds;
+                                 a job without is skipped by the ScanContext kernels and none of its five descriptor outputs is written) */
   int *sig_idx;               /* out: capacity num_s*num_r */
   double *sig_val;            /* out: capacity num_s*num_r */
   int *n_sig;                 /* out */

@@ -57,7 +57,7 @@ def generate(pts, lidar_range, num_s=60, num_r=20):
 def generate_spherical_points(kf_ids, kf_pose_wc, cur_cw, lidar_range, pt_kf_id, pt_xyz):
     """generate_spherical_points.h:27-85 restated with numpy/scipy (TEST INFRASTRUCTURE).  cur_cw: 3x4 camera<-world.
     Keyframes rotated by more than 0.5 rad against the current one are trimmed (:33-41); points of trimmed / unknown
-    keyframes and points at or beyond lidar_range are dropped (:55-64); per voxel of 1 x 0.5 x 1 m (RES_X/Y/Z :23-25) the
+    keyframes and points not inside lidar_range (non-finite ones included) are dropped (:55-64); per voxel of 1 x 0.5 x 1 m (RES_X/Y/Z :23-25) the
     highest point (smallest y) is kept, first one on ties (:73-76).  Output order: ascending voxel index (the reference's
     unordered_map order is implementation defined)."""
     from scipy.spatial.transform import Rotation
@@ -76,8 +76,10 @@ def generate_spherical_points(kf_ids, kf_pose_wc, cur_cw, lidar_range, pt_kf_id,
     for i, (k, g) in enumerate(zip(pt_kf_id, np.asarray(pt_xyz, np.float64).reshape(-1, 3))):
         if not keep.get(int(k), False):
             continue
-        p = np.array([((cur_cw[r, 0] * g[0] + cur_cw[r, 1] * g[1]) + cur_cw[r, 2] * g[2]) + cur_cw[r, 3] for r in range(3)])
-        if np.sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]) >= lidar_range:
+        with np.errstate(all="ignore"):  # (1e308 squared, 0 * inf: the decision below is what counts)
+            p = np.array([((cur_cw[r, 0] * g[0] + cur_cw[r, 1] * g[1]) + cur_cw[r, 2] * g[2]) + cur_cw[r, 3] for r in range(3)])
+            norm = np.sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2])
+        if not norm < lidar_range:  # (a NaN norm -- a non-finite point -- is dropped as well)
             continue
         xi, yi, zi = (int(np.floor((p[a] + lidar_range) * steps[a])) for a in range(3))
         loc = xi + yi * vs0 + zi * vs0 * vs1
