@@ -169,6 +169,24 @@ class TraceJob(C.Structure):
     ]
 
 
+class SelectParams(C.Structure):
+    _fields_ = [
+        ("min_grad_hist_cut", C.c_float), ("min_grad_hist_add", C.c_float), ("grad_downweight_per_level", C.c_float),
+        ("select_direction_distribution", C.c_int), ("th_factor", C.c_float), ("recursions", C.c_int), ("pattern_padding", C.c_int),
+        ("outlier_th", C.c_float), ("outlier_th_sum_component", C.c_float), ("overall_energy_th_weight", C.c_float),
+    ]
+
+
+class SelectJob(C.Structure):
+    _fields_ = [
+        ("tracker", C.c_void_p), ("slot", C.c_int), ("b_inv", c_float_p), ("density", C.c_float), ("potential_io", c_int_p),
+        ("max_pts", C.c_int), ("u", c_float_p), ("v", c_float_p), ("energy_th", c_float_p), ("grad_h", c_float_p), ("color", c_float_p),
+        ("weights", c_float_p), ("status", C.POINTER(C.c_ubyte)), ("idepth_min", c_float_p), ("idepth_max", c_float_p),
+        ("quality", c_float_p), ("type", c_float_p), ("n_pts_out", c_int_p), ("num_total_out", c_int_p), ("counts_out", c_int_p),
+        ("passes_out", c_int_p), ("map_out", C.POINTER(C.c_ubyte)),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -327,6 +345,12 @@ SYMBOLS = {
     "dsm_trace_params_default": (C.c_int, [C.POINTER(TraceParams)]),
     "dsm_trace_points_batch": (C.c_int, [_vp, C.c_int, C.POINTER(TraceJob), C.POINTER(TraceParams)]),
     "dsm_trace_points_host": (C.c_int, [C.c_int, C.c_int, c_float_p, C.POINTER(TraceJob), C.POINTER(TraceParams)]),
+    "dsm_select_params_default": (C.c_int, [C.POINTER(SelectParams)]),
+    "dsm_pixel_selector_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(_vp)]),
+    "dsm_pixel_selector_destroy": (C.c_int, [_vp]),
+    "dsm_select_pixels_batch": (C.c_int, [_vp, C.c_int, C.POINTER(SelectJob), C.POINTER(SelectParams)]),
+    "dsm_select_pixels_host": (C.c_int, [C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(SelectJob),
+                                         C.POINTER(SelectParams)]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

@@ -150,6 +150,9 @@ const char *immature_settings_error(float huber_th, float min_idepth_h_act, int 
 const char *immature_job_error(const dsm_immature_job &J);
 const char *trace_params_error(const dsm_trace_params *p);
 const char *trace_job_error(const dsm_trace_job &J);
+const char *select_params_error(const dsm_select_params *p);
+const char *select_geometry_error(int w, int h); // of the level-0 frame
+const char *select_job_error(const dsm_select_job &J);
 int ensure_batch_capacity(dsm_context *ctx, int nprob, int partial_stride);
 int ensure_stage(dsm_context *ctx, size_t floats);
 // the device-visible address of a caller's array if it lies in page-locked memory, else null

@@ -1,8 +1,9 @@
 // points_host.cpp -- the three point calls of the front end as the reference runs them, one sequential loop each, and the rules for
 // their jobs: activation (dsm_activate_points_host), optimisation of immature points
-// (dsm_optimize_immature_points_host, section 13) and tracing (dsm_trace_points_host, section 14).  The host forms are what the CPU
-// suite checks against the numpy checkers and what the device forms (distmap_kernels.hip, immature_kernels.hip, trace_kernels.hip)
-// must equal bit for bit: the arithmetic is shared through point_math.hpp, immature_math.hpp and trace_math.hpp, the job rules
+// (dsm_optimize_immature_points_host, section 13), tracing (dsm_trace_points_host, section 14) and, before them all, the selection of
+// the pixels that become points (dsm_select_pixels_host, section 15).  The host forms are what the CPU suite checks against the numpy
+// checkers and what the device forms (distmap_kernels.hip, immature_kernels.hip, trace_kernels.hip, select_kernels.hip) must equal
+// bit for bit: the arithmetic is shared through point_math.hpp, immature_math.hpp, trace_math.hpp and select_math.hpp, the job rules
 // through the *_error functions below.  Plain C++; no device code.
 #include <algorithm>
 #include <cmath>
@@ -12,6 +13,7 @@
 
 #include "dsm_internal.hpp"
 #include "immature_math.hpp"
+#include "select_math.hpp"
 #include "trace_math.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -68,6 +70,32 @@ const char *trace_job_error(const dsm_trace_job &J) {
     if (J.host[i] < 0 || J.host[i] >= J.n_hosts) return "host outside [0, n_hosts)";
     if (J.status[i] > DSM_IPS_UNINITIALIZED) return "a status byte above 5";
   }
+  return nullptr;
+}
+
+const char *select_params_error(const dsm_select_params *p) {
+  if (!p) return "no parameters";
+  if (p->recursions < 0 || p->recursions > 4) return "recursions outside [0, 4]";
+  if (p->pattern_padding < 2 || p->pattern_padding > 8) return "pattern_padding outside [2, 8]";
+  if (!std::isfinite(p->min_grad_hist_cut) || !std::isfinite(p->min_grad_hist_add) || !std::isfinite(p->grad_downweight_per_level) ||
+      !std::isfinite(p->th_factor) || !std::isfinite(p->outlier_th) || !std::isfinite(p->outlier_th_sum_component) ||
+      !std::isfinite(p->overall_energy_th_weight))
+    return "a non-finite parameter";
+  return nullptr;
+}
+const char *select_geometry_error(int w, int h) {
+  if (w < 32 || h < 32) return "the frame is smaller than 32 x 32";
+  if ((long long)w * h > (1ll << 26)) return "the frame is larger than 2^26 pixels";
+  return nullptr;
+}
+const char *select_job_error(const dsm_select_job &J) {
+  if (!J.potential_io || !J.n_pts_out || !J.num_total_out) return "NULL potential_io, n_pts_out or num_total_out";
+  if (*J.potential_io < 1 || *J.potential_io > DSM_SELECT_MAX_POTENTIAL) return "a potential outside [1, 4096]";
+  if (!std::isfinite(J.density) || !(J.density > 0)) return "a density that is not finite or not positive";
+  if (J.max_pts < 0) return "a negative max_pts";
+  if (J.max_pts && (!J.u || !J.v || !J.energy_th || !J.grad_h || !J.color || !J.weights || !J.status || !J.idepth_min || !J.idepth_max ||
+                    !J.quality || !J.type))
+    return "NULL point array";
   return nullptr;
 }
 } // namespace dsm
@@ -346,5 +374,160 @@ extern "C" int dsm_trace_points_host(int w, int h, const float *target_I, const 
     counts[P.status]++;
   }
   if (J.counts_out) memcpy(J.counts_out, counts, sizeof counts); // T16
+  return DSM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// FrontEnd::makeNewTraces (FrontEnd.cpp:936-962) as upstream runs it: PixelSelector::makeMaps with select() as ONE sequential loop --
+// the direction of a cell is read through the running count n2 of the hits before it, and the bestIdx = -2 flags say that a block
+// holds a hit of a finer level -- then the ImmaturePoint constructor per map entry.  P1-P14: DESIGN.md section 15.  The per-pixel
+// expressions are select_math.hpp, shared with the device kernels, which run the same rules free of the scan order.
+// ---------------------------------------------------------------------------------------------
+extern "C" int dsm_select_params_default(dsm_select_params *p) {
+  if (!p) return DSM_ERR_INVALID;
+  p->min_grad_hist_cut = 0.5f, p->min_grad_hist_add = 7.0f, p->grad_downweight_per_level = 0.75f;
+  p->select_direction_distribution = 1, p->th_factor = 1.0f, p->recursions = 1, p->pattern_padding = 2;
+  p->outlier_th = 144.0f, p->outlier_th_sum_component = 2500.0f, p->overall_energy_th_weight = 1.0f;
+  return DSM_OK;
+}
+
+namespace {
+struct HostSelector {
+  int w, h, w32, h32;
+  const float *I0, *I1, *I2, *b_inv;
+  const unsigned char *rp;
+  const dsm_select_params *S;
+  std::vector<float> ths_smoothed;
+  std::vector<unsigned char> map;
+
+  void make_hists() { // P2, P3
+    std::vector<float> ths((size_t)w32 * h32);
+    for (int y = 0; y < h32; y++)
+      for (int x = 0; x < w32; x++) {
+        int hist[50] = {};
+        for (int j = 0; j < 32; j++)
+          for (int i = 0; i < 32; i++) {
+            const int it = i + 32 * x, jt = j + 32 * y;
+            if (!dsm::sel::in_histogram(it, jt, w, h)) continue;
+            hist[dsm::sel::hist_bin(dsm::sel::abs_grad(I0, w, h, it, jt, b_inv))]++;
+            hist[0]++;
+          }
+        ths[x + y * w32] = (float)dsm::sel::hist_quantile(hist, S->min_grad_hist_cut) + S->min_grad_hist_add;
+      }
+    ths_smoothed.resize(ths.size());
+    for (int y = 0; y < h32; y++)
+      for (int x = 0; x < w32; x++) ths_smoothed[x + y * w32] = dsm::sel::smoothed_threshold(ths.data(), w32, h32, x, y);
+  }
+
+  // PixelSelector::select: P5-P9 in upstream's sequential form
+  void select(int pot, int n[3]) {
+    using namespace dsm::sel;
+    std::fill(map.begin(), map.end(), 0);
+    int n2 = 0, n3 = 0, n4 = 0;
+    for (int y4 = 0; y4 < h; y4 += 4 * pot)
+      for (int x4 = 0; x4 < w; x4 += 4 * pot) {
+        const int my3 = std::min(4 * pot, h - y4), mx3 = std::min(4 * pot, w - x4);
+        long long bestIdx4 = -1;
+        float bestVal4 = 0;
+        const int dir4 = rp[n2] & 15;
+        for (int y3 = 0; y3 < my3; y3 += 2 * pot)
+          for (int x3 = 0; x3 < mx3; x3 += 2 * pot) {
+            const int x34 = x3 + x4, y34 = y3 + y4;
+            const int my2 = std::min(2 * pot, h - y34), mx2 = std::min(2 * pot, w - x34);
+            long long bestIdx3 = -1;
+            float bestVal3 = 0;
+            const int dir3 = rp[n2] & 15;
+            for (int y2 = 0; y2 < my2; y2 += pot)
+              for (int x2 = 0; x2 < mx2; x2 += pot) {
+                const int x234 = x2 + x34, y234 = y2 + y34;
+                const int my1 = std::min(pot, h - y234), mx1 = std::min(pot, w - x234);
+                long long bestIdx2 = -1;
+                float bestVal2 = 0;
+                const int dir2 = rp[n2] & 15;
+                for (int y1 = 0; y1 < my1; y1++)
+                  for (int x1 = 0; x1 < mx1; x1++) {
+                    const int xf = x1 + x234, yf = y1 + y234;
+                    const long long idx = xf + (long long)w * yf;
+                    if (!in_scan_window(xf, yf, w, h)) continue;
+                    const float t0 = ths_smoothed[threshold_index(xf, yf, w32, h32)];
+                    float gx, gy;
+                    const float ag0 = abs_grad(I0, w, h, xf, yf, b_inv, gx, gy);
+                    if (ag0 > level_threshold(t0, 0, *S)) {
+                      const float dirNorm = rank_value(gx, gy, ag0, dir2, *S);
+                      if (dirNorm > bestVal2) bestVal2 = dirNorm, bestIdx2 = idx, bestIdx3 = -2, bestIdx4 = -2;
+                    }
+                    if (bestIdx3 == -2) continue;
+                    const float ag1 = coarse_abs_grad(I1, w, h, 1, xf, yf, b_inv);
+                    if (ag1 > level_threshold(t0, 1, *S)) {
+                      const float dirNorm = rank_value(gx, gy, ag1, dir3, *S);
+                      if (dirNorm > bestVal3) bestVal3 = dirNorm, bestIdx3 = idx, bestIdx4 = -2;
+                    }
+                    if (bestIdx4 == -2) continue;
+                    const float ag2 = coarse_abs_grad(I2, w, h, 2, xf, yf, b_inv);
+                    if (ag2 > level_threshold(t0, 2, *S)) {
+                      const float dirNorm = rank_value(gx, gy, ag2, dir4, *S);
+                      if (dirNorm > bestVal4) bestVal4 = dirNorm, bestIdx4 = idx;
+                    }
+                  }
+                if (bestIdx2 > 0) map[bestIdx2] = 1, bestVal3 = 1e10f, n2++;
+              }
+            if (bestIdx3 > 0) map[bestIdx3] = 2, bestVal4 = 1e10f, n3++;
+          }
+        if (bestIdx4 > 0) map[bestIdx4] = 4, n4++;
+      }
+    n[0] = n2, n[1] = n3, n[2] = n4;
+  }
+};
+} // namespace
+
+extern "C" int dsm_select_pixels_host(int w, int h, const float *I0, const float *I1, const float *I2, const unsigned char *random_pattern,
+                                      const dsm_select_job *job, const dsm_select_params *params) {
+  using namespace dsm::sel;
+  auto fail = [](const char *msg) { return refuse("dsm_select_pixels_host", msg); };
+  if (!I0 || !I1 || !I2 || !random_pattern || !job) return fail("bad argument");
+  if (const char *e = dsm::select_params_error(params)) return fail(e);
+  if (const char *e = dsm::select_geometry_error(w, h)) return fail(e);
+  if (const char *e = dsm::select_job_error(*job)) return fail(e);
+  const dsm_select_job &J = *job;
+  const dsm_select_params &S = *params;
+  HostSelector P{w, h, w / 32, h / 32, I0, I1, I2, J.b_inv, random_pattern, params, {}, {}};
+  P.map.resize((size_t)w * h);
+  P.make_hists();
+  int pot = *J.potential_io, passes = 0, n[3];
+  Adapt A;
+  for (int left = S.recursions;; left--) { // P10
+    P.select(pot, n);
+    passes++;
+    A = adapt(n[0], n[1], n[2], J.density, pot, left);
+    if (!A.next_pot) break;
+    pot = A.next_pot;
+  }
+  int num_total = n[0] + n[1] + n[2];
+  unsigned char char_th;
+  if (thinning(A.quot, char_th)) { // P11
+    size_t rn = 0;
+    for (size_t i = 0; i < P.map.size(); i++)
+      if (P.map[i]) {
+        if (random_pattern[rn] > char_th) P.map[i] = 0, num_total--;
+        rn++;
+      }
+  }
+  *J.potential_io = A.ideal; // P12
+  int n_pts = 0;
+  for (int y = 0; y < h; y++) // P13
+    for (int x = 0; x < w; x++) {
+      const unsigned char m = P.map[x + (size_t)w * y];
+      NewPoint Q;
+      if (!m || !in_point_window(x, y, w, h, S.pattern_padding) || !construct(I0, w, h, x, y, S, Q)) continue;
+      const int i = n_pts++;
+      if (i >= J.max_pts) continue;
+      J.u[i] = (float)x, J.v[i] = (float)y, J.energy_th[i] = Q.energy_th;
+      memcpy(J.grad_h + 4 * (size_t)i, Q.grad_h, 16), memcpy(J.color + 8 * (size_t)i, Q.color, 32), memcpy(J.weights + 8 * (size_t)i, Q.weights, 32);
+      J.status[i] = DSM_IPS_UNINITIALIZED, J.idepth_min[i] = 0.f, J.idepth_max[i] = NAN, J.quality[i] = 10000.f, J.type[i] = (float)m;
+    }
+  *J.n_pts_out = n_pts, *J.num_total_out = num_total;
+  if (J.counts_out) memcpy(J.counts_out, n, sizeof n);
+  if (J.passes_out) *J.passes_out = passes;
+  if (J.map_out) memcpy(J.map_out, P.map.data(), P.map.size());
   return DSM_OK;
 }

@@ -57,6 +57,7 @@ typedef struct dsm_comm dsm_comm;       /* communicator of the sharded ring-key 
 typedef struct dsm_pose_estimator dsm_pose_estimator; /* loop-closure direct alignment (PoseEstimator) */
 typedef struct dsm_distmap dsm_distmap; /* one CoarseDistanceMap: the level-1 distance map of a window */
 typedef struct dsm_window dsm_window;   /* the level-0 intensity planes of the keyframes of one window (frame_hessians_) */
+typedef struct dsm_pixel_selector dsm_pixel_selector; /* PixelSelector: the random pattern and all scratch of dsm_select_pixels_batch */
 
 /* Runtime parameters.  These are DSO globals / literals in the reference; the values
  * written by dsm_params_default() are the upstream DSO defaults as used by the
@@ -1103,6 +1104,68 @@ int dsm_trace_points_batch(dsm_context *ctx, int n_jobs, const dsm_trace_job *jo
 /* The same for one job as one plain sequential loop on the host plane target_I (w * h floats); the target fields of the job are
  * ignored.  The CPU baseline of tools/trace_timing.py and a checker that needs no device. */
 int dsm_trace_points_host(int w, int h, const float *target_I, const dsm_trace_job *job, const dsm_trace_params *params);
+
+/* ---- Selecting candidate pixels and creating the immature points ----------------------------------------------
+ * replaces FrontEnd::makeNewTraces (FrontEnd.cpp:936-962, called at :824): PixelSelector::makeMaps and the ImmaturePoint constructor
+ * (both UPSTREAM-DSO, parity unpinned) as the rules P1-P14 of DESIGN.md section 15 state them, for the new keyframes of many sequences
+ * in one call.  Everything is float32 without contraction, or integer. */
+#define DSM_SELECT_MAX_POTENTIAL 4096 /* largest potential a job may enter with or adapt to (P10) */
+
+/* the settings makeMaps and the ImmaturePoint constructor read; dsm_select_params_default fills the upstream defaults */
+typedef struct dsm_select_params {
+  float min_grad_hist_cut;           /* 0.5f   setting_minGradHistCut */
+  float min_grad_hist_add;           /* 7      setting_minGradHistAdd */
+  float grad_downweight_per_level;   /* 0.75f  setting_gradDownweightPerLevel */
+  int select_direction_distribution; /* 1      setting_selectDirectionDistribution */
+  float th_factor;                   /* 1      thFactor of makeMaps */
+  int recursions;                    /* 1      recursionsLeft of makeMaps, 0 .. 4 */
+  int pattern_padding;               /* 2      patternPadding, 2 .. 8 */
+  float outlier_th;                  /* 144    setting_outlierTH (12 * 12) */
+  float outlier_th_sum_component;    /* 2500   setting_outlierTHSumComponent (50 * 50) */
+  float overall_energy_th_weight;    /* 1      setting_overallEnergyTHWeight */
+} dsm_select_params;
+
+/* The new keyframe of one sequence: levels 0-2 of frame slot `slot` of `tracker`.  The point arrays have the layout dsm_trace_job
+ * consumes, so they go straight into the next dsm_trace_points_batch; only the first max_pts points are written. */
+typedef struct dsm_select_job {
+  dsm_tracker *tracker; /* >= 3 levels, a frame in `slot` (0 or 1) */
+  int slot;
+  const float *b_inv;   /* optional (NULL), 256: the inverse response; weights the squared gradients (P1) */
+  float density;        /* setting_desiredImmatureDensity (1500 in the reference's presets) */
+  int *potential_io;    /* in/out: currentPotential of the sequence's PixelSelector, 3 at first use */
+  int max_pts;          /* capacity of the point arrays */
+  float *u, *v, *energy_th; /* max_pts each */
+  float *grad_h;            /* max_pts * 4: gradH, row-major */
+  float *color, *weights;   /* max_pts * 8 each */
+  unsigned char *status;    /* max_pts: DSM_IPS_UNINITIALIZED */
+  float *idepth_min, *idepth_max, *quality; /* max_pts each: 0, NaN, 10000 */
+  float *type;              /* max_pts: the map value 1, 2 or 4 (my_type; dsm_activation_job.cand_type) */
+  int *n_pts_out;           /* the points found (P13), which may exceed max_pts */
+  int *num_total_out;       /* makeMaps' return value: the map entries left after the thinning (P11) */
+  int *counts_out;          /* optional (NULL), 3: n2, n3, n4 of the last pass */
+  int *passes_out;          /* optional (NULL): select passes run, 1 .. recursions + 1 */
+  unsigned char *map_out;   /* optional (NULL), w * h: the selection map after the thinning */
+} dsm_select_job;
+
+/* the upstream defaults listed above */
+int dsm_select_params_default(dsm_select_params *p);
+/* The device copy of the random pattern (w * h bytes; upstream: srand(3141592), rand() & 0xFF, which depends on the libc) and all
+ * scratch for max_jobs jobs of geometry w x h, allocated here and never afterwards.  w, h >= 32, max_jobs in [1, 4096]. */
+int dsm_pixel_selector_create(dsm_context *ctx, int w, int h, int max_jobs, const unsigned char *random_pattern, dsm_pixel_selector **sel_out);
+int dsm_pixel_selector_destroy(dsm_pixel_selector *sel);
+/* FrontEnd.cpp:936-962 for every job: one staged copy through the context's page-locked arena, a fixed launch sequence (the
+ * adaptation of the potential, P10, is decided on the device: every pass is enqueued and jobs that do not recurse leave it at
+ * once), one host wait for the whole batch; nothing is allocated once the arena has grown to the batch size; a job's results do not
+ * depend on the other jobs of the call.  Validation is all or nothing, before anything is enqueued: DSM_ERR_INVALID for NULL
+ * arrays, n_jobs outside [1, max_jobs], a potential outside [1, DSM_SELECT_MAX_POTENTIAL], a density that is not finite or not
+ * positive, a negative max_pts, recursions outside [0, 4], pattern_padding outside [2, 8], any non-finite setting, a tracker of
+ * another context or with an empty slot, a geometry other than the selector's, fewer than 3 levels. */
+int dsm_select_pixels_batch(dsm_pixel_selector *sel, int n_jobs, const dsm_select_job *jobs, const dsm_select_params *params);
+/* The same for one job as one plain sequential loop on the host (upstream's loop with its running counter): I0, I1, I2 are the
+ * intensity planes of levels 0-2 ((w >> l) * (h >> l) floats), random_pattern w * h bytes; job->tracker and job->slot are ignored;
+ * w < 32 or h < 32 is refused.  The CPU baseline of tools/select_timing.py and a checker that needs no device. */
+int dsm_select_pixels_host(int w, int h, const float *I0, const float *I1, const float *I2, const unsigned char *random_pattern,
+                           const dsm_select_job *job, const dsm_select_params *params);
 
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
