@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void read_bw_chunked_kernel(const fvec4d *__re
   if (s == 123456.789f) out[0] = s;
 }
 
-// Queue probe (ensure_streams, dsm_capi.hip): a kernel that stays resident for `ticks` of the constant-rate wall clock (bounded: it
+// Queue probe (ensure_streams, lm_schedule.hip): a kernel that stays resident for `ticks` of the constant-rate wall clock (bounded: it
 // leaves after 2^22 polls whatever the clock says) and an empty one.  A HIP stream is mapped onto one of a few hardware queues by the
 // runtime (four by default, shared round robin with every other stream of the process); two streams on ONE queue run their kernels
 // one after the other however independent they are -- the probe makes that visible: the empty kernel on stream B finishes while the
@@ -148,14 +148,14 @@ extern "C" int dsm_diag_read_bandwidth_chunked(dsm_context *ctx, size_t bytes, s
   DSM_HIP(hipMalloc(&out, 64));
   DSM_HIP(hipMemsetAsync(buf, 0x3c, bytes, ctx->stream));
   for (int i = -1; i < iters; i++) {
-    if (i == 0) DSM_HIP(hipEventRecord(ctx->ev_total[0], ctx->stream));
+    if (i == 0) DSM_HIP(hipEventRecord(ctx->timers.ev_total[0], ctx->stream));
     hipLaunchKernelGGL(dsm::read_bw_chunked_kernel, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream, (const dsm::fvec4d *)buf,
                        chunk_bytes / 16, out);
   }
-  DSM_HIP(hipEventRecord(ctx->ev_total[1], ctx->stream));
+  DSM_HIP(hipEventRecord(ctx->timers.ev_total[1], ctx->stream));
   DSM_HIP(hipStreamSynchronize(ctx->stream));
   float ms = 0;
-  DSM_HIP(hipEventElapsedTime(&ms, ctx->ev_total[0], ctx->ev_total[1]));
+  DSM_HIP(hipEventElapsedTime(&ms, ctx->timers.ev_total[0], ctx->timers.ev_total[1]));
   *gbps_out = (double)bytes * iters / (ms * 1e-3) / 1e9;
   DSM_HIP(hipFree(buf));
   DSM_HIP(hipFree(out));
@@ -175,13 +175,13 @@ extern "C" int dsm_diag_read_bandwidth(dsm_context *ctx, size_t bytes, int iters
   const size_t n4 = bytes / 16;
   const int grid = 256 * 8;
   hipLaunchKernelGGL(dsm::read_bw_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const dsm::fvec4d *)buf, n4, out);
-  DSM_HIP(hipEventRecord(ctx->ev_total[0], ctx->stream));
+  DSM_HIP(hipEventRecord(ctx->timers.ev_total[0], ctx->stream));
   for (int i = 0; i < iters; i++)
     hipLaunchKernelGGL(dsm::read_bw_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const dsm::fvec4d *)buf, n4, out);
-  DSM_HIP(hipEventRecord(ctx->ev_total[1], ctx->stream));
+  DSM_HIP(hipEventRecord(ctx->timers.ev_total[1], ctx->stream));
   DSM_HIP(hipStreamSynchronize(ctx->stream));
   float ms = 0;
-  DSM_HIP(hipEventElapsedTime(&ms, ctx->ev_total[0], ctx->ev_total[1]));
+  DSM_HIP(hipEventElapsedTime(&ms, ctx->timers.ev_total[0], ctx->timers.ev_total[1]));
   *gbps_out = (double)bytes * iters / (ms * 1e-3) / 1e9;
   DSM_HIP(hipFree(buf));
   DSM_HIP(hipFree(out));

@@ -21,81 +21,103 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
     if (e__ != hipSuccess) return dsm::hip_fail(e__, #expr, __FILE__, __LINE__); \
   } while (0)
 
+// Everything the context holds beyond its device and its stream belongs to one of the owners below: a plain aggregate whose release()
+// gives back exactly what it holds and leaves it null (context_capi.hip; the arena's in call_arena.hip).  dsm_context_destroy selects
+// the device, drains the streams, calls every owner's release() and destroys the stream; whoever grows a buffer is named at its owner.
 struct dsm_context {
   int device = 0;
   hipStream_t stream = nullptr;
   // batched calls may split the batch over several streams so that one group's small kernels overlap
-  // another group's (dsm_context_set_streams); single calls always use `stream`
-  int n_streams = 1;
-  std::vector<hipStream_t> extra_streams;
-  std::vector<hipEvent_t> join_events;
-  hipEvent_t fork_event = nullptr;
-  int streams_sharing_a_queue = 0;        // streams of ensure_streams that could not be given a hardware queue of their own
-  hipStream_t companion_stream = nullptr; // the companion segment of dsm_track_and_scale_batch
-  hipEvent_t companion_event = nullptr;
-  hipEvent_t copy_event = nullptr; // end of a host->device hand-over (dsm_tracker_upload_image)
-  // descriptor updates of a batch in one copy (sync_descs): [n descriptors][n destination pointers], pinned + device
-  unsigned char *h_desc_stage = nullptr, *d_desc_stage = nullptr;
-  int desc_stage_cap = 0;
-  hipEvent_t desc_event = nullptr;
-  bool desc_stage_busy = false;
-  // batched hand-over (dsm_upload_images): copies on a stream of their own, one event per group of images
-  hipStream_t copy_stream = nullptr;
-  // asynchronous hand-over (dsm_upload_images_async): its own work stream; copies_event = the caller's buffers are
-  // free, done_event = the pyramids are built
-  hipStream_t upload_stream = nullptr;
-  hipEvent_t upload_copies_event = nullptr, upload_done_event = nullptr;
-  bool upload_pending = false;
-  bool enqueue_pending = false; // dsm_upload_images_enqueue: copy_event not yet waited for
-  int async_copy_blocks = 48;  // workgroups of the host-read kernel of the asynchronous hand-over (measured: DESIGN.md section 2)
-  std::vector<hipEvent_t> upload_events;
-  dsm::PyrJob *d_pyr_jobs = nullptr, *h_pyr_jobs = nullptr; // h: pinned
-  int pyr_jobs_cap = 0;
-  // batch workspaces (grown on demand)
-  int cap_prob = 0;
-  int partial_stride = 0; // floats per problem
-  dsm::TrackerDev **d_tracker_ptrs = nullptr;
-  dsm::TrackerDev **h_tracker_ptrs = nullptr; // pinned
-  dsm::LMState *d_states = nullptr;
-  dsm::LMState *h_states = nullptr; // pinned
-  float *d_partials = nullptr;
-  dsm::StartInfo *d_start = nullptr;
-  dsm::StartInfo *h_start = nullptr; // pinned
-  dsm::SingleOut *d_single = nullptr;
-  dsm::SingleOut *h_single = nullptr; // pinned
-  int *d_status = nullptr;
-  int *h_status = nullptr; // pinned
-  dsm::WorkQueue *d_queue = nullptr, *h_queue = nullptr; // work-queue kernel: header (device / pinned copy)
-  unsigned long long *d_qitems = nullptr;
-  size_t qcap = 0;
-  int queue_blocks[3] = {0, 0, 0}; // co-resident grid size per mode
-  int *d_rowmap = nullptr, *h_rowmap = nullptr; // compact launches: row -> problem (relative to the segment), device / pinned
-  int *d_tickets = nullptr; // per-problem arrival counters of the fused eval+LM kernels (zero between launches)
-  // staging for host->device template / frame uploads
-  float *d_stage = nullptr;
-  size_t stage_floats = 0;
-  // the staging arena of the batched calls (loop chain, ring-key search of many indexes, ICP, distance map, immature points, trace):
-  // device buffer and page-locked mirror, owned and laid out by call_arena.hpp alone
-  void *arena_dev = nullptr, *arena_pin = nullptr;
-  size_t arena_dev_bytes = 0, arena_pin_bytes = 0;
-  // dsm_set_refs_from_points: page-locked mirror of the jobs' points and job table, and of their counts
-  float *h_tpl_stage = nullptr;
-  size_t tpl_stage_floats = 0;
-  int *h_tpl_counts = nullptr;
-  size_t tpl_counts_cap = 0;
-  // speculative launch schedule per mode (0 = track, 1 = scale, 2 = loop-closure pose) and level, adapted after every call
-  int sched[3][DSM_MAX_LEVELS] = {{6, 8, 10, 12, 16, 16}, {4, 4, 4, 4, 4, 4}, {6, 8, 10, 12, 16, 16}};
-  // ... and the number of launches after which only a level's stragglers are still at work (the third quartile of the
-  // rounds the problems of recent calls needed): from there on a round is ONE fused evaluate + step launch (dsm_params.fuse_lm = 1)
-  int sched_bulk[3][DSM_MAX_LEVELS] = {{1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30}, {1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30},
-                                       {1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30}};
-  int sched_bulk_key = -1; // batch-size bucket and launch form the sched_bulk figures were learnt on
-  // stats / timing
-  bool timing = false;
-  dsm_stats stats{};
-  dsm_stats stats2{}; // companion segment of the last dsm_track_and_scale_batch
-  std::vector<hipEvent_t> ev_pool;
-  hipEvent_t ev_total[2] = {nullptr, nullptr};
+  // another group's (dsm_context_set_streams); single calls always use `stream`.  Grown by lm_schedule.hip (bind_streams)
+  struct StreamGroups {
+    int n_streams = 1;
+    std::vector<hipStream_t> extra_streams;
+    std::vector<hipEvent_t> join_events;
+    hipEvent_t fork_event = nullptr;
+    int streams_sharing_a_queue = 0;        // streams of ensure_streams that could not be given a hardware queue of their own
+    hipStream_t companion_stream = nullptr; // the companion segment of dsm_track_and_scale_batch
+    hipEvent_t companion_event = nullptr;
+    void release();
+  } groups;
+  // descriptor updates of a batch in one copy (sync_descs, tracker_capi.hip): [n descriptors][n destination pointers], pinned + device
+  struct DescStaging {
+    unsigned char *h_desc_stage = nullptr, *d_desc_stage = nullptr;
+    int desc_stage_cap = 0;
+    hipEvent_t desc_event = nullptr;
+    bool desc_stage_busy = false;
+    void release();
+  } descs;
+  // image hand-over (handover_capi.hip; dsm_tracker_upload_image records copy_event too)
+  struct HandOver {
+    hipEvent_t copy_event = nullptr; // end of a host->device hand-over (dsm_tracker_upload_image)
+    // batched hand-over (dsm_upload_images): copies on a stream of their own, one event per group of images
+    hipStream_t copy_stream = nullptr;
+    // asynchronous hand-over (dsm_upload_images_async): its own work stream; copies_event = the caller's buffers are
+    // free, done_event = the pyramids are built
+    hipStream_t upload_stream = nullptr;
+    hipEvent_t upload_copies_event = nullptr, upload_done_event = nullptr;
+    bool upload_pending = false;
+    bool enqueue_pending = false; // dsm_upload_images_enqueue: copy_event not yet waited for
+    int async_copy_blocks = 48;  // workgroups of the host-read kernel of the asynchronous hand-over (measured: DESIGN.md section 2)
+    std::vector<hipEvent_t> upload_events;
+    dsm::PyrJob *d_pyr_jobs = nullptr, *h_pyr_jobs = nullptr; // h: pinned
+    int pyr_jobs_cap = 0;
+    // before something a hand-over may still touch is freed (a tracker's buffers, an undistorter's tables): the context's stream
+    // `main`, the upload stream and the copy stream are idle
+    int drain(hipStream_t main);
+    // the copies of a pending asynchronous or enqueued hand-over are through: its job table and the caller's buffers are free
+    int wait_copies();
+    void release();
+  } handover;
+  // workspaces of the LM batch form (batch_capi.hip: ensure_batch_capacity, run_queue; read by diag_capi.hip, pose_capi.hip and stream_capi.hip)
+  struct LmWorkspace {
+    int cap_prob = 0;
+    int partial_stride = 0; // floats per problem
+    dsm::TrackerDev **d_tracker_ptrs = nullptr;
+    dsm::TrackerDev **h_tracker_ptrs = nullptr; // pinned
+    dsm::LMState *d_states = nullptr;
+    dsm::LMState *h_states = nullptr; // pinned
+    float *d_partials = nullptr;
+    dsm::StartInfo *d_start = nullptr;
+    dsm::StartInfo *h_start = nullptr; // pinned
+    dsm::SingleOut *d_single = nullptr;
+    dsm::SingleOut *h_single = nullptr; // pinned
+    int *d_status = nullptr;
+    int *h_status = nullptr; // pinned
+    dsm::WorkQueue *d_queue = nullptr, *h_queue = nullptr; // work-queue kernel: header (device / pinned copy)
+    unsigned long long *d_qitems = nullptr;
+    size_t qcap = 0;
+    int queue_blocks[3] = {0, 0, 0}; // co-resident grid size per mode
+    int *d_rowmap = nullptr, *h_rowmap = nullptr; // compact launches: row -> problem (relative to the segment), device / pinned
+    int *d_tickets = nullptr; // per-problem arrival counters of the fused eval+LM kernels (zero between launches)
+    void release();
+  } lm;
+  // the staging arena of every call that stages its inputs, runs its kernels and reads its results back once (the users are listed in
+  // call_arena.hpp): device buffer and page-locked mirror, grown and laid out by CallArena alone
+  struct ArenaBuffers {
+    void *arena_dev = nullptr, *arena_pin = nullptr;
+    size_t arena_dev_bytes = 0, arena_pin_bytes = 0;
+    void release();
+  } arena;
+  // the learnt launch schedule of the batch form (batch_capi.hip: account_and_learn); holds no resource
+  struct LearntSchedule {
+    // speculative launch schedule per mode (0 = track, 1 = scale, 2 = loop-closure pose) and level, adapted after every call
+    int sched[3][DSM_MAX_LEVELS] = {{6, 8, 10, 12, 16, 16}, {4, 4, 4, 4, 4, 4}, {6, 8, 10, 12, 16, 16}};
+    // ... and the number of launches after which only a level's stragglers are still at work (the third quartile of the
+    // rounds the problems of recent calls needed): from there on a round is ONE fused evaluate + step launch (dsm_params.fuse_lm = 1)
+    int sched_bulk[3][DSM_MAX_LEVELS] = {{1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30}, {1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30},
+                                         {1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30, 1 << 30}};
+    int sched_bulk_key = -1; // batch-size bucket and launch form the sched_bulk figures were learnt on
+  } learnt;
+  // stats / timing (ev_pool grown by lm_schedule.hip: get_event)
+  struct Timing {
+    bool timing = false;
+    dsm_stats stats{};
+    dsm_stats stats2{}; // companion segment of the last dsm_track_and_scale_batch
+    std::vector<hipEvent_t> ev_pool;
+    hipEvent_t ev_total[2] = {nullptr, nullptr};
+    void release();
+  } timers;
 };
 
 struct dsm_tracker {
@@ -127,6 +149,12 @@ struct dsm_undistorter {
   dsm::UndistortTables tab{}; // device pointers + sizes (dsm_kernels.hpp)
 };
 
+// dsm_pose_estimator_create (pose_capi.hip): a tracker whose every level has the level-0 capacity, and the points narrowed to float
+struct dsm_pose_estimator {
+  dsm_tracker *t = nullptr;
+  std::vector<float> x, y, z;
+};
+
 // dsm_window_create (immature_kernels.hip): the level-0 intensity planes of a window's keyframes; also a target of trace_kernels.hip
 struct dsm_window {
   dsm_context *ctx = nullptr;
@@ -153,13 +181,26 @@ const char *trace_job_error(const dsm_trace_job &J);
 const char *select_params_error(const dsm_select_params *p);
 const char *select_geometry_error(int w, int h); // of the level-0 frame
 const char *select_job_error(const dsm_select_job &J);
-int ensure_batch_capacity(dsm_context *ctx, int nprob, int partial_stride);
-int ensure_stage(dsm_context *ctx, size_t floats);
-// the device-visible address of a caller's array if it lies in page-locked memory, else null
+// context_capi.hip: the device-visible address of a caller's array if it lies in page-locked memory, else null
 const void *pinned_device_pointer(const void *p);
+int take_params(const dsm_params *params, dsm_params *out); // the caller's parameters, checked, or the defaults
+// tracker_capi.hip: the bytes of one intensity plane; the small host math and the pieces of a tracker's device descriptor
+// (dsm_pose_estimate_batch builds its jobs' descriptors from the same pieces)
+size_t plane_bytes(int w, int h);
+void se3_from_matrix(const double T[16], double pose[7]);
+void desc_init(TrackerDev &D, int nlevels, const dsm_params &P);
+void desc_cam1(TrackerDev &D, int nlevels, const float K1[4]);
+void desc_make_k(TrackerDev &D, int nlevels, float fx, float fy, float cx, float cy);
 int sync_desc(dsm_tracker *t);
 int sync_descs(dsm_context *ctx, dsm_tracker *const *ts, int n);
 int check_ready(dsm_tracker *t, int mode);
+// batch_capi.hip: the batch form of the LM scheduler, as the pose estimators and the diagnostic calls run it
+int round8(int x);
+int prepare_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mode, int n2 = 0, int mode2 = 1);
+int run_lm_batch(dsm_context *ctx, int n, dsm_tracker *const *ts, int mode, int coarsest, int n2 = 0, int mode2 = 1);
+// pose_capi.hip: the loading half of PoseEstimator::estimate (dsm_diag_pose_estimator_eval loads the same way)
+int pose_estimator_load(dsm_pose_estimator *pe, int n_pts, const double *xyz, const float *const *ref_colors, float ref_ab_exposure,
+                        const float *const *new_dIp, float new_ab_exposure, const float new_cam[4]);
 
 // a device / pinned array of n elements into *p, which is null or holds an earlier allocation (freed first)
 template <typename T>
@@ -177,7 +218,19 @@ int realloc_pinned(T **p, size_t n) {
   return DSM_OK;
 }
 
-// ---- lm_schedule.hip: what the schedulers of the LM kernels share (the batch form, run_lm_batch in dsm_capi.hip; the pass
+// an owner's release(): the array goes (null: nothing to do) and the pointer is left null
+template <typename T>
+void release_dev(T *&p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+template <typename T>
+void release_pinned(T *&p) {
+  if (p) (void)hipHostFree(p);
+  p = nullptr;
+}
+
+// ---- lm_schedule.hip: what the schedulers of the LM kernels share (the batch form, run_lm_batch in batch_capi.hip; the pass
 // engine and the tick engine of stream_capi.hip) ----
 
 // A segment of a launch schedule: problems (or slots) [i0, i1) of one mode on one HIP stream.  The main batch is split into

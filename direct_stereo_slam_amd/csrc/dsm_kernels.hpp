@@ -1,6 +1,6 @@
-// dsm_kernels.hpp -- host-side launch interface of the HIP kernels (tracker_kernels.hip,
-// ringkey_kernels.hip).  Internal to the shared library; the public boundary is
-// include/dsm_hotpath.h.
+// dsm_kernels.hpp -- host-side launch interface of the HIP kernels, grouped by the file that defines them: tracker_kernels.hip,
+// template_kernels.hip, frame_kernels.hip, pose_batch_kernels.hip, diag_kernels.hip, ringkey_kernels.hip.  Internal to the shared
+// library; the public boundary is include/dsm_hotpath.h.
 #pragma once
 #include "dsm_device.hpp"
 
@@ -65,6 +65,7 @@ struct StartInfo { // host -> device, one per problem
   int residual_only; // single evaluation only (dsm_diag_single_eval): EvalIn::residual_only
 };
 
+// ---- tracker_kernels.hip ----
 // mode: 0 = pose (calcResPose + calcGSSSEPose), 1 = scale (calcResScale + calcGSSSEScale)
 // rowmap != nullptr: compact launch over nprob rows, row r = problem rowmap[r] (indices relative to trackers / states)
 void launch_eval(hipStream_t s, int mode, int lvl, int grid_x, int nprob,
@@ -177,8 +178,17 @@ void launch_diag_chain_eval(hipStream_t s, int mode, const LMState *states, floa
 // structures are the public ones of include/dsm_hotpath.h
 void launch_diag_lm_propose(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_propose_in *in,
                             ::dsm_lm_propose_out *out, bool spec, bool helper);
+// descriptors of many trackers in one launch (sync_descs): d_dst[i] <- d_src[i]
+void launch_desc_scatter(hipStream_t s, int n, const TrackerDev *d_src, TrackerDev *const *d_dst);
+// Template lists are allocated with this many entries of slack (zeroed).  The evaluation loop prefetches template entries up to three
+// trips (3 x 256 points) past the end of a chunk; its buffer loads are range-checked against the list (an entry beyond it reads as
+// zeros, never used: masked), so the slack is only a second line of defence for the paths that read the list with plain loads
+constexpr int kTemplatePad = 1024;
+// chunks of an evaluation of level L of a tracker
+inline int level_chunks(const TrackerDev &d, int L) { return num_chunks(d.lv[L].n, d.p.geometry); }
 
-// row A4 / N3: makeCoarseDepthL0 on the device (template_kernels.hip), batched over the keyframes of a call
+// ---- template_kernels.hip ----
+// row A4 / N3: makeCoarseDepthL0 on the device, batched over the keyframes of a call
 struct TplJob {
   int npts, pad;
   const float *pt; // [pu | pv | pidepth | pweight], npts each
@@ -201,12 +211,8 @@ struct ScaleDepthArgs { // every level of one template in one launch (blockIdx.y
   float4 *pts[DSM_MAX_LEVELS];
 };
 void launch_scale_depth_levels(hipStream_t s, const ScaleDepthArgs &a, int max_n, float scale);
-// Template lists are allocated with this many entries of slack (zeroed).  The evaluation loop prefetches template entries up to three
-// trips (3 x 256 points) past the end of a chunk; its buffer loads are range-checked against the list (an entry beyond it reads as
-// zeros, never used: masked), so the slack is only a second line of defence for the paths that read the list with plain loads
-constexpr int kTemplatePad = 1024;
-// chunks of an evaluation of level L of a tracker
-inline int level_chunks(const TrackerDev &d, int L) { return num_chunks(d.lv[L].n, d.p.geometry); }
+
+// ---- frame_kernels.hip ----
 // makeImages (upstream DSO): the intensity plane of level 0 from the float image, of level l from level l-1
 void launch_pyramid(hipStream_t s, int w, int h, int nlevels, const float *raw, float *const *img);
 // the reference's (I, dx, dy) texels out of / into an intensity plane; with d_bad != nullptr import counts the texels whose
@@ -220,8 +226,22 @@ struct PyrJob {
   float *img[DSM_MAX_LEVELS];
   const void *src; // device-visible address of the caller's pinned image (kernel copy path), else null
 };
-void launch_desc_scatter(hipStream_t s, int n, const TrackerDev *d_src, TrackerDev *const *d_dst);
-// dsm_pose_estimate_batch (pose_batch_kernels.hip): one job's template pack and one job's pyramid import
+// raw <- src for every job, rows of row_bytes at pitch `pitch` in src (tight in raw); unit: 16, 4 or 1 bytes per access
+void launch_host_rows_copy(hipStream_t s, const PyrJob *d_jobs, int njobs, int row_bytes, int rows, size_t pitch, int unit, int max_blocks);
+void launch_pyramid_batched(hipStream_t s, int w, int h, int nlevels, const PyrJob *d_jobs, int njobs, bool u8);
+// dsm_undistorter: remap = w_out * h_out (x, y) source coordinates (x < 0: outside; null: passthrough), G = 256 floats,
+// vig = w_in * h_in inverse vignette (each null when absent)
+struct UndistortTables {
+  int w_in, h_in, w_out, h_out;
+  const float2 *remap;
+  const float *G, *vig;
+};
+// the batched pyramids of dsm_upload_images_undistorted: level 0 (and 1) from the staged camera bytes of every job, the
+// other levels as launch_pyramid_batched builds them -- as many launches as that
+void launch_undistort_pyramid_batched(hipStream_t s, const UndistortTables &u, int nlevels, const PyrJob *d_jobs, int njobs);
+
+// ---- pose_batch_kernels.hip ----
+// dsm_pose_estimate_batch: one job's template pack and one job's pyramid import
 struct PosePackJob {
   const double *xyz;                // n x 3 (the staged arena, or the caller's page-locked array)
   const float *col[DSM_MAX_LEVELS]; // n each
@@ -237,25 +257,13 @@ struct PoseImportJob {
 void launch_pose_pack(hipStream_t s, const PosePackJob *d_jobs, int njobs, int nlevels, int max_n);
 // every level of a wave of jobs in one launch; check: count the texels whose gradient channels are not makeImages' (as launch_dip_import)
 void launch_pose_import(hipStream_t s, const PoseImportJob *d_jobs, int njobs, int w, int h, int nlevels, bool check, float tol);
-// raw <- src for every job, rows of row_bytes at pitch `pitch` in src (tight in raw); unit: 16, 4 or 1 bytes per access
-void launch_host_rows_copy(hipStream_t s, const PyrJob *d_jobs, int njobs, int row_bytes, int rows, size_t pitch, int unit, int max_blocks);
-void launch_pyramid_batched(hipStream_t s, int w, int h, int nlevels, const PyrJob *d_jobs, int njobs, bool u8);
-// dsm_undistorter: remap = w_out * h_out (x, y) source coordinates (x < 0: outside; null: passthrough), G = 256 floats,
-// vig = w_in * h_in inverse vignette (each null when absent)
-struct UndistortTables {
-  int w_in, h_in, w_out, h_out;
-  const float2 *remap;
-  const float *G, *vig;
-};
-// the batched pyramids of dsm_upload_images_undistorted: level 0 (and 1) from the staged camera bytes of every job, the
-// other levels as launch_pyramid_batched builds them -- as many launches as that
-void launch_undistort_pyramid_batched(hipStream_t s, const UndistortTables &u, int nlevels, const PyrJob *d_jobs, int njobs);
 
-// queue probe of ensure_streams (diag_kernels.hip): a kernel resident for `ticks` of the wall clock, and an empty one
+// ---- diag_kernels.hip ----
+// queue probe of ensure_streams: a kernel resident for `ticks` of the wall clock, and an empty one
 void launch_queue_probe_wait(hipStream_t s, long long ticks);
 void launch_queue_probe_empty(hipStream_t s);
 
-// ring-key kernels
+// ---- ringkey_kernels.hip ----
 void launch_ringkey_knn(hipStream_t s, const float *keysT, int64_t cap, int64_t n_local, int dim,
                         int k, float thres, int shard_rank, int shard_count, const float *d_queries,
                         int nq, unsigned long long *d_scratch, int n_slices,

@@ -1,4 +1,4 @@
-// lm_schedule.hip -- what the host schedulers of the LM kernels share: the batch form (run_lm_batch, dsm_capi.hip), the pass engine
+// lm_schedule.hip -- what the host schedulers of the LM kernels share: the batch form (run_lm_batch, batch_capi.hip), the pass engine
 // and the tick engine of a dsm_stream (stream_capi.hip).  Segments and their HIP streams, fork and join, the (evaluate, step)
 // round with its launch rules, the per-dispatch timing, and the rules of what a problem starts from, what it costs and what it
 // writes back.  Host code only; each rule is stated here once.
@@ -56,7 +56,7 @@ static int streams_overlap(dsm_context *ctx, hipStream_t a, hipStream_t b, bool 
 }
 // a new stream whose kernels run concurrently with those of every stream in `with` (up to 12 candidates: the runtime hands out its
 // queues round robin, so a few rejected candidates later one on a free queue comes up); none found -- fewer hardware queues than
-// streams wanted (GPU_MAX_HW_QUEUES) --: the last candidate, counted in ctx->streams_sharing_a_queue
+// streams wanted (GPU_MAX_HW_QUEUES) --: the last candidate, counted in ctx->groups.streams_sharing_a_queue
 static int create_concurrent_stream(dsm_context *ctx, const std::vector<hipStream_t> &with, hipStream_t *out) {
   std::vector<hipStream_t> rejected;
   hipStream_t found = nullptr;
@@ -78,7 +78,7 @@ static int create_concurrent_stream(dsm_context *ctx, const std::vector<hipStrea
   if (!found && rc == DSM_OK && !rejected.empty()) {
     found = rejected.back();
     rejected.pop_back();
-    ctx->streams_sharing_a_queue++;
+    ctx->groups.streams_sharing_a_queue++;
   }
   for (hipStream_t st : rejected) hipStreamDestroy(st);
   *out = found;
@@ -90,23 +90,23 @@ static int create_concurrent_stream(dsm_context *ctx, const std::vector<hipStrea
 static int ensure_streams(dsm_context *ctx, int ng, bool companion) {
   auto in_use = [&]() {
     std::vector<hipStream_t> v{ctx->stream};
-    v.insert(v.end(), ctx->extra_streams.begin(), ctx->extra_streams.end());
-    if (ctx->companion_stream) v.push_back(ctx->companion_stream);
+    v.insert(v.end(), ctx->groups.extra_streams.begin(), ctx->groups.extra_streams.end());
+    if (ctx->groups.companion_stream) v.push_back(ctx->groups.companion_stream);
     return v;
   };
-  while ((int)ctx->extra_streams.size() < ng - 1) { // (the groups first: they carry the large kernels)
+  while ((int)ctx->groups.extra_streams.size() < ng - 1) { // (the groups first: they carry the large kernels)
     hipStream_t st;
     const int rc = create_concurrent_stream(ctx, in_use(), &st);
     if (rc) return rc;
-    ctx->extra_streams.push_back(st);
+    ctx->groups.extra_streams.push_back(st);
     hipEvent_t ev;
     DSM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    ctx->join_events.push_back(ev);
+    ctx->groups.join_events.push_back(ev);
   }
-  if (companion && !ctx->companion_stream) {
-    const int rc = create_concurrent_stream(ctx, in_use(), &ctx->companion_stream);
+  if (companion && !ctx->groups.companion_stream) {
+    const int rc = create_concurrent_stream(ctx, in_use(), &ctx->groups.companion_stream);
     if (rc) return rc;
-    DSM_HIP(hipEventCreateWithFlags(&ctx->companion_event, hipEventDisableTiming));
+    DSM_HIP(hipEventCreateWithFlags(&ctx->groups.companion_event, hipEventDisableTiming));
   }
   return DSM_OK;
 }
@@ -118,7 +118,7 @@ int bind_streams(dsm_context *ctx, std::vector<Seg> &segs) {
   const int rc = ensure_streams(ctx, ng, !segs.empty() && segs.back().companion && segs.size() > 1);
   if (rc) return rc;
   for (size_t si = 0; si < segs.size(); si++)
-    segs[si].st = si == 0 ? ctx->stream : segs[si].companion ? ctx->companion_stream : ctx->extra_streams[si - 1];
+    segs[si].st = si == 0 ? ctx->stream : segs[si].companion ? ctx->groups.companion_stream : ctx->groups.extra_streams[si - 1];
   return DSM_OK;
 }
 
@@ -126,9 +126,9 @@ int fork_segments(dsm_context *ctx, const std::vector<Seg> &segs, bool with_comp
   bool recorded = false;
   for (size_t si = 1; si < segs.size(); si++) {
     if (segs[si].companion && !with_companion) continue;
-    if (!recorded) DSM_HIP(hipEventRecord(ctx->fork_event, ctx->stream));
+    if (!recorded) DSM_HIP(hipEventRecord(ctx->groups.fork_event, ctx->stream));
     recorded = true;
-    DSM_HIP(hipStreamWaitEvent(segs[si].st, ctx->fork_event, 0));
+    DSM_HIP(hipStreamWaitEvent(segs[si].st, ctx->groups.fork_event, 0));
   }
   return DSM_OK;
 }
@@ -136,7 +136,7 @@ int fork_segments(dsm_context *ctx, const std::vector<Seg> &segs, bool with_comp
 int join_segments(dsm_context *ctx, const std::vector<Seg> &segs, bool with_companion) {
   for (size_t si = 1; si < segs.size(); si++) {
     if (segs[si].companion && !with_companion) continue;
-    hipEvent_t ev = segs[si].companion ? ctx->companion_event : ctx->join_events[si - 1];
+    hipEvent_t ev = segs[si].companion ? ctx->groups.companion_event : ctx->groups.join_events[si - 1];
     DSM_HIP(hipEventRecord(ev, segs[si].st));
     DSM_HIP(hipStreamWaitEvent(ctx->stream, ev, 0));
   }
@@ -145,17 +145,17 @@ int join_segments(dsm_context *ctx, const std::vector<Seg> &segs, bool with_comp
 
 // ---- per-dispatch timing ----
 hipEvent_t get_event(dsm_context *ctx, size_t idx) {
-  while (ctx->ev_pool.size() <= idx) {
+  while (ctx->timers.ev_pool.size() <= idx) {
     hipEvent_t ev;
     if (hipEventCreate(&ev) != hipSuccess) return nullptr;
-    ctx->ev_pool.push_back(ev);
+    ctx->timers.ev_pool.push_back(ev);
   }
-  return ctx->ev_pool[idx];
+  return ctx->timers.ev_pool[idx];
 }
 
 int timed_eval_begin(dsm_context *ctx, const Seg &sg, int L, EvalTimer &tm, hipEvent_t *end) {
   *end = nullptr;
-  if (!ctx->timing || sg.companion) return DSM_OK;
+  if (!ctx->timers.timing || sg.companion) return DSM_OK;
   hipEvent_t begin = get_event(ctx, tm.used++);
   *end = get_event(ctx, tm.used++);
   tm.lvl.push_back(L);
@@ -170,8 +170,8 @@ void collect_eval_timing(dsm_context *ctx, const std::vector<int> &ev_lvl, int n
   std::vector<std::pair<float, float>> iv[DSM_MAX_LEVELS];
   for (size_t i = 0; i < ev_lvl.size(); i++) {
     float m = 0, a = 0;
-    if (hipEventElapsedTime(&m, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]) == hipSuccess &&
-        hipEventElapsedTime(&a, ctx->ev_total[0], ctx->ev_pool[2 * i]) == hipSuccess) {
+    if (hipEventElapsedTime(&m, ctx->timers.ev_pool[2 * i], ctx->timers.ev_pool[2 * i + 1]) == hipSuccess &&
+        hipEventElapsedTime(&a, ctx->timers.ev_total[0], ctx->timers.ev_pool[2 * i]) == hipSuccess) {
       st.eval_kernel_ms[ev_lvl[i]] += m;
       st.eval_dispatches[ev_lvl[i]]++;
       iv[ev_lvl[i]].push_back(std::make_pair(a, a + m));

@@ -255,8 +255,8 @@ int dsm_stream_destroy(dsm_stream *s) {
   if (!s) return DSM_OK;
   hipSetDevice(s->ctx->device);
   hipStreamSynchronize(s->ctx->stream);
-  for (hipStream_t st : s->ctx->extra_streams) hipStreamSynchronize(st);
-  if (s->ctx->companion_stream) hipStreamSynchronize(s->ctx->companion_stream);
+  for (hipStream_t st : s->ctx->groups.extra_streams) hipStreamSynchronize(st);
+  if (s->ctx->groups.companion_stream) hipStreamSynchronize(s->ctx->groups.companion_stream);
   stream_free(s);
   return DSM_OK;
 }
@@ -587,14 +587,14 @@ static int pass_read_back(dsm_stream *s, Pass &p) {
   dsm_context *ctx = s->ctx;
   const int N = s->N, nlevels = s->nlevels;
   DSM_HIP(hipMemcpyAsync(s->h_states, s->d_states, sizeof(LMState) * N, hipMemcpyDeviceToHost, ctx->stream));
-  DSM_HIP(hipEventRecord(ctx->ev_total[1], ctx->stream));
+  DSM_HIP(hipEventRecord(ctx->timers.ev_total[1], ctx->stream));
   DSM_HIP(hipStreamSynchronize(ctx->stream));
   s->passes++;
   float ms = 0;
-  DSM_HIP(hipEventElapsedTime(&ms, ctx->ev_total[0], ctx->ev_total[1]));
+  DSM_HIP(hipEventElapsedTime(&ms, ctx->timers.ev_total[0], ctx->timers.ev_total[1]));
   s->stats[0].total_ms += ms, s->stats[1].total_ms += ms;
   s->stats[0].polls += 1;
-  if (ctx->timing) collect_eval_timing(ctx, p.tm.lvl, nlevels, s->stats[0]);
+  if (ctx->timers.timing) collect_eval_timing(ctx, p.tm.lvl, nlevels, s->stats[0]);
   for (int i = 0; i < N; i++) {
     Slot &sl = s->slots[i];
     if (sl.state == SLOT_FREE) continue;
@@ -644,13 +644,13 @@ static int pass_advance(dsm_stream *s) {
   dsm_context *ctx = s->ctx;
   DSM_HIP(hipSetDevice(ctx->device));
   Pass p;
-  p.segs = build_segments(ctx->n_streams, s->cap[0], 0, s->cap[1], 1);
+  p.segs = build_segments(ctx->groups.n_streams, s->cap[0], 0, s->cap[1], 1);
   pass_admit(s, p);
   if (!pass_survey(s, p)) return DSM_OK;
   int rc = bind_streams(ctx, p.segs);
   if (rc) return rc;
   if (!p.fresh.empty() && (rc = sync_descs(ctx, p.fresh.data(), (int)p.fresh.size()))) return rc;
-  DSM_HIP(hipEventRecord(ctx->ev_total[0], ctx->stream));
+  DSM_HIP(hipEventRecord(ctx->timers.ev_total[0], ctx->stream));
   if ((rc = pass_row_maps(s, p)) || (rc = pass_start_admitted(s, p)) || (rc = pass_rounds(s, p)) || (rc = pass_read_back(s, p))) return rc;
   pass_learn(s);
   return DSM_OK;
@@ -773,7 +773,7 @@ int dsm_stream_advance(dsm_stream *s) {
 static int tick_setup(dsm_stream *s) {
   dsm_context *ctx = s->ctx;
   const int cap0 = s->cap[0], N = s->N;
-  s->tsegs = build_segments(ctx->n_streams, cap0, 0, s->cap[1], 1);
+  s->tsegs = build_segments(ctx->groups.n_streams, cap0, 0, s->cap[1], 1);
   const int nseg = (int)s->tsegs.size();
   tick_free(s); // (an earlier attempt that failed half way left its allocations behind: ADVICE r04)
   int rc = realloc_dev(&s->d_segctl, nseg);
@@ -942,7 +942,7 @@ static int tick_hand_over(dsm_stream *s, Advance &a) {
   int rc;
   if (!fresh.empty() && (rc = sync_descs(ctx, fresh.data(), (int)fresh.size()))) return rc;
   DSM_HIP(hipEventRecord(s->ev_begin[a.par], ctx->stream));
-  if (ctx->timing) DSM_HIP(hipEventRecord(ctx->ev_total[0], ctx->stream)); // (collect_eval_timing places the dispatches relative to it)
+  if (ctx->timers.timing) DSM_HIP(hipEventRecord(ctx->timers.ev_total[0], ctx->stream)); // (collect_eval_timing places the dispatches relative to it)
   for (int mode = 0; mode < 2; mode++) {
     if (!a.n_new[mode]) continue;
     const int ring = s->ring[mode];
@@ -1038,7 +1038,7 @@ static int tick_ticks(dsm_stream *s, const Advance &a) {
   }
   s->parity = (s->parity + a.T) & 1;
   s->inflight_parity[a.par] = s->parity;
-  s->inflight_timed[a.par] = ctx->timing;
+  s->inflight_timed[a.par] = ctx->timers.timing;
   DSM_HIP(hipGetLastError());
   return DSM_OK;
 }
@@ -1069,7 +1069,7 @@ static int tick_advance(dsm_stream *s) {
       s->handed[0] == s->seen[0].admitted && s->handed[1] == s->seen[1].admitted)
     return DSM_OK; // idle
   if ((rc = bind_streams(ctx, s->tsegs))) return rc;
-  if ((s->advances - s->collected >= 2 || ctx->timing) && (rc = tick_sync(s))) return rc; // (at most one advance behind: the pinned copies are two deep;
+  if ((s->advances - s->collected >= 2 || ctx->timers.timing) && (rc = tick_sync(s))) return rc; // (at most one advance behind: the pinned copies are two deep;
                                                                                           // a timed advance reads its own events alone)
   Advance a{};
   a.k = s->advances;
@@ -1081,7 +1081,7 @@ static int tick_advance(dsm_stream *s) {
   s->total_ticks += a.T;
   s->passes++;
   // what was in flight before this advance has finished on the device by now, or finishes while the host is busy here
-  return tick_sync(s, ctx->timing || !s->pipelined ? s->advances : s->advances - 1);
+  return tick_sync(s, ctx->timers.timing || !s->pipelined ? s->advances : s->advances - 1);
 }
 
 extern "C" {

@@ -11,6 +11,7 @@
 //     order (block counts -> exclusive scan -> ordered writes), so the template order -- and with it
 //     the chunking and every reduction of the eval kernels -- equals the reference's emit order.
 // The idepth_/weight_sums_ side products (only read by debugPlotIDepthMap) are not kept.
+// At the end: the template helpers of dsm_tracker_set_ref / _get_template (interleave, de-interleave) and scaleCoarseDepthL0.
 #include "dsm_kernels.hpp"
 
 namespace dsm {
@@ -256,6 +257,54 @@ void launch_make_coarse_depth(hipStream_t s, int w, int h, int nlevels, const Tp
     }
     off += wl * hl;
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// template helpers
+// ------------------------------------------------------------------------------------------
+__global__ void interleave_kernel(int n, const float *__restrict__ u, const float *__restrict__ v,
+                                  const float *__restrict__ id, const float *__restrict__ c,
+                                  float4 *__restrict__ out) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    out[i] = make_float4(u[i], v[i], id[i], c[i]);
+}
+__global__ void deinterleave_kernel(int n, const float4 *__restrict__ in, float *u, float *v, float *id,
+                                    float *c) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float4 p = in[i];
+    u[i] = p.x;
+    v[i] = p.y;
+    id[i] = p.z;
+    c[i] = p.w;
+  }
+}
+// scaleCoarseDepthL0 (:329-336): lpc_idepth[p] /= scale
+__global__ void scale_depth_kernel(int n, float4 *pts, float scale) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) pts[i].z = pts[i].z / scale;
+}
+static inline int grid_for(int n, int block = 256) {
+  int g = (n + block - 1) / block;
+  return g < 1 ? 1 : (g > 2048 ? 2048 : g);
+}
+
+void launch_interleave_template(hipStream_t s, int n, const float *u, const float *v, const float *id,
+                                const float *c, float4 *out) {
+  if (n > 0) hipLaunchKernelGGL(interleave_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, u, v, id, c, out);
+}
+void launch_deinterleave_template(hipStream_t s, int n, const float4 *in, float *u, float *v, float *id,
+                                  float *c) {
+  if (n > 0) hipLaunchKernelGGL(deinterleave_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, in, u, v, id, c);
+}
+void launch_scale_depth(hipStream_t s, int n, float4 *pts, float scale) {
+  if (n > 0) hipLaunchKernelGGL(scale_depth_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, pts, scale);
+}
+__global__ void scale_depth_levels_kernel(ScaleDepthArgs a, float scale) {
+  const int l = blockIdx.y, n = a.n[l];
+  float4 *pts = a.pts[l];
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) pts[i].z = pts[i].z / scale; // (:333, as scale_depth_kernel)
+}
+void launch_scale_depth_levels(hipStream_t s, const ScaleDepthArgs &a, int max_n, float scale) {
+  if (max_n > 0) hipLaunchKernelGGL(scale_depth_levels_kernel, dim3(grid_for(max_n), a.nlevels), dim3(256), 0, s, a, scale);
 }
 
 } // namespace dsm

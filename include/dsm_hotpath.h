@@ -196,7 +196,7 @@ int dsm_context_set_streams(dsm_context *ctx, int n_streams);
 void *dsm_context_stream(dsm_context *ctx);
 /* The stream groups (dsm_context_set_streams, dsm_stream_*) only overlap if their HIP streams sit on different HARDWARE queues; the
  * runtime hands its few queues (GPU_MAX_HW_QUEUES, 4 by default) out round robin to every stream of the process.  The library therefore
- * probes each stream it creates for a group (a resident kernel on one, an empty kernel on the other: docs in dsm_capi.hip) and keeps
+ * probes each stream it creates for a group (a resident kernel on one, an empty kernel on the other: docs in csrc/lm_schedule.hip, ensure_streams) and keeps
  * only streams that run concurrently with the groups it already has.  streams_out: group streams in use (the context's own included),
  * sharing_out: how many of them had to share a queue with another group after 12 candidates (0 on a default runtime). */
 int dsm_context_stream_queues(dsm_context *ctx, int *streams_out, int *sharing_out);

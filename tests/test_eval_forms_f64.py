@@ -11,20 +11,21 @@ Each with residual_only 0 and 1, under the three chunk tables.
 
 Full evaluations: the assertions of test_normal_equations_f64.py (tests/_gn_checks.py) for every form; form 0 is bit for bit
 dsm_tracker_calc_res_pose / _scale, and every other form is bit for bit form 0 -- rs, H, b, h00, h01 -- at EVERY level:
-  * the forms share eval_chunk_impl's reduction (tracker_kernels.hip:575-628: row16_sum, the 16 rows in order) and
-    LM_OP_SINGLE_FINISH; the arrival ticket (:605-612) hands the same additions in the same order to another wave;
-  * on levels >= 1 forms 2 and 3 run the two-point loop (:513-546) where form 0 runs the one-point loop (:547-569).  Both call stage_b
-    for the thread's points k = 0 .. P - 1 in that order, and stage_b is the only place the accumulators, E and the counts are added to
-    (:370-376, :401, :419-421).  The two-point loop's extra call at odd P (P = 1: point k + 1 = P) is masked: `listed(.., false)` is an
-    empty lane mask, so every term is an exact zero of either sign added to a sum that is never -0 (:383-394 mask the Jacobian's
-    inputs, :376-377 the energy and the weight), which leaves the bits alone.  VC only chooses the register file of loop constants.
+  * the forms share the reduction at the end of eval_chunk_impl (tracker_kernels.hip: row16_sum, the 16 rows in order) and
+    LM_OP_SINGLE_FINISH; the arrival ticket the waves take there hands the same additions in the same order to another wave;
+  * on levels >= 1 forms 2 and 3 run eval_chunk_impl's two-point loop (DEEP) where form 0 runs its one-point loop.  Both call stage_b
+    for the thread's points k = 0 .. P - 1 in that order, and stage_b is the only place the accumulators, E and the counts are added to.
+    The two-point loop's extra call at odd P (P = 1: point k + 1 = P) is masked: `listed(.., false)` is an
+    empty lane mask, so every term is an exact zero of either sign added to a sum that is never -0 (stage_b masks the Jacobian's
+    inputs, the energy and the weight), which leaves the bits alone.  VC only chooses the register file of loop constants.
   So the per-thread addition order is the same and bit equality is asserted on levels >= 1 as well.
 
-Residual-only evaluations: numTermsInE, the saturated share and the padded warped count equal the reference's -- eval_chunk_impl counts
-n_warped from the same `use` mask whether RO or not (:368-372), so a residual-only evaluation reports the full evaluation's count; E and
+Residual-only evaluations: numTermsInE, the saturated share and the padded warped count equal the reference's -- stage_b counts
+n_warped from the same `use` mask whether RO or not, so a residual-only evaluation reports the full evaluation's count; E and
 the flow indicators within the bounds; rs bit for bit the full evaluation's of the same form, table and inputs (the intensity is
-interpolated by the same four products in the same order from two 8-byte loads instead of four loads, :147-153, :178); and every H / b
-entry, h00 and h01 exactly 0 (:581: the partial slots are written as zeros).  With no usable point (n_warped = 0) LM_OP_SINGLE_FINISH's
+interpolated by the same four products in the same order from two 8-byte loads instead of four loads: taps_load / taps_interp with
+GRAD = false); and every H / b entry, h00 and h01 exactly 0 (eval_chunk_impl's reduction writes a residual-only evaluation's partial
+slots as zeros).  With no usable point (n_warped = 0) LM_OP_SINGLE_FINISH's
 1 / n is infinite and H, b, h are not compared -- as for full evaluations, where the same holds."""
 import ctypes as C
 

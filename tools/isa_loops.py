@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Lists the loops of one kernel in an `hipcc -S` listing with their instruction mix.
-    hipcc --offload-arch=gfx950 ... -S --cuda-device-only -o t.s tracker_kernels.hip
+    hipcc --offload-arch=gfx950 ... -S --cuda-device-only -o t.s tracker_kernels.hip     (or any other kernel file of csrc/)
     python tools/isa_loops.py t.s '<mangled kernel name prefix>' [min_instructions]
 A loop = a backward branch to a label; the body = the lines between the label and the branch (inner blocks included)."""
 import collections
