@@ -23,10 +23,12 @@ DSM_HD Dir direction(int d) {
 }
 DSM_HD float dir_norm(float gx, float gy, Dir d) { return fabsf(gx * d.x + gy * d.y); }
 
-// P1: central differences of an intensity plane, zero on the border rows and columns
+// P1: central differences of an intensity plane on the flat index, as dip_gradients (frame_kernels.hip) forms them: zero on rows 0 and
+// hl - 1; in columns 0 and wl - 1 of the other rows the x difference wraps into the neighbouring row (p[-1] is the last pixel of the
+// row above, p[1] the first of the row below), both inside the plane
 DSM_HD void gradient(const float *I, int wl, int hl, int x, int y, float &gx, float &gy) {
   gx = gy = 0.f;
-  if (x < 1 || y < 1 || x > wl - 2 || y > hl - 2) return;
+  if (y < 1 || y > hl - 2) return;
   const float *p = I + ((long long)y * wl + x);
   gx = pt::grad_fix(0.5f * (p[1] - p[-1]));
   gy = pt::grad_fix(0.5f * (p[wl] - p[-wl]));
@@ -34,7 +36,7 @@ DSM_HD void gradient(const float *I, int wl, int hl, int x, int y, float &gx, fl
 // P1: the squared gradient, weighted by the slope of the inverse response at the pixel's intensity if b_inv is given
 DSM_HD float abs_grad(const float *I, int wl, int hl, int x, int y, const float *b_inv, float &gx, float &gy) {
   gradient(I, wl, hl, x, y, gx, gy);
-  if (x < 1 || y < 1 || x > wl - 2 || y > hl - 2) return 0.f;
+  if (y < 1 || y > hl - 2) return 0.f;
   float ag = gx * gx + gy * gy;
   if (b_inv) {
     const float c = I[(long long)y * wl + x] + 0.5f;

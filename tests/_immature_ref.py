@@ -3,7 +3,8 @@ ImmaturePoint::linearizeResidual as the project states it, one point at a time i
 float32; the LM step and the convergence test are Python floats = double).  Written from the statement, not from the C code.
 
 optimize(w, h, job, frames, ...) returns per point: status, idepth, res_state, hdd, bd, energy, iterations, and `trace`, the
-branches taken.  make_case / case build the seeded scenes the tests share; a case is computed once per process."""
+branches taken.  make_case / case build the seeded 96 x 64 scenes the tests share, make_case_at / geometry_case a window at any geometry
+whose frames shift the pattern towards every side; a case is computed once per process."""
 import numpy as np
 
 f32 = np.float32
@@ -255,6 +256,81 @@ def case(name):
         job, frames = make_case(**kw)
         _cache[name] = (job, frames, optimize(W, H, job, frames, gn_iterations=its), its)
     return _cache[name]
+
+
+# ---- a window at any geometry: make_case above is hard-wired to 96 x 64 and to sideways motion -------------------------------------------
+GEOMETRY = (101, 53)
+SIDES = ("left", "right", "top", "bottom")
+
+
+def make_case_at(w, h, seed=1, n_frames=9, n_random=48, per_side=10):
+    """A window of n_frames w x h frames looking at one plane (idepth 0.25, R = I): frame 0 at the origin, frame k at
+    0.08 k times (1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, -1), (1, -1), (-1, 1) in turn (and 0.002 k forwards), so that the other
+    frames see a point's pattern shifted towards every side, by 1.6 k px at the plane; a 6 x 4 block of NaN in frame 2.  Points at
+    integer pixels: n_random anywhere on any host, then per_side next to each side (3 .. 8 px from it), idepth intervals as make_case's.
+    Returns (job without "window", frames)."""
+    rng = np.random.default_rng(seed)
+    fx, fy = CAM[:2]
+    cam = (fx, fy, f32((w - 1) / 2.0), f32((h - 1) / 2.0))
+    dirs = [(1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, -1), (1, -1), (-1, 1)]
+    cams = [np.zeros(3)] + [np.array([0.08 * k * dirs[(k - 1) % 8][0], 0.08 * k * dirs[(k - 1) % 8][1], 0.002 * k]) for k in range(1, n_frames)]
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    frames = [texture(seed, xs - float(fx) * c[0] * PLANE_IDEPTH, ys - float(fy) * c[1] * PLANE_IDEPTH).astype(f32) for c in cams]
+    if n_frames > 2:
+        frames[2][h // 2 - 2:h // 2 + 2, w // 2:w // 2 + 6] = np.nan
+    pre_R = np.tile(np.eye(3, dtype=f32).reshape(9), (n_frames, n_frames, 1))
+    pre_t = np.zeros((n_frames, n_frames, 3), f32)
+    for a in range(n_frames):
+        for b in range(n_frames):
+            pre_t[a, b] = (cams[b] - cams[a]).astype(f32)
+    pre_aff = np.tile(np.array([1.0, 0.0], f32), (n_frames, n_frames, 1))
+    n_pts = n_random + 4 * per_side
+    host = rng.integers(0, n_frames, n_pts).astype(np.int32)
+    u, v = rng.integers(3, w - 3, n_pts).astype(f32), rng.integers(3, h - 3, n_pts).astype(f32)
+    for s in range(4):
+        sl = slice(n_random + s * per_side, n_random + (s + 1) * per_side)
+        d = rng.integers(3, 9, per_side).astype(f32)
+        if s < 2:
+            u[sl] = d if s == 0 else f32(w - 1) - d
+        else:
+            v[sl] = d if s == 2 else f32(h - 1) - d
+    color = np.zeros((n_pts, 8), f32)
+    for i in range(n_pts):
+        for k, (dx, dy) in enumerate(PATTERN):
+            color[i, k] = frames[host[i]][int(v[i]) + dy, int(u[i]) + dx]
+    color[~np.isfinite(color)] = 128.0
+    weights = np.sqrt(2500.0 / (2500.0 + rng.uniform(0, 400, (n_pts, 8)))).astype(f32)
+    centre = PLANE_IDEPTH * (1.0 + rng.uniform(-0.4, 0.4, n_pts))
+    half = rng.uniform(0, 0.05, n_pts)
+    job = dict(cam=cam, cam_inv=(f32(1.0) / fx, f32(1.0) / fy), frame_ids=np.arange(100, 100 + n_frames, dtype=np.int32), pre_R=pre_R, pre_t=pre_t,
+               pre_aff=pre_aff, host=host, u=u, v=v, idepth_min=(centre - half).astype(f32), idepth_max=(centre + half).astype(f32),
+               energy_th=np.full(n_pts, 8 * 144.0, f32), color=color, weights=weights, min_obs=1)
+    return job, frames
+
+
+def sides_left_at(w, h, job, i, f):
+    """the sides over which the pattern of point i leaves frame f at the idepth the optimisation starts from (float64): the guard is
+    1.1 < Ku < w - 3, 1.1 < Kv < h - 3"""
+    fx, fy, cx, cy = (float(x) for x in job["cam"])
+    hst = int(job["host"][i])
+    nf = len(job["frame_ids"])
+    t = np.asarray(job["pre_t"], np.float64).reshape(nf, nf, 3)[hst, f]
+    idepth = 0.5 * (float(job["idepth_max"][i]) + float(job["idepth_min"][i]))
+    out = set()
+    for dx, dy in PATTERN:
+        k0, k1 = (float(job["u"][i]) + dx - cx) / fx, (float(job["v"][i]) + dy - cy) / fy
+        z = 1.0 + t[2] * idepth
+        Ku, Kv = (k0 + t[0] * idepth) / z * fx + cx, (k1 + t[1] * idepth) / z * fy + cy
+        out |= {s for s, gone in zip(SIDES, (Ku <= 1.1, Ku >= w - 3, Kv <= 1.1, Kv >= h - 3)) if gone}
+    return out
+
+
+def geometry_case():
+    """(job, frames, expected) at GEOMETRY with nine frames, computed once"""
+    if "geometry" not in _cache:
+        job, frames = make_case_at(*GEOMETRY, seed=8)
+        _cache["geometry"] = (job, frames, optimize(*GEOMETRY, job, frames))
+    return _cache["geometry"]
 
 
 FIELDS_BITS = ("idepth", "hdd", "bd", "energy")

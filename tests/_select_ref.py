@@ -1,6 +1,7 @@
 """The authority for the pixel selection: numpy float32, written from the rules with upstream's sequential
 select() loop -- the running counter n2 behind every direction and the bestIdx = -2 flags.  It shares no code with the library.
-Also the scene the selection tests run on, and what the coverage assertions of tests/test_select_ref.py count."""
+Also the scene the selection tests run on, the cases (CASES at 96 x 64 and 104 x 72; EDGE_CASES at remainder and camera sizes), and what
+the coverage assertions of tests/test_select_ref.py and tests/test_select_edges_ref.py count."""
 import functools
 
 import numpy as np
@@ -63,10 +64,15 @@ def pyramid(I0):
 
 # ---- P1 --------------------------------------------------------------------------------------------------------------------------
 def gradients(I):
+    """central differences on the flat index for idx in [w, w (h - 1)): rows 0 and h - 1 stay zero; in columns 0 and w - 1 of the other
+    rows the x difference wraps into the neighbouring row"""
+    I = np.ascontiguousarray(I, f32)
+    h, w = I.shape
     gx, gy = np.zeros_like(I), np.zeros_like(I)
+    flat = I.reshape(-1)
     with np.errstate(invalid="ignore", over="ignore"):
-        gx[1:-1, 1:-1] = f32(0.5) * (I[1:-1, 2:] - I[1:-1, :-2])
-        gy[1:-1, 1:-1] = f32(0.5) * (I[2:, 1:-1] - I[:-2, 1:-1])
+        gx.reshape(-1)[w:w * (h - 1)] = f32(0.5) * (flat[w + 1:w * (h - 1) + 1] - flat[w - 1:w * (h - 1) - 1])
+        gy[1:-1, :] = f32(0.5) * (I[2:, :] - I[:-2, :])
     gx[~np.isfinite(gx)] = 0
     gy[~np.isfinite(gy)] = 0
     return gx, gy
@@ -80,7 +86,6 @@ def abs_grad(I, b_inv=None):
         gw = np.asarray(b_inv, f32)[c + 1] - np.asarray(b_inv, f32)[c]
         ag = ag * (gw * gw)
         ag[0, :] = ag[-1, :] = 0
-        ag[:, 0] = ag[:, -1] = 0
     return ag.astype(f32), gx, gy
 
 
@@ -380,6 +385,87 @@ def expected(name):
     w, h = case["shape"]
     return select_ref(image_of(case), pattern(w, h), case["potential"], case["density"], case.get("max_pts", MAX_PTS),
                       b_inv_table() if case.get("b_inv") else None, **case["params"])
+
+
+# ---- remainder and camera sizes: a short case list of their own (SHAPES multiplies every case, these do not) ------------------------------
+EDGE_SHAPES = [(105, 73), (106, 70), (107, 75), (33, 33), (63, 47)]  # w % 4 = 1, 2, 3 and odd h or h % 4 = 2; one 32-block; w32 = h32 = 1
+CAMERA_SHAPES = [(1241, 376), (1226, 370)]  # tests/golden/cams
+EDGE_MAX_PTS = 1500
+CAMERA_MAX_PTS = 26000
+UP_DENSITY = {(33, 33): 4.0, (63, 47): 12.0}  # what sends potential 3 up (quot < 0.25) where the frame has few cells
+
+
+def _edge_cases():
+    c = {}
+    for w, h in EDGE_SHAPES:
+        s = f"{w}x{h}"
+        for pot in (1, 3, 7, 40):  # 4 * 40 exceeds both sides: a single padded block
+            c[f"{s}-pot{pot}"] = dict(shape=(w, h), potential=pot, density=1500.0, params=dict(recursions=0))
+        c[f"{s}-down"] = dict(shape=(w, h), potential=3, density=3000.0, params={})
+        c[f"{s}-up"] = dict(shape=(w, h), potential=3, density=UP_DENSITY.get((w, h), 30.0), params={})
+        c[f"{s}-pot4096"] = dict(shape=(w, h), potential=4096, density=1500.0, params=dict(recursions=0))
+        c[f"{s}-pot4096-rec2"] = dict(shape=(w, h), potential=4096, density=1500.0, params=dict(recursions=2))
+    for w, h in CAMERA_SHAPES:
+        s = f"{w}x{h}"
+        c[f"{s}-pot1"] = dict(shape=(w, h), potential=1, density=20000.0, max_pts=CAMERA_MAX_PTS, params={})  # quot 0.31: one pass
+        c[f"{s}-pot3"] = dict(shape=(w, h), potential=3, density=2000.0, max_pts=CAMERA_MAX_PTS, params={})
+        c[f"{s}-pot4096-rec2"] = dict(shape=(w, h), potential=4096, density=2000.0, max_pts=CAMERA_MAX_PTS, params=dict(recursions=2))
+    w, h = CAMERA_SHAPES[1]
+    c[f"{w}x{h}-pot5"] = dict(shape=(w, h), potential=5, density=3000.0, max_pts=CAMERA_MAX_PTS, params={})  # the fourth job of the batch
+    w, h = EDGE_SHAPES[2]
+    c["no_point_arrays"] = dict(shape=(w, h), potential=3, density=300.0, max_pts=0, params={})
+    return c
+
+
+EDGE_CASES = _edge_cases()
+BATCH_OF_FOUR = [f"1226x370-{k}" for k in ("pot1", "pot3", "pot4096-rec2", "pot5")]  # run under one dsm_select_params: batch_expected
+
+
+def edge_job_of(case, **more):
+    return dict(density=case["density"], potential=case["potential"], max_pts=case.get("max_pts", EDGE_MAX_PTS), b_inv=None, **more)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_expected(name):
+    """the checker's result for an edge case, computed once and shared: do not modify it"""
+    case = EDGE_CASES[name]
+    w, h = case["shape"]
+    return select_ref(scene(w, h), pattern(w, h), case["potential"], case["density"], case.get("max_pts", EDGE_MAX_PTS), None, **case["params"])
+
+
+@functools.lru_cache(maxsize=None)
+def batch_expected(name, recursions):
+    """a batch has one dsm_select_params: the case's job under `recursions`.  Shared with edge_expected where the case's own is the same"""
+    case = EDGE_CASES[name]
+    if dict(DEFAULTS, **case["params"])["recursions"] == recursions:
+        return edge_expected(name)
+    w, h = case["shape"]
+    return select_ref(scene(w, h), pattern(w, h), case["potential"], case["density"], case.get("max_pts", EDGE_MAX_PTS), None,
+                      **dict(case["params"], recursions=recursions))
+
+
+def null_point_arrays(batch, j):
+    """job j of a pixelselect.SelectBatch without any point array (allowed with max_pts = 0)"""
+    for k in ("u", "v", "energy_th", "grad_h", "color", "weights", "status", "idepth_min", "idepth_max", "quality", "type"):
+        setattr(batch.arr[j], k, None)
+    assert not batch.arr[j].u and not batch.arr[j].status
+
+
+def level2_last_column_reads(F):
+    """P1, P9: the scanned pixels that read level 2 in its last column w_2 - 1 -> (how many, how many of them have ag_2 > t2 under
+    the flat-index rule, how many would under a rule that zeroes the border columns)"""
+    w, h = F.w, F.h
+    w2 = w >> 2
+    reads = new = old = 0
+    for yf in range(4, h - 3):
+        for xf in range(4, w - 5):
+            if int(xf * 0.25 + 0.125) != w2 - 1:
+                continue
+            reads += 1
+            above = F.ag[2][int(yf * 0.25 + 0.125)][w2 - 1] > F.th[2][yf][xf]
+            new += above
+            old += 0.0 > F.th[2][yf][xf]
+    return reads, new, old
 
 
 # ---- for tools/select_host_standalone.cpp ------------------------------------------------------------------------------------------

@@ -3,8 +3,10 @@ one point at a time in numpy float32 (every operation rounds to float32; the eig
 array elements, their sums are chains of float32 additions in pattern order).  Written from the rules, not from the C code.
 
 trace(w, h, target, job, **params) returns the state after the call (status, idepth_min, idepth_max, quality, trace_uv,
-trace_interval), steps, counts, and `branches`: per branch name the number of points that took it.  make_scene / case build the seeded
-160 x 64 scene the tests share; a case is computed once per process."""
+trace_interval), steps, counts, `branches`: per branch name the number of points that took it, and `point_branches`: per point the
+set of its branches.  make_scene / case build the seeded
+160 x 64 scene the tests share, make_scene_at / geometry_case the same kinds of points at any geometry, with points on either side of
+T2's bound next to all four sides; a case is computed once per process."""
 import numpy as np
 
 f32 = np.float32
@@ -248,7 +250,7 @@ def trace(w, h, target, job, **params):
     uv = np.asarray(job["trace_uv"], f32).reshape(n, 2)
     out = dict(status=np.zeros(n, np.uint8), idepth_min=np.zeros(n, f32), idepth_max=np.zeros(n, f32), quality=np.zeros(n, f32),
                trace_uv=np.zeros((n, 2), f32), trace_interval=np.zeros(n, f32), steps=np.zeros(n, np.int32))
-    branches = dict.fromkeys(BRANCHES, 0)
+    branches, point_branches = dict.fromkeys(BRANCHES, 0), []
     with np.errstate(all="ignore"):
         for i in range(n):
             hst = int(job["host"][i])
@@ -259,10 +261,11 @@ def trace(w, h, target, job, **params):
             st, steps, br = trace_point(w, h, I, krki[hst], kt[hst], aff[hst], pt, S)
             out["status"][i], out["idepth_min"][i], out["idepth_max"][i], out["quality"][i] = st["status"], st["idepth_min"], st["idepth_max"], st["quality"]
             out["trace_uv"][i], out["trace_interval"][i], out["steps"][i] = (st["uv0"], st["uv1"]), st["interval"], steps
+            point_branches.append(br)
             for name in br:
                 branches[name] += 1
     out["counts"] = np.bincount(out["status"], minlength=6).astype(np.int32)
-    out["branches"] = branches
+    out["branches"], out["point_branches"] = branches, point_branches
     return out
 
 
@@ -414,6 +417,111 @@ def make_scene(seed=1, plain=False, n_random=150, noise=1.0, only=None):
                idepth_max=np.array([p[5] for p in pts], f32), quality=np.array([p[6] for p in pts], f32), trace_uv=np.zeros((n, 2), f32),
                trace_interval=np.zeros(n, f32))
     return job, target, PLANE_IDEPTH
+
+
+# ---- a scene at any geometry: the 160 x 64 scene above is hard-wired to its size ------------------------------------------------------------
+TX, TY = 8.0, 4.0  # pixels per unit of inverse depth of the sideways and of the vertical hosts: powers of two, so that a bound is met exactly
+SIDES = ("left", "right", "top", "bottom")
+SIDE_DELTAS = (0.25, 0.6, 1.2, 0.0, -0.25, -0.6, -1.2)  # how far inside the bound of T2 the projection at idepth_min lies; <= 0: outside
+
+
+def side_bound(side, w, h):
+    """(axis, bound, sign): T2 keeps a projection p when sign * (p[axis] - bound) > 0"""
+    return {"left": (0, 4.0, 1), "right": (0, w - 5.0, -1), "top": (1, 4.0, 1), "bottom": (1, h - 5.0, -1)}[side]
+
+
+def geometry_hosts(w, h):
+    """five hosts: translations to the right, to the left, down and up (K R K^-1 the identity, exactly), and a small rotation"""
+    K = np.array([[0.4 * w, 0, (w - 1) / 2.0], [0, 0.4 * w, (h - 1) / 2.0], [0, 0, 1.0]])
+    a, b = 0.012, -0.01
+    Rz = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+    Ry = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]])
+    krki = np.stack([np.eye(3)] * 4 + [K @ Rz @ Ry @ np.linalg.inv(K)])
+    kts = [(TX, 0, 0), (-TX, 0, 0), (0, TY, 0), (0, -TY, 0), (-5.0, 3.0, 0.02)]
+    affs = [(1.0, 0.0), (1.03, -2.0), (1.0, 0.0), (0.97, 2.0), (1.0, 1.0)]
+    return krki.reshape(-1, 9).astype(f32), np.array(kts, f32), np.array(affs, f32)
+
+
+def geometry_texture(seed, x, y, w):
+    """the six sinusoids of `texture`; the columns [0.55 w, 0.8 w) hold stripes that depend on y alone (no gradient along a sideways
+    epipolar line: T6)"""
+    v = texture(seed, x, y, plain=True)
+    return np.where((x >= int(0.55 * w)) & (x < int(0.8 * w)), 128.0 + 35.0 * np.sin(2 * np.pi * y / 9.0 + 1.0), v)
+
+
+def make_scene_at(w, h, seed=1, n_random=60, noise=1.0):
+    """(job, target plane, sides): the plane at idepth 0.25 seen by geometry_hosts; fresh and narrowed points on every host, skipped,
+    ill-conditioned, outlier and out-of-bounds points, and next to each of the four sides points whose projection at idepth_min
+    lies SIDE_DELTAS inside (or outside) the bound of T2.  sides: side -> the indices of its points, in SIDE_DELTAS' order."""
+    rng = np.random.default_rng(seed)
+    krki, kt, aff = geometry_hosts(w, h)
+    nh = len(kt)
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    target = geometry_texture(seed, xs, ys, w).astype(f32)
+    host_img = []
+    for k in range(nh):
+        px, py = project(krki[k], kt[k], xs, ys, PLANE_IDEPTH)
+        host_img.append(((geometry_texture(seed, px, py, w) - aff[k, 1]) / aff[k, 0]).astype(f32))
+    pts, sides = [], {}
+    ru, rv = (lambda: int(rng.integers(3, w - 3))), (lambda: int(rng.integers(3, h - 3)))
+    fresh = lambda hst, u, v, nan=False: pts.append((hst, u, v, UNINITIALIZED, 0.0, np.nan if nan else np.inf, 10000.0, 0.0))
+    narrowed = lambda hst, u, v, lo, hi, status=GOOD, off=0.0: pts.append((hst, u, v, status, lo, hi, rng.uniform(1.0, 3.0), off))
+    for i in range(n_random):
+        fresh(i % nh, ru(), rv(), nan=bool(i & 1))
+    for i in range(n_random):  # intervals of every width around the truth
+        r, c = rng.uniform(0.02, 1.5), PLANE_IDEPTH * rng.uniform(0.8, 1.25)
+        narrowed(i % nh, ru(), rv(), c * (1 - r), c * (1 + r))
+    for i in range(8):  # T3: less than slack_interval = 1.5 px between the ends
+        narrowed(i % 4, ru(), rv(), PLANE_IDEPTH, PLANE_IDEPTH + rng.uniform(0.2, 1.2) / (TX, TX, TY, TY)[i % 4])
+    for i in range(6):  # T1
+        narrowed(i % nh, ru(), rv(), 0.2, 0.3, status=OOB)
+    for i in range(12):  # T12: colours of another surface, half of them outliers already
+        narrowed(i % 2, int(rng.integers(8, max(9, int(0.5 * w)))), rv(), 0.05, 0.6, status=OUTLIER if i & 1 else GOOD, off=90.0)
+    for i in range(10):  # T6: stripes along the epipolar line of the sideways hosts
+        narrowed(i % 2, int(rng.integers(int(0.55 * w) + 1, max(int(0.55 * w) + 2, int(0.8 * w) - 1))), rv(), 0.1, 0.5)
+    for side in SIDES:
+        axis, bound, sign = side_bound(side, w, h)
+        hst = {"left": 1, "right": 0, "top": 3, "bottom": 2}[side]  # the host that moves the point towards the side
+        g = (TX, TY)[axis]
+        sides[side] = list(range(len(pts), len(pts) + len(SIDE_DELTAS)))
+        for k, delta in enumerate(SIDE_DELTAS):
+            at = 6 + k % 4  # the point's own distance from the side, in pixels: 6 .. 9
+            lo = (at - 4 - delta) / g  # TX, TY and the bounds are exact in float32: delta = 0 meets the bound exactly
+            along = int(rng.integers(8, (h, w)[axis] - 8))
+            u, v = ((at, along), (w - 1 - at, along), (along, at), (along, h - 1 - at))[SIDES.index(side)]
+            if k % 2:
+                narrowed(hst, u, v, lo, lo + 0.3)
+            else:
+                pts.append((hst, u, v, GOOD, lo, np.inf, 2.0, 0.0))  # T4 behind a T2 that is passed or not
+    n = len(pts)
+    host = np.array([p[0] for p in pts], np.int32)
+    u, v = np.array([p[1] for p in pts], f32), np.array([p[2] for p in pts], f32)
+    color, grad_h, weights = np.zeros((n, 8), f32), np.zeros((n, 4), f32), np.zeros((n, 8), f32)
+    for i, p in enumerate(pts):
+        img = host_img[p[0]]
+        for k, (dx, dy) in enumerate(PATTERN):
+            x, y = int(p[1]) + dx, int(p[2]) + dy
+            gx, gy = f32(0.5) * (img[y, x + 1] - img[y, x - 1]), f32(0.5) * (img[y + 1, x] - img[y - 1, x])
+            color[i, k] = img[y, x] + f32(p[7]) + f32(rng.normal(0, noise) if noise else 0.0)
+            grad_h[i] += np.array([gx * gx, gx * gy, gx * gy, gy * gy], f32)
+            weights[i, k] = np.sqrt(f32(2500.0) / (f32(2500.0) + (gx * gx + gy * gy)))
+    job = dict(krki=krki, kt=kt, aff=aff, host=host, u=u, v=v, energy_th=np.full(n, 8 * 144.0, f32), grad_h=grad_h, color=color, weights=weights,
+               status=np.array([p[3] for p in pts], np.uint8), idepth_min=np.array([p[4] for p in pts], f32),
+               idepth_max=np.array([p[5] for p in pts], f32), quality=np.array([p[6] for p in pts], f32), trace_uv=np.zeros((n, 2), f32),
+               trace_interval=np.zeros(n, f32))
+    return job, target, sides
+
+
+GEOMETRIES = [(101, 53), (24, 20)]  # odd sizes, 184 points: partial waves at another stride; just above the 8 x 8 minimum
+_geometry_cache = {}
+
+
+def geometry_case(w, h):
+    """(job, target, expected, sides) at a geometry, computed once"""
+    if (w, h) not in _geometry_cache:
+        job, target, sides = make_scene_at(w, h, seed=5)
+        _geometry_cache[(w, h)] = (job, target, trace(w, h, target, job), sides)
+    return _geometry_cache[(w, h)]
 
 
 # name -> (make_scene arguments, dsm_trace_params fields); "defaults" and "wide" are the two cases whose branch coverage is asserted

@@ -113,6 +113,116 @@ def test_map_too_large_for_lds(ctx):
     check(run(ctx, (1024, 768), [job])[0], exp_map, exp_dec)
 
 
+# ---- maps whose byte count is no multiple of 16 (odd w1): the padding of the 16-byte fill and of the copy through LDS ------------------
+ODD_GEOMS = [(70, 50), (106, 54), (98, 46)]  # maps of 35 x 25 = 875, 53 x 27 = 1431, 49 x 23 = 1127 bytes
+
+
+def points_on_the_last_column_and_row(job, w, h, rng, each=3):
+    """(host, u, v, idepth) of points that the job's hosts project into the last column and into the last row of the map"""
+    w1, h1 = w >> 1, h >> 1
+    n, nh = 4000, len(job["krki"])
+    hst, u, v = rng.integers(0, nh, n).astype(np.int32), rng.uniform(-4, w + 4, n).astype(np.float32), rng.uniform(-4, h + 4, n).astype(np.float32)
+    d = rng.uniform(0.1, 2.0, n).astype(np.float32)
+    c = R.project(job["krki"], job["kt"], hst, u, v, d, w1, h1)[0]
+    col, row = np.flatnonzero((c >= 0) & (c % w1 == w1 - 1))[:each], np.flatnonzero((c >= 0) & (c // w1 == h1 - 1))[:each]
+    pick = np.concatenate([col, row])
+    return hst[pick], u[pick], v[pick], d[pick]
+
+
+def odd_case(geom, k):
+    """job k of three at an odd geometry, with seeds (k = 0, 2) and candidates put into the last column and row
+    -> (job, expected map, expected decisions, info, seed cells, candidate cells, candidates activated in the last column or row)"""
+    w, h = geom
+    name = f"odd-{w}x{h}-{k}"
+    if name not in _big:
+        job = R.make_case(seed=600 + 10 * ODD_GEOMS.index(geom) + k, w=w, h=h, n_hosts=3, n_seeds=(40, 0, 15)[k], n_cand=300,
+                          min_act_dist=(1.5, 2.0, 1.0)[k])
+        rng = np.random.default_rng(700 + k)
+        for kind in (("seed",) if k != 1 else ()) + ("cand",):
+            extra = points_on_the_last_column_and_row(job, w, h, rng)
+            for key, a in zip(("host", "u", "v", "idepth"), extra):
+                job[f"{kind}_{key}"] = np.concatenate([job[f"{kind}_{key}"], a])
+            if kind == "cand":  # type 1: the lowest threshold, so that some of them activate and are added at the edge
+                job["cand_type"] = np.concatenate([job["cand_type"], np.ones(len(extra[0]), np.float32)])
+        w1, h1 = w >> 1, h >> 1
+        sc = R.project(job["krki"], job["kt"], job["seed_host"], job["seed_u"], job["seed_v"], job["seed_idepth"], w1, h1)[0]
+        cc = R.project(job["krki"], job["kt"], job["cand_host"], job["cand_u"], job["cand_v"], job["cand_idepth"], w1, h1)[0]
+        m, dec, info = R.activate(w, h, job)
+        edge = (cc >= 0) & ((cc % w1 == w1 - 1) | (cc // w1 == h1 - 1))
+        _big[name] = (job, m, dec, info, sc[sc >= 0], cc[cc >= 0], int((dec[edge] == 1).sum()))
+    return _big[name]
+
+
+@pytest.mark.parametrize("geom", ODD_GEOMS)
+def test_odd_maps_made_alone(ctx, geom):
+    w1, h1 = geom[0] >> 1, geom[1] >> 1
+    assert (w1 * h1) % 16 and w1 % 2 == 1 and w1 * h1 in (875, 1431, 1127)
+    cs = [odd_case(geom, k) for k in range(3)]
+    for c in (cs[0], cs[2]):  # seeds in the last column and in the last row: 3 .. 5 each
+        assert ((c[4] % w1) == w1 - 1).sum() >= 3 and ((c[4] // w1) == h1 - 1).sum() >= 3
+    got = run(ctx, geom, [c[0] for c in cs], make_only=True)
+    for c, g in zip(cs, got):
+        assert g[0].shape == (h1, w1) and np.array_equal(g[0], c[3]["initial_map"])
+
+
+@pytest.mark.parametrize("geom", ODD_GEOMS)
+def test_odd_maps_fifty_adds_read_back_after_each(ctx, geom):
+    from direct_stereo_slam_amd import distmap
+
+    w, h = geom
+    w1, h1 = w >> 1, h >> 1
+    job, _, _, info = odd_case(geom, 0)[:4]
+    dm = distmap.DistanceMap(ctx, w, h)
+    assert dm.get().shape == (h1, w1) and (dm.get() == 1000).all()
+    distmap.make_distance_maps(ctx, [dict(job, map=dm)])
+    ref = [int(v) for v in info["initial_map"].reshape(-1)]
+    rng = np.random.default_rng(6)
+    for i in range(50):
+        u, v = int(rng.integers(0, w1)), int(rng.integers(0, h1))
+        if i % 5 == 0:
+            u = w1 - 1 if i % 2 else u  # the last column, the last row and (i = 45 .. : both) the last cell of the map
+            v = h1 - 1 if i % 2 == 0 or i >= 45 else v
+        dm.add(u, v)
+        R.add(ref, w1, h1, u + w1 * v)
+        assert np.array_equal(dm.get(), R.as_float(ref, w1, h1)), i
+    dm.close()
+
+
+@pytest.mark.parametrize("geom", ODD_GEOMS)
+def test_odd_maps_batch_of_three_equals_each_alone_equals_checker(ctx, geom):
+    w1, h1 = geom[0] >> 1, geom[1] >> 1
+    cs = [odd_case(geom, k) for k in range(3)]
+    for c in cs:  # candidates in the last column and in the last row, and both decisions
+        cc = c[5]
+        assert ((cc % w1) == w1 - 1).sum() >= 3 and ((cc // w1) == h1 - 1).sum() >= 3 and c[6] >= 3  # 6 .. 13 of them activate: adds at the edge
+        assert (c[2] == 1).sum() >= 10 and (c[2] == 0).sum() >= 10 and (c[2] == 2).sum() >= 10
+    together = run(ctx, geom, [c[0] for c in cs])
+    for c, g in zip(cs, together):
+        check(g, c[1], c[2])
+        alone = run(ctx, geom, [c[0]])[0]
+        assert np.array_equal(alone[0], g[0]) and np.array_equal(alone[1], g[1]) and alone[2] == g[2]
+
+
+# ---- the switch between the map in LDS and the map in global memory: bytes16 <= 138 240 ------------------------------------------------
+def test_largest_map_held_in_lds(ctx):
+    """960 x 576: the 480 x 288 map is 138 240 bytes, exactly what the selection kernel holds in LDS, no byte to spare.
+    The checker takes 0.21 s on the CPU (that of test_kitti_shape_map_held_in_lds: 0.11 s)."""
+    assert (960 >> 1) * (576 >> 1) == 138240 == 135 * 1024
+    job, exp_map, exp_dec, _ = big_case("lds_limit", 960, 576, seed=33, n_hosts=4, n_seeds=3000, n_cand=1000, min_act_dist=2.0)
+    assert (exp_dec == 1).sum() >= 100 and (exp_dec == 0).sum() >= 100, ((exp_dec == 1).sum(), (exp_dec == 0).sum())  # 344 and 523
+    check(run(ctx, (960, 576), [job])[0], exp_map, exp_dec)
+
+
+def test_smallest_map_left_in_global_memory(ctx):
+    """1106 x 500: the 553 x 250 map is 138 250 bytes, 138 256 with its padding: the first size past the LDS limit.
+    The checker takes 0.22 s on the CPU."""
+    w1, h1 = 1106 >> 1, 500 >> 1
+    assert w1 * h1 == 138250 and (w1 * h1 + 15) // 16 * 16 == 138256 > 135 * 1024
+    job, exp_map, exp_dec, _ = big_case("global_limit", 1106, 500, seed=34, n_hosts=4, n_seeds=3000, n_cand=1000, min_act_dist=2.0)
+    assert (exp_dec == 1).sum() >= 100 and (exp_dec == 0).sum() >= 100, ((exp_dec == 1).sum(), (exp_dec == 0).sum())  # 385 and 535
+    check(run(ctx, (1106, 500), [job])[0], exp_map, exp_dec)
+
+
 def edge_job(n_seeds, n_cand, min_act, seed=40, **over):
     job = R.make_case(seed=seed, w=96, h=64, n_hosts=2, n_seeds=n_seeds, n_cand=n_cand, min_act_dist=min_act)
     job.update(over)

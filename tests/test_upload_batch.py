@@ -54,6 +54,23 @@ def test_u8_pixels_equal_their_float_image(ctx):
         _pyramids_equal(trk, s, O.make_images(u8[s].astype(np.float32), sc.nl))
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.uint8])
+def test_more_pixels_than_one_trip_of_the_grid(ctx, dtype):
+    """1045 x 503 = 525 635 pixels: more than the 2048 x 256 = 524 288 threads of the batched pyramid's largest grid, so level 0 takes
+    a second trip of its loop (no other test hands dsm_upload_images that many: the largest is 1241 x 376 in test_upload_undistort.py)"""
+    from direct_stereo_slam_amd.tracker import TrackerAndScaler
+
+    w, h, nl = 1045, 503, 4
+    assert w * h > 2048 * 256
+    trk = TrackerAndScaler(ctx, w, h, nl, S.KITTI_T_STEREO, (700.0, 700.0, 522.0, 251.0))
+    rng = np.random.default_rng(31)
+    imgs = [(rng.random((h, w)) * 255).astype(dtype) for _ in range(2)]
+    ctx.upload_images([trk, trk], [0, 1], imgs)
+    for s in (0, 1):
+        _pyramids_equal(trk, s, O.make_images(imgs[s].astype(np.float32), nl))
+    trk.close()
+
+
 def test_row_pitch_applies_the_calibration_crop(ctx):
     """camera image 318x98, working size 308x92 (crop origin (5, 3)): pointer to the crop origin + the camera's pitch"""
     sc = make_scene("small", seed=24)

@@ -26,7 +26,7 @@ def _photometric(kind, w_in, h_in):
     G = vig = None
     if kind in ("G", "G+vig"):
         G = (255.0 * (np.arange(256) / 255.0) ** 0.8).astype(np.float32)  # a rescaled response
-    if kind == "G+vig":
+    if kind in ("G+vig", "vig"):  # "vig": a vignette without a response table
         X, Y = np.meshgrid(np.linspace(-1, 1, w_in), np.linspace(-1, 1, h_in))
         vig = (1.0 / (1.0 - 0.3 * (X * X + Y * Y) / 2.0)).astype(np.float32)
     return G, vig
@@ -59,14 +59,72 @@ def _check(trk, slot, img, tabs, nl):
         np.testing.assert_array_equal(trk.get_frame(slot, lvl), want[lvl], err_msg=f"level {lvl}")
 
 
-@pytest.mark.parametrize("photo", ["none", "G", "G+vig"])
-@pytest.mark.parametrize("conf", sorted(CONFIGS))
+# every configuration under none, G and G+vig; the vignette without a response table on one remap and on the passthrough form
+PYRAMID_CASES = [(conf, photo) for conf in sorted(CONFIGS) for photo in ("none", "G", "G+vig")] + [("robotcar_preset2", "vig"), ("passthrough", "vig")]
+
+
+def _setup_passthrough(ctx, photo, nl=5):
+    """mode "none" at the KITTI camera size 1241 x 376 (odd width: the quads of the last column have no right half)"""
+    from direct_stereo_slam_amd.tracker import TrackerAndScaler, Undistorter
+
+    calib, size_in = (718.8560, 718.8560, 607.1928, 185.2157), (1241, 376)
+    G, vig = _photometric(photo, *size_in)
+    und = Undistorter.pinhole(ctx, calib=calib, size_in=size_in, mode="none", G=G, vignette_inv=vig)
+    assert und.size == size_in
+    return und, [TrackerAndScaler(ctx, *size_in, nl, S.KITTI_T_STEREO, und.K)], (None, None, G, vig), nl
+
+
+@pytest.mark.parametrize("conf,photo", PYRAMID_CASES, ids=[f"{c}-{p}" for c, p in PYRAMID_CASES])
 def test_pyramids_equal_the_restatement(ctx, conf, photo):
-    und, (trk,), tabs, nl = _setup(ctx, conf, photo)
+    und, (trk,), tabs, nl = _setup_passthrough(ctx, photo) if conf == "passthrough" else _setup(ctx, conf, photo)
+    assert (tabs[2] is None and tabs[3] is not None) == (photo == "vig")
     imgs = _raw(np.random.default_rng(1), und, 2)
     ctx.upload_images_undistorted(und, [trk, trk], [0, 1], imgs)
     for s in (0, 1):
         _check(trk, s, imgs[s], tabs, nl)
+    und.close()
+
+
+def test_odd_output_size_with_a_remap(ctx):
+    """211 x 97 cropped from a 240 x 120 camera: the quads of the last column and of the last row are halves, the last quad a
+    single pixel, in the remap form; levels 105 x 48, 52 x 24, 26 x 12 drop a column or a row each"""
+    from direct_stereo_slam_amd.tracker import TrackerAndScaler, Undistorter, pinhole_undistort_map
+
+    calib, size_in, size_out, nl = (190.0, 185.0, 121.3, 58.9), (240, 120), (211, 97), 4
+    K, passthrough, rx, ry = pinhole_undistort_map(calib, size_in, "crop", size_out)
+    assert not passthrough and rx.shape == (97, 211) and (rx[:, -1] >= 0).all() and (rx[-1] >= 0).all()  # the last column and row are inside
+    assert (rx != np.floor(rx)).mean() > 0.9 and (ry != np.floor(ry)).mean() > 0.9  # a real interpolation nearly everywhere
+    G, vig = _photometric("G+vig", *size_in)
+    und = Undistorter(ctx, size_in, size_out, rx, ry, G, vig, K)
+    trk = TrackerAndScaler(ctx, *size_out, nl, S.KITTI_T_STEREO, K)
+    imgs = [np.random.default_rng(9).integers(0, 256, size_in[::-1], dtype=np.uint8) for _ in range(2)]
+    ctx.upload_images_undistorted(und, [trk, trk], [0, 1], imgs)
+    for s in (0, 1):
+        _check(trk, s, imgs[s], (rx, ry, G, vig), nl)
+    np.testing.assert_array_equal(trk.get_frame(0, 0)[..., 0], R.undistort(imgs[0], rx, ry, G, vig))
+    und.close()
+
+
+def test_more_quads_than_one_trip_of_the_grid(ctx):
+    """1501 x 1399 from a 1536 x 1440 camera: 751 x 700 = 525 700 quads, more than the 2048 x 256 = 524 288 threads of the largest grid,
+    so the quad loop takes a second trip (the last 1 412 quads); remap form, a vignette without a response table, two levels"""
+    from direct_stereo_slam_amd.tracker import TrackerAndScaler, Undistorter, pinhole_undistort_map
+
+    calib, size_in, size_out, nl = (1210.0, 1190.0, 770.2, 717.6), (1536, 1440), (1501, 1399), 2
+    assert ((size_out[0] + 1) // 2) * ((size_out[1] + 1) // 2) > 2048 * 256 and size_out[0] * size_out[1] > 2097152
+    K, passthrough, rx, ry = pinhole_undistort_map(calib, size_in, "crop", size_out)
+    assert not passthrough and (rx >= 0).mean() > 0.99
+    G, vig = _photometric("vig", *size_in)
+    und = Undistorter(ctx, size_in, size_out, rx, ry, G, vig, K)
+    trk = TrackerAndScaler(ctx, *size_out, nl, S.KITTI_T_STEREO, K)
+    img = np.random.default_rng(10).integers(0, 256, size_in[::-1], dtype=np.uint8)
+    ctx.upload_images_undistorted(und, [trk], [0], [img])
+    want0 = R.undistort(img, rx, ry, G, vig)
+    got0 = trk.get_frame(0, 0)[..., 0]
+    second_trip = 2 * (524288 // 751)  # the row of the first quad of the second trip
+    assert second_trip < size_out[1] - 2 and want0[second_trip:].any()
+    np.testing.assert_array_equal(got0[second_trip:], want0[second_trip:], err_msg="the rows of the second trip")
+    _check(trk, 0, img, (rx, ry, G, vig), nl)
     und.close()
 
 
