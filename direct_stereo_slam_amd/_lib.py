@@ -187,6 +187,29 @@ class SelectJob(C.Structure):
     ]
 
 
+class LinearizeParams(C.Structure):
+    _fields_ = [
+        ("huber_th", C.c_float), ("outlier_th_sum_component", C.c_float), ("scale_idepth", C.c_float), ("scale_f", C.c_float),
+        ("scale_c", C.c_float), ("thn", C.c_float), ("fac_median", C.c_float), ("cw", C.c_float), ("ow", C.c_float),
+        ("zero_jab_a", C.c_int), ("zero_jab_b", C.c_int),
+    ]
+
+
+class LinearizeJob(C.Structure):
+    _fields_ = [
+        ("window", C.c_void_p), ("cam", C.c_float * 4), ("cam_inv", C.c_float * 2), ("n_frames", C.c_int), ("frame_ids", c_int_p),
+        ("pre_RTll_0", c_float_p), ("pre_tTll_0", c_float_p), ("pre_KRKiTll", c_float_p), ("pre_KtTll", c_float_p),
+        ("pre_aff_mode", c_float_p), ("pre_b0_mode", c_float_p), ("frame_energy_th", c_float_p),
+        ("n_pts", C.c_int), ("host", c_int_p), ("u", c_float_p), ("v", c_float_p), ("idepth_scaled", c_float_p),
+        ("idepth_zero_scaled", c_float_p), ("color", c_float_p), ("weights", c_float_p),
+        ("n_res", C.c_int), ("point", c_int_p), ("target", c_int_p), ("state_in", C.POINTER(C.c_ubyte)), ("energy_in", c_float_p),
+        ("is_new", C.POINTER(C.c_ubyte)), ("fix_linearization", C.c_int),
+        ("new_state", C.POINTER(C.c_ubyte)), ("new_energy", c_float_p), ("new_energy_with_outlier", c_float_p),
+        ("J_out", c_float_p), ("center_projected_to", c_float_p), ("projected_to", c_float_p), ("keep", C.POINTER(C.c_ubyte)),
+        ("rel_bs", c_float_p), ("energy_out", c_double_p), ("new_frame_energy_th_out", c_float_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -351,6 +374,9 @@ SYMBOLS = {
     "dsm_select_pixels_batch": (C.c_int, [_vp, C.c_int, C.POINTER(SelectJob), C.POINTER(SelectParams)]),
     "dsm_select_pixels_host": (C.c_int, [C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_ubyte), C.POINTER(SelectJob),
                                          C.POINTER(SelectParams)]),
+    "dsm_linearize_params_default": (C.c_int, [C.POINTER(LinearizeParams)]),
+    "dsm_linearize_residuals_batch": (C.c_int, [_vp, C.c_int, C.POINTER(LinearizeJob), C.POINTER(LinearizeParams)]),
+    "dsm_linearize_residuals_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(LinearizeJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams)]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

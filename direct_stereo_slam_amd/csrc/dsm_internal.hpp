@@ -155,7 +155,7 @@ struct dsm_pose_estimator {
   std::vector<float> x, y, z;
 };
 
-// dsm_window_create (immature_kernels.hip): the level-0 intensity planes of a window's keyframes; also a target of trace_kernels.hip
+// dsm_window_create (immature_kernels.hip): the level-0 intensity planes of a window's keyframes; also a target of trace_kernels.hip and the images of linearize_kernels.hip
 struct dsm_window {
   dsm_context *ctx = nullptr;
   int w = 0, h = 0, capacity = 0;
@@ -181,6 +181,10 @@ const char *trace_job_error(const dsm_trace_job &J);
 const char *select_params_error(const dsm_select_params *p);
 const char *select_geometry_error(int w, int h); // of the level-0 frame
 const char *select_job_error(const dsm_select_job &J);
+const char *linearize_params_error(const dsm_linearize_params *p);
+const char *linearize_job_error(const dsm_linearize_job &J);
+// points_host.cpp: B1 and B2 of DESIGN.md section 16 from the job's filled new_energy / new_energy_with_outlier arrays, for both forms
+void linearize_job_summary(const dsm_linearize_job &J, const dsm_linearize_params &S);
 // context_capi.hip: the device-visible address of a caller's array if it lies in page-locked memory, else null
 const void *pinned_device_pointer(const void *p);
 int take_params(const dsm_params *params, dsm_params *out); // the caller's parameters, checked, or the defaults

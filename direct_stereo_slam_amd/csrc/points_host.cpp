@@ -1,10 +1,11 @@
 // points_host.cpp -- the three point calls of the front end as the reference runs them, one sequential loop each, and the rules for
 // their jobs: activation (dsm_activate_points_host), optimisation of immature points
 // (dsm_optimize_immature_points_host, section 13), tracing (dsm_trace_points_host, section 14) and, before them all, the selection of
-// the pixels that become points (dsm_select_pixels_host, section 15).  The host forms are what the CPU suite checks against the numpy
-// checkers and what the device forms (distmap_kernels.hip, immature_kernels.hip, trace_kernels.hip, select_kernels.hip) must equal
-// bit for bit: the arithmetic is shared through point_math.hpp, immature_math.hpp, trace_math.hpp and select_math.hpp, the job rules
-// through the *_error functions below.  Plain C++; no device code.
+// the pixels that become points (dsm_select_pixels_host, section 15); and the linearisation of the window optimisation's active
+// residuals (dsm_linearize_residuals_host, section 16).  The host forms are what the CPU suite checks against the numpy
+// checkers and what the device forms (distmap_kernels.hip, immature_kernels.hip, trace_kernels.hip, select_kernels.hip,
+// linearize_kernels.hip) must equal bit for bit: the arithmetic is shared through point_math.hpp, immature_math.hpp, trace_math.hpp,
+// select_math.hpp and linearize_math.hpp, the job rules through the *_error functions below.  Plain C++; no device code.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,6 +14,7 @@
 
 #include "dsm_internal.hpp"
 #include "immature_math.hpp"
+#include "linearize_math.hpp"
 #include "select_math.hpp"
 #include "trace_math.hpp"
 
@@ -97,6 +99,55 @@ const char *select_job_error(const dsm_select_job &J) {
                     !J.quality || !J.type))
     return "NULL point array";
   return nullptr;
+}
+
+const char *linearize_params_error(const dsm_linearize_params *p) {
+  if (!p) return "no parameters";
+  if (!std::isfinite(p->huber_th) || !std::isfinite(p->outlier_th_sum_component) || !std::isfinite(p->scale_idepth) ||
+      !std::isfinite(p->scale_f) || !std::isfinite(p->scale_c) || !std::isfinite(p->thn) || !std::isfinite(p->fac_median) ||
+      !std::isfinite(p->cw) || !std::isfinite(p->ow))
+    return "a non-finite parameter";
+  if (!(p->thn >= 0.0f && p->thn < 1.0f)) return "thn outside [0, 1)";
+  return nullptr;
+}
+const char *linearize_job_error(const dsm_linearize_job &J) {
+  if (J.n_frames < 1 || J.n_frames > DSM_WINDOW_MAX_FRAMES || J.n_pts < 0 || J.n_res < 0 || !J.frame_ids || !J.pre_RTll_0 || !J.pre_tTll_0 ||
+      !J.pre_KRKiTll || !J.pre_KtTll || !J.pre_aff_mode || !J.pre_b0_mode || !J.frame_energy_th || !J.energy_out || !J.new_frame_energy_th_out)
+    return "n_frames outside [1, 16], a negative count or a NULL array";
+  if (J.n_pts && (!J.host || !J.u || !J.v || !J.idepth_scaled || !J.idepth_zero_scaled || !J.color || !J.weights)) return "NULL point array";
+  if (J.n_res && (!J.point || !J.target || !J.state_in || !J.energy_in || !J.new_state || !J.new_energy || !J.new_energy_with_outlier ||
+                  (J.fix_linearization && !J.is_new)))
+    return "NULL residual array";
+  for (int i = 0; i < J.n_pts; i++)
+    if (J.host[i] < 0 || J.host[i] >= J.n_frames) return "host outside [0, n_frames)";
+  for (int r = 0; r < J.n_res; r++) {
+    if (J.point[r] < 0 || J.point[r] >= J.n_pts) return "point outside [0, n_pts)";
+    if (J.target[r] < 0 || J.target[r] >= J.n_frames) return "target outside [0, n_frames)";
+    if (J.target[r] == J.host[J.point[r]]) return "a residual whose target is its point's host";
+    if (J.state_in[r] != DSM_RES_IN && J.state_in[r] != DSM_RES_OOB && J.state_in[r] != DSM_RES_OUTLIER) return "a state_in that is no residual state";
+  }
+  return nullptr;
+}
+
+// B1: the double sum of the returned values in residual order.  B2: setNewFrameEnergyTH (:79-120) on the residuals against the newest frame.
+void linearize_job_summary(const dsm_linearize_job &J, const dsm_linearize_params &S) {
+  double energy = 0;
+  std::vector<float> all;
+  for (int r = 0; r < J.n_res; r++) {
+    energy += J.new_energy[r];
+    if (J.target[r] == J.n_frames - 1 && J.new_energy_with_outlier[r] >= 0) all.push_back(J.new_energy_with_outlier[r]);
+  }
+  *J.energy_out = energy;
+  float th = DSM_LINEARIZE_EMPTY_FRAME_ENERGY_TH;
+  if (!all.empty()) {
+    const int nth = (int)(S.thn * (float)all.size()); // a float32 product, below the count for every thn < 1
+    std::nth_element(all.begin(), all.begin() + nth, all.end());
+    th = sqrtf(all[nth]) * S.fac_median;
+    th = 26.0f * S.cw + th * (1 - S.cw);
+    th = th * th;
+    th *= S.ow * S.ow;
+  }
+  *J.new_frame_energy_th_out = th;
 }
 } // namespace dsm
 
@@ -529,5 +580,85 @@ extern "C" int dsm_select_pixels_host(int w, int h, const float *I0, const float
   if (J.counts_out) memcpy(J.counts_out, n, sizeof n);
   if (J.passes_out) *J.passes_out = passes;
   if (J.map_out) memcpy(J.map_out, P.map.data(), P.map.size());
+  return DSM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// FrontEnd::linearizeAll (dso_helpers/FrontEndOptimize.cpp:121-179) as the reference runs it on one thread: PointFrameResidual::linearize
+// per active residual in residual order, then the energy sum, setNewFrameEnergyTH and, with fixLinearization, the keep verdict and the
+// relative baseline.  L1-L8, B1-B4: DESIGN.md section 16.  The per-residual expressions are linearize_math.hpp, shared with the device
+// kernel; the twelve sums are plain loops in pattern order.
+// ---------------------------------------------------------------------------------------------
+extern "C" int dsm_linearize_params_default(dsm_linearize_params *p) {
+  if (!p) return DSM_ERR_INVALID;
+  p->huber_th = DSM_LINEARIZE_HUBER_TH, p->outlier_th_sum_component = DSM_LINEARIZE_OUTLIER_TH_SUM_COMPONENT;
+  p->scale_idepth = DSM_LINEARIZE_SCALE_IDEPTH, p->scale_f = DSM_LINEARIZE_SCALE_F, p->scale_c = DSM_LINEARIZE_SCALE_C;
+  p->thn = DSM_LINEARIZE_FRAME_ENERGY_TH_N, p->fac_median = DSM_LINEARIZE_FRAME_ENERGY_TH_FAC_MEDIAN;
+  p->cw = DSM_LINEARIZE_FRAME_ENERGY_TH_CONST_WEIGHT, p->ow = DSM_LINEARIZE_OVERALL_ENERGY_TH_WEIGHT;
+  p->zero_jab_a = 0, p->zero_jab_b = 0;
+  return DSM_OK;
+}
+
+extern "C" int dsm_linearize_residuals_host(int w, int h, const dsm_linearize_job *job, const float *const *frame_I,
+                                            const dsm_linearize_params *params) {
+  using namespace dsm::lin;
+  auto fail = [](const char *msg) { return refuse("dsm_linearize_residuals_host", msg); };
+  if (w < 8 || h < 8 || !job || !frame_I) return fail("bad argument");
+  if (const char *e = dsm::linearize_params_error(params)) return fail(e);
+  if (const char *e = dsm::linearize_job_error(*job)) return fail(e);
+  const dsm_linearize_job &J = *job;
+  for (int f = 0; f < J.n_frames; f++)
+    if (!frame_I[f]) return fail("NULL frame");
+  const Cam C{J.cam[0], J.cam[1], J.cam[2], J.cam[3], J.cam_inv[0], J.cam_inv[1], w, h};
+  const Settings S{params->huber_th, params->outlier_th_sum_component, params->scale_idepth, params->scale_f, params->scale_c};
+  const int nf = J.n_frames;
+  for (int r = 0; r < J.n_res; r++) {
+    const int p = J.point[r], tgt = J.target[r], hst = J.host[p], pair = hst * nf + tgt;
+    const float *M = J.pre_KRKiTll + 9 * pair, *Kt = J.pre_KtTll + 3 * pair;
+    int state = RES_OOB; // L1
+    float E = J.energy_in[r], with_outlier = -1.0f;
+    float row[J_FLOATS], proj[16];
+    Centre c;
+    if (J.state_in[r] != DSM_RES_OOB && centre(C, J.pre_RTll_0 + 9 * pair, J.pre_tTll_0 + 3 * pair, J.u[p], J.v[p], J.idepth_zero_scaled[p], c)) {
+      geometric(C, J.pre_RTll_0 + 9 * pair, J.pre_tTll_0 + 3 * pair, c, S, row + J_PDXI);
+      float sum[N_SUMS];
+      for (int k = 0; k < N_SUMS; k++) sum[k] = 0.0f;
+      int idx = 0;
+      for (; idx < 8; idx++) { // L4-L6
+        int dx, dy;
+        dsm::pt::pattern(idx, dx, dy);
+        Pixel P;
+        if (!pixel(C, frame_I[tgt], M, Kt, J.pre_aff_mode + 2 * pair, J.pre_b0_mode[pair], J.u[p], J.v[p], dx, dy, J.idepth_scaled[p],
+                   J.color[8 * p + idx], J.weights[8 * p + idx], S, P))
+          break;
+        proj[2 * idx] = P.Ku, proj[2 * idx + 1] = P.Kv;
+        row[J_RESF + idx] = P.resF, row[J_IDX + idx] = P.gx, row[J_IDX + 8 + idx] = P.gy;
+        row[J_ABF + idx] = params->zero_jab_a ? 0.0f : P.ja, row[J_ABF + 8 + idx] = params->zero_jab_b ? 0.0f : P.jb;
+        for (int k = 0; k < N_SUMS; k++) sum[k] += P.T[k];
+      }
+      if (idx == 8) {
+        row[J_IDX2] = sum[S_XX], row[J_IDX2 + 1] = row[J_IDX2 + 2] = sum[S_XY], row[J_IDX2 + 3] = sum[S_YY];
+        row[J_ABJIDX] = sum[S_AX], row[J_ABJIDX + 1] = sum[S_AY], row[J_ABJIDX + 2] = sum[S_BX], row[J_ABJIDX + 3] = sum[S_BY];
+        row[J_AB2] = sum[S_AA], row[J_AB2 + 1] = row[J_AB2 + 2] = sum[S_AB], row[J_AB2 + 3] = sum[S_BB];
+        with_outlier = E = sum[S_E];
+        state = verdict(E, sum[S_WJI2], J.frame_energy_th[hst], J.frame_energy_th[tgt]); // L7
+      }
+    }
+    J.new_state[r] = (unsigned char)state, J.new_energy[r] = E, J.new_energy_with_outlier[r] = with_outlier;
+    if (state != RES_OOB) { // L8
+      if (J.J_out) memcpy(J.J_out + (size_t)J_FLOATS * r, row, sizeof row);
+      if (J.projected_to) memcpy(J.projected_to + (size_t)16 * r, proj, sizeof proj);
+      if (J.center_projected_to) {
+        float *q = J.center_projected_to + (size_t)3 * r;
+        q[0] = c.Ku, q[1] = c.Kv, q[2] = c.new_idepth;
+      }
+    }
+    if (J.fix_linearization) { // B3
+      const bool keep = J.state_in[r] != DSM_RES_OOB && state == RES_IN;
+      if (J.keep) J.keep[r] = keep;
+      if (J.rel_bs) J.rel_bs[r] = keep && J.is_new[r] ? rel_baseline(M, Kt, J.u[p], J.v[p], J.idepth_scaled[p]) : 0.0f;
+    }
+  }
+  dsm::linearize_job_summary(J, *params); // B1, B2
   return DSM_OK;
 }

@@ -1167,6 +1167,98 @@ int dsm_select_pixels_batch(dsm_pixel_selector *sel, int n_jobs, const dsm_selec
 int dsm_select_pixels_host(int w, int h, const float *I0, const float *I1, const float *I2, const unsigned char *random_pattern,
                            const dsm_select_job *job, const dsm_select_params *params);
 
+/* ---- Linearising the active residuals of the window optimisation ------------------------------------------------
+ * replaces FrontEnd::linearizeAll (dso_helpers/FrontEndOptimize.cpp:121-179), which FrontEnd::optimize runs 8 to 14 times per keyframe:
+ * PointFrameResidual::linearize (UPSTREAM-DSO, parity unpinned) for every active residual of the windows of many sequences in one call,
+ * as the rules L1-L8 of DESIGN.md section 16 state it, with the per-window work around it (B1-B4): the energy sum, setNewFrameEnergyTH
+ * and, in the fixLinearization pass, the keep / remove verdict and the relative baseline.  The call is stateless: the caller holds
+ * state_state / state_energy, applies applyRes and decides whether the step is accepted.  Everything is float32 without contraction
+ * except the energy sum (double) and the 0.01 factor of the relative baseline (double). */
+#define DSM_LINEARIZE_HUBER_TH 9.0f                      /* setting_huberTH */
+#define DSM_LINEARIZE_OUTLIER_TH_SUM_COMPONENT 2500.0f   /* setting_outlierTHSumComponent (50 * 50) */
+#define DSM_LINEARIZE_SCALE_IDEPTH 1.0f                  /* SCALE_IDEPTH */
+#define DSM_LINEARIZE_SCALE_F 50.0f                      /* SCALE_F */
+#define DSM_LINEARIZE_SCALE_C 50.0f                      /* SCALE_C */
+#define DSM_LINEARIZE_FRAME_ENERGY_TH_N 0.7f             /* setting_frameEnergyTHN */
+#define DSM_LINEARIZE_FRAME_ENERGY_TH_FAC_MEDIAN 1.5f    /* setting_frameEnergyTHFacMedian */
+#define DSM_LINEARIZE_FRAME_ENERGY_TH_CONST_WEIGHT 0.5f  /* setting_frameEnergyTHConstWeight */
+#define DSM_LINEARIZE_OVERALL_ENERGY_TH_WEIGHT 1.0f      /* setting_overallEnergyTHWeight */
+#define DSM_LINEARIZE_EMPTY_FRAME_ENERGY_TH 1152.0f      /* 12 * 12 * patternNum: no residual against the newest frame (B2) */
+#define DSM_LINEARIZE_J_FLOATS 74                        /* one RawResidualJacobian row (L8) */
+
+/* the settings linearize and setNewFrameEnergyTH read; dsm_linearize_params_default fills the upstream defaults */
+typedef struct dsm_linearize_params {
+  float huber_th;                 /* 9     */
+  float outlier_th_sum_component; /* 2500  */
+  float scale_idepth;             /* 1     */
+  float scale_f;                  /* 50    */
+  float scale_c;                  /* 50    */
+  float thn;                      /* 0.7   in [0, 1) */
+  float fac_median;               /* 1.5   */
+  float cw;                       /* 0.5   */
+  float ow;                       /* 1     */
+  int zero_jab_a;                 /* 0     setting_affineOptModeA < 0: JabF[0] is stored as 0 (L6) */
+  int zero_jab_b;                 /* 0     setting_affineOptModeB < 0: JabF[1] is stored as 0 */
+} dsm_linearize_params;
+
+/* One window.  frame_ids: frame_hessians_ in order; pre_*: the FrameFramePrecalc fields of every [host][target] pair in float32
+ * (row-major 3 x 3), the diagonal is not read; frame_energy_th: frameEnergyTH of every frame, which this pass compares against.
+ * A point is a PointHessian (host: an index into frame_ids), a residual a PointFrameResidual of it (point: an index into the points,
+ * target: an index into frame_ids, never the point's host) with its committed state_state / state_energy. */
+typedef struct dsm_linearize_job {
+  dsm_window *window;         /* ignored by dsm_linearize_residuals_host */
+  float cam[4];               /* fxl, fyl, cxl, cyl */
+  float cam_inv[2];           /* fxli, fyli */
+  int n_frames;               /* 1 .. DSM_WINDOW_MAX_FRAMES */
+  const int *frame_ids;       /* n_frames */
+  const float *pre_RTll_0;    /* n_frames * n_frames * 9, [host][target] */
+  const float *pre_tTll_0;    /* n_frames * n_frames * 3 */
+  const float *pre_KRKiTll;   /* n_frames * n_frames * 9 */
+  const float *pre_KtTll;     /* n_frames * n_frames * 3 */
+  const float *pre_aff_mode;  /* n_frames * n_frames * 2 */
+  const float *pre_b0_mode;   /* n_frames * n_frames */
+  const float *frame_energy_th; /* n_frames */
+  int n_pts;
+  const int *host;            /* n_pts */
+  const float *u, *v, *idepth_scaled, *idepth_zero_scaled; /* n_pts each */
+  const float *color;         /* n_pts * 8 */
+  const float *weights;       /* n_pts * 8 */
+  int n_res;
+  const int *point;           /* n_res */
+  const int *target;          /* n_res */
+  const unsigned char *state_in; /* n_res: DSM_RES_IN / _OOB / _OUTLIER */
+  const float *energy_in;     /* n_res: state_energy */
+  const unsigned char *is_new;   /* n_res: isNew; read only with fix_linearization */
+  int fix_linearization;
+  unsigned char *new_state;   /* n_res: state_NewState */
+  float *new_energy;          /* n_res: the value linearize returns (state_NewEnergy; energy_in for a residual that ends OOB) */
+  float *new_energy_with_outlier; /* n_res: state_NewEnergyWithOutlier, -1 for a residual that ends OOB */
+  float *J_out;               /* optional (NULL), n_res * 74: resF[8], Jpdxi[2][6], Jpdc[2][4], Jpdd[2], JIdx[2][8], JabF[2][8], JIdx2[4],
+                                 JabJIdx[4], Jab2[4]; like the next two, the row of a residual that ends OOB is not written */
+  float *center_projected_to; /* optional (NULL), n_res * 3 */
+  float *projected_to;        /* optional (NULL), n_res * 16: (Ku, Kv) of every pattern pixel */
+  unsigned char *keep;        /* optional (NULL), n_res; written with fix_linearization only: 1 = the residual stays active */
+  float *rel_bs;              /* optional (NULL), n_res; written with fix_linearization only: the relative baseline of a kept new
+                                 residual, 0 for every other */
+  double *energy_out;         /* the sum of new_energy in residual order, in double (B1) */
+  float *new_frame_energy_th_out; /* setNewFrameEnergyTH: the next frameEnergyTH of the newest frame, frame_ids[n_frames - 1] (B2) */
+} dsm_linearize_job;
+
+/* the upstream defaults listed above */
+int dsm_linearize_params_default(dsm_linearize_params *p);
+/* FrontEndOptimize.cpp:121-179 for every job: one staged copy through the context's page-locked arena, one launch, one host wait for
+ * the whole batch; the energy sum and the order statistic of B2 are formed on the host from the read-back; nothing is allocated once
+ * the arena has grown to the batch size; a job's results do not depend on the other jobs of the call.  A window may serve several
+ * jobs; one geometry per call; n_res == 0, n_pts == 0 and a job of one frame are valid (energy 0, threshold 1152).  Validation is
+ * all or nothing, before anything is enqueued: DSM_ERR_INVALID for NULL required arrays or negative counts, n_frames outside
+ * [1, DSM_WINDOW_MAX_FRAMES], a host, point or target index out of range, a target equal to the host of the residual's point, a
+ * state_in other than DSM_RES_IN / _OOB / _OUTLIER, a frame id that is not in the window, mixed geometries, non-finite parameters,
+ * thn outside [0, 1). */
+int dsm_linearize_residuals_batch(dsm_context *ctx, int n_jobs, const dsm_linearize_job *jobs, const dsm_linearize_params *params);
+/* The same for one job as one plain sequential loop on the host: job->window is ignored, frame_I[i] is the w * h level-0 intensity
+ * plane of frame_ids[i].  The CPU baseline of tools/linearize_timing.py and a checker that needs no device. */
+int dsm_linearize_residuals_host(int w, int h, const dsm_linearize_job *job, const float *const *frame_I, const dsm_linearize_params *params);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.
