@@ -88,7 +88,7 @@ enum LMStatus { ST_IDLE = 0, ST_RUNNING = 1, ST_GOOD = 2, ST_ABORTED = 3, ST_BAD
 struct alignas(16) LMState {
   int status, lvl, phase, iteration;
   int have_repeated, coarsest, is_scale /* problem kind: 0 pose, 1 scale, 2 loop-closure pose (3-D points) */;
-  int stepped; // tick engine: this tick's LM step(s) of the slot already ran inside the evaluation launch (a chain, tracker_kernels.hip);
+  int stepped; // tick engine: this tick's LM step(s) of the slot already ran inside the evaluation launch (a chain: tick_eval_kernel, form_tick.hpp);
                // the tick's LM launch clears the flag and leaves the slot alone
   float lambda, level_cutoff_repeat;
   float inc_f;      // scale: last increment (for the signed break test :937)

@@ -65,7 +65,12 @@ struct StartInfo { // host -> device, one per problem
   int residual_only; // single evaluation only (dsm_diag_single_eval): EvalIn::residual_only
 };
 
-// ---- tracker_kernels.hip ----
+// ---- tracker_kernels.hip (one translation unit; grouped by the part that defines each launcher, in its include order) ----
+// -- lm_step.hpp: the LM state machine --
+// bounded waits of the LM steps' wave hand-shakes that expired since the library was loaded (0 unless something is badly wrong)
+int lm_spin_expired();
+
+// -- form_launch.hpp: launch-per-step form --
 // mode: 0 = pose (calcResPose + calcGSSSEPose), 1 = scale (calcResScale + calcGSSSEScale)
 // rowmap != nullptr: compact launch over nprob rows, row r = problem rowmap[r] (indices relative to trackers / states)
 void launch_eval(hipStream_t s, int mode, int lvl, int grid_x, int nprob,
@@ -76,6 +81,7 @@ void launch_lm(hipStream_t s, int mode, int op, int lvl, int nprob, const Tracke
                LMState *states, const float *partials, int partial_stride, const StartInfo *start,
                SingleOut *single_out, int *status_out, bool spec = false, const int *rowmap = nullptr);
 
+// -- form_queue.hpp: work-queue form --
 // work-queue kernel (queue_kernel): header of the device-side queue, zeroed before every launch; counters on their
 // own 128-byte lines.  Items: (index + 1) << 32 | problem << kQueueChunkBits | chunk.
 struct WorkQueue {
@@ -89,7 +95,12 @@ int queue_kernel_blocks_per_cu(int mode);
 void launch_queue(hipStream_t s, int mode, int nblocks, int nprob, const TrackerDev *const *trackers, LMState *states,
                   float *partials, int partial_stride, int *tickets, WorkQueue *q, unsigned long long *items, unsigned qmask);
 
-// ---- tick engine of the streaming form (dsm_stream_*, stream_capi.hip) --------------------------------------------
+// -- form_chain.hpp: chain form --
+// persistent LM loop of the levels whose evaluation is ONE chunk (chain_kernel: the tick engine's chain as a launch of its own, one
+// workgroup per problem, until the problem reaches a level of several chunks or terminates; no speculative candidates)
+void launch_chain(hipStream_t s, int mode, int nprob, const TrackerDev *const *trackers, LMState *states, int *status_out);
+
+// -- form_tick.hpp: tick engine of the streaming form (dsm_stream_*, stream_capi.hip) --
 // One TICK advances every resident problem by one LM round, whatever level it stands on: ONE evaluation launch over a
 // device-built list of (problem, chunk) items of all levels mixed, then ONE LM launch (a workgroup per slot) that steps the
 // problems, builds the next tick's list, retires finished problems into a result array and refills their slots from the
@@ -164,13 +175,8 @@ void launch_tick_eval(hipStream_t s, int mode, int grid, const LMState *states, 
 void launch_tick_lm(hipStream_t s, int mode, int nslots, const TrackerDev **trackers, LMState *states, const float *partials, int partial_stride,
                     const TickList &next, TickModeCtl *mc, const TickPending *pending, TickResult *results, unsigned long long *slot_ticket,
                     int speculate, int opts /* bit 0: helper waves in the LM step, bit 1: the next items' place in the list asked for early */);
-// bounded waits of the LM steps' wave hand-shakes that expired since the library was loaded (0 unless something is badly wrong)
-int lm_spin_expired();
 
-// persistent LM loop of the levels whose evaluation is ONE chunk (chain_kernel: the tick engine's chain as a launch of its own, one
-// workgroup per problem, until the problem reaches a level of several chunks or terminates; no speculative candidates)
-void launch_chain(hipStream_t s, int mode, int nprob, const TrackerDev *const *trackers, LMState *states, int *status_out);
-
+// -- form_diag.hpp: the diagnostic kernels --
 // dsm_diag_single_eval: problem 0's staged evaluation (one chunk) in the chains' form, its partial into partials[0 .. 52)
 void launch_diag_chain_eval(hipStream_t s, int mode, const LMState *states, float *partials);
 
@@ -178,6 +184,8 @@ void launch_diag_chain_eval(hipStream_t s, int mode, const LMState *states, floa
 // structures are the public ones of include/dsm_hotpath.h
 void launch_diag_lm_propose(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_propose_in *in,
                             ::dsm_lm_propose_out *out, bool spec, bool helper);
+
+// -- tracker_kernels.hip itself --
 // descriptors of many trackers in one launch (sync_descs): d_dst[i] <- d_src[i]
 void launch_desc_scatter(hipStream_t s, int n, const TrackerDev *d_src, TrackerDev *const *d_dst);
 // Template lists are allocated with this many entries of slack (zeroed).  The evaluation loop prefetches template entries up to three

@@ -1,6 +1,6 @@
 // lm_math.hpp -- double precision device math of the LM drivers: Sophus SE3 exp / product,
-// Eigen quaternion->rotation, DSO AffLight::fromToVecExposure (the pivoted LDLT solve is wave-parallel
-// and lives in tracker_kernels.hip).
+// Eigen quaternion->rotation, DSO AffLight::fromToVecExposure (the pivoted LDLT solve is wave-parallel:
+// wave_ldlt_solve8 in lm_step.hpp).
 // These are the un-vendored third-party pieces the reference calls at
 // TrackerAndScaler.cpp:509-534 (ldlt().solve), :551 (SE3::exp, operator*), :715/:1023
 // (rotationMatrix), :647-649/:717-720 (fromToVecExposure); restated from their published

@@ -217,7 +217,7 @@ int launch_round(dsm_context *ctx, const LMBuffers &B, const dsm_params &P, cons
   // 38.6-38.8 k, the speculative candidate on every level of the compact rounds 38.9 k: the pair's second launch and the
   // doubled rows cost what they save.)
   const bool fused = L > 0 && (P.fuse_lm >= 2 || (P.fuse_lm == 1 && (R.fuse_count <= 8 || R.fuse_also)));
-  // Large levels: the residual-only evaluations (the level's last ones, tracker_kernels.hip) get a launch of their own
+  // Large levels: the residual-only evaluations (the level's last ones; eval_kernel's ROSEL, form_launch.hpp) get a launch of their own
   // behind the full ones -- an instantiation without the 45 accumulators, 30-41 VGPRs = eight waves per SIMD instead
   // of four or five.  Never in a level's first round (its evaluation is the level's first).  Measured (S2 dense, 512
   // frames): level-0 evaluations 4.62 -> 4.40 ms per step, 54.3 -> 55.7 k frames/s with levels 0 and 1 split; with

@@ -13,9 +13,9 @@ The bound, u = 2^-24, P = points per thread of the level (dsm_kernels.hpp pts_pe
 
   |H_dev - H64|_ij <= u ((P + K_TREE) A_ij + F_ij)        (b, h00 / h01 alike; E: u (P + K_TREE + K_HUBER) E64)
 
-* K_TREE = 24 roundings besides the thread's P sequential fmaf (tracker_kernels.hip): J_r w (1), the 16-lane DPP tree
+* K_TREE = 24 roundings besides the thread's P sequential fmaf (eval_chunk_impl, tracker_kernels.hip): J_r w (1), the 16-lane DPP tree
   row16_sum (4), the 16 rows in order (15), the chunk partial stored as float and the chunks added in double
-  (reduce_partials_groups / _final: below 2^-40 for 4096 chunks), the float of the double sum (build_H_elem, build_rs: 1),
+  (reduce_partials_groups / _final, lm_step.hpp: below 2^-40 for 4096 chunks), the float of the double sum (build_H_elem, build_rs: 1),
   and for the scale problem the float product with 1 / n (LM_OP_SINGLE_FINISH: 1) -- 22, plus the doubles of the scales.
 * The per-point values are NOT all the oracle's bits: the integer outputs and the residual are (same float32 operations),
   but the Jacobian and the Huber weight are formed differently (tracker_kernels.hip taps_gradients, stage_a / stage_b):

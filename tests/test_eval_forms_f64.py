@@ -11,7 +11,7 @@ Each with residual_only 0 and 1, under the three chunk tables.
 
 Full evaluations: the assertions of test_normal_equations_f64.py (tests/_gn_checks.py) for every form; form 0 is bit for bit
 dsm_tracker_calc_res_pose / _scale, and every other form is bit for bit form 0 -- rs, H, b, h00, h01 -- at EVERY level:
-  * the forms share the reduction at the end of eval_chunk_impl (tracker_kernels.hip: row16_sum, the 16 rows in order) and
+  * the forms share the reduction at the end of eval_chunk_impl (tracker_kernels.hip: row16_sum of wave_ops.hpp, the 16 rows in order) and
     LM_OP_SINGLE_FINISH; the arrival ticket the waves take there hands the same additions in the same order to another wave;
   * on levels >= 1 forms 2 and 3 run eval_chunk_impl's two-point loop (DEEP) where form 0 runs its one-point loop.  Both call stage_b
     for the thread's points k = 0 .. P - 1 in that order, and stage_b is the only place the accumulators, E and the counts are added to.

@@ -1,5 +1,5 @@
 """The float64 reference of tests/_gn_f64.py and its bound, on the CPU:
-  (a) the device's documented summation tree (tracker_kernels.hip eval_chunk_impl, row16_sum, reduce_partials_groups / _final),
+  (a) the device's documented summation tree (eval_chunk_impl in tracker_kernels.hip, row16_sum in wave_ops.hpp, reduce_partials_groups / _final in lm_step.hpp),
       restated in numpy float32 on the oracle's per-point values, lies well inside the reduction part of the bound for every
       chunk table -- so the bound is not tight against the order the device really uses;
   (b) the bound has teeth: a lost or doubled point and an entry off by 100 u A pass the whole-matrix bars of

@@ -1,5 +1,5 @@
 #!/bin/bash
-# VGPRs / scratch / occupancy / LDS of every kernel in tracker_kernels.hip, or in the file of csrc/ given as $1 (developer aid)
+# VGPRs / scratch / occupancy / LDS of every kernel of the translation unit tracker_kernels.hip (its wave_ops / lm_step / form_* headers included), or of the file of csrc/ given as $1 (developer aid)
 cd "$(dirname "$0")/../direct_stereo_slam_amd/csrc" || exit 1
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -S --cuda-device-only \
   -Rpass-analysis=kernel-resource-usage ${1:-tracker_kernels.hip} -o /dev/null 2>&1 |
