@@ -227,6 +227,31 @@ class LmProposeOut(C.Structure):
     ]
 
 
+class LmStepEval(C.Structure):
+    _fields_ = [
+        ("M", C.c_float * 9), ("t", C.c_float * 3), ("aff0", C.c_float), ("aff1", C.c_float), ("cutoff", C.c_float),
+        ("max_energy", C.c_float), ("residual_only", C.c_int), ("scale", C.c_float), ("Ki", C.c_float * 9), ("n", C.c_int),
+    ]
+
+
+class LmStepState(C.Structure):
+    _fields_ = [
+        ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
+        ("cand", C.c_double * 7), ("aff_cand", C.c_double * 2), ("spec_cand", C.c_double * 7), ("spec_aff_cand", C.c_double * 2),
+        ("inc_norm", C.c_double), ("spec_inc_norm", C.c_double), ("res_old", C.c_double * 6),
+        ("min_res", C.c_double * MAX_LEVELS), ("last_residuals", C.c_double * MAX_LEVELS), ("last_inners", C.c_double * MAX_LEVELS),
+        ("flow", C.c_double * 3),
+        ("evals", C.c_longlong * MAX_LEVELS), ("evals_ro", C.c_longlong * MAX_LEVELS), ("rounds", C.c_longlong * MAX_LEVELS),
+        ("status", C.c_int), ("lvl", C.c_int), ("phase", C.c_int), ("iteration", C.c_int), ("have_repeated", C.c_int),
+        ("coarsest", C.c_int), ("spec_valid", C.c_int), ("ticks", C.c_int),
+        ("lam", C.c_float), ("level_cutoff_repeat", C.c_float),
+        ("inc_f", C.c_float), ("spec_inc_f", C.c_float), ("scale_cur", C.c_float), ("scale_cand", C.c_float),
+        ("spec_scale_cand", C.c_float), ("Hs", C.c_float), ("bs", C.c_float),
+        ("nch", C.c_int),
+        ("ev", LmStepEval), ("spec_ev", LmStepEval),
+    ]
+
+
 # every symbol include/dsm_hotpath.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _pp_f = C.POINTER(c_float_p)
@@ -306,6 +331,8 @@ SYMBOLS = {
     "dsm_diag_pose_estimator_eval": (C.c_int, [_vp, C.c_int, c_double_p, _pp_f, C.c_float, _pp_f, C.c_float, c_float_p, C.c_int, c_double_p, c_double_p,
                                                C.c_float, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
     "dsm_diag_lm_propose": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmProposeIn), C.c_int, C.c_int, C.POINTER(LmProposeOut)]),
+    "dsm_diag_lm_step": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmStepState), c_float_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(LmStepState)]),
     "dsm_diag_icp_stages": (C.c_int, [_vp, C.c_int, C.POINTER(IcpJob), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
                                       c_float_p, C.POINTER(C.c_uint64), _vp]),
     "dsm_tracker_track": (C.c_int, [_vp, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),

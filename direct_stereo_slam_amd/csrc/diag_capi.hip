@@ -189,4 +189,64 @@ int dsm_diag_lm_propose(dsm_tracker *t, int mode, int lvl, int n, const dsm_lm_p
   return DSM_OK;
 }
 
+static_assert(sizeof(dsm_lm_step_eval) == 112 && sizeof(dsm_lm_step_state) == 1464, "mirrored by _lib.py's LmStepEval / LmStepState");
+static_assert(DSM_LM_IDLE == ST_IDLE && DSM_LM_RUNNING == ST_RUNNING && DSM_LM_GOOD == ST_GOOD && DSM_LM_ABORTED == ST_ABORTED &&
+                  DSM_LM_BAD_AFFINE == ST_BAD_AFFINE,
+              "dsm_lm_step_state.status is LMState::status");
+int dsm_diag_lm_step(dsm_tracker *t, int mode, int lvl, int n, const dsm_lm_step_state *in, const float *partials,
+                     long long partial_stride, int spec, int spec_off, int helper, int coherent, dsm_lm_step_state *out) {
+  if (!t || !in || !out || !partials) return invalid("dsm_diag_lm_step: null argument");
+  if (n < 1 || n > 65536) return invalid("dsm_diag_lm_step: n is 1 .. 65536");
+  if (mode < 0 || mode > 2) return invalid("dsm_diag_lm_step: mode is 0 (pose), 1 (scale) or 2 (loop-closure pose)");
+  if (lvl < 0 || lvl >= t->nlevels) return invalid("dsm_diag_lm_step: level out of range");
+  if (!t->have_k) return invalid("dsm_diag_lm_step: dsm_tracker_make_k first");
+  if (partial_stride < 4 || partial_stride % 4 || partial_stride > (1ll << 24)) return invalid("dsm_diag_lm_step: partial_stride is a multiple of 4, 4 .. 2^24");
+  if (spec && (spec_off < 0 || spec_off % 4 || spec_off > partial_stride)) return invalid("dsm_diag_lm_step: spec_off is a multiple of 4 inside the problem's block");
+  for (int i = 0; i < n; i++) { // every 16-byte read of the reduction stays inside the problem's block
+    const long long floats = (long long)in[i].nch * kPartialStride;
+    if (in[i].nch < 0 || in[i].nch > 4096) return invalid("dsm_diag_lm_step: nch is 0 .. 4096");
+    if (in[i].phase != PH_INIT && in[i].phase != PH_ITER) return invalid("dsm_diag_lm_step: phase is 0 or 1");
+    if (floats > (spec ? (long long)spec_off : partial_stride) || (spec && spec_off + floats > partial_stride))
+      return invalid("dsm_diag_lm_step: the partials of nch chunks do not fit partial_stride / spec_off");
+  }
+  dsm_context *ctx = t->ctx;
+  DSM_HIP(hipSetDevice(ctx->device));
+  int rc = sync_desc(t);
+  if (rc) return rc;
+  const int expired_before = lm_spin_expired();
+  if (expired_before < 0) return hip_fail(hipGetLastError(), "lm_spin_expired", __FILE__, __LINE__);
+  dsm_lm_step_state *d_in = nullptr, *d_out = nullptr;
+  LMState *d_states = nullptr;
+  float *d_partials = nullptr;
+  const size_t io_bytes = sizeof(dsm_lm_step_state) * (size_t)n, part_bytes = sizeof(float) * (size_t)partial_stride * (size_t)n;
+  std::vector<dsm_lm_step_state> h_out((size_t)n); // (the caller's array is written only by a call that succeeds)
+  hipError_t e = hipMalloc(&d_in, io_bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_out, io_bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_states, sizeof(LMState) * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc(&d_partials, part_bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, io_bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_partials, partials, part_bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, io_bytes, ctx->stream);
+  if (e == hipSuccess) {
+    launch_diag_lm_step(ctx->stream, mode, lvl, t->d_desc, n, d_in, d_out, d_states, d_partials, partial_stride, spec != 0, spec ? spec_off : 0,
+                        helper != 0, coherent != 0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out, io_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t sync = hipStreamSynchronize(ctx->stream); // (also before the buffers are freed after a failed enqueue)
+  if (e == hipSuccess) e = sync;
+  if (d_in) (void)hipFree(d_in);
+  if (d_out) (void)hipFree(d_out);
+  if (d_states) (void)hipFree(d_states);
+  if (d_partials) (void)hipFree(d_partials);
+  DSM_HIP(e);
+  const int expired_after = lm_spin_expired();
+  if (expired_after != expired_before) {
+    set_error("dsm_diag_lm_step: a bounded wait of the LM step's wave hand-shake expired");
+    return DSM_ERR_STATE;
+  }
+  memcpy(out, h_out.data(), io_bytes);
+  return DSM_OK;
+}
+
 } // extern "C"

@@ -6,6 +6,7 @@
 
 struct dsm_lm_propose_in; // include/dsm_hotpath.h
 struct dsm_lm_propose_out;
+struct dsm_lm_step_state;
 
 namespace dsm {
 
@@ -184,6 +185,13 @@ void launch_diag_chain_eval(hipStream_t s, int mode, const LMState *states, floa
 // structures are the public ones of include/dsm_hotpath.h
 void launch_diag_lm_propose(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_propose_in *in,
                             ::dsm_lm_propose_out *out, bool spec, bool helper);
+
+// dsm_diag_lm_step: one production LM step (lm_step_block) per problem on caller-supplied states and partials, one workgroup per
+// problem; `states`: n LMState of device scratch the kernel builds the problems in; partials: problem p's at p * partial_stride floats,
+// the speculative evaluation's spec_off floats behind (the caller has checked that they fit)
+void launch_diag_lm_step(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_step_state *in,
+                         ::dsm_lm_step_state *out, LMState *states, const float *partials, long long partial_stride, bool spec, int spec_off,
+                         bool helper, bool coherent);
 
 // -- tracker_kernels.hip itself --
 // descriptors of many trackers in one launch (sync_descs): d_dst[i] <- d_src[i]

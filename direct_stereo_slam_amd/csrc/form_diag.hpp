@@ -1,5 +1,6 @@
-// form_diag.hpp -- the two diagnostic kernels of the tracker kernels (a part of tracker_kernels.hip, see the map at the top of that
-// file): one evaluation in the form the chains run it, and the proposing half of an LM step on caller-supplied systems.
+// form_diag.hpp -- the diagnostic kernels of the tracker kernels (a part of tracker_kernels.hip, see the map at the top of that
+// file): one evaluation in the form the chains run it, the proposing half of an LM step on caller-supplied systems, and one whole LM
+// step on caller-supplied states and partials.
 #pragma once
 
 namespace dsm {
@@ -102,6 +103,118 @@ __global__ __launch_bounds__(kLmThreads) void diag_lm_propose_kernel(int mode, i
 void launch_diag_lm_propose(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_propose_in *in,
                             ::dsm_lm_propose_out *out, bool spec, bool helper) {
   hipLaunchKernelGGL(diag_lm_propose_kernel, dim3(n), dim3(kLmThreads), 0, s, mode, lvl, tracker, n, in, out, spec ? 1 : 0, helper ? 1 : 0);
+}
+
+// dsm_diag_lm_step: ONE production LM step -- lm_step_block unchanged: the fixed-order reduction of the caller's partials, build_rs /
+// build_H_elem / build_b_elem, lm_step_wave0 with end_level, begin_level and finish_track, the speculative block and the helper waves
+// where asked for -- on a caller-supplied state, one workgroup per problem.  The problem is built in device memory, where the
+// production kernels keep it: a zeroed LMState takes the level part of both candidates' blocks (as begin_level leaves them) and the
+// caller's fields; the pending evaluation's n / ppt are set so that chunks_of gives the caller's chunk count.  After the step the
+// state is read back from device memory (what lm_step_block stored, not its LDS copy).
+__device__ __forceinline__ void diag_eval_in(EvalIn &e, const ::dsm_lm_step_eval &v, int mode, int nch) {
+  if (mode == 1) { // (M, t and the affine pair are the level's: make_eval_level)
+    e.scale = v.scale;
+  } else {
+    for (int i = 0; i < 9; i++) e.M[i] = v.M[i];
+    for (int i = 0; i < 3; i++) e.t[i] = v.t[i];
+    e.aff0 = v.aff0, e.aff1 = v.aff1;
+  }
+  e.cutoff = v.cutoff, e.max_energy = v.max_energy;
+  e.residual_only = v.residual_only;
+  e.n = nch * kThreads, e.ppt = 1; // chunks_of(n, ppt) == nch
+}
+__device__ __forceinline__ void diag_eval_out(::dsm_lm_step_eval &v, const EvalIn &e) {
+  for (int i = 0; i < 9; i++) v.M[i] = e.M[i], v.Ki[i] = e.Ki[i];
+  for (int i = 0; i < 3; i++) v.t[i] = e.t[i];
+  v.aff0 = e.aff0, v.aff1 = e.aff1, v.cutoff = e.cutoff, v.max_energy = e.max_energy;
+  v.residual_only = e.residual_only;
+  v.scale = e.scale;
+  v.n = e.n;
+}
+template <bool COH>
+__global__ __launch_bounds__(kLmThreads) void diag_lm_step_kernel(int mode, int lvl, const TrackerDev *__restrict__ Tg, int n,
+                                                                  const ::dsm_lm_step_state *__restrict__ in, ::dsm_lm_step_state *__restrict__ out,
+                                                                  LMState *states, const float *partials, long long partial_stride, int spec,
+                                                                  int spec_off, int helper) {
+  __shared__ LmShared sh;
+  __shared__ LmSpecShared sps;
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  if (prob >= n) return; // workgroup-uniform
+  LMState &S = states[prob];
+  const ::dsm_lm_step_state &I = in[prob];
+  for (int i = tid; i < kLmS16; i += kLmThreads) ((uint4 *)&S)[i] = uint4{0, 0, 0, 0};
+  __syncthreads();
+  if (tid < 64) S.H[tid] = I.H[tid];
+  if (tid < 8) S.b[tid] = I.b[tid];
+  if (tid == 0) {
+    S.status = ST_RUNNING;
+    S.lvl = lvl;
+    S.phase = I.phase;
+    S.is_scale = mode;
+    S.iteration = I.iteration;
+    S.have_repeated = I.have_repeated;
+    S.coarsest = I.coarsest;
+    S.lambda = I.lambda;
+    S.level_cutoff_repeat = I.level_cutoff_repeat;
+    S.inc_f = I.inc_f, S.scale_cur = I.scale_cur, S.scale_cand = I.scale_cand, S.Hs = I.Hs, S.bs = I.bs;
+    S.inc_norm = I.inc_norm;
+    for (int i = 0; i < 7; i++) S.cur[i] = I.cur[i], S.cand[i] = I.cand[i], S.spec_cand[i] = I.spec_cand[i];
+    for (int i = 0; i < 2; i++) S.aff_cur[i] = I.aff_cur[i], S.aff_cand[i] = I.aff_cand[i], S.spec_aff_cand[i] = I.spec_aff_cand[i];
+    for (int i = 0; i < 6; i++) S.res_old[i] = I.res_old[i];
+    for (int i = 0; i < DSM_MAX_LEVELS; i++) {
+      S.min_res[i] = I.min_res[i], S.last_residuals[i] = I.last_residuals[i], S.last_inners[i] = I.last_inners[i];
+      S.evals[i] = I.evals[i], S.evals_ro[i] = I.evals_ro[i], S.rounds[i] = I.rounds[i];
+    }
+    for (int i = 0; i < 3; i++) S.flow[i] = I.flow[i];
+    S.spec_valid = I.spec_valid;
+    S.ticks = I.ticks;
+    S.spec_scale_cand = I.spec_scale_cand, S.spec_inc_f = I.spec_inc_f;
+    S.spec_inc_norm = I.spec_inc_norm;
+    make_eval_level(*Tg, S.in, mode, lvl);
+    make_eval_level(*Tg, S.spec_in, mode, lvl);
+    diag_eval_in(S.in, I.ev, mode, I.nch);
+    diag_eval_in(S.spec_in, I.spec_ev, mode, I.nch);
+  }
+  __threadfence(); // the state is read back below by other threads, in the coherent form with device-scope loads
+  __syncthreads();
+  lm_step_block<COH>(mode, lvl, prob, Tg, S, partials + (size_t)prob * (size_t)partial_stride, sh, tid, nullptr, spec ? &sps : nullptr, spec_off,
+                     nullptr, (LmNoEarly *)nullptr, helper != 0);
+  __threadfence(); // wave 0's stores of the state
+  __syncthreads();
+  if (tid != 0) return;
+  uint4 *back = (uint4 *)&sh.st; // (the step is over: its LDS copy is free) the stored state, through the path that stored it
+  for (int i = 0; i < kLmS16; i++) back[i] = COH ? load16_coherent((const uint4 *)&S + i) : ((const uint4 *)&S)[i];
+  const LMState &R = sh.st;
+  ::dsm_lm_step_state &O = out[prob];
+  for (int i = 0; i < 64; i++) O.H[i] = R.H[i];
+  for (int i = 0; i < 8; i++) O.b[i] = R.b[i];
+  for (int i = 0; i < 7; i++) O.cur[i] = R.cur[i], O.cand[i] = R.cand[i], O.spec_cand[i] = R.spec_cand[i];
+  for (int i = 0; i < 2; i++) O.aff_cur[i] = R.aff_cur[i], O.aff_cand[i] = R.aff_cand[i], O.spec_aff_cand[i] = R.spec_aff_cand[i];
+  O.inc_norm = R.inc_norm, O.spec_inc_norm = R.spec_inc_norm;
+  for (int i = 0; i < 6; i++) O.res_old[i] = R.res_old[i];
+  for (int i = 0; i < DSM_MAX_LEVELS; i++) {
+    O.min_res[i] = R.min_res[i], O.last_residuals[i] = R.last_residuals[i], O.last_inners[i] = R.last_inners[i];
+    O.evals[i] = R.evals[i], O.evals_ro[i] = R.evals_ro[i], O.rounds[i] = R.rounds[i];
+  }
+  for (int i = 0; i < 3; i++) O.flow[i] = R.flow[i];
+  O.status = R.status, O.lvl = R.lvl, O.phase = R.phase, O.iteration = R.iteration, O.have_repeated = R.have_repeated;
+  O.coarsest = R.coarsest, O.spec_valid = R.spec_valid, O.ticks = R.ticks;
+  O.lambda = R.lambda, O.level_cutoff_repeat = R.level_cutoff_repeat;
+  O.inc_f = R.inc_f, O.spec_inc_f = R.spec_inc_f, O.scale_cur = R.scale_cur, O.scale_cand = R.scale_cand;
+  O.spec_scale_cand = R.spec_scale_cand, O.Hs = R.Hs, O.bs = R.bs;
+  O.nch = I.nch;
+  diag_eval_out(O.ev, R.in);
+  diag_eval_out(O.spec_ev, R.spec_in);
+}
+void launch_diag_lm_step(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_step_state *in,
+                         ::dsm_lm_step_state *out, LMState *states, const float *partials, long long partial_stride, bool spec, int spec_off,
+                         bool helper, bool coherent) {
+  if (coherent)
+    hipLaunchKernelGGL(diag_lm_step_kernel<true>, dim3(n), dim3(kLmThreads), 0, s, mode, lvl, tracker, n, in, out, states, partials,
+                       partial_stride, spec ? 1 : 0, spec_off, helper ? 1 : 0);
+  else
+    hipLaunchKernelGGL(diag_lm_step_kernel<false>, dim3(n), dim3(kLmThreads), 0, s, mode, lvl, tracker, n, in, out, states, partials,
+                       partial_stride, spec ? 1 : 0, spec_off, helper ? 1 : 0);
 }
 
 } // namespace dsm

@@ -11,11 +11,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import MAX_LEVELS, LmProposeIn, LmProposeOut, Params, Stats, c_double_p, c_float_p, c_int_p, check
+from ._lib import MAX_LEVELS, LmProposeIn, LmProposeOut, LmStepState, Params, Stats, c_double_p, c_float_p, c_int_p, check
 
 # numpy record layouts of dsm_lm_propose_in / dsm_lm_propose_out (the field names of _lib.LmProposeIn / LmProposeOut)
 LM_PROPOSE_IN = np.dtype(LmProposeIn)
 LM_PROPOSE_OUT = np.dtype(LmProposeOut)
+LM_STEP_STATE = np.dtype(LmStepState)  # dsm_lm_step_state
 
 
 def _fp(a):
@@ -625,6 +626,19 @@ class TrackerAndScaler:
         out = np.zeros(len(problems), LM_PROPOSE_OUT)
         check(self.L.dsm_diag_lm_propose(self.h, mode, lvl, len(problems), problems.ctypes.data_as(C.POINTER(LmProposeIn)), int(spec), int(helper),
                                          out.ctypes.data_as(C.POINTER(LmProposeOut))))
+        return out
+
+    def diagLmStep(self, mode, lvl, states, partials, spec=False, spec_off=0, helper=False, coherent=False):
+        """one production LM step per problem on caller-supplied states and partials (dsm_diag_lm_step).  states: a numpy array of
+        LM_STEP_STATE records; partials: float32 [len(states), partial_stride] (view integer slots as float32), the speculative
+        evaluation's spec_off floats behind the main ones.  Returns an array of LM_STEP_STATE records: the states after the step"""
+        states = np.ascontiguousarray(states, LM_STEP_STATE)
+        partials = np.ascontiguousarray(partials, np.float32)
+        assert partials.ndim == 2 and len(partials) == len(states)
+        out = np.zeros(len(states), LM_STEP_STATE)
+        check(self.L.dsm_diag_lm_step(self.h, mode, lvl, len(states), states.ctypes.data_as(C.POINTER(LmStepState)), _fp(partials),
+                                      partials.shape[1], int(spec), int(spec_off), int(helper), int(coherent),
+                                      out.ctypes.data_as(C.POINTER(LmStepState))))
         return out
 
     def trackNewestCoarse(self, lastToNew, aff_g2l, coarsestLvl, minResForAbort=None):

@@ -432,6 +432,56 @@ typedef struct dsm_lm_propose_out {
 int dsm_diag_lm_propose(dsm_tracker *t, int mode, int lvl, int n, const dsm_lm_propose_in *in, int spec, int helper,
                         dsm_lm_propose_out *out);
 
+/* test aid (no reference counterpart): the FIRST half of a Levenberg-Marquardt round -- the fixed-order reduction of an evaluation's
+ * chunk partials, their conversion into rs, H and b, and the state machine that consumes them (the cut-off repeat, accept / reject,
+ * the lambda update, the iteration bound, the "small step" test, the consumption of a speculative candidate, the end of a level, the
+ * level repeat, the hand-down and the verdicts: TrackerAndScaler.cpp:475-489, :556-638 pose, :873-885, :913-964 scale) -- run by the
+ * production device code (one unchanged LM step per problem, one workgroup each, n problems per call) on caller-supplied states and
+ * partials.  A step that goes on also stages the next proposal, as dsm_diag_lm_propose runs it alone.  The tracker supplies the
+ * parameters, K^-1 of the levels (dsm_tracker_make_k must have been called), the reference affine and the exposures; no template or
+ * frame is needed.  mode: 0 pose, 1 stereo scale, 2 loop-closure pose; every problem of a call stands on level lvl.
+ * The state goes in and comes out in the same structure, so that a result can be handed to the next call as it is:
+ *   in:  every field but status and lvl (the problem is running, at lvl) and, of ev and spec_ev, what the level alone determines:
+ *        Ki and n, in mode 1 also M, t, aff0, aff1, in modes 0 and 2 scale (1).  nch = chunks of the evaluation the step consumes.
+ *   out: every field after the step; status (DSM_LM_RUNNING ...), lvl (the level the problem now stands on), ev / spec_ev = the main
+ *        and the speculative evaluation as staged (what the step did not write is as handed in); nch as handed in.
+ * partials: problem p's chunk partials at partials + p * partial_stride, chunk-major, 64 floats per chunk, slots 49-51 integer bit
+ * patterns; spec != 0: the step is given a speculative block (it consumes the speculative evaluation where spec_valid is set and may
+ * stage a new one) and the speculative evaluation's partials sit spec_off floats behind the main ones.  helper != 0 (modes 0, 2):
+ * helper waves form the affine part of the staged evaluations, as in production.  coherent != 0: the instantiation that reads and
+ * writes the state with device-coherent accesses (the work-queue form's).
+ * DSM_ERR_INVALID with nothing written for a NULL pointer (partials included), n < 1 or n > 65536, a bad mode or level, a tracker
+ * without makeK, a phase other than 0 / 1, nch < 0 or > 4096, a partial_stride that is not a multiple of 4 in 4 .. 2^24, with spec a
+ * spec_off that is negative or not a multiple of 4, or partials that would not fit: 64 nch > (spec ? spec_off : partial_stride),
+ * spec_off + 64 nch > partial_stride.  DSM_ERR_STATE (outputs not written) when a bounded wait of the wave hand-shake expired during
+ * the call.  No production path calls this. */
+enum { DSM_LM_IDLE = 0, DSM_LM_RUNNING = 1, DSM_LM_GOOD = 2, DSM_LM_ABORTED = 3, DSM_LM_BAD_AFFINE = 4 };
+typedef struct dsm_lm_step_eval { /* the candidate's part of the inputs of an evaluation */
+  float M[9], t[3], aff0, aff1, cutoff, max_energy;
+  int residual_only;
+  float scale; /* mode 1 */
+  float Ki[9]; /* out: K^-1 of the level the evaluation is staged for */
+  int n;       /* out: template points of that level */
+} dsm_lm_step_eval;
+typedef struct dsm_lm_step_state {
+  double H[64], b[8]; /* modes 0, 2 */
+  double cur[7], aff_cur[2], cand[7], aff_cand[2];
+  double spec_cand[7], spec_aff_cand[2];
+  double inc_norm, spec_inc_norm;
+  double res_old[6];
+  double min_res[DSM_MAX_LEVELS], last_residuals[DSM_MAX_LEVELS], last_inners[DSM_MAX_LEVELS], flow[3];
+  long long evals[DSM_MAX_LEVELS], evals_ro[DSM_MAX_LEVELS], rounds[DSM_MAX_LEVELS];
+  int status, lvl; /* out */
+  int phase;       /* 0: the level's first evaluation is pending, 1: a proposal's */
+  int iteration, have_repeated, coarsest, spec_valid, ticks;
+  float lambda, level_cutoff_repeat;
+  float inc_f, spec_inc_f, scale_cur, scale_cand, spec_scale_cand, Hs, bs; /* mode 1 */
+  int nch;
+  dsm_lm_step_eval ev, spec_ev;
+} dsm_lm_step_state;
+int dsm_diag_lm_step(dsm_tracker *t, int mode, int lvl, int n, const dsm_lm_step_state *in, const float *partials,
+                     long long partial_stride, int spec, int spec_off, int helper, int coherent, dsm_lm_step_state *out);
+
 /* replaces TrackerAndScaler::trackNewestCoarse (TrackerAndScaler.cpp:451-638).
  * min_res_for_abort / last_residuals: DSM_MAX_LEVELS doubles (reference: Vec5; NaN = no limit).
  * flow_out = lastFlowIndicators.  *good = the reference's bool return value. */

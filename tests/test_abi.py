@@ -28,6 +28,16 @@ def test_header_symbols_are_all_exported(built):
     assert sorted(_lib.SYMBOLS) == names
 
 
+def test_lm_diagnostic_records_have_the_headers_sizes(built):
+    """the sizes diag_capi.hip static_asserts for dsm_lm_propose_in / _out and dsm_lm_step_eval / _state"""
+    from direct_stereo_slam_amd import _lib
+    from direct_stereo_slam_amd.tracker import LM_PROPOSE_IN, LM_PROPOSE_OUT, LM_STEP_STATE
+
+    assert (C.sizeof(_lib.LmProposeIn), C.sizeof(_lib.LmProposeOut)) == (672, 264) == (LM_PROPOSE_IN.itemsize, LM_PROPOSE_OUT.itemsize)
+    assert (C.sizeof(_lib.LmStepEval), C.sizeof(_lib.LmStepState)) == (112, 1464) and LM_STEP_STATE.itemsize == 1464
+    assert LM_STEP_STATE.fields["ev"][1] == 1464 - 224 and LM_STEP_STATE.fields["nch"][1] == 1464 - 228
+
+
 def test_library_contains_gfx950_code_object(built):
     from direct_stereo_slam_amd import _lib
 
