@@ -252,6 +252,52 @@ class LmStepState(C.Structure):
     ]
 
 
+# dsm_diag_tick_*: the tick engine's lists and rings (DSM_TICK_* of include/dsm_hotpath.h)
+TICK_SENTINEL, TICK_NOOP, TICK_CAND, TICK_CHUNK_BITS, TICK_MAX_SEGS = 0x3FFFF5A5, 0x80000000, 0x40000000, 12, 20
+
+
+class TickSeg(C.Structure):
+    _fields_ = [("mode", C.c_int), ("i0", C.c_int), ("ns", C.c_int)]
+
+
+class TickListCfg(C.Structure):
+    _fields_ = [("cap", C.c_int), ("chain_cap", C.c_int), ("chain_max_n0", C.c_int), ("buf", C.c_int), ("count", C.c_int), ("chain", C.c_int)]
+
+
+class TickSegCtl(C.Structure):
+    _fields_ = [("count", C.c_int * 2), ("overflow", C.c_int), ("chain", C.c_int * 2), ("pad", C.c_int * 27)]
+
+
+class TickModeCtl(C.Structure):
+    _fields_ = [("pending_head", C.c_longlong), ("pending_count", C.c_longlong), ("retired", C.c_longlong), ("ring", C.c_int), ("pad", C.c_int),
+                ("sched_evals", C.c_longlong * MAX_LEVELS), ("sched_ro", C.c_longlong * MAX_LEVELS), ("sched_items", C.c_longlong * MAX_LEVELS)]
+
+
+class TickPending(C.Structure):
+    _fields_ = [("pose", C.c_double * 7), ("aff", C.c_double * 2), ("min_res", C.c_double * MAX_LEVELS), ("scale", C.c_float),
+                ("coarsest", C.c_int), ("ticket", C.c_uint64)]
+
+
+_TICK_RESULT_TAIL = [("cur", C.c_double * 7), ("aff_cur", C.c_double * 2), ("last_residuals", C.c_double * MAX_LEVELS), ("flow", C.c_double * 3),
+                     ("scale_cur", C.c_float), ("pad1", C.c_float),
+                     ("evals", C.c_longlong * MAX_LEVELS), ("evals_ro", C.c_longlong * MAX_LEVELS), ("rounds", C.c_longlong * MAX_LEVELS)]
+
+
+class TickResult(C.Structure):
+    _fields_ = [("ticket", C.c_uint64), ("status", C.c_int), ("ticks", C.c_int)] + _TICK_RESULT_TAIL
+
+
+class TickSlot(C.Structure):
+    _fields_ = [("status", C.c_int), ("lvl", C.c_int), ("n", C.c_int), ("ppt", C.c_int), ("spec_valid", C.c_int), ("n0", C.c_int),
+                ("residual_only", C.c_int), ("ticks", C.c_int), ("stepped", C.c_int), ("reserve", C.c_int), ("res_base", C.c_int),
+                ("res_total", C.c_int), ("ticket", C.c_uint64)] + _TICK_RESULT_TAIL
+
+
+class TickSlotOut(C.Structure):
+    _fields_ = [("status", C.c_int), ("lvl", C.c_int), ("stepped", C.c_int), ("n", C.c_int), ("ppt", C.c_int), ("spec_valid", C.c_int),
+                ("n0", C.c_int), ("residual_only", C.c_int), ("tracker_set", C.c_int), ("pad", C.c_int), ("ticket", C.c_uint64)]
+
+
 # every symbol include/dsm_hotpath.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _pp_f = C.POINTER(c_float_p)
@@ -333,7 +379,18 @@ SYMBOLS = {
     "dsm_diag_lm_propose": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmProposeIn), C.c_int, C.c_int, C.POINTER(LmProposeOut)]),
     "dsm_diag_lm_step": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmStepState), c_float_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(LmStepState)]),
-    "dsm_diag_icp_stages": (C.c_int, [_vp, C.c_int, C.POINTER(IcpJob), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
+    "dsm_diag_tick_reserve": (C.c_int, [_vp, C.c_int, C.POINTER(TickSeg), C.c_int, C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong),
+                                        C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_int_p]),
+    "dsm_diag_tick_stage": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(TickSlot), C.POINTER(TickListCfg), C.POINTER(TickModeCtl), C.c_int,
+                                      C.POINTER(TickPending), C.c_int, C.POINTER(C.c_uint), c_int_p, C.POINTER(TickSegCtl), C.POINTER(TickModeCtl),
+                                      C.POINTER(TickResult), C.POINTER(TickSlotOut), C.POINTER(LmStepState), C.POINTER(C.c_ubyte), c_int_p,
+                                      C.POINTER(C.c_ubyte)]),
+    "dsm_diag_tick_step": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmStepState), C.POINTER(TickSlot), c_float_p, C.c_longlong, C.c_int,
+                                     C.c_int, C.POINTER(TickListCfg), C.POINTER(TickModeCtl), C.c_int, C.POINTER(TickPending),
+                                     C.POINTER(C.c_longlong), C.POINTER(C.c_uint), c_int_p, C.POINTER(TickSegCtl), C.POINTER(TickModeCtl),
+                                     C.POINTER(TickResult), C.POINTER(TickSlotOut), C.POINTER(LmStepState), C.POINTER(C.c_ubyte), c_int_p,
+                                     C.POINTER(C.c_ubyte)]),
+    "dsm_diag_icp_stages":(C.c_int, [_vp, C.c_int, C.POINTER(IcpJob), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
                                       c_float_p, C.POINTER(C.c_uint64), _vp]),
     "dsm_tracker_track": (C.c_int, [_vp, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
     "dsm_tracker_optimize_scale": (C.c_int, [_vp, c_float_p, C.c_int, c_float_p]),

@@ -7,6 +7,8 @@
 struct dsm_lm_propose_in; // include/dsm_hotpath.h
 struct dsm_lm_propose_out;
 struct dsm_lm_step_state;
+struct dsm_tick_slot;
+struct dsm_tick_slot_out;
 
 namespace dsm {
 
@@ -192,6 +194,17 @@ void launch_diag_lm_propose(hipStream_t s, int mode, int lvl, const TrackerDev *
 void launch_diag_lm_step(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_step_state *in,
                          ::dsm_lm_step_state *out, LMState *states, const float *partials, long long partial_stride, bool spec, int spec_off,
                          bool helper, bool coherent);
+
+// dsm_diag_tick_stage: tick_after_step (behind the slot's reservation) on n host-built slot states, one wave per slot in one launch
+void launch_diag_tick_stage(hipStream_t s, int mode, int n, const ::dsm_tick_slot *slots, const TrackerDev **trackers, LMState *states,
+                            const TickList &list, TickModeCtl *mc, const TickPending *pending, TickResult *results,
+                            unsigned long long *slot_ticket, int stepped);
+// dsm_diag_tick_step: n slot states built as launch_diag_lm_step builds its problems (slots: the stepped flag, an idle status)
+void launch_diag_tick_fill(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_step_state *in,
+                           const ::dsm_tick_slot *slots, LMState *states);
+// both: the states as dsm_lm_step_state records, and status / level / flags, ticket and "the tracker pointer is `tracker`" per slot
+void launch_diag_tick_unpack(hipStream_t s, int n, const LMState *states, const TrackerDev *const *trackers, const TrackerDev *tracker,
+                             const unsigned long long *slot_ticket, ::dsm_lm_step_state *state_out, ::dsm_tick_slot_out *slot_out);
 
 // -- tracker_kernels.hip itself --
 // descriptors of many trackers in one launch (sync_descs): d_dst[i] <- d_src[i]

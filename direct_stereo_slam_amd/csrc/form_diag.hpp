@@ -1,6 +1,7 @@
 // form_diag.hpp -- the diagnostic kernels of the tracker kernels (a part of tracker_kernels.hip, see the map at the top of that
-// file): one evaluation in the form the chains run it, the proposing half of an LM step on caller-supplied systems, and one whole LM
-// step on caller-supplied states and partials.
+// file): one evaluation in the form the chains run it, the proposing half of an LM step on caller-supplied systems, one whole LM
+// step on caller-supplied states and partials, and the tick engine's reservation and staging (tick_after_step) on caller-supplied
+// slot states, with the kernels that build and unpack the slots of dsm_diag_tick_step.
 #pragma once
 
 namespace dsm {
@@ -131,17 +132,8 @@ __device__ __forceinline__ void diag_eval_out(::dsm_lm_step_eval &v, const EvalI
   v.scale = e.scale;
   v.n = e.n;
 }
-template <bool COH>
-__global__ __launch_bounds__(kLmThreads) void diag_lm_step_kernel(int mode, int lvl, const TrackerDev *__restrict__ Tg, int n,
-                                                                  const ::dsm_lm_step_state *__restrict__ in, ::dsm_lm_step_state *__restrict__ out,
-                                                                  LMState *states, const float *partials, long long partial_stride, int spec,
-                                                                  int spec_off, int helper) {
-  __shared__ LmShared sh;
-  __shared__ LmSpecShared sps;
-  const int prob = blockIdx.x, tid = threadIdx.x;
-  if (prob >= n) return; // workgroup-uniform
-  LMState &S = states[prob];
-  const ::dsm_lm_step_state &I = in[prob];
+// all threads of the workgroup: the problem dsm_diag_lm_step describes, built in S (device memory); ends with a workgroup barrier
+__device__ __forceinline__ void diag_fill_state(LMState &S, const ::dsm_lm_step_state &I, const TrackerDev *Tg, int mode, int lvl, int tid) {
   for (int i = tid; i < kLmS16; i += kLmThreads) ((uint4 *)&S)[i] = uint4{0, 0, 0, 0};
   __syncthreads();
   if (tid < 64) S.H[tid] = I.H[tid];
@@ -177,15 +169,9 @@ __global__ __launch_bounds__(kLmThreads) void diag_lm_step_kernel(int mode, int 
   }
   __threadfence(); // the state is read back below by other threads, in the coherent form with device-scope loads
   __syncthreads();
-  lm_step_block<COH>(mode, lvl, prob, Tg, S, partials + (size_t)prob * (size_t)partial_stride, sh, tid, nullptr, spec ? &sps : nullptr, spec_off,
-                     nullptr, (LmNoEarly *)nullptr, helper != 0);
-  __threadfence(); // wave 0's stores of the state
-  __syncthreads();
-  if (tid != 0) return;
-  uint4 *back = (uint4 *)&sh.st; // (the step is over: its LDS copy is free) the stored state, through the path that stored it
-  for (int i = 0; i < kLmS16; i++) back[i] = COH ? load16_coherent((const uint4 *)&S + i) : ((const uint4 *)&S)[i];
-  const LMState &R = sh.st;
-  ::dsm_lm_step_state &O = out[prob];
+}
+// one thread: the state R as dsm_diag_lm_step hands it back
+__device__ __forceinline__ void diag_state_out(::dsm_lm_step_state &O, const LMState &R, int nch) {
   for (int i = 0; i < 64; i++) O.H[i] = R.H[i];
   for (int i = 0; i < 8; i++) O.b[i] = R.b[i];
   for (int i = 0; i < 7; i++) O.cur[i] = R.cur[i], O.cand[i] = R.cand[i], O.spec_cand[i] = R.spec_cand[i];
@@ -202,9 +188,29 @@ __global__ __launch_bounds__(kLmThreads) void diag_lm_step_kernel(int mode, int 
   O.lambda = R.lambda, O.level_cutoff_repeat = R.level_cutoff_repeat;
   O.inc_f = R.inc_f, O.spec_inc_f = R.spec_inc_f, O.scale_cur = R.scale_cur, O.scale_cand = R.scale_cand;
   O.spec_scale_cand = R.spec_scale_cand, O.Hs = R.Hs, O.bs = R.bs;
-  O.nch = I.nch;
+  O.nch = nch;
   diag_eval_out(O.ev, R.in);
   diag_eval_out(O.spec_ev, R.spec_in);
+}
+template <bool COH>
+__global__ __launch_bounds__(kLmThreads) void diag_lm_step_kernel(int mode, int lvl, const TrackerDev *__restrict__ Tg, int n,
+                                                                  const ::dsm_lm_step_state *__restrict__ in, ::dsm_lm_step_state *__restrict__ out,
+                                                                  LMState *states, const float *partials, long long partial_stride, int spec,
+                                                                  int spec_off, int helper) {
+  __shared__ LmShared sh;
+  __shared__ LmSpecShared sps;
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  if (prob >= n) return; // workgroup-uniform
+  LMState &S = states[prob];
+  diag_fill_state(S, in[prob], Tg, mode, lvl, tid);
+  lm_step_block<COH>(mode, lvl, prob, Tg, S, partials + (size_t)prob * (size_t)partial_stride, sh, tid, nullptr, spec ? &sps : nullptr, spec_off,
+                     nullptr, (LmNoEarly *)nullptr, helper != 0);
+  __threadfence(); // wave 0's stores of the state
+  __syncthreads();
+  if (tid != 0) return;
+  uint4 *back = (uint4 *)&sh.st; // (the step is over: its LDS copy is free) the stored state, through the path that stored it
+  for (int i = 0; i < kLmS16; i++) back[i] = COH ? load16_coherent((const uint4 *)&S + i) : ((const uint4 *)&S)[i];
+  diag_state_out(out[prob], sh.st, in[prob].nch);
 }
 void launch_diag_lm_step(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_step_state *in,
                          ::dsm_lm_step_state *out, LMState *states, const float *partials, long long partial_stride, bool spec, int spec_off,
@@ -215,6 +221,73 @@ void launch_diag_lm_step(hipStream_t s, int mode, int lvl, const TrackerDev *tra
   else
     hipLaunchKernelGGL(diag_lm_step_kernel<false>, dim3(n), dim3(kLmThreads), 0, s, mode, lvl, tracker, n, in, out, states, partials,
                        partial_stride, spec ? 1 : 0, spec_off, helper ? 1 : 0);
+}
+
+// dsm_diag_tick_stage: one wave per slot, every slot of the call in one launch (the list's and the ring's atomics contend).  The slot's
+// state -- built by the host, as it stands after a step -- is staged into LDS as tick_lm_kernel holds it; the wave makes the slot's
+// reservation through TickReserve itself (or takes the caller's base and total) and calls tick_after_step as tick_lm_kernel does.
+__global__ __launch_bounds__(64) void diag_tick_stage_kernel(int mode, int n, const ::dsm_tick_slot *__restrict__ slots, const TrackerDev **trackers,
+                                                             LMState *states, TickList L, TickModeCtl *mc, const TickPending *pending,
+                                                             TickResult *results, unsigned long long *slot_ticket, int stepped) {
+  __shared__ __attribute__((aligned(16))) LMState st;
+  __shared__ __attribute__((aligned(16))) TrackerDev trk;
+  const int prob = blockIdx.x, lane = threadIdx.x;
+  if (prob >= n) return; // workgroup-uniform
+  stage_in(st, &states[prob], lane, 64);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  const int req = slots[prob].reserve;
+  TickReserve rsv{L, 0, 0};
+  if (req == 1 || req == 2)
+    rsv(st, lane, req == 2);
+  else if (req == 3)
+    rsv.base = slots[prob].res_base, rsv.total = slots[prob].res_total;
+  const int res_base = __builtin_amdgcn_readfirstlane(rsv.base);
+  tick_after_step(mode, prob, trackers, states, st, trk, L, mc, pending, results, slot_ticket, lane, stepped, res_base, rsv.total);
+}
+void launch_diag_tick_stage(hipStream_t s, int mode, int n, const ::dsm_tick_slot *slots, const TrackerDev **trackers, LMState *states,
+                            const TickList &list, TickModeCtl *mc, const TickPending *pending, TickResult *results,
+                            unsigned long long *slot_ticket, int stepped) {
+  hipLaunchKernelGGL(diag_tick_stage_kernel, dim3(n), dim3(64), 0, s, mode, n, slots, trackers, states, list, mc, pending, results, slot_ticket,
+                     stepped);
+}
+
+// dsm_diag_tick_step: the slots' states, built as dsm_diag_lm_step builds its problems; a free slot is the same state, idle
+__global__ __launch_bounds__(kLmThreads) void diag_tick_fill_kernel(int mode, int lvl, const TrackerDev *__restrict__ Tg, int n,
+                                                                    const ::dsm_lm_step_state *__restrict__ in,
+                                                                    const ::dsm_tick_slot *__restrict__ slots, LMState *states) {
+  const int prob = blockIdx.x, tid = threadIdx.x;
+  if (prob >= n) return; // workgroup-uniform
+  LMState &S = states[prob];
+  diag_fill_state(S, in[prob], Tg, mode, lvl, tid);
+  if (tid == 0) {
+    S.stepped = slots[prob].stepped;
+    if (slots[prob].status == ST_IDLE) S.status = ST_IDLE;
+  }
+}
+void launch_diag_tick_fill(hipStream_t s, int mode, int lvl, const TrackerDev *tracker, int n, const ::dsm_lm_step_state *in,
+                           const ::dsm_tick_slot *slots, LMState *states) {
+  hipLaunchKernelGGL(diag_tick_fill_kernel, dim3(n), dim3(kLmThreads), 0, s, mode, lvl, tracker, n, in, slots, states);
+}
+
+// both tick diagnostics: every slot's state as a dsm_lm_step_state and what else an admission may have written, one thread per slot
+__global__ __launch_bounds__(64) void diag_tick_unpack_kernel(int n, const LMState *__restrict__ states, const TrackerDev *const *__restrict__ trackers,
+                                                              const TrackerDev *tracker, const unsigned long long *__restrict__ slot_ticket,
+                                                              ::dsm_lm_step_state *__restrict__ state_out, ::dsm_tick_slot_out *__restrict__ slot_out) {
+  const int prob = blockIdx.x * 64 + threadIdx.x;
+  if (prob >= n) return;
+  const LMState &S = states[prob];
+  diag_state_out(state_out[prob], S, S.in.ppt > 0 ? chunks_of(S.in.n, S.in.ppt) : 0);
+  ::dsm_tick_slot_out &O = slot_out[prob];
+  O.status = S.status, O.lvl = S.lvl, O.stepped = S.stepped, O.n = S.in.n, O.ppt = S.in.ppt, O.spec_valid = S.spec_valid, O.n0 = S.n0;
+  O.residual_only = S.in.residual_only;
+  O.tracker_set = trackers[prob] == tracker ? 1 : 0, O.pad = 0;
+  O.ticket = slot_ticket[prob];
+}
+void launch_diag_tick_unpack(hipStream_t s, int n, const LMState *states, const TrackerDev *const *trackers, const TrackerDev *tracker,
+                             const unsigned long long *slot_ticket, ::dsm_lm_step_state *state_out, ::dsm_tick_slot_out *slot_out) {
+  hipLaunchKernelGGL(diag_tick_unpack_kernel, dim3((n + 63) / 64), dim3(64), 0, s, n, states, trackers, tracker, slot_ticket, state_out, slot_out);
 }
 
 } // namespace dsm

@@ -31,7 +31,8 @@ __device__ __forceinline__ void tick_push(const LMState &St, int prob, const Tic
   }
   int base = res_base;
   if (total > res_total) { // nothing reserved (a reservation is never too short: it is made for the same level, with the twin counted)
-    for (int i = lane; i < res_total; i += 64) L.items[res_base + i] = kTickNoop;
+    for (int i = lane; i < res_total; i += 64)
+      if (res_base + i < L.cap) L.items[res_base + i] = kTickNoop; // (a reservation that ran over the list lies partly behind it: the chain entries are there)
     res_total = 0;
     if (lane == 0) {
       base = atomicAdd(&L.seg->count[L.buf], total);
@@ -137,7 +138,8 @@ __device__ __forceinline__ void tick_after_step(int mode, int prob, const Tracke
     tick_push(st, prob, L, mc, lane, res_base, res_total);
     return;
   }
-  for (int i = lane; i < res_total; i += 64) L.items[res_base + i] = kTickNoop; // (cannot happen: a step that proposes does not terminate)
+  for (int i = lane; i < res_total; i += 64) // (cannot happen: a step that proposes does not terminate -- tests/test_tick_lists.py, E)
+    if (res_base + i < L.cap) L.items[res_base + i] = kTickNoop;
   if (lane == 0) {
     const long long r = (long long)atomicAdd((unsigned long long *)&mc->retired, 1ull); // monotonic; the host never lets more problems in than the result ring has room for
     TickResult &R = results[r & (mc->ring - 1)];

@@ -23,7 +23,8 @@
 //   form_chain.hpp    chain form: tick_chain_round, chain_kernel, launch_chain.
 //   form_tick.hpp     tick engine: tick_push, admission, tick_chain_finish, tick_eval_kernel, tick_lm_kernel, the five launch_tick_*.
 //                     After form_chain.hpp (tick_chain_round) and form_launch.hpp (lm_start_problem).
-//   form_diag.hpp     diag_chain_eval_kernel, diag_lm_propose_kernel, diag_lm_step_kernel and their launchers.
+//   form_diag.hpp     diag_chain_eval_kernel, diag_lm_propose_kernel, diag_lm_step_kernel, diag_tick_stage_kernel, diag_tick_fill_kernel,
+//                     diag_tick_unpack_kernel and their launchers.  Last: the tick diagnostics run form_tick.hpp's device functions.
 //   (this file)       desc_scatter_kernel.
 // Why one translation unit: g_lm_spin_expired must have one copy, and the two noinline functions tick_chain_round / tick_chain_finish
 // are shared by the kernels that call them; build time is no reason to split (a full compile takes about 16 s).

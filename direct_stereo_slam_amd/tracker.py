@@ -11,12 +11,40 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import MAX_LEVELS, LmProposeIn, LmProposeOut, LmStepState, Params, Stats, c_double_p, c_float_p, c_int_p, check
+from ._lib import (MAX_LEVELS, LmProposeIn, LmProposeOut, LmStepState, Params, Stats, TickListCfg, TickModeCtl, TickPending, TickResult, TickSeg,
+                   TickSegCtl, TickSlot, TickSlotOut, c_double_p, c_float_p, c_int_p, check)
 
 # numpy record layouts of dsm_lm_propose_in / dsm_lm_propose_out (the field names of _lib.LmProposeIn / LmProposeOut)
 LM_PROPOSE_IN = np.dtype(LmProposeIn)
 LM_PROPOSE_OUT = np.dtype(LmProposeOut)
 LM_STEP_STATE = np.dtype(LmStepState)  # dsm_lm_step_state
+# dsm_diag_tick_*: dsm_tick_slot / _slot_out / _pending / _result
+TICK_SLOT, TICK_SLOT_OUT, TICK_PENDING, TICK_RESULT = np.dtype(TickSlot), np.dtype(TickSlotOut), np.dtype(TickPending), np.dtype(TickResult)
+
+
+def _tick_call(fn, head_args, n, list_cfg, ctl, pending):
+    """the common tail of dsm_diag_tick_stage / _step: asks for the length of the item allocation, runs, returns a dict of everything read back"""
+    lc = TickListCfg(**list_cfg)
+    mc = TickModeCtl(pending_head=ctl["pending_head"], pending_count=ctl["pending_count"], retired=ctl["retired"], ring=ctl["ring"])
+    pending = np.ascontiguousarray(pending if pending is not None else np.zeros(0, TICK_PENDING), TICK_PENDING)
+    npend, ring = len(pending), int(ctl["ring"])
+    pend_p = pending.ctypes.data_as(C.POINTER(TickPending)) if npend else None
+    length, sbytes = C.c_int(0), C.c_int(0)
+
+    def call(*outs):
+        check(fn(*head_args(C.byref(lc), C.byref(mc), npend, pend_p), *outs))
+
+    call(None, C.byref(length), None, None, None, None, None, None, C.byref(sbytes), None)
+    items = np.zeros(length.value, np.uint32)
+    seg, mc_out = TickSegCtl(), TickModeCtl()
+    results = np.zeros(max(ring, 0), TICK_RESULT)
+    slot_out, state_out = np.zeros(n, TICK_SLOT_OUT), np.zeros(n, LM_STEP_STATE)
+    raw, start_raw = np.zeros((n, sbytes.value), np.uint8), np.zeros((npend, sbytes.value), np.uint8)
+    ub = C.POINTER(C.c_ubyte)
+    call(items.ctypes.data_as(C.POINTER(C.c_uint)), C.byref(length), C.byref(seg), C.byref(mc_out), results.ctypes.data_as(C.POINTER(TickResult)),
+         slot_out.ctypes.data_as(C.POINTER(TickSlotOut)), state_out.ctypes.data_as(C.POINTER(LmStepState)), raw.ctypes.data_as(ub), C.byref(sbytes),
+         start_raw.ctypes.data_as(ub) if npend else None)
+    return dict(items=items, seg=seg, ctl=mc_out, results=results, slot_out=slot_out, state_out=state_out, state_raw=raw, start_raw=start_raw)
 
 
 def _fp(a):
@@ -92,6 +120,17 @@ class Context:
 
     def sync(self):
         check(self.L.dsm_context_sync(self.h))
+
+    def diagTickReserve(self, segs, running, head, count):
+        """tick_reserve_kernel alone (dsm_diag_tick_reserve).  segs: (mode, i0, ns) triples; running: per slot, nonzero = a running
+        problem; head / count: the two kinds' pending_head / pending_count.  Returns (admit_idx [nslots] int64, heads [2], ctl_intact)"""
+        sg = (TickSeg * max(len(segs), 1))(*[TickSeg(*s) for s in segs])
+        running = np.ascontiguousarray(running, np.uint8)
+        hd, cn = (C.c_longlong * 2)(*head), (C.c_longlong * 2)(*count)
+        idx, hout, intact = np.zeros(len(running), np.int64), (C.c_longlong * 2)(), C.c_int()
+        check(self.L.dsm_diag_tick_reserve(self.h, len(segs), sg, len(running), running.ctypes.data_as(C.POINTER(C.c_ubyte)), hd, cn,
+                                           idx.ctypes.data_as(C.POINTER(C.c_longlong)), hout, C.byref(intact)))
+        return idx, [int(hout[0]), int(hout[1])], bool(intact.value)
 
     def set_timing(self, on):
         check(self.L.dsm_context_set_timing(self.h, int(on)))
@@ -640,6 +679,31 @@ class TrackerAndScaler:
                                       partials.shape[1], int(spec), int(spec_off), int(helper), int(coherent),
                                       out.ctypes.data_as(C.POINTER(LmStepState))))
         return out
+
+    def diagTickStage(self, mode, slots, list_cfg, ctl, pending=None, stepped=0):
+        """tick_after_step behind each slot's reservation, one wave per slot in one launch (dsm_diag_tick_stage).  slots: TICK_SLOT
+        records; list_cfg: dict(cap, chain_cap, chain_max_n0, buf, count, chain); ctl: dict(pending_head, pending_count, retired, ring);
+        pending: TICK_PENDING records.  Returns a dict: items (the whole allocation), seg, ctl, results, slot_out, state_out, state_raw,
+        start_raw"""
+        slots = np.ascontiguousarray(slots, TICK_SLOT)
+        sp = slots.ctypes.data_as(C.POINTER(TickSlot))
+        return _tick_call(self.L.dsm_diag_tick_stage, lambda lc, mc, npend, pend: (self.h, mode, len(slots), sp, lc, mc, npend, pend, int(stepped)),
+                          len(slots), list_cfg, ctl, pending)
+
+    def diagTickStep(self, mode, lvl, states, slots, partials, speculate, opts, list_cfg, ctl, pending=None, admit_idx=None):
+        """the production tick_admit_kernel (admit_idx given) and tick_lm_kernel on slots built as diagLmStep builds its problems
+        (dsm_diag_tick_step; opts bit 2: the admission alone).  Returns diagTickStage's dict"""
+        states = np.ascontiguousarray(states, LM_STEP_STATE)
+        slots = np.ascontiguousarray(slots, TICK_SLOT)
+        partials = np.ascontiguousarray(partials, np.float32)
+        assert partials.ndim == 2 and len(partials) == len(states) == len(slots)
+        adm = None if admit_idx is None else np.ascontiguousarray(admit_idx, np.int64)
+        adm_p = None if adm is None else adm.ctypes.data_as(C.POINTER(C.c_longlong))
+        st_p, sl_p = states.ctypes.data_as(C.POINTER(LmStepState)), slots.ctypes.data_as(C.POINTER(TickSlot))
+        return _tick_call(self.L.dsm_diag_tick_step,
+                          lambda lc, mc, npend, pend: (self.h, mode, lvl, len(states), st_p, sl_p, _fp(partials), partials.shape[1], int(speculate),
+                                                       int(opts), lc, mc, npend, pend, adm_p),
+                          len(states), list_cfg, ctl, pending)
 
     def trackNewestCoarse(self, lastToNew, aff_g2l, coarsestLvl, minResForAbort=None):
         """returns (good, lastToNew_out, aff_g2l_out, lastResiduals) and sets lastFlowIndicators"""

@@ -482,6 +482,97 @@ typedef struct dsm_lm_step_state {
 int dsm_diag_lm_step(dsm_tracker *t, int mode, int lvl, int n, const dsm_lm_step_state *in, const float *partials,
                      long long partial_stride, int spec, int spec_off, int helper, int coherent, dsm_lm_step_state *out);
 
+/* test aids (no reference counterpart): the tick engine's reservation, admission and item lists (csrc/form_tick.hpp) alone.  Each call
+ * builds its inputs in device memory, runs the production device code unchanged and copies back everything that code may have written.
+ * The words behind an item list are cap + chain_cap + G, G = every word every slot of the call could write (its reservation, both
+ * candidates' positions, the first items of a problem admitted into it), all prefilled with DSM_TICK_SENTINEL -- neither a no-op nor
+ * an item of a call's slots (n <= 65536): a write the list's bounds should have stopped shows as a changed word behind `cap`, never
+ * as a fault.  No call waits on another workgroup.  No production path calls these.
+ *
+ * dsm_diag_tick_reserve: tick_reserve_kernel on nseg segment descriptors over nslots slots (running[s] != 0: slot s holds a running
+ *   problem) and the waiting rings' head / count of both kinds.  admit_idx[s]: the ring index slot s takes, -1 for none, -2 where no
+ *   segment covers the slot; head_out: both heads afterwards; *ctl_intact: no other word of the two control blocks changed.
+ *   DSM_ERR_INVALID (nothing written): a NULL argument, nseg < 0 or > DSM_TICK_MAX_SEGS, nslots < 1 or > 65536, a segment with a mode
+ *   other than 0 / 1, a negative i0 or ns, or slots beyond nslots.
+ * dsm_diag_tick_stage: n crafted post-step slot states, one wave per slot and all in one launch; each wave makes the slot's
+ *   reservation (reserve 0: none; 1 / 2: TickReserve::operator() with want_spec 0 / 1; 3: res_base, res_total as given) and calls
+ *   tick_after_step as tick_lm_kernel does, with `stepped`.  The waiting ring holds n_pending entries from ctl->pending_head on (every
+ *   one this tracker, its own start and ticket); ctl->pending_count may not exceed head + n_pending.
+ *   Outputs: items[0 .. *items_len) -- with items NULL the call only writes the length it needs to *items_len --, the segment's and
+ *   the kind's control blocks, the result ring (ctl->ring entries, prefilled with bytes 0xA5), per slot a dsm_tick_slot_out and the
+ *   state as a dsm_lm_step_state (nch: the chunks of the evaluation now pending) and as raw bytes (state_bytes each, n of them), and
+ *   per pending entry what launch_lm(LM_OP_START) leaves in a zeroed state, raw (start_raw).
+ * dsm_diag_tick_step: the production tick_admit_kernel (admit_idx != NULL: per slot the ring index to take or -1) and then the
+ *   production tick_lm_kernel with `speculate` and `opts` on n slots built as dsm_diag_lm_step builds its problems (all at level lvl,
+ *   partials as there, the speculative ones partial_stride / 2 behind); slot[s].status DSM_LM_IDLE: a free slot (the state as built,
+ *   but idle); slot[s].stepped: the state's flag.  opts: bits 0 and 1 are tick_lm_kernel's (helper waves, the early reservation),
+ *   bit 2: the admission alone, no LM launch.  admit_idx names entries of [pending_head, pending_head + n_pending) only.  The list
+ *   written is buffer list->buf; buffer buf ^ 1 starts with count and chain 7 (tick_lm_kernel's slot 0 clears them).  The trackers[]
+ *   of the slots start as a copy of the descriptor, so tracker_set tells an admission's pointer.  Outputs as dsm_diag_tick_stage's.
+ * DSM_ERR_INVALID (nothing written) for both: a NULL argument, n < 1 or n > 65536, a point count whose positions do not fit the item
+ *   encoding, a ring that is not a power of two in 1 .. 2^20, negative cap, counts, offsets or heads, count > cap, chain > chain_cap,
+ *   buf other than 0 / 1, an explicit reservation outside [0, cap + chain_cap + G), pending_count > pending_head + n_pending,
+ *   n_pending > ring, *items_len smaller than needed; and what dsm_diag_lm_step refuses. */
+#define DSM_TICK_SENTINEL 0x3FFFF5A5u
+#define DSM_TICK_NOOP 0x80000000u
+#define DSM_TICK_CAND 0x40000000u
+#define DSM_TICK_CHUNK_BITS 12
+#define DSM_TICK_MAX_SEGS 20
+typedef struct dsm_tick_seg {
+  int mode, i0, ns;
+} dsm_tick_seg;
+typedef struct dsm_tick_list_cfg {
+  int cap, chain_cap, chain_max_n0, buf;
+  int count, chain; /* of buffer buf, at the start */
+} dsm_tick_list_cfg;
+typedef struct dsm_tick_seg_ctl { /* TickSegCtl */
+  int count[2], overflow, chain[2], pad[27];
+} dsm_tick_seg_ctl;
+typedef struct dsm_tick_mode_ctl { /* TickModeCtl */
+  long long pending_head, pending_count, retired;
+  int ring, pad;
+  long long sched_evals[DSM_MAX_LEVELS], sched_ro[DSM_MAX_LEVELS], sched_items[DSM_MAX_LEVELS];
+} dsm_tick_mode_ctl;
+typedef struct dsm_tick_pending { /* a waiting problem: what dsm_stream_submit_* hands over */
+  double pose[7], aff[2], min_res[DSM_MAX_LEVELS];
+  float scale;
+  int coarsest;
+  unsigned long long ticket;
+} dsm_tick_pending;
+typedef struct dsm_tick_result { /* TickResult */
+  unsigned long long ticket;
+  int status, ticks;
+  double cur[7], aff_cur[2], last_residuals[DSM_MAX_LEVELS], flow[3];
+  float scale_cur, pad1;
+  long long evals[DSM_MAX_LEVELS], evals_ro[DSM_MAX_LEVELS], rounds[DSM_MAX_LEVELS];
+} dsm_tick_result;
+typedef struct dsm_tick_slot { /* dsm_diag_tick_stage: a slot after its step; dsm_diag_tick_step: status, stepped and ticket alone */
+  int status, lvl, n, ppt, spec_valid, n0, residual_only, ticks; /* n, ppt: EvalIn::n / ppt of the pending evaluation */
+  int stepped, reserve, res_base, res_total;
+  unsigned long long ticket;
+  double cur[7], aff_cur[2], last_residuals[DSM_MAX_LEVELS], flow[3]; /* what a terminated slot's result carries */
+  float scale_cur, pad1;
+  long long evals[DSM_MAX_LEVELS], evals_ro[DSM_MAX_LEVELS], rounds[DSM_MAX_LEVELS];
+} dsm_tick_slot;
+typedef struct dsm_tick_slot_out {
+  int status, lvl, stepped, n, ppt, spec_valid, n0, residual_only;
+  int tracker_set, pad; /* trackers[slot] is the tracker's descriptor (an admission wrote it) */
+  unsigned long long ticket; /* slot_ticket[slot] */
+} dsm_tick_slot_out;
+int dsm_diag_tick_reserve(dsm_context *ctx, int nseg, const dsm_tick_seg *segs, int nslots, const unsigned char *running,
+                          const long long head[2], const long long count[2], long long *admit_idx, long long head_out[2], int *ctl_intact);
+int dsm_diag_tick_stage(dsm_tracker *t, int mode, int n, const dsm_tick_slot *slots, const dsm_tick_list_cfg *list,
+                        const dsm_tick_mode_ctl *ctl, int n_pending, const dsm_tick_pending *pending, int stepped, unsigned *items,
+                        int *items_len, dsm_tick_seg_ctl *seg_out, dsm_tick_mode_ctl *ctl_out, dsm_tick_result *results,
+                        dsm_tick_slot_out *slot_out, dsm_lm_step_state *state_out, unsigned char *state_raw, int *state_bytes,
+                        unsigned char *start_raw);
+int dsm_diag_tick_step(dsm_tracker *t, int mode, int lvl, int n, const dsm_lm_step_state *in, const dsm_tick_slot *slots,
+                       const float *partials, long long partial_stride, int speculate, int opts, const dsm_tick_list_cfg *list,
+                       const dsm_tick_mode_ctl *ctl, int n_pending, const dsm_tick_pending *pending, const long long *admit_idx,
+                       unsigned *items, int *items_len, dsm_tick_seg_ctl *seg_out, dsm_tick_mode_ctl *ctl_out, dsm_tick_result *results,
+                       dsm_tick_slot_out *slot_out, dsm_lm_step_state *state_out, unsigned char *state_raw, int *state_bytes,
+                       unsigned char *start_raw);
+
 /* replaces TrackerAndScaler::trackNewestCoarse (TrackerAndScaler.cpp:451-638).
  * min_res_for_abort / last_residuals: DSM_MAX_LEVELS doubles (reference: Vec5; NaN = no limit).
  * flow_out = lastFlowIndicators.  *good = the reference's bool return value. */

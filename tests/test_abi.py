@@ -38,6 +38,21 @@ def test_lm_diagnostic_records_have_the_headers_sizes(built):
     assert LM_STEP_STATE.fields["ev"][1] == 1464 - 224 and LM_STEP_STATE.fields["nch"][1] == 1464 - 228
 
 
+def test_tick_diagnostic_records_have_the_headers_sizes(built):
+    """the sizes diag_capi.hip static_asserts for the dsm_tick_* structures, and the header's item encoding"""
+    from direct_stereo_slam_amd import _lib
+    from direct_stereo_slam_amd.tracker import TICK_PENDING, TICK_RESULT, TICK_SLOT, TICK_SLOT_OUT
+
+    sizes = {n: C.sizeof(getattr(_lib, n)) for n in ("TickSeg", "TickListCfg", "TickSegCtl", "TickModeCtl", "TickPending", "TickResult", "TickSlot", "TickSlotOut")}
+    assert sizes == dict(TickSeg=12, TickListCfg=24, TickSegCtl=128, TickModeCtl=176, TickPending=136, TickResult=312, TickSlot=352, TickSlotOut=48)
+    assert (TICK_PENDING.itemsize, TICK_RESULT.itemsize, TICK_SLOT.itemsize, TICK_SLOT_OUT.itemsize) == (136, 312, 352, 48)
+    assert TICK_SLOT.fields["ticket"][1] == 48 and TICK_SLOT.fields["cur"][1] == 56 and TICK_RESULT.fields["cur"][1] == 16
+    hdr = open(os.path.join(ROOT, "include", "dsm_hotpath.h")).read()
+    for name, value in (("SENTINEL", _lib.TICK_SENTINEL), ("NOOP", _lib.TICK_NOOP), ("CAND", _lib.TICK_CAND), ("CHUNK_BITS", _lib.TICK_CHUNK_BITS),
+                        ("MAX_SEGS", _lib.TICK_MAX_SEGS)):
+        assert int(re.search(rf"#define DSM_TICK_{name} (\w+)", hdr).group(1).rstrip("u"), 0) == value, name
+
+
 def test_library_contains_gfx950_code_object(built):
     from direct_stereo_slam_amd import _lib
 
