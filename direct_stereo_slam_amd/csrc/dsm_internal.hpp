@@ -69,7 +69,8 @@ struct dsm_context {
     int wait_copies();
     void release();
   } handover;
-  // workspaces of the LM batch form (batch_capi.hip: ensure_batch_capacity, run_queue; read by diag_capi.hip, pose_capi.hip and stream_capi.hip)
+  // workspaces of the LM batch form (batch_capi.hip: ensure_batch_capacity, run_queue; read by diag_capi.hip and pose_capi.hip; a dsm_stream has
+  // slot arrays of its own, stream_internal.hpp)
   struct LmWorkspace {
     int cap_prob = 0;
     int partial_stride = 0; // floats per problem
@@ -235,7 +236,7 @@ void release_pinned(T *&p) {
 }
 
 // ---- lm_schedule.hip: what the schedulers of the LM kernels share (the batch form, run_lm_batch in batch_capi.hip; the pass
-// engine and the tick engine of stream_capi.hip) ----
+// engine of stream_pass.hip and the tick engine of stream_tick.hip) ----
 
 // A segment of a launch schedule: problems (or slots) [i0, i1) of one mode on one HIP stream.  The main batch is split into
 // contiguous stream groups, each with its own HIP stream: a group's lm_kernel -- one small workgroup per problem -- and its

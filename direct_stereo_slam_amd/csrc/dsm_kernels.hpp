@@ -175,6 +175,11 @@ void launch_tick_eval(hipStream_t s, int mode, int grid, const LMState *states, 
                       TickSegCtl *seg, int buf, int cap, const TickChainArgs &chain,
                       bool with_chains /* the list may hold chain entries (now or from an earlier setting): the launch must look at them, if only
                                           to turn them into items (chain.max_rounds 0) */);
+// the same launch, the list it evaluates given as the TickList it was built as (its chain_cap and chain_max_n0 are not read)
+inline void launch_tick_eval(hipStream_t s, int mode, int grid, const LMState *states, float *partials, int partial_stride, const TickList &list,
+                             const TickChainArgs &chain, bool with_chains) {
+  launch_tick_eval(s, mode, grid, states, partials, partial_stride, list.items, list.seg, list.buf, list.cap, chain, with_chains);
+}
 void launch_tick_lm(hipStream_t s, int mode, int nslots, const TrackerDev **trackers, LMState *states, const float *partials, int partial_stride,
                     const TickList &next, TickModeCtl *mc, const TickPending *pending, TickResult *results, unsigned long long *slot_ticket,
                     int speculate, int opts /* bit 0: helper waves in the LM step, bit 1: the next items' place in the list asked for early */);

@@ -64,7 +64,7 @@ int dsm_search_sc(const int *sig_idx, const double *sig_val, int n_sig, int n_ca
 }
 
 // The hypothesis loop of FrontEnd::trackNewCoarse (FrontEnd.cpp:194-256) replayed from tries run without abort (the stream's hypothesis
-// groups, stream_capi.hip; the same replay as dsm_host::trackHypotheses and tracker.track_hypotheses)
+// groups, stream_groups.hip; the same replay as dsm_host::trackHypotheses and tracker.track_hypotheses)
 int dsm_hypotheses_resolve(int n_tries, const double *tries, const double aff_last[2], int coarsest_lvl, double last_coarse_rmse0,
                            double retrack_threshold, int k, const int *good, const double *pose, const double *aff,
                            const double *last_residuals, const double *flow, dsm_stream_hyp_result *out, int *decided_out) {

@@ -1,5 +1,5 @@
 // lm_schedule.hip -- what the host schedulers of the LM kernels share: the batch form (run_lm_batch, batch_capi.hip), the pass engine
-// and the tick engine of a dsm_stream (stream_capi.hip).  Segments and their HIP streams, fork and join, the (evaluate, step)
+// and the tick engine of a dsm_stream (stream_pass.hip, stream_tick.hip).  Segments and their HIP streams, fork and join, the (evaluate, step)
 // round with its launch rules, the per-dispatch timing, and the rules of what a problem starts from, what it costs and what it
 // writes back.  Host code only; each rule is stated here once.
 #include <algorithm>
