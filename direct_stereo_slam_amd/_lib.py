@@ -210,6 +210,19 @@ class LinearizeJob(C.Structure):
     ]
 
 
+class HessianJob(C.Structure):
+    _fields_ = [
+        ("lin", LinearizeJob), ("ad_host", c_double_p), ("ad_target", c_double_p),
+        ("prior", c_float_p), ("delta", c_float_p), ("hdd_lin", c_float_p), ("bd_lin", c_float_p), ("hcd_lin", c_float_p),
+        ("shift_prior_to_zero", C.c_int),
+        ("H_A", c_double_p), ("b_A", c_double_p), ("H_sc", c_double_p), ("b_sc", c_double_p),
+        ("acc_top", c_double_p), ("acc_D", c_double_p), ("acc_E", c_double_p), ("acc_EB", c_double_p), ("acc_Hcc", c_double_p),
+        ("acc_bc", c_double_p), ("active", C.POINTER(C.c_ubyte)), ("JpJdF", c_float_p),
+        ("hdd_acc", c_float_p), ("bd_acc", c_float_p), ("hcd_acc", c_float_p), ("hdi", c_float_p), ("bd_sum", c_float_p),
+        ("idepth_hessian", c_float_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -461,6 +474,8 @@ SYMBOLS = {
     "dsm_linearize_params_default": (C.c_int, [C.POINTER(LinearizeParams)]),
     "dsm_linearize_residuals_batch": (C.c_int, [_vp, C.c_int, C.POINTER(LinearizeJob), C.POINTER(LinearizeParams)]),
     "dsm_linearize_residuals_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(LinearizeJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams)]),
+    "dsm_window_hessian_batch": (C.c_int, [_vp, C.c_int, C.POINTER(HessianJob), C.POINTER(LinearizeParams)]),
+    "dsm_window_hessian_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(HessianJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams)]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

@@ -21,8 +21,7 @@
 #include <string>
 #include <vector>
 
-#include "call_arena.hpp"
-#include "linearize_math.hpp"
+#include "linearize_launch.hpp"
 
 using namespace dsm;
 
@@ -30,18 +29,8 @@ namespace {
 
 constexpr int kWavesPerBlock = 4;
 constexpr int kResPerBlock = 8 * kWavesPerBlock;
-constexpr int kHeadWords = 4; // per residual: new_state | keep << 8, new_energy, new_energy_with_outlier, rel_bs
+constexpr int kHeadWords = kLinHeadWords;
 constexpr size_t kMaxResiduals = 1u << 24;
-
-struct LinJob {
-  const float *plane[DSM_WINDOW_MAX_FRAMES]; // level-0 planes in frame_ids order
-  float fx, fy, cx, cy, fxi, fyi;
-  int n_frames, n_res, fix;
-  // 4-byte words into the staged inputs
-  int off_R0, off_t0, off_M, off_Kt, off_aff, off_b0, off_eth, off_host, off_u, off_v, off_id, off_idz, off_color, off_wt, off_point, off_target,
-      off_ein, off_flags;
-  long long o_head, o_J, o_cpt, o_proj; // 4-byte words into the output; -1: the job does not ask for it
-};
 
 template <int CTRL>
 __device__ __forceinline__ float dpp(float v) { // lanes without a source get 0; they never use it
@@ -138,16 +127,20 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void linearize_kernel(const Li
   }
 }
 
-// all-or-nothing validation of a batch: nothing is enqueued before every job has passed
-int check_jobs(dsm_context *ctx, int n_jobs, const dsm_linearize_job *jobs, const dsm_linearize_params *params, size_t *res_out) {
-  auto bad = [](const char *msg) { return invalid((std::string("dsm_linearize_residuals_batch: ") + msg).c_str()); };
+} // namespace
+
+namespace dsm {
+
+int linearize_check_jobs(const char *call, dsm_context *ctx, int n_jobs, const dsm_linearize_job *const *jobs, const dsm_linearize_params *params,
+                         size_t *res_out) {
+  auto bad = [call](const char *msg) { return invalid((std::string(call) + ": " + msg).c_str()); };
   if (!ctx || n_jobs < 1 || !jobs) return bad("bad argument");
   if (const char *e = linearize_params_error(params)) return bad(e);
   size_t res = 0;
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_linearize_job &J = jobs[j];
+    const dsm_linearize_job &J = *jobs[j];
     if (!J.window || J.window->ctx != ctx) return bad("no window, or a window of another context");
-    if (J.window->w != jobs[0].window->w || J.window->h != jobs[0].window->h) return bad("one geometry per call");
+    if (J.window->w != jobs[0]->window->w || J.window->h != jobs[0]->window->h) return bad("one geometry per call");
     if (const char *e = linearize_job_error(J)) return bad(e);
     for (int f = 0; f < J.n_frames; f++)
       if (J.window->find(J.frame_ids[f]) < 0) return bad("a frame id that is not in the window");
@@ -158,20 +151,78 @@ int check_jobs(dsm_context *ctx, int n_jobs, const dsm_linearize_job *jobs, cons
   return DSM_OK;
 }
 
-} // namespace
+// the six precalc tables, frame_energy_th, the point arrays and the residual arrays
+size_t linearize_stage_words(const dsm_linearize_job &J) {
+  const size_t nf = J.n_frames;
+  return 27 * nf * nf + nf + 21 * (size_t)J.n_pts + 4 * (size_t)J.n_res;
+}
+
+void linearize_stage(const dsm_linearize_job &J, LinJob &D, WordPacker &W) {
+  const size_t nf = J.n_frames, n = J.n_pts, nr = J.n_res;
+  for (size_t f = 0; f < nf; f++) D.plane[f] = J.window->plane(J.window->find(J.frame_ids[f]));
+  D.fx = J.cam[0], D.fy = J.cam[1], D.cx = J.cam[2], D.cy = J.cam[3], D.fxi = J.cam_inv[0], D.fyi = J.cam_inv[1];
+  D.n_frames = J.n_frames, D.n_res = J.n_res, D.fix = J.fix_linearization != 0;
+  W.put(&D.off_R0, J.pre_RTll_0, 9 * nf * nf);
+  W.put(&D.off_t0, J.pre_tTll_0, 3 * nf * nf);
+  W.put(&D.off_M, J.pre_KRKiTll, 9 * nf * nf);
+  W.put(&D.off_Kt, J.pre_KtTll, 3 * nf * nf);
+  W.put(&D.off_aff, J.pre_aff_mode, 2 * nf * nf);
+  W.put(&D.off_b0, J.pre_b0_mode, nf * nf);
+  W.put(&D.off_eth, J.frame_energy_th, nf);
+  W.put(&D.off_host, J.host, n);
+  W.put(&D.off_u, J.u, n);
+  W.put(&D.off_v, J.v, n);
+  W.put(&D.off_id, J.idepth_scaled, n);
+  W.put(&D.off_idz, J.idepth_zero_scaled, n);
+  W.put(&D.off_color, J.color, 8 * n);
+  W.put(&D.off_wt, J.weights, 8 * n);
+  W.put(&D.off_point, J.point, nr);
+  W.put(&D.off_target, J.target, nr);
+  W.put(&D.off_ein, J.energy_in, nr);
+  int *flags = (int *)W.reserve(&D.off_flags, nr);
+  for (size_t r = 0; r < nr; r++) flags[r] = J.state_in[r] | (J.fix_linearization && J.is_new[r] ? 256 : 0);
+}
+
+int linearize_launch(dsm_context *ctx, int n_jobs, int max_res, const LinJob *dev_jobs, const float *dev_stage, float *out, int w, int h,
+                     const dsm_linearize_params &params) {
+  const lin::Settings S{params.huber_th, params.outlier_th_sum_component, params.scale_idepth, params.scale_f, params.scale_c};
+  hipLaunchKernelGGL(linearize_kernel, dim3((max_res + kResPerBlock - 1) / kResPerBlock, n_jobs), dim3(64 * kWavesPerBlock), 0, ctx->stream,
+                     dev_jobs, dev_stage, out, w, h, S, params.zero_jab_a != 0, params.zero_jab_b != 0);
+  DSM_HIP(hipGetLastError());
+  return DSM_OK;
+}
+
+void linearize_unpack(const dsm_linearize_job &J, const float *ho, long long o_head, long long o_cpt, long long o_proj, long long o_J) {
+  for (int r = 0; r < J.n_res; r++) {
+    const float *q = ho + o_head + (size_t)kHeadWords * r;
+    unsigned word;
+    memcpy(&word, q, 4);
+    const int state = word & 0xff;
+    J.new_state[r] = (unsigned char)state, J.new_energy[r] = q[1], J.new_energy_with_outlier[r] = q[2];
+    if (J.fix_linearization) {
+      if (J.keep) J.keep[r] = (unsigned char)(word >> 8);
+      if (J.rel_bs) J.rel_bs[r] = q[3];
+    }
+    if (state == lin::RES_OOB) continue; // L8
+    if (o_cpt >= 0) memcpy(J.center_projected_to + (size_t)3 * r, ho + o_cpt + (size_t)3 * r, 12);
+    if (o_proj >= 0) memcpy(J.projected_to + (size_t)16 * r, ho + o_proj + (size_t)16 * r, 64);
+    if (o_J >= 0) memcpy(J.J_out + (size_t)lin::J_FLOATS * r, ho + o_J + (size_t)lin::J_FLOATS * r, 4 * lin::J_FLOATS);
+  }
+}
+
+} // namespace dsm
 
 extern "C" int dsm_linearize_residuals_batch(dsm_context *ctx, int n_jobs, const dsm_linearize_job *jobs, const dsm_linearize_params *params) {
   size_t res = 0;
-  int rc = check_jobs(ctx, n_jobs, jobs, params, &res);
+  std::vector<const dsm_linearize_job *> list;
+  for (int j = 0; jobs && j < n_jobs; j++) list.push_back(jobs + j);
+  int rc = linearize_check_jobs("dsm_linearize_residuals_batch", ctx, n_jobs, jobs ? list.data() : nullptr, params, &res);
   if (rc) return rc;
   if (res) {
     // staged [job table | the six precalc tables, frame_energy_th, the point arrays and the residual arrays of every job], read back
     // [head of every job | per job, as asked for: centre, projections, rows]
     size_t words = 0;
-    for (int j = 0; j < n_jobs; j++) {
-      const size_t nf = jobs[j].n_frames;
-      words += 27 * nf * nf + nf + 21 * (size_t)jobs[j].n_pts + 4 * (size_t)jobs[j].n_res;
-    }
+    for (int j = 0; j < n_jobs; j++) words += linearize_stage_words(jobs[j]);
     CallArena A;
     const size_t o_jobs = A.in.take(sizeof(LinJob) * n_jobs), o_stage = A.in.take(4 * words);
     std::vector<long long> o_head(n_jobs), o_cpt(n_jobs, -1), o_proj(n_jobs, -1), o_J(n_jobs, -1);
@@ -187,61 +238,19 @@ extern "C" int dsm_linearize_residuals_batch(dsm_context *ctx, int n_jobs, const
     WordPacker W{A.host_in<float>(o_stage)};
     int max_res = 0;
     for (int j = 0; j < n_jobs; j++) {
-      const dsm_linearize_job &J = jobs[j];
-      const size_t nf = J.n_frames, n = J.n_pts, nr = J.n_res;
       LinJob &D = hj[j];
       memset(&D, 0, sizeof D);
-      for (size_t f = 0; f < nf; f++) D.plane[f] = J.window->plane(J.window->find(J.frame_ids[f]));
-      D.fx = J.cam[0], D.fy = J.cam[1], D.cx = J.cam[2], D.cy = J.cam[3], D.fxi = J.cam_inv[0], D.fyi = J.cam_inv[1];
-      D.n_frames = J.n_frames, D.n_res = J.n_res, D.fix = J.fix_linearization != 0;
       D.o_head = o_head[j], D.o_cpt = o_cpt[j], D.o_proj = o_proj[j], D.o_J = o_J[j];
-      W.put(&D.off_R0, J.pre_RTll_0, 9 * nf * nf);
-      W.put(&D.off_t0, J.pre_tTll_0, 3 * nf * nf);
-      W.put(&D.off_M, J.pre_KRKiTll, 9 * nf * nf);
-      W.put(&D.off_Kt, J.pre_KtTll, 3 * nf * nf);
-      W.put(&D.off_aff, J.pre_aff_mode, 2 * nf * nf);
-      W.put(&D.off_b0, J.pre_b0_mode, nf * nf);
-      W.put(&D.off_eth, J.frame_energy_th, nf);
-      W.put(&D.off_host, J.host, n);
-      W.put(&D.off_u, J.u, n);
-      W.put(&D.off_v, J.v, n);
-      W.put(&D.off_id, J.idepth_scaled, n);
-      W.put(&D.off_idz, J.idepth_zero_scaled, n);
-      W.put(&D.off_color, J.color, 8 * n);
-      W.put(&D.off_wt, J.weights, 8 * n);
-      W.put(&D.off_point, J.point, nr);
-      W.put(&D.off_target, J.target, nr);
-      W.put(&D.off_ein, J.energy_in, nr);
-      int *flags = (int *)W.reserve(&D.off_flags, nr);
-      for (size_t r = 0; r < nr; r++) flags[r] = J.state_in[r] | (J.fix_linearization && J.is_new[r] ? 256 : 0);
-      max_res = std::max(max_res, J.n_res);
+      linearize_stage(jobs[j], D, W);
+      max_res = std::max(max_res, jobs[j].n_res);
     }
     if ((rc = A.upload())) return rc;
-    const lin::Settings S{params->huber_th, params->outlier_th_sum_component, params->scale_idepth, params->scale_f, params->scale_c};
-    hipLaunchKernelGGL(linearize_kernel, dim3((max_res + kResPerBlock - 1) / kResPerBlock, n_jobs), dim3(64 * kWavesPerBlock), 0, ctx->stream,
-                       A.dev_in<const LinJob>(o_jobs), A.dev_in<const float>(o_stage), A.dev_out<float>(0), jobs[0].window->w, jobs[0].window->h,
-                       S, params->zero_jab_a != 0, params->zero_jab_b != 0);
-    DSM_HIP(hipGetLastError());
+    if ((rc = linearize_launch(ctx, n_jobs, max_res, A.dev_in<const LinJob>(o_jobs), A.dev_in<const float>(o_stage), A.dev_out<float>(0),
+                               jobs[0].window->w, jobs[0].window->h, *params)))
+      return rc;
     if ((rc = A.fetch(A.out.used))) return rc;
     const float *ho = A.host_out<float>(0);
-    for (int j = 0; j < n_jobs; j++) {
-      const dsm_linearize_job &J = jobs[j];
-      for (int r = 0; r < J.n_res; r++) {
-        const float *q = ho + o_head[j] + (size_t)kHeadWords * r;
-        unsigned word;
-        memcpy(&word, q, 4);
-        const int state = word & 0xff;
-        J.new_state[r] = (unsigned char)state, J.new_energy[r] = q[1], J.new_energy_with_outlier[r] = q[2];
-        if (J.fix_linearization) {
-          if (J.keep) J.keep[r] = (unsigned char)(word >> 8);
-          if (J.rel_bs) J.rel_bs[r] = q[3];
-        }
-        if (state == lin::RES_OOB) continue; // L8
-        if (o_cpt[j] >= 0) memcpy(J.center_projected_to + (size_t)3 * r, ho + o_cpt[j] + (size_t)3 * r, 12);
-        if (o_proj[j] >= 0) memcpy(J.projected_to + (size_t)16 * r, ho + o_proj[j] + (size_t)16 * r, 64);
-        if (o_J[j] >= 0) memcpy(J.J_out + (size_t)lin::J_FLOATS * r, ho + o_J[j] + (size_t)lin::J_FLOATS * r, 4 * lin::J_FLOATS);
-      }
-    }
+    for (int j = 0; j < n_jobs; j++) linearize_unpack(jobs[j], ho, o_head[j], o_cpt[j], o_proj[j], o_J[j]);
   }
   for (int j = 0; j < n_jobs; j++) linearize_job_summary(jobs[j], *params); // B1, B2
   return DSM_OK;

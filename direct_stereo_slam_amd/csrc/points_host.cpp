@@ -2,10 +2,11 @@
 // their jobs: activation (dsm_activate_points_host), optimisation of immature points
 // (dsm_optimize_immature_points_host, section 13), tracing (dsm_trace_points_host, section 14) and, before them all, the selection of
 // the pixels that become points (dsm_select_pixels_host, section 15); and the linearisation of the window optimisation's active
-// residuals (dsm_linearize_residuals_host, section 16).  The host forms are what the CPU suite checks against the numpy
+// residuals (dsm_linearize_residuals_host, section 16) with the accumulation of the Hessian and Schur terms over them
+// (dsm_window_hessian_host, section 17).  The host forms are what the CPU suite checks against the numpy
 // checkers and what the device forms (distmap_kernels.hip, immature_kernels.hip, trace_kernels.hip, select_kernels.hip,
-// linearize_kernels.hip) must equal bit for bit: the arithmetic is shared through point_math.hpp, immature_math.hpp, trace_math.hpp,
-// select_math.hpp and linearize_math.hpp, the job rules through the *_error functions below.  Plain C++; no device code.
+// linearize_kernels.hip, hessian_kernels.hip) must equal bit for bit: the arithmetic is shared through point_math.hpp, immature_math.hpp,
+// trace_math.hpp, select_math.hpp, linearize_math.hpp and hessian_math.hpp, the job rules through the *_error functions below.  Plain C++; no device code.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -14,6 +15,7 @@
 
 #include "dsm_internal.hpp"
 #include "immature_math.hpp"
+#include "hessian_math.hpp"
 #include "linearize_math.hpp"
 #include "select_math.hpp"
 #include "trace_math.hpp"
@@ -148,6 +150,126 @@ void linearize_job_summary(const dsm_linearize_job &J, const dsm_linearize_param
     th *= S.ow * S.ow;
   }
   *J.new_frame_energy_th_out = th;
+}
+
+// V of DESIGN.md section 17, after linearize_job_error has passed
+const char *hessian_job_error(const dsm_hessian_job &J) {
+  const dsm_linearize_job &L = J.lin;
+  if (!J.ad_host || !J.ad_target) return "NULL ad_host or ad_target";
+  if (!J.H_A || !J.b_A || !J.H_sc || !J.b_sc) return "NULL H_A, b_A, H_sc or b_sc";
+  const size_t n_ad = (size_t)L.n_frames * L.n_frames * 64;
+  for (size_t i = 0; i < n_ad; i++)
+    if (!std::isfinite(J.ad_host[i]) || !std::isfinite(J.ad_target[i])) return "a non-finite ad_host or ad_target";
+  const float *per_point[] = {J.prior, J.delta, J.hdd_lin, J.bd_lin};
+  for (const float *a : per_point)
+    for (int i = 0; a && i < L.n_pts; i++)
+      if (!std::isfinite(a[i])) return "a non-finite prior, delta, hdd_lin or bd_lin";
+  for (int i = 0; J.hcd_lin && i < 4 * L.n_pts; i++)
+    if (!std::isfinite(J.hcd_lin[i])) return "a non-finite hcd_lin";
+  std::vector<unsigned> seen((size_t)L.n_pts, 0u); // n_frames <= 16: one bit per target
+  for (int r = 0; r < L.n_res; r++) {
+    const unsigned bit = 1u << L.target[r];
+    if (seen[L.point[r]] & bit) return "a point with two residuals against one target";
+    seen[L.point[r]] |= bit;
+  }
+  return nullptr;
+}
+
+namespace {
+// C (M x N) = A (M x K) * B (K x N): every entry the double sum over ascending k, from 0.0.  The k loop is the outer one of a row, so
+// that the compiler may work on the N entries of the row at once; each entry's own order is unchanged.
+template <int M, int K, int N>
+inline void small_mul(const double *A, int lda, const double *B, int ldb, double *C) {
+  for (int i = 0; i < M; i++) {
+    double s[N];
+    for (int j = 0; j < N; j++) s[j] = 0.0;
+    for (int q = 0; q < K; q++) {
+      const double a = A[i * lda + q];
+      for (int j = 0; j < N; j++) s[j] += a * B[q * ldb + j];
+    }
+    for (int j = 0; j < N; j++) C[i * N + j] = s[j];
+  }
+}
+void add_block(double *H, int N, int r0, int c0, const double *C, int m, int n, bool transposed = false) {
+  for (int i = 0; i < m; i++)
+    for (int j = 0; j < n; j++) H[(size_t)(r0 + i) * N + c0 + j] += transposed ? C[j * m + i] : C[i * n + j];
+}
+void mirror_upper(double *H, int N) {
+  for (int i = 0; i < N; i++)
+    for (int j = i + 1; j < N; j++) H[(size_t)j * N + i] = H[(size_t)i * N + j];
+}
+} // namespace
+
+void hessian_stitch(const dsm_hessian_job &J, const double *top, const double *D, const double *E, const double *EB, const double *Hcc,
+                    const double *bc) {
+  const int nf = J.lin.n_frames, N = 4 + 8 * nf;
+  double *HA = J.H_A, *bA = J.b_A, *HS = J.H_sc, *bS = J.b_sc;
+  std::fill(HA, HA + (size_t)N * N, 0.0), std::fill(HS, HS + (size_t)N * N, 0.0);
+  std::fill(bA, bA + N, 0.0), std::fill(bS, bS + N, 0.0);
+  double C[64], Mh[64], Mt[64];
+  // the transposes of every ad_host / ad_target block, once: the products below then read both factors row by row
+  const size_t n_blocks = (size_t)nf * nf;
+  std::vector<double> adT(2 * n_blocks * 64);
+  for (size_t p = 0; p < n_blocks; p++)
+    for (int i = 0; i < 8; i++)
+      for (int j = 0; j < 8; j++)
+        adT[p * 64 + 8 * j + i] = J.ad_host[p * 64 + 8 * i + j], adT[(n_blocks + p) * 64 + 8 * j + i] = J.ad_target[p * 64 + 8 * i + j];
+  const double *hostT = adT.data(), *targetT = adT.data() + n_blocks * 64;
+  for (int h = 0; h < nf; h++) // H_A, b_A: pairs in (h, t) order; a frame is no target of its own points
+    for (int t = 0; t < nf; t++) {
+      if (t == h) continue;
+      const double *A = top + (size_t)(h * nf + t) * 169, *Ah = J.ad_host + (size_t)(h * nf + t) * 64, *At = J.ad_target + (size_t)(h * nf + t) * 64;
+      const double *AhT = hostT + (size_t)(h * nf + t) * 64, *AtT = targetT + (size_t)(h * nf + t) * 64;
+      const int ih = 4 + 8 * h, it = 4 + 8 * t;
+      for (int a = 0; a < 4; a++) {
+        for (int b = 0; b < 4; b++) HA[(size_t)a * N + b] += A[a * 13 + b];
+        bA[a] += A[a * 13 + 12];
+      }
+      small_mul<4, 8, 8>(A + 4, 13, AhT, 8, C), add_block(HA, N, 0, ih, C, 4, 8);
+      small_mul<4, 8, 8>(A + 4, 13, AtT, 8, C), add_block(HA, N, 0, it, C, 4, 8);
+      small_mul<8, 8, 8>(Ah, 8, A + 4 * 13 + 4, 13, Mh), small_mul<8, 8, 8>(At, 8, A + 4 * 13 + 4, 13, Mt);
+      small_mul<8, 8, 8>(Mh, 8, AhT, 8, C), add_block(HA, N, ih, ih, C, 8, 8);
+      small_mul<8, 8, 8>(Mh, 8, AtT, 8, C), add_block(HA, N, ih, it, C, 8, 8);
+      small_mul<8, 8, 8>(Mt, 8, AhT, 8, C), add_block(HA, N, it, ih, C, 8, 8);
+      small_mul<8, 8, 8>(Mt, 8, AtT, 8, C), add_block(HA, N, it, it, C, 8, 8);
+      small_mul<8, 8, 1>(Ah, 8, A + 4 * 13 + 12, 13, C), add_block(bA, 1, ih, 0, C, 8, 1);
+      small_mul<8, 8, 1>(At, 8, A + 4 * 13 + 12, 13, C), add_block(bA, 1, it, 0, C, 8, 1);
+    }
+  mirror_upper(HA, N);
+  for (int c = 0; c < 4; c++) { // H_sc, b_sc
+    for (int d = 0; d < 4; d++) HS[(size_t)c * N + d] = Hcc[4 * c + d];
+    bS[c] = bc[c];
+  }
+  for (int h = 0; h < nf; h++)
+    for (int t1 = 0; t1 < nf; t1++) {
+      if (t1 == h) continue;
+      const size_t p1 = (size_t)(h * nf + t1);
+      const double *Ah1 = J.ad_host + p1 * 64, *At1 = J.ad_target + p1 * 64;
+      const int ih = 4 + 8 * h, i1 = 4 + 8 * t1;
+      small_mul<8, 8, 4>(Ah1, 8, E + p1 * 32, 4, C), add_block(HS, N, 0, ih, C, 4, 8, true);
+      small_mul<8, 8, 4>(At1, 8, E + p1 * 32, 4, C), add_block(HS, N, 0, i1, C, 4, 8, true);
+      small_mul<8, 8, 1>(Ah1, 8, EB + p1 * 8, 1, C), add_block(bS, 1, ih, 0, C, 8, 1);
+      small_mul<8, 8, 1>(At1, 8, EB + p1 * 8, 1, C), add_block(bS, 1, i1, 0, C, 8, 1);
+      for (int t2 = 0; t2 < nf; t2++) {
+        if (t2 == h) continue;
+        const size_t p2 = (size_t)(h * nf + t2);
+        const double *Ah2T = hostT + p2 * 64, *At2T = targetT + p2 * 64, *Dk = D + (p1 * nf + t2) * 64;
+        const int i2 = 4 + 8 * t2;
+        small_mul<8, 8, 8>(Ah1, 8, Dk, 8, Mh), small_mul<8, 8, 8>(At1, 8, Dk, 8, Mt);
+        small_mul<8, 8, 8>(Mh, 8, Ah2T, 8, C), add_block(HS, N, ih, ih, C, 8, 8);
+        small_mul<8, 8, 8>(Mh, 8, At2T, 8, C), add_block(HS, N, ih, i2, C, 8, 8);
+        small_mul<8, 8, 8>(Mt, 8, Ah2T, 8, C), add_block(HS, N, i1, ih, C, 8, 8);
+        small_mul<8, 8, 8>(Mt, 8, At2T, 8, C), add_block(HS, N, i1, i2, C, 8, 8);
+      }
+    }
+  mirror_upper(HS, N);
+  const size_t n2 = (size_t)nf * nf;
+  if (J.acc_top) memcpy(J.acc_top, top, 8 * n2 * 169);
+  if (J.acc_D) memcpy(J.acc_D, D, 8 * n2 * nf * 64);
+  if (J.acc_E) memcpy(J.acc_E, E, 8 * n2 * 32);
+  if (J.acc_EB) memcpy(J.acc_EB, EB, 8 * n2 * 8);
+  if (J.acc_Hcc) memcpy(J.acc_Hcc, Hcc, 8 * 16);
+  if (J.acc_bc) memcpy(J.acc_bc, bc, 8 * 4);
 }
 } // namespace dsm
 
@@ -660,5 +782,96 @@ extern "C" int dsm_linearize_residuals_host(int w, int h, const dsm_linearize_jo
     }
   }
   dsm::linearize_job_summary(J, *params); // B1, B2
+  return DSM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// accumulateAF_MT / accumulateSCF_MT of FrontEnd::optimize (dso_helpers/FrontEndOptimize.cpp:332-486) after linearizeAll, as one thread
+// runs them: the linearisation above, then per active residual its record (A1, A2), the pair accumulators in residual order (A3, P1),
+// the points' sums (S1, S2), the Schur accumulators in point order (S3) and the stitch (T1).  DESIGN.md section 17; the expressions
+// are hessian_math.hpp, shared with the device kernels.
+// ---------------------------------------------------------------------------------------------
+extern "C" int dsm_window_hessian_host(int w, int h, const dsm_hessian_job *job, const float *const *frame_I, const dsm_linearize_params *params) {
+  using namespace dsm::hes;
+  auto fail = [](const char *msg) { return refuse("dsm_window_hessian_host", msg); };
+  if (w < 8 || h < 8 || !job || !frame_I) return fail("bad argument");
+  if (const char *e = dsm::linearize_params_error(params)) return fail(e);
+  if (const char *e = dsm::linearize_job_error(job->lin)) return fail(e);
+  if (const char *e = dsm::hessian_job_error(*job)) return fail(e);
+  const dsm_hessian_job &J = *job;
+  for (int f = 0; f < J.lin.n_frames; f++)
+    if (!frame_I[f]) return fail("NULL frame");
+  const int nf = J.lin.n_frames, np = J.lin.n_pts, nr = J.lin.n_res;
+  dsm_linearize_job L = J.lin;
+  std::vector<float> rows;
+  if (!L.J_out) rows.resize((size_t)nr * dsm::lin::J_FLOATS), L.J_out = rows.data();
+  const int rc = dsm_linearize_residuals_host(w, h, &L, frame_I, params);
+  if (rc) return rc;
+  const size_t n2 = (size_t)nf * nf;
+  std::vector<double> top(n2 * 169, 0.0), D(n2 * nf * 64, 0.0), E(n2 * 32, 0.0), EB(n2 * 8, 0.0), Hcc(16, 0.0), bc(4, 0.0);
+  std::vector<float> rec((size_t)nr * R_FLOATS), prec((size_t)np * P_FLOATS, 0.0f);
+  std::vector<unsigned char> act((size_t)nr);
+  std::vector<int> start((size_t)np + 1, 0), list((size_t)nr), n_act((size_t)np, 0);
+  for (int r = 0; r < nr; r++) start[L.point[r] + 1]++;
+  for (int p = 0; p < np; p++) start[p + 1] += start[p];
+  {
+    std::vector<int> at(start.begin(), start.end() - 1);
+    for (int r = 0; r < nr; r++) list[at[L.point[r]]++] = r; // ascending within a point
+  }
+  for (int r = 0; r < nr; r++) { // A0-A3, P1
+    act[r] = L.state_in[r] != DSM_RES_OOB && L.new_state[r] == DSM_RES_IN;
+    if (J.active) J.active[r] = act[r];
+    if (!act[r]) continue;
+    float *q = rec.data() + (size_t)r * R_FLOATS;
+    residual_record(L.J_out + (size_t)r * dsm::lin::J_FLOATS, q);
+    if (J.JpJdF) memcpy(J.JpJdF + (size_t)8 * r, q + R_JP, 32);
+    double *T = top.data() + (size_t)(L.host[L.point[r]] * nf + L.target[r]) * 169;
+    for (int a = 0; a < kTop; a++)
+      for (int b = a; b < kTop; b++) T[a * kTop + b] += (double)top_term(q, a, b);
+  }
+  for (size_t pair = 0; pair < n2; pair++)
+    for (int a = 0; a < kTop; a++)
+      for (int b = a + 1; b < kTop; b++) top[pair * 169 + b * kTop + a] = top[pair * 169 + a * kTop + b];
+  for (int p = 0; p < np; p++) { // S1, S2
+    float *P = prec.data() + (size_t)p * P_FLOATS;
+    for (int k = start[p]; k < start[p + 1]; k++)
+      if (act[list[k]]) point_add(rec.data() + (size_t)list[k] * R_FLOATS, P[P_BD], P[P_HDD], P[P_HCD], P[P_HCD + 1], P[P_HCD + 2], P[P_HCD + 3]), n_act[p]++;
+    point_finish(P, n_act[p], J.prior ? J.prior[p] : 0.0f, J.delta ? J.delta[p] : 0.0f, J.hdd_lin ? J.hdd_lin[p] : 0.0f,
+                 J.bd_lin ? J.bd_lin[p] : 0.0f, J.hcd_lin ? J.hcd_lin + 4 * p : nullptr, J.shift_prior_to_zero != 0);
+    if (J.hdd_acc) J.hdd_acc[p] = P[P_HDD];
+    if (J.bd_acc) J.bd_acc[p] = P[P_BD];
+    if (J.hcd_acc) memcpy(J.hcd_acc + 4 * p, P + P_HCD, 16);
+    if (J.hdi) J.hdi[p] = P[P_HDI];
+    if (J.bd_sum) J.bd_sum[p] = P[P_BDSUM];
+    if (J.idepth_hessian) J.idepth_hessian[p] = P[P_IDH];
+  }
+  for (int p = 0; p < np; p++) { // S3
+    if (!n_act[p]) continue;
+    const float *P = prec.data() + (size_t)p * P_FLOATS;
+    const int hst = L.host[p];
+    for (int c = 0; c < 4; c++) {
+      for (int d = 0; d < 4; d++) Hcc[4 * c + d] += (double)term_Hcc(P, c, d);
+      bc[c] += (double)term_bc(P, c);
+    }
+    for (int k1 = start[p]; k1 < start[p + 1]; k1++) {
+      const int r1 = list[k1];
+      if (!act[r1]) continue;
+      const float *j1 = rec.data() + (size_t)r1 * R_FLOATS + R_JP;
+      const size_t p1 = (size_t)(hst * nf + L.target[r1]);
+      for (int a = 0; a < 8; a++) {
+        for (int c = 0; c < 4; c++) E[p1 * 32 + 4 * a + c] += (double)term_E(P, j1, a, c);
+        EB[p1 * 8 + a] += (double)term_EB(P, j1, a);
+      }
+      for (int k2 = start[p]; k2 < start[p + 1]; k2++) {
+        const int r2 = list[k2];
+        if (!act[r2]) continue;
+        const float *j2 = rec.data() + (size_t)r2 * R_FLOATS + R_JP;
+        double *Dk = D.data() + (p1 * nf + L.target[r2]) * 64;
+        for (int a = 0; a < 8; a++)
+          for (int b = 0; b < 8; b++) Dk[8 * a + b] += (double)term_D(P, j1, j2, a, b);
+      }
+    }
+  }
+  dsm::hessian_stitch(J, top.data(), D.data(), E.data(), EB.data(), Hcc.data(), bc.data());
   return DSM_OK;
 }

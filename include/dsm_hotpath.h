@@ -1400,6 +1400,52 @@ int dsm_linearize_residuals_batch(dsm_context *ctx, int n_jobs, const dsm_linear
  * plane of frame_ids[i].  The CPU baseline of tools/linearize_timing.py and a checker that needs no device. */
 int dsm_linearize_residuals_host(int w, int h, const dsm_linearize_job *job, const float *const *frame_I, const dsm_linearize_params *params);
 
+/* ---- Hessian and Schur accumulation of the window optimisation ---------------------------------------------------
+ * replaces, for the active residuals, what FrontEnd::optimize (dso_helpers/FrontEndOptimize.cpp:332-486) does between linearizeAll
+ * and the solve of solveSystem: accumulateAF_MT / accumulateSCF_MT, that is AccumulatedTopHessianSSE::addPoint and
+ * AccumulatedSCHessianSSE::addPoint per point and their stitchDouble (UPSTREAM-DSO, parity unpinned), as the rules A0-A3, P1, S1-S3
+ * and T1 of DESIGN.md section 17 state them.  One call linearises (lin, section 16, every output with the same meaning) and
+ * accumulates; the Jacobian rows stay on the device unless lin.J_out asks for them.  The call is stateless: a rejected trial step
+ * discards its accumulators.  Products are float32 without contraction, the accumulators and the stitch are double. */
+#define DSM_HESSIAN_TOP 13 /* one pair's accumulator: C (4), xi (6), a, b, r */
+
+/* One window: lin and what the accumulation reads and returns on top of it; n = lin.n_frames, N = 4 + 8 n. */
+typedef struct dsm_hessian_job {
+  dsm_linearize_job lin;      /* J_out is normally NULL */
+  const double *ad_host;      /* n * n * 8 * 8, [host][target], row-major: EF->adHost */
+  const double *ad_target;    /* n * n * 8 * 8: EF->adTarget */
+  const float *prior;         /* the next seven: optional (NULL: zeros).  n_pts: priorF */
+  const float *delta;         /* n_pts: deltaF */
+  const float *hdd_lin;       /* n_pts: Hdd_accLF */
+  const float *bd_lin;        /* n_pts: bd_accLF */
+  const float *hcd_lin;       /* n_pts * 4: Hcd_accLF */
+  int shift_prior_to_zero;    /* solveSystemF passes 1: bd_sum takes prior * delta */
+  double *H_A, *b_A;          /* N * N (full, symmetric) and N: accumulateAF after stitchDouble */
+  double *H_sc, *b_sc;        /* N * N and N: accumulateSCF after stitchDouble */
+  double *acc_top;            /* the rest: optional (NULL).  n * n * 13 * 13, full: acc[tid][h + n t] of AccumulatedTopHessianSSE */
+  double *acc_D;              /* n * n * n * 8 * 8 as [host][t1][t2] */
+  double *acc_E;              /* n * n * 8 * 4 */
+  double *acc_EB;             /* n * n * 8 */
+  double *acc_Hcc;            /* 16 */
+  double *acc_bc;             /* 4 */
+  unsigned char *active;      /* n_res: 1 = the residual contributes (A0) */
+  float *JpJdF;               /* n_res * 8, written for active residuals only: what resubstituteFPt reads */
+  float *hdd_acc, *bd_acc;    /* n_pts each: Hdd_accAF, bd_accAF */
+  float *hcd_acc;             /* n_pts * 4: Hcd_accAF */
+  float *hdi, *bd_sum, *idepth_hessian; /* n_pts each: HdiF, bdSumF, idepth_hessian (all 0 for a point without an active residual) */
+} dsm_hessian_job;
+
+/* accumulateAF_MT + accumulateSCF_MT after linearizeAll for every job: one staged copy through the context's arena, the launch of
+ * dsm_linearize_residuals_batch and four more, one read-back of the heads, the accumulators and the optional arrays; the stitch (T1)
+ * and B1 / B2 run on the host.  A job's results do not depend on the other jobs of the call or on the launch geometry.  Validation is
+ * all or nothing, before anything is enqueued: DSM_ERR_INVALID for everything dsm_linearize_residuals_batch refuses, a NULL ad_host,
+ * ad_target, H_A, b_A, H_sc or b_sc, a non-finite ad_*, prior, delta or *_lin, and a point with two residuals against one target.
+ * n_res == 0, n_pts == 0 and a job of one frame are valid and give zero matrices. */
+int dsm_window_hessian_batch(dsm_context *ctx, int n_jobs, const dsm_hessian_job *jobs, const dsm_linearize_params *params);
+/* The same for one job as plain sequential loops on the host planes frame_I (as dsm_linearize_residuals_host; job->lin.window is
+ * ignored).  The CPU baseline of tools/hessian_timing.py and a checker that needs no device. */
+int dsm_window_hessian_host(int w, int h, const dsm_hessian_job *job, const float *const *frame_I, const dsm_linearize_params *params);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.
