@@ -452,9 +452,9 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
     };
     {
       // Template stream: entry (start + tid) of the list = one coalesced 16-byte load per lane from a wave-uniform base (SGPR pair)
-      // plus this thread's constant byte offset -- no per-point index arithmetic.  Entries past the chunk (the loop prefetches up to
-      // three trips ahead) or past the list are never used: their lanes are masked, and an entry past the list reads as zeros (the
-      // buffer descriptor checks the range).
+      // plus this thread's constant byte offset -- no per-point index arithmetic.  The two-point loop fetches the entries of the wave's
+      // trips and one more (its last steady trip prefetches for a trip that is peeled), the one-point loop two more; such an entry is
+      // never used: its lanes are masked, and an entry past the list reads as zeros (the buffer descriptor checks the range).
       const unsigned voff = 16u * (unsigned)tid;
       const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)c.pts, 0, 16 * n, 0x00020000);
       auto load_pt = [=](int start) {
@@ -470,6 +470,17 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
         if (!trip) return 0ull;
         return mask_sgpr(tail ? (lmask)__builtin_amdgcn_sicmp(tid, n - start, kSLT) : full);
       };
+      // This wave's trip bound: the trips in which one of its lanes holds a point of the list, at least one (a wave wholly past the
+      // list runs one masked trip: no zero-trip case) -- P in every chunk but the list's last, where the loop used to run P trips
+      // whatever the chunk held.  Wave-uniform (an SGPR).  stage_b is still called for this thread's points k = 0 .. Pw - 1 in that
+      // order and is the only place the accumulators, E and the counts are added to; what the trips from Pw on added were and_f(.., 0)
+      // to E, popcount(0) to the counts and fma(+-0, x, acc) to accumulators that are never -0: the bits stay what they were.
+      int Pw = P;
+      if (tail) {
+        const int left = n - chunk_start - (__builtin_amdgcn_readfirstlane(tid) & ~63); // points from this wave's first lane on
+        const int trips = (left + kThreads - 1) / kThreads;                              // (kThreads is a power of two: a shift)
+        Pw = left <= 0 ? 1 : trips < P ? trips : P;
+      }
       const int i = chunk_start;
       const fvec4 p0 = load_pt(i);
       if (DEEP) {
@@ -497,15 +508,22 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
         Taps Ta, Tb;
         stage_a(p0, listed(i, true), Wa, Ta);
         int ia = i + kThreads; // start of the entries held in ea (eb: ia + kThreads)
-        for (int k = 0; k < P; k += 2) {
-          stage_a(ea, listed(ia, k + 1 < P), Wb, Tb); // point k+1
+        // The last trip is peeled: it has no point k+2 to warp and nothing to fetch.  (As a trip of the loop it made the call under an
+        // empty lane mask -- 18 warp operations, the quotients, the compares and four gathers at the safe texel, P + 1 warp stages for
+        // P points -- and loaded two entries past the chunk.)  The steady trip is what it was.
+        int k = 0;
+        for (; k + 2 < Pw; k += 2) {
+          stage_a(ea, listed(ia, true), Wb, Tb); // point k+1
           ea = load_pt(ia + 2 * kThreads);
           stage_b(Wa, Ta); // point k
-          stage_a(eb, listed(ia + kThreads, k + 2 < P), Wa, Ta); // point k+2
-          eb = load_pt(ia + 3 * kThreads);
-          stage_b(Wb, Tb); // point k+1 (masked when k+1 == P)
+          stage_a(eb, listed(ia + kThreads, true), Wa, Ta); // point k+2
+          eb = load_pt(ia + 3 * kThreads); // (the last steady trip's is entry Pw, or Pw + 1 at odd Pw: the one entry fetched and not used)
+          stage_b(Wb, Tb); // point k+1
           ia += 2 * kThreads;
         }
+        stage_a(ea, listed(ia, k + 1 < Pw), Wb, Tb); // point k+1 (masked when k+1 == Pw: odd Pw)
+        stage_b(Wa, Ta); // point k
+        stage_b(Wb, Tb); // point k+1
       } else {
         // Template stream prefetched one point ahead.
         int i2 = i + kThreads;
@@ -514,10 +532,12 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
         Warped Wc;
         Taps Tc;
         stage_a(p0, listed(i, true), Wc, Tc);
-        for (int k = 0; k < P; k++) {
+        // Pw trips; the last one's stage A (point Pw) runs under an empty lane mask.  Not peeled as the two-point loop's last trip is: with
+        // a second stage B behind the loop the kernels of five waves per SIMD spill (eval_kernel<0 / 2, false, false, *>: 8 and 12 bytes).
+        for (int k = 0; k < Pw; k++) {
           // stage A for point k+1 (its template entry was prefetched one iteration ago)
           const fvec4 p = p_next;
-          const lmask in_next = listed(i2, k + 1 < P);
+          const lmask in_next = listed(i2, k + 1 < Pw);
           const int i3 = i2 + kThreads;
           p_next = load_pt(i3);
           Warped Wn;
