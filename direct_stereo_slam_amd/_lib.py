@@ -223,6 +223,14 @@ class HessianJob(C.Structure):
     ]
 
 
+class SolveJob(C.Structure):
+    _fields_ = [
+        ("hes", HessianJob), ("H_L", c_double_p), ("b_L", c_double_p), ("H_M", c_double_p), ("b_M", c_double_p), ("delta_x", c_double_p),
+        ("lambda_", C.c_double), ("n_null", C.c_int), ("null_basis", c_double_p), ("null_pinv", c_double_p),
+        ("x", c_double_p), ("step", c_float_p), ("flags", c_int_p), ("last_HS", c_double_p), ("last_bS", c_double_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -476,6 +484,8 @@ SYMBOLS = {
     "dsm_linearize_residuals_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(LinearizeJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams)]),
     "dsm_window_hessian_batch": (C.c_int, [_vp, C.c_int, C.POINTER(HessianJob), C.POINTER(LinearizeParams)]),
     "dsm_window_hessian_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(HessianJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams)]),
+    "dsm_window_solve_batch": (C.c_int, [_vp, C.c_int, C.POINTER(SolveJob), C.POINTER(LinearizeParams)]),
+    "dsm_window_solve_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(SolveJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams)]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

@@ -187,7 +187,13 @@ const char *linearize_job_error(const dsm_linearize_job &J);
 // points_host.cpp: B1 and B2 of DESIGN.md section 16 from the job's filled new_energy / new_energy_with_outlier arrays, for both forms
 void linearize_job_summary(const dsm_linearize_job &J, const dsm_linearize_params &S);
 // points_host.cpp: what both forms of the Hessian call refuse beyond linearize_job_error
-const char *hessian_job_error(const dsm_hessian_job &J);
+// (stitched_required false: the solve call, where H_A, b_A, H_sc and b_sc are optional)
+const char *hessian_job_error(const dsm_hessian_job &J, bool stitched_required = true);
+// solve_host.cpp: what both forms of the solve call refuse beyond that
+const char *solve_job_error(const dsm_solve_job &J);
+// points_host.cpp: the copies of the optional raw accumulators alone
+void hessian_copy_raw(const dsm_hessian_job &J, const double *top, const double *D, const double *E, const double *EB, const double *Hcc,
+                      const double *bc);
 // points_host.cpp: T1 of section 17 -- H_A, b_A, H_sc, b_sc of the job from its raw accumulators, for both forms; then the copies of
 // the optional raw accumulators
 void hessian_stitch(const dsm_hessian_job &J, const double *top, const double *D, const double *E, const double *EB, const double *Hcc,

@@ -24,7 +24,7 @@
 #include <string>
 #include <vector>
 
-#include "linearize_launch.hpp"
+#include "hessian_launch.hpp"
 
 #include "hessian_math.hpp"
 
@@ -197,63 +197,88 @@ extern "C" int dsm_window_hessian_batch(dsm_context *ctx, int n_jobs, const dsm_
   if (rc) return rc;
   for (int j = 0; j < n_jobs; j++)
     if (const char *e = hessian_job_error(jobs[j])) return bad(e);
-
-  // staged [linearize job table | job table | per job: the linearisation's inputs, the index lists, the optional per-point inputs],
-  // device only [per job: rows (unless lin.J_out), records, slot table], read back [heads | per job: point results, accumulators |
-  // per job, as asked for: JpJdF, centre, projections, rows]
   CallArena A;
+  HesPlan P;
+  for (int j = 0; j < n_jobs; j++) P.jobs.push_back(&jobs[j]);
+  hessian_layout(P, A);
+  if ((rc = A.bind(ctx))) return rc;
+  hessian_stage(P, A);
+  if ((rc = A.upload())) return rc;
+  if ((rc = hessian_launch(ctx, P, A, *params))) return rc;
+  DSM_HIP(hipGetLastError());
+  if ((rc = A.fetch(A.out.used))) return rc;
+  hessian_unpack(P, A, *params);
+  return DSM_OK;
+}
+
+namespace dsm {
+
+// staged [linearize job table | job table | per job: the linearisation's inputs, the index lists, the optional per-point inputs],
+// device only [per job: rows (unless lin.J_out), records, slot table], read back [heads | per job: point results, accumulators |
+// per job, as asked for: JpJdF, centre, projections, rows]; a lean plan keeps the point results and the accumulators of a job that
+// asks for none of them in the device-only part
+void hessian_layout(HesPlan &P, CallArena &A) {
+  const int n_jobs = (int)P.jobs.size();
+  auto job = [&P](int j) -> const dsm_hessian_job & { return *P.jobs[j]; };
   size_t words = 0;
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_hessian_job &H = jobs[j];
+    const dsm_hessian_job &H = job(j);
     const size_t nf = H.lin.n_frames, np = H.lin.n_pts, nr = H.lin.n_res;
     words += linearize_stage_words(H.lin) + (nf * nf + 1) + nr + (np + 1) + nr + (nf + 1) + np;
     words += np * ((H.prior != nullptr) + (H.delta != nullptr) + (H.hdd_lin != nullptr) + (H.bd_lin != nullptr) + 4 * (H.hcd_lin != nullptr));
   }
-  const size_t o_lin = A.in.take(sizeof(LinJob) * n_jobs), o_hes = A.in.take(sizeof(HesJob) * n_jobs), o_stage = A.in.take(4 * words);
-  struct Where {
-    size_t rows = 0, rec, slot;                  // bytes into work
-    bool rows_out = false;
-    size_t head, prec, top, D, E, EB, Hcc, bc;   // bytes into out
-    long long jp = -1, cpt = -1, proj = -1, J = -1; // bytes into out; -1: not asked for
-  };
-  std::vector<Where> at(n_jobs);
+  P.o_lin = A.in.take(sizeof(LinJob) * n_jobs), P.o_hes = A.in.take(sizeof(HesJob) * n_jobs), P.o_stage = A.in.take(4 * words);
+  std::vector<HesWhere> &at = P.at;
+  at.assign(n_jobs, HesWhere());
   for (int j = 0; j < n_jobs; j++) {
-    const size_t nf = jobs[j].lin.n_frames, np = jobs[j].lin.n_pts, nr = jobs[j].lin.n_res;
-    Where &w = at[j];
-    w.rows_out = jobs[j].lin.J_out && nr;
+    const size_t nf = job(j).lin.n_frames, np = job(j).lin.n_pts, nr = job(j).lin.n_res;
+    HesWhere &w = at[j];
+    w.rows_out = job(j).lin.J_out && nr;
     if (!w.rows_out) w.rows = A.work.take(4 * lin::J_FLOATS * nr);
     w.rec = A.work.take(4 * hes::R_FLOATS * nr), w.slot = A.work.take(4 * np * nf);
   }
-  for (int j = 0; j < n_jobs; j++) at[j].head = A.out.take(4 * kLinHeadWords * (size_t)jobs[j].lin.n_res);
+  for (int j = 0; j < n_jobs; j++) at[j].head = A.out.take(4 * kLinHeadWords * (size_t)job(j).lin.n_res);
   for (int j = 0; j < n_jobs; j++) {
-    const size_t nf = jobs[j].lin.n_frames, n2 = nf * nf;
-    Where &w = at[j];
-    w.prec = A.out.take(4 * hes::P_FLOATS * (size_t)jobs[j].lin.n_pts);
-    w.top = A.out.take(8 * n2 * 169), w.D = A.out.take(8 * n2 * nf * 64), w.E = A.out.take(8 * n2 * 32), w.EB = A.out.take(8 * n2 * 8);
-    w.Hcc = A.out.take(8 * 16), w.bc = A.out.take(8 * 4);
+    const dsm_hessian_job &H = job(j);
+    const size_t nf = H.lin.n_frames, n2 = nf * nf;
+    HesWhere &w = at[j];
+    const bool prec_out = !P.lean || H.hdd_acc || H.bd_acc || H.hcd_acc || H.hdi || H.bd_sum || H.idepth_hessian;
+    const bool raw_out = !P.lean || H.acc_top || H.acc_D || H.acc_E || H.acc_EB || H.acc_Hcc || H.acc_bc;
+    auto take = [&A](bool out, size_t bytes) {
+      HesSpot s;
+      s.out = out, s.at = (out ? A.out : A.work).take(bytes);
+      return s;
+    };
+    w.prec = take(prec_out, 4 * hes::P_FLOATS * (size_t)H.lin.n_pts);
+    w.top = take(raw_out, 8 * n2 * 169), w.D = take(raw_out, 8 * n2 * nf * 64), w.E = take(raw_out, 8 * n2 * 32), w.EB = take(raw_out, 8 * n2 * 8);
+    w.Hcc = take(raw_out, 8 * 16), w.bc = take(raw_out, 8 * 4);
   }
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_linearize_job &L = jobs[j].lin;
+    const dsm_linearize_job &L = job(j).lin;
     const size_t n = L.n_res;
-    Where &w = at[j];
-    if (jobs[j].JpJdF && n) w.jp = (long long)A.out.take(4 * 8 * n);
+    HesWhere &w = at[j];
+    if (job(j).JpJdF && n) w.jp = (long long)A.out.take(4 * 8 * n);
     if (L.center_projected_to && n) w.cpt = (long long)A.out.take(4 * 3 * n);
     if (L.projected_to && n) w.proj = (long long)A.out.take(4 * 16 * n);
     if (w.rows_out) w.J = (long long)A.out.take(4 * lin::J_FLOATS * n);
   }
-  if ((rc = A.bind(ctx))) return rc;
+}
+
+void hessian_stage(HesPlan &P, CallArena &A) {
+  const int n_jobs = (int)P.jobs.size();
   // the kernels count 4-byte words from the start of the device-only part; the read-back part follows it
-  const long long out0 = (long long)(A.work.used / 4);
+  const long long out0 = P.out0 = (long long)(A.work.used / 4);
   auto from_out = [out0](long long bytes) { return bytes < 0 ? -1ll : out0 + bytes / 4; };
-  LinJob *hl = A.host_in<LinJob>(o_lin);
-  HesJob *hh = A.host_in<HesJob>(o_hes);
-  WordPacker W{A.host_in<float>(o_stage)};
+  LinJob *hl = A.host_in<LinJob>(P.o_lin);
+  HesJob *hh = A.host_in<HesJob>(P.o_hes);
+  WordPacker W{A.host_in<float>(P.o_stage)};
   int max_res = 0, max_pts = 0, max_nf = 1;
+  P.view.assign(n_jobs, HesView());
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_hessian_job &H = jobs[j];
+    const dsm_hessian_job &H = *P.jobs[j];
     const dsm_linearize_job &L = H.lin;
     const int nf = L.n_frames, np = L.n_pts, nr = L.n_res;
-    const Where &w = at[j];
+    const HesWhere &w = P.at[j];
     LinJob &D = hl[j];
     memset(&D, 0, sizeof D);
     D.o_head = from_out((long long)w.head), D.o_cpt = from_out(w.cpt), D.o_proj = from_out(w.proj);
@@ -263,8 +288,8 @@ extern "C" int dsm_window_hessian_batch(dsm_context *ctx, int n_jobs, const dsm_
     memset(&G, 0, sizeof G);
     G.n_frames = nf, G.n_pts = np, G.n_res = nr, G.shift = H.shift_prior_to_zero != 0;
     G.o_rows = D.o_J, G.o_rec = (long long)(w.rec / 4), G.o_slot = (long long)(w.slot / 4);
-    G.o_prec = from_out((long long)w.prec), G.o_jp = from_out(w.jp), G.o_top = from_out((long long)w.top), G.o_D = from_out((long long)w.D);
-    G.o_E = from_out((long long)w.E), G.o_EB = from_out((long long)w.EB), G.o_Hcc = from_out((long long)w.Hcc), G.o_bc = from_out((long long)w.bc);
+    G.o_prec = w.prec.word(out0), G.o_jp = from_out(w.jp), G.o_top = w.top.word(out0), G.o_D = w.D.word(out0);
+    G.o_E = w.E.word(out0), G.o_EB = w.EB.word(out0), G.o_Hcc = w.Hcc.word(out0), G.o_bc = w.bc.word(out0);
     // the two index lists, one counting pass each: the residuals of every [host][target] pair and of every point in ascending index,
     // the points grouped by host in ascending index
     int *pair_start = (int *)W.reserve(&G.off_pair_start, (size_t)nf * nf + 1), *pair_list = (int *)W.reserve(&G.off_pair_list, nr);
@@ -288,27 +313,40 @@ extern "C" int dsm_window_hessian_batch(dsm_context *ctx, int n_jobs, const dsm_
     if (H.bd_lin) W.put(&G.off_bd_lin, H.bd_lin, np);
     if (H.hcd_lin) W.put(&G.off_hcd_lin, H.hcd_lin, 4 * (size_t)np);
     max_res = std::max(max_res, nr), max_pts = std::max(max_pts, np), max_nf = std::max(max_nf, nf);
+    HesView &V = P.view[j];
+    V.n_frames = nf, V.n_pts = np, V.n_res = nr;
+    V.off_pt_start = G.off_pt_start, V.off_pt_list = G.off_pt_list, V.off_target = D.off_target, V.off_host = D.off_host;
+    V.o_rec = G.o_rec, V.o_prec = G.o_prec, V.o_top = G.o_top, V.o_D = G.o_D, V.o_E = G.o_E, V.o_EB = G.o_EB, V.o_Hcc = G.o_Hcc, V.o_bc = G.o_bc;
   }
-  if ((rc = A.upload())) return rc;
-  const LinJob *dl = A.dev_in<const LinJob>(o_lin);
-  const HesJob *dh = A.dev_in<const HesJob>(o_hes);
-  const float *ds = A.dev_in<const float>(o_stage);
-  float *base = A.dev_work<float>(0);
+  P.max_res = max_res, P.max_pts = max_pts, P.max_nf = max_nf;
+  P.dev_stage = A.dev_in<const float>(P.o_stage), P.dev_base = A.dev_work<float>(0);
+}
+
+int hessian_launch(dsm_context *ctx, HesPlan &P, CallArena &A, const dsm_linearize_params &params) {
+  const int n_jobs = (int)P.jobs.size(), max_res = P.max_res, max_pts = P.max_pts, max_nf = P.max_nf;
+  const LinJob *dl = A.dev_in<const LinJob>(P.o_lin);
+  const HesJob *dh = A.dev_in<const HesJob>(P.o_hes);
+  const float *ds = P.dev_stage;
+  float *base = P.dev_base;
   if (max_res) {
-    if ((rc = linearize_launch(ctx, n_jobs, max_res, dl, ds, base, jobs[0].lin.window->w, jobs[0].lin.window->h, *params))) return rc;
+    const dsm_window *win = P.jobs[0]->lin.window;
+    if (int rc = linearize_launch(ctx, n_jobs, max_res, dl, ds, base, win->w, win->h, params)) return rc;
     hipLaunchKernelGGL(hes_residual_kernel, dim3((max_res + kResBlock - 1) / kResBlock, n_jobs), dim3(kResBlock), 0, ctx->stream, dl, dh, ds, base);
   }
   if (max_pts)
     hipLaunchKernelGGL(hes_point_kernel, dim3((max_pts + kPtBlock - 1) / kPtBlock, n_jobs), dim3(kPtBlock), 0, ctx->stream, dl, dh, ds, base);
   hipLaunchKernelGGL(hes_pair_kernel, dim3(max_nf * max_nf, n_jobs), dim3(kPairBlock), 0, ctx->stream, dh, ds, base);
   hipLaunchKernelGGL(hes_schur_kernel, dim3(max_nf * max_nf + 1, n_jobs), dim3(64 * max_nf), 0, ctx->stream, dh, ds, base);
-  DSM_HIP(hipGetLastError());
-  if ((rc = A.fetch(A.out.used))) return rc;
+  return DSM_OK;
+}
+
+void hessian_unpack(const HesPlan &P, const CallArena &A, const dsm_linearize_params &params) {
+  const int n_jobs = (int)P.jobs.size();
   const unsigned char *ho = A.host_out<unsigned char>(0);
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_hessian_job &H = jobs[j];
+    const dsm_hessian_job &H = *P.jobs[j];
     const dsm_linearize_job &L = H.lin;
-    const Where &w = at[j];
+    const HesWhere &w = P.at[j];
     const float *hf = reinterpret_cast<const float *>(ho);
     linearize_unpack(L, hf, (long long)(w.head / 4), w.cpt < 0 ? -1 : w.cpt / 4, w.proj < 0 ? -1 : w.proj / 4, w.J < 0 ? -1 : w.J / 4);
     for (int r = 0; r < L.n_res; r++) {
@@ -316,8 +354,8 @@ extern "C" int dsm_window_hessian_batch(dsm_context *ctx, int n_jobs, const dsm_
       if (H.active) H.active[r] = active;
       if (active && w.jp >= 0) memcpy(H.JpJdF + (size_t)8 * r, ho + w.jp + (size_t)32 * r, 32);
     }
-    const float *prec = reinterpret_cast<const float *>(ho + w.prec);
-    for (int p = 0; p < L.n_pts; p++) {
+    const float *prec = reinterpret_cast<const float *>(ho + w.prec.at);
+    for (int p = 0; w.prec.out && p < L.n_pts; p++) {
       const float *P = prec + (size_t)hes::P_FLOATS * p;
       if (H.hdd_acc) H.hdd_acc[p] = P[hes::P_HDD];
       if (H.bd_acc) H.bd_acc[p] = P[hes::P_BD];
@@ -326,10 +364,11 @@ extern "C" int dsm_window_hessian_batch(dsm_context *ctx, int n_jobs, const dsm_
       if (H.bd_sum) H.bd_sum[p] = P[hes::P_BDSUM];
       if (H.idepth_hessian) H.idepth_hessian[p] = P[hes::P_IDH];
     }
-    hessian_stitch(H, reinterpret_cast<const double *>(ho + w.top), reinterpret_cast<const double *>(ho + w.D),
-                   reinterpret_cast<const double *>(ho + w.E), reinterpret_cast<const double *>(ho + w.EB),
-                   reinterpret_cast<const double *>(ho + w.Hcc), reinterpret_cast<const double *>(ho + w.bc));
-    linearize_job_summary(L, *params); // B1, B2
+    auto raw = [ho](const HesSpot &s) { return reinterpret_cast<const double *>(ho + s.at); };
+    if (!P.lean) hessian_stitch(H, raw(w.top), raw(w.D), raw(w.E), raw(w.EB), raw(w.Hcc), raw(w.bc));
+    else if (w.top.out) hessian_copy_raw(H, raw(w.top), raw(w.D), raw(w.E), raw(w.EB), raw(w.Hcc), raw(w.bc));
+    linearize_job_summary(L, params); // B1, B2
   }
-  return DSM_OK;
 }
+
+} // namespace dsm

@@ -153,10 +153,10 @@ void linearize_job_summary(const dsm_linearize_job &J, const dsm_linearize_param
 }
 
 // V of DESIGN.md section 17, after linearize_job_error has passed
-const char *hessian_job_error(const dsm_hessian_job &J) {
+const char *hessian_job_error(const dsm_hessian_job &J, bool stitched_required) {
   const dsm_linearize_job &L = J.lin;
   if (!J.ad_host || !J.ad_target) return "NULL ad_host or ad_target";
-  if (!J.H_A || !J.b_A || !J.H_sc || !J.b_sc) return "NULL H_A, b_A, H_sc or b_sc";
+  if (stitched_required && (!J.H_A || !J.b_A || !J.H_sc || !J.b_sc)) return "NULL H_A, b_A, H_sc or b_sc";
   const size_t n_ad = (size_t)L.n_frames * L.n_frames * 64;
   for (size_t i = 0; i < n_ad; i++)
     if (!std::isfinite(J.ad_host[i]) || !std::isfinite(J.ad_target[i])) return "a non-finite ad_host or ad_target";
@@ -263,7 +263,12 @@ void hessian_stitch(const dsm_hessian_job &J, const double *top, const double *D
       }
     }
   mirror_upper(HS, N);
-  const size_t n2 = (size_t)nf * nf;
+  hessian_copy_raw(J, top, D, E, EB, Hcc, bc);
+}
+
+void hessian_copy_raw(const dsm_hessian_job &J, const double *top, const double *D, const double *E, const double *EB, const double *Hcc,
+                      const double *bc) {
+  const size_t nf = J.lin.n_frames, n2 = nf * nf;
   if (J.acc_top) memcpy(J.acc_top, top, 8 * n2 * 169);
   if (J.acc_D) memcpy(J.acc_D, D, 8 * n2 * nf * 64);
   if (J.acc_E) memcpy(J.acc_E, E, 8 * n2 * 32);

@@ -1446,6 +1446,45 @@ int dsm_window_hessian_batch(dsm_context *ctx, int n_jobs, const dsm_hessian_job
  * ignored).  The CPU baseline of tools/hessian_timing.py and a checker that needs no device. */
 int dsm_window_hessian_host(int w, int h, const dsm_hessian_job *job, const float *const *frame_I, const dsm_linearize_params *params);
 
+/* ---- Stitch, damping, solve and back-substitution of the window optimisation -------------------------------------
+ * replaces, together with the section above, everything FrontEnd::optimize (dso_helpers/FrontEndOptimize.cpp:332-486) does between
+ * backupState and doStepFromBackup for one trial step: linearizeAll, accumulateAF_MT / accumulateSCF_MT, the non-SVD,
+ * non-ORTHOGONALIZE_SYSTEM branch of EnergyFunctional::solveSystemF with the orthogonalize projection on a caller-supplied basis, and
+ * resubstituteF_MT / resubstituteFPt (UPSTREAM-DSO, parity unpinned), as the rules T1d, F1-F8, R1-R3 and V of DESIGN.md section 18
+ * state them.  All arithmetic is IEEE, left to right as written, without contraction. */
+#define DSM_SOLVE_MAX_NULL 8
+#define DSM_SOLVE_X_NOT_FINITE 1    /* flags bit 0: some x[i] is not finite */
+#define DSM_SOLVE_STEP_NOT_FINITE 2 /* flags bit 1: some point's step is not finite */
+
+/* One window: hes and what the solve reads and returns on top of it; n = hes.lin.n_frames, N = 4 + 8 n. */
+typedef struct dsm_solve_job {
+  dsm_hessian_job hes;        /* H_A, b_A, H_sc, b_sc are optional (NULL) here; every other field with the same meaning */
+  const double *H_L, *b_L;    /* N * N (row-major) and N: accumulateLF_MT's stitched result */
+  const double *H_M, *b_M;    /* the next three: optional (NULL: zeros).  N * N and N: HM, bM */
+  const double *delta_x;      /* N: getStitchedDeltaF */
+  double lambda;              /* finite, > -1; the caller applies SOLVER_FIX_LAMBDA / SOLVER_USE_GN itself */
+  int n_null;                 /* 0 .. DSM_SOLVE_MAX_NULL; 0: no projection (F7) */
+  const double *null_basis;   /* N * n_null, row-major: the nullspaces to project out; read with n_null > 0 only */
+  const double *null_pinv;    /* n_null * N: their pseudo-inverse */
+  double *x;                  /* N: lastX; the steps are -x */
+  float *step;                /* n_pts: the inverse-depth step of every point (0 for a point without an active residual) */
+  int *flags;                 /* one word: DSM_SOLVE_X_NOT_FINITE | DSM_SOLVE_STEP_NOT_FINITE; nothing is clamped or replaced */
+  double *last_HS, *last_bS;  /* optional (NULL).  N * N and N: HFinal - H_sc and bFinal before damping */
+} dsm_solve_job;
+
+/* One trial step for every job: the staged copy and the five launches of dsm_window_hessian_batch, then three more (stitch, solve,
+ * back-substitution) on the same arena, one read-back of the heads, x, the steps, the flags and what the job asks for on top: the
+ * stitched matrices, the raw accumulators and the per-point results cost their read-back only when a job asks for them.  A job's
+ * results do not depend on the other jobs of the call or on the launch geometry.  Validation is all or nothing, before anything is
+ * enqueued: DSM_ERR_INVALID for everything dsm_window_hessian_batch refuses except a NULL H_A, b_A, H_sc or b_sc, and for a NULL H_L,
+ * b_L, x, step or flags, a non-finite lambda or lambda <= -1, a non-finite H_L, b_L, H_M, b_M, delta_x, null_basis or null_pinv,
+ * n_null outside [0, DSM_SOLVE_MAX_NULL], n_null > 0 with a NULL basis or pseudo-inverse.  n_res == 0, n_pts == 0 and a job of one
+ * frame are valid: the system is then H_L + H_M alone. */
+int dsm_window_solve_batch(dsm_context *ctx, int n_jobs, const dsm_solve_job *jobs, const dsm_linearize_params *params);
+/* The same for one job on the host: dsm_window_hessian_host, then plain loops over F1-R3.  The CPU baseline of tools/solve_timing.py
+ * and a checker that needs no device. */
+int dsm_window_solve_host(int w, int h, const dsm_solve_job *job, const float *const *frame_I, const dsm_linearize_params *params);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.
