@@ -231,6 +231,27 @@ class SolveJob(C.Structure):
     ]
 
 
+class StepParams(C.Structure):
+    _fields_ = [
+        ("scale_xi_trans", C.c_double), ("scale_xi_rot", C.c_double), ("scale_a", C.c_double), ("scale_b", C.c_double),
+        ("th_opt_iterations", C.c_double),
+    ]
+
+
+class StepJob(C.Structure):
+    _fields_ = [
+        ("sol", SolveJob), ("world_to_cam_eval", c_double_p), ("state_zero", c_double_p), ("state_backup", c_double_p),
+        ("frame_step", c_double_p), ("calib_zero", c_double_p), ("calib_backup", c_double_p), ("calib_step", c_double_p),
+        ("idepth_backup", c_float_p), ("idepth_step", c_float_p), ("exposure", c_float_p), ("stepfac", C.c_float * 5),
+        ("prior", c_double_p), ("prior_zero", c_double_p),
+        ("state_out", c_double_p), ("calib_out", c_double_p), ("idepth_out", c_float_p), ("world_to_cam_out", c_double_p),
+        ("cam_to_world_out", c_double_p), ("can_break", c_int_p), ("step_sums", c_float_p), ("energy_m", c_double_p),
+        ("cam_out", c_float_p), ("pre_RTll_0_out", c_float_p), ("pre_tTll_0_out", c_float_p), ("pre_KRKiTll_out", c_float_p),
+        ("pre_KtTll_out", c_float_p), ("pre_aff_mode_out", c_float_p), ("pre_b0_mode_out", c_float_p),
+        ("delta_x_out", c_double_p), ("H_L_out", c_double_p), ("b_L_out", c_double_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -486,6 +507,9 @@ SYMBOLS = {
     "dsm_window_hessian_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(HessianJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams)]),
     "dsm_window_solve_batch": (C.c_int, [_vp, C.c_int, C.POINTER(SolveJob), C.POINTER(LinearizeParams)]),
     "dsm_window_solve_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(SolveJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams)]),
+    "dsm_step_params_default": (C.c_int, [C.POINTER(StepParams)]),
+    "dsm_window_step_batch": (C.c_int, [_vp, C.c_int, C.POINTER(StepJob), C.POINTER(LinearizeParams), C.POINTER(StepParams)]),
+    "dsm_window_step_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(StepJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams), C.POINTER(StepParams)]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

@@ -191,6 +191,10 @@ void linearize_job_summary(const dsm_linearize_job &J, const dsm_linearize_param
 const char *hessian_job_error(const dsm_hessian_job &J, bool stitched_required = true);
 // solve_host.cpp: what both forms of the solve call refuse beyond that
 const char *solve_job_error(const dsm_solve_job &J);
+// step_host.cpp: what both forms of the step call refuse on top of that, before the solve call's rules see the completed job
+// 
+const char *step_params_error(const dsm_step_params *p);
+const char *step_job_error(const dsm_step_job &J);
 // points_host.cpp: the copies of the optional raw accumulators alone
 void hessian_copy_raw(const dsm_hessian_job &J, const double *top, const double *D, const double *E, const double *EB, const double *Hcc,
                       const double *bc);

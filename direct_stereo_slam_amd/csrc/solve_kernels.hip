@@ -3,7 +3,7 @@
 // R1-R3, V of DESIGN.md section 18.
 //
 // One dsm_window_solve_batch = one staged copy, the FIVE launches of dsm_window_hessian_batch (hessian_launch.hpp), THREE more on the
-// same stream and arena, one read-back:
+// same stream and arena, one read-back (as pieces in solve_launch.hpp, which dsm_window_step_batch runs too):
 //   sol_stitch_kernel  one 64-lane workgroup per (job, 8 x 8 block of the upper block triangle), one per (job, frame) for the C rows
 //                      and the right-hand sides of the frame's block, one per job for the 4 x 4 corner (T1d).  Lane (a, b) holds the
 //                      block's entry and walks the contributing pairs in T1's order; the Mh / Mt intermediate of a product goes
@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "hessian_launch.hpp"
+#include "solve_launch.hpp"
 
 #include "solve_math.hpp"
 
@@ -296,25 +296,34 @@ extern "C" int dsm_window_solve_batch(dsm_context *ctx, int n_jobs, const dsm_so
     if (const char *e = hessian_job_error(jobs[j].hes, false)) return bad(e);
     if (const char *e = solve_job_error(jobs[j])) return bad(e);
   }
-  // on top of the Hessian call's parts: staged [job table | doubles: ad_host, ad_target, H_L, b_L and the optional inputs], device only
-  // or read back (a job that asks for one of them) [H_A, b_A, H_sc, b_sc], read back [x, steps, flags, as asked for: last_HS, last_bS]
   CallArena A;
-  HesPlan P;
-  P.lean = true;
-  for (int j = 0; j < n_jobs; j++) P.jobs.push_back(&jobs[j].hes);
-  hessian_layout(P, A);
-  struct Where {
-    HesSpot HA, bA, HS, bS;
-    size_t x, step, flags;        // bytes into out
-    long long lastH = -1, lastb = -1; // bytes into out; -1: not asked for
-  };
-  std::vector<Where> at(n_jobs);
+  SolPlan P;
+  for (int j = 0; j < n_jobs; j++) P.jobs.push_back(&jobs[j]);
+  solve_layout(P, A);
+  if ((rc = A.bind(ctx))) return rc;
+  solve_stage(P, A);
+  if ((rc = A.upload())) return rc;
+  if ((rc = solve_launch(ctx, P, A, *params))) return rc;
+  if ((rc = A.fetch(A.out.used))) return rc;
+  solve_unpack(P, A, *params);
+  return DSM_OK;
+}
+
+namespace dsm {
+
+// on top of the Hessian call's parts: staged [job table | doubles: ad_host, ad_target, H_L, b_L and the optional inputs], device only
+// or read back (a job that asks for one of them) [H_A, b_A, H_sc, b_sc], read back [x, steps, flags, as asked for: last_HS, last_bS]
+void solve_layout(SolPlan &P, CallArena &A) {
+  const int n_jobs = (int)P.jobs.size();
+  P.hes.lean = true;
+  for (int j = 0; j < n_jobs; j++) P.hes.jobs.push_back(&P.jobs[j]->hes);
+  hessian_layout(P.hes, A);
+  P.at.assign(n_jobs, SolWhere());
   size_t doubles = 0;
-  int max_N = 12;
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_solve_job &S = jobs[j];
+    const dsm_solve_job &S = *P.jobs[j];
     const size_t nf = S.hes.lin.n_frames, N = 4 + 8 * nf;
-    Where &w = at[j];
+    SolWhere &w = P.at[j];
     doubles += 2 * nf * nf * 64 + N * N + N + (S.H_M ? N * N : 0) + (S.b_M ? N : 0) + (S.delta_x ? N : 0) + 2 * N * (size_t)S.n_null;
     const bool out = S.hes.H_A || S.hes.b_A || S.hes.H_sc || S.hes.b_sc;
     auto take = [&A, out](size_t bytes) {
@@ -326,13 +335,16 @@ extern "C" int dsm_window_solve_batch(dsm_context *ctx, int n_jobs, const dsm_so
     w.x = A.out.take(8 * N), w.step = A.out.take(4 * (size_t)S.hes.lin.n_pts), w.flags = A.out.take(4);
     if (S.last_HS) w.lastH = (long long)A.out.take(8 * N * N);
     if (S.last_bS) w.lastb = (long long)A.out.take(8 * N);
-    max_N = std::max(max_N, (int)N);
+    P.max_N = std::max(P.max_N, (int)N);
   }
-  const size_t o_sol = A.in.take(sizeof(SolJob) * n_jobs), o_sd = A.in.take(8 * doubles);
-  if ((rc = A.bind(ctx))) return rc;
-  hessian_stage(P, A);
-  SolJob *hs = A.host_in<SolJob>(o_sol);
-  double *hd = A.host_in<double>(o_sd);
+  P.o_sol = A.in.take(sizeof(SolJob) * n_jobs), P.o_sd = A.in.take(8 * doubles);
+}
+
+void solve_stage(SolPlan &P, CallArena &A) {
+  const int n_jobs = (int)P.jobs.size();
+  hessian_stage(P.hes, A);
+  SolJob *hs = A.host_in<SolJob>(P.o_sol);
+  double *hd = A.host_in<double>(P.o_sd);
   size_t used = 0;
   auto put = [&](const double *a, size_t n) {
     if (!a) return -1ll;
@@ -340,40 +352,50 @@ extern "C" int dsm_window_solve_batch(dsm_context *ctx, int n_jobs, const dsm_so
     used += n;
     return (long long)(used - n);
   };
+  const long long out0 = P.hes.out0;
+  P.view.assign(n_jobs, SolView());
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_solve_job &S = jobs[j];
+    const dsm_solve_job &S = *P.jobs[j];
     const size_t nf = S.hes.lin.n_frames, N = 4 + 8 * nf;
-    const Where &w = at[j];
+    const SolWhere &w = P.at[j];
     SolJob &G = hs[j];
     memset(&G, 0, sizeof G);
-    G.V = P.view[j], G.N = (int)N, G.n_null = S.n_null, G.lambda = S.lambda;
+    G.V = P.hes.view[j], G.N = (int)N, G.n_null = S.n_null, G.lambda = S.lambda;
     G.d_adh = put(S.hes.ad_host, nf * nf * 64), G.d_adt = put(S.hes.ad_target, nf * nf * 64);
     G.d_HL = put(S.H_L, N * N), G.d_bL = put(S.b_L, N), G.d_HM = put(S.H_M, N * N), G.d_bM = put(S.b_M, N), G.d_dx = put(S.delta_x, N);
     G.d_basis = put(S.n_null ? S.null_basis : nullptr, N * S.n_null), G.d_pinv = put(S.n_null ? S.null_pinv : nullptr, N * S.n_null);
-    G.o_HA = w.HA.word(P.out0), G.o_bA = w.bA.word(P.out0), G.o_HS = w.HS.word(P.out0), G.o_bS = w.bS.word(P.out0);
-    G.o_x = P.out0 + (long long)(w.x / 4), G.o_step = P.out0 + (long long)(w.step / 4), G.o_flags = P.out0 + (long long)(w.flags / 4);
-    G.o_lastH = w.lastH < 0 ? -1 : P.out0 + w.lastH / 4, G.o_lastb = w.lastb < 0 ? -1 : P.out0 + w.lastb / 4;
+    G.o_HA = w.HA.word(out0), G.o_bA = w.bA.word(out0), G.o_HS = w.HS.word(out0), G.o_bS = w.bS.word(out0);
+    G.o_x = out0 + (long long)(w.x / 4), G.o_step = out0 + (long long)(w.step / 4), G.o_flags = out0 + (long long)(w.flags / 4);
+    G.o_lastH = w.lastH < 0 ? -1 : out0 + w.lastH / 4, G.o_lastb = w.lastb < 0 ? -1 : out0 + w.lastb / 4;
+    P.view[j] = SolView{(int)N, G.d_HL, G.d_bL, G.d_HM, G.d_bM, G.d_dx};
   }
-  if ((rc = A.upload())) return rc;
-  if ((rc = hessian_launch(ctx, P, A, *params))) return rc;
-  const SolJob *ds = A.dev_in<const SolJob>(o_sol);
-  const double *dd = A.dev_in<const double>(o_sd);
-  const int nf = P.max_nf;
-  const size_t lds = solve_lds_bytes(max_N);
+}
+
+int solve_launch(dsm_context *ctx, SolPlan &P, CallArena &A, const dsm_linearize_params &params) {
+  const int n_jobs = (int)P.jobs.size();
+  if (int rc = hessian_launch(ctx, P.hes, A, params)) return rc;
+  const SolJob *ds = A.dev_in<const SolJob>(P.o_sol);
+  const double *dd = A.dev_in<const double>(P.o_sd);
+  const int nf = P.hes.max_nf;
+  const size_t lds = solve_lds_bytes(P.max_N);
   if (lds > 64 * 1024) DSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sol_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(sol_stitch_kernel, dim3(nf * (nf + 1) / 2 + nf + 1, n_jobs), dim3(64), 0, ctx->stream, ds, dd, P.dev_base);
-  hipLaunchKernelGGL(sol_solve_kernel, dim3(n_jobs), dim3(kSolveBlock), lds, ctx->stream, ds, dd, P.dev_base);
-  if (P.max_pts)
-    hipLaunchKernelGGL(sol_step_kernel, dim3((P.max_pts + kStepBlock - 1) / kStepBlock, n_jobs), dim3(kStepBlock), 0, ctx->stream, ds, dd, P.dev_stage,
-                       P.dev_base);
+  hipLaunchKernelGGL(sol_stitch_kernel, dim3(nf * (nf + 1) / 2 + nf + 1, n_jobs), dim3(64), 0, ctx->stream, ds, dd, P.hes.dev_base);
+  hipLaunchKernelGGL(sol_solve_kernel, dim3(n_jobs), dim3(kSolveBlock), lds, ctx->stream, ds, dd, P.hes.dev_base);
+  if (P.hes.max_pts)
+    hipLaunchKernelGGL(sol_step_kernel, dim3((P.hes.max_pts + kStepBlock - 1) / kStepBlock, n_jobs), dim3(kStepBlock), 0, ctx->stream, ds, dd,
+                       P.hes.dev_stage, P.hes.dev_base);
   DSM_HIP(hipGetLastError());
-  if ((rc = A.fetch(A.out.used))) return rc;
-  hessian_unpack(P, A, *params);
+  return DSM_OK;
+}
+
+void solve_unpack(const SolPlan &P, const CallArena &A, const dsm_linearize_params &params) {
+  const int n_jobs = (int)P.jobs.size();
+  hessian_unpack(P.hes, A, params);
   const unsigned char *ho = A.host_out<unsigned char>(0);
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_solve_job &S = jobs[j];
+    const dsm_solve_job &S = *P.jobs[j];
     const size_t N = 4 + 8 * (size_t)S.hes.lin.n_frames;
-    const Where &w = at[j];
+    const SolWhere &w = P.at[j];
     if (S.hes.H_A) memcpy(S.hes.H_A, ho + w.HA.at, 8 * N * N);
     if (S.hes.b_A) memcpy(S.hes.b_A, ho + w.bA.at, 8 * N);
     if (S.hes.H_sc) memcpy(S.hes.H_sc, ho + w.HS.at, 8 * N * N);
@@ -384,5 +406,6 @@ extern "C" int dsm_window_solve_batch(dsm_context *ctx, int n_jobs, const dsm_so
     if (S.last_HS) memcpy(S.last_HS, ho + w.lastH, 8 * N * N);
     if (S.last_bS) memcpy(S.last_bS, ho + w.lastb, 8 * N);
   }
-  return DSM_OK;
 }
+
+} // namespace dsm

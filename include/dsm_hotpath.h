@@ -1485,6 +1485,76 @@ int dsm_window_solve_batch(dsm_context *ctx, int n_jobs, const dsm_solve_job *jo
  * and a checker that needs no device. */
 int dsm_window_solve_host(int w, int h, const dsm_solve_job *job, const float *const *frame_I, const dsm_linearize_params *params);
 
+/* ---- Applying a step and re-linearising: one iteration of the window optimisation in one call -------------------
+ * replaces, together with the three sections above, one iteration of the loop of FrontEnd::optimize (dso_helpers/FrontEndOptimize.cpp:
+ * 332-486): doStepFromBackup (:182-262, the non-SOLVER_MOMENTUM branch) with what it calls -- FrameHessian::setState,
+ * CalibHessian::setValue, PointHessian::setIdepth / setIdepthZero, setPrecalcValues (:300-323, FrameFramePrecalc::set and
+ * EnergyFunctional::setDeltaF), calcMEnergyF and the prior lines of the stitch (UPSTREAM-DSO, parity unpinned; the priors are
+ * FrontEnd.cpp:964-972's) -- as the rules D1-D4, Q1-Q4, E1-E3 and V of DESIGN.md section 19 state them, and then everything
+ * dsm_window_solve_batch does, at the trial state.  The call takes the backed-up state and a step, forms the trial state and what
+ * derives from it on the device, and returns the trial state, its energies, can_break and the next step, computed as if the trial
+ * were accepted.  Accept: commit the returned state and pass the returned x (as frame_step = -x, calib_step = -x[0..3], idepth_step =
+ * step) to the next call.  Reject: call again with all five factors 0 and lambda * 100.
+ * NOT here: SOLVER_MOMENTUM; the step-size heuristic (:390-405; the caller passes the factors); calcLEnergy and accumulateLF_MT (zero
+ * while no residual is linearised, which is all of optimize); setAdjointsF (ad_host / ad_target stay the caller's: the evaluation point
+ * does not move inside optimize); the nullspaces; setEvalPT after the loop (:455-464); applyRes; the accept decision; marginalisation.
+ * All arithmetic is IEEE, left to right as written, without contraction. */
+typedef struct dsm_step_params {
+  double scale_xi_trans;     /* 0.5   SCALE_XI_TRANS */
+  double scale_xi_rot;       /* 1     SCALE_XI_ROT */
+  double scale_a;            /* 10    SCALE_A */
+  double scale_b;            /* 1000  SCALE_B */
+  double th_opt_iterations;  /* 1.2   setting_thOptIterations */
+} dsm_step_params;
+
+/* One window; n = sol.hes.lin.n_frames, N = 4 + 8 n, n_pts = sol.hes.lin.n_pts; poses are {qx,qy,qz,qw,tx,ty,tz}.  In sol, every field
+ * the device does not form keeps its meaning.  What the device forms MUST be NULL: sol.hes.lin.pre_RTll_0, pre_tTll_0, pre_KRKiTll,
+ * pre_KtTll, pre_aff_mode, pre_b0_mode, idepth_scaled, idepth_zero_scaled, sol.hes.delta and sol.delta_x.  sol.hes.lin.cam and cam_inv
+ * are not read. */
+typedef struct dsm_step_job {
+  dsm_solve_job sol;
+  const double *world_to_cam_eval; /* n * 7: worldToCam_evalPT, unit quaternions */
+  const double *state_zero;        /* n * 8, unscaled: state_zero */
+  const double *state_backup;      /* n * 8: state_backup */
+  const double *frame_step;        /* n * 8: fh->step, which is -x of F8 */
+  const double *calib_zero;        /* 4: value_zero */
+  const double *calib_backup;      /* 4: value_backup */
+  const double *calib_step;        /* 4: h_calib_.step */
+  const float *idepth_backup;      /* n_pts */
+  const float *idepth_step;        /* n_pts: ph->step */
+  const float *exposure;           /* n: ab_exposure */
+  float stepfac[5];                /* C, T, R, A, D */
+  const double *prior;             /* the next two: optional (NULL: no prior).  N: cPrior, then every frame's prior */
+  const double *prior_zero;        /* N: the calibration's value_zero, then every frame's getPriorZero */
+  double *state_out;               /* n * 8: the trial state */
+  double *calib_out;               /* 4 */
+  float *idepth_out;               /* n_pts */
+  double *world_to_cam_out;        /* n * 7: PRE_worldToCam */
+  double *cam_to_world_out;        /* optional (NULL), n * 7: PRE_camToWorld */
+  int *can_break;                  /* one word: what doStepFromBackup returns */
+  float *step_sums;                /* 6: sumA, sumB, sumR, sumT, sumID, sumNID after their divisions */
+  double *energy_m;                /* calcMEnergyF */
+  float *cam_out;                  /* the rest: optional (NULL), what the device formed in the shapes dsm_solve_job takes it, so that a
+                                      returned set is a valid input of dsm_window_solve_batch.  6: cam, cam_inv */
+  float *pre_RTll_0_out, *pre_tTll_0_out, *pre_KRKiTll_out, *pre_KtTll_out, *pre_aff_mode_out, *pre_b0_mode_out; /* n * n * (9, 3, 9, 3, 2, 1) */
+  double *delta_x_out;             /* N */
+  double *H_L_out, *b_L_out;       /* N * N and N: H_L, b_L with the priors added (E3) */
+} dsm_step_job;
+
+/* the upstream defaults listed above */
+int dsm_step_params_default(dsm_step_params *p);
+/* One iteration for every job: the staged copy of dsm_window_solve_batch with the step's inputs on top, two launches (stp_frame_kernel,
+ * stp_point_kernel) that write the trial state's tables where the eight launches of dsm_window_solve_batch read them, those eight
+ * launches unchanged, one read-back.  A job's results do not depend on the other jobs of the call or on the launch geometry.
+ * Validation is all or nothing, before anything is enqueued: DSM_ERR_INVALID for everything dsm_window_solve_batch refuses (except
+ * the NULLs this call requires), one of the must-be-NULL fields given, a NULL required array, a non-finite input or step factor, a
+ * world_to_cam_eval quaternion whose squared norm is further than 1e-9 from 1, prior without prior_zero or the reverse, non-finite or
+ * non-positive step parameters.  n_res == 0, n_pts == 0 and a job of one frame are valid. */
+int dsm_window_step_batch(dsm_context *ctx, int n_jobs, const dsm_step_job *jobs, const dsm_linearize_params *lp, const dsm_step_params *sp);
+/* The same for one job on the host: D1-E3 as plain loops, then dsm_window_solve_host.  A checker that needs no device. */
+int dsm_window_step_host(int w, int h, const dsm_step_job *job, const float *const *frame_I, const dsm_linearize_params *lp,
+                         const dsm_step_params *sp);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.
