@@ -416,6 +416,10 @@ SYMBOLS = {
     "dsm_tracker_calc_res_scale": (C.c_int, [_vp, C.c_int, C.c_float, C.c_float, c_double_p, c_float_p, c_float_p, c_int_p]),
     "dsm_diag_single_eval": (C.c_int, [_vp, C.c_int, C.c_int, c_double_p, c_double_p, C.c_float, C.c_float, C.c_int, C.c_int, c_double_p, c_double_p,
                                        c_double_p, c_float_p, c_float_p, c_int_p]),
+    "dsm_diag_eval_facts": (C.c_int, [_vp, C.c_int, c_double_p, c_int_p, c_float_p]),
+    "dsm_diag_tracker_force_general": (C.c_int, [_vp, C.c_int]),
+    "dsm_pose_fact_host": (C.c_int, [C.c_int, c_float_p, c_int_p]),
+    "dsm_fact_rules_host": (C.c_int, [C.c_int, c_float_p, c_int_p]),
     "dsm_diag_pose_estimator_eval": (C.c_int, [_vp, C.c_int, c_double_p, _pp_f, C.c_float, _pp_f, C.c_float, c_float_p, C.c_int, c_double_p, c_double_p,
                                                C.c_float, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
     "dsm_diag_lm_propose": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(LmProposeIn), C.c_int, C.c_int, C.POINTER(LmProposeOut)]),

@@ -125,6 +125,39 @@ int dsm_diag_single_eval(dsm_tracker *t, int mode, int lvl, const double pose[7]
   return DSM_OK;
 }
 
+int dsm_diag_eval_facts(dsm_tracker *t, int lvl, const double pose[7], int out[4], float bounds[5]) {
+  if (!t || !pose || !out || lvl < 0 || lvl >= t->nlevels) return invalid("dsm_diag_eval_facts: bad argument");
+  dsm_context *ctx = t->ctx;
+  DSM_HIP(hipSetDevice(ctx->device));
+  int rc = sync_desc(t);
+  if (rc) return rc;
+  void *d = nullptr;
+  int h[9];
+  DSM_HIP(hipMalloc(&d, 64 + sizeof h));
+  hipError_t e = hipMemcpyAsync(d, pose, 7 * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    launch_diag_eval_facts(ctx->stream, t->d_desc, lvl, (const double *)d, (int *)((char *)d + 64));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h, (char *)d + 64, sizeof h, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t sync = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d);
+  DSM_HIP(e);
+  DSM_HIP(sync);
+  memcpy(out, h, 4 * sizeof(int));
+  if (bounds) memcpy(bounds, h + 4, 5 * sizeof(float));
+  return DSM_OK;
+}
+
+int dsm_diag_tracker_force_general(dsm_tracker *t, int on) {
+  if (!t || !t->facts.d) return invalid("dsm_diag_tracker_force_general: bad argument");
+  DSM_HIP(hipSetDevice(t->ctx->device));
+  const int v = on ? 1 : 0;
+  DSM_HIP(hipMemcpyAsync(&t->facts.d->force_general, &v, sizeof v, hipMemcpyHostToDevice, t->ctx->stream));
+  DSM_HIP(hipStreamSynchronize(t->ctx->stream)); // (v is a local)
+  return DSM_OK;
+}
+
 int dsm_diag_pose_estimator_eval(dsm_pose_estimator *pe, int n_pts, const double *xyz, const float *const *ref_colors,
                                  float ref_ab_exposure, const float *const *new_dIp, float new_ab_exposure, const float new_cam[4],
                                  int lvl, const double pose[7], const double aff[2], float cutoff_th, int form, int residual_only,

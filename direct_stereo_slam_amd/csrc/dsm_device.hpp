@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "eval_facts.hpp"
+
 #define DSM_MAX_LEVELS 6
 
 namespace dsm {
@@ -55,6 +57,8 @@ struct alignas(16) TrackerDev {
   float ref_exposure;  // lastRef->ab_exposure
   float exposure[2];   // new_frame_->ab_exposure, fh1_->ab_exposure
   double T10[7];       // tfm_f1_f0_ as {qx,qy,qz,qw,tx,ty,tz}
+  const TrackerFacts *facts; // device-written facts of the template lists and frame buffers (eval_facts.hpp); null: none established
+  int img_set[2];            // the buffer set (TrackerFacts::img_plain row) behind each frame slot; swapped with the buffers
 };
 
 // Inputs of one fused evaluation, produced on the device by the LM kernel.
@@ -64,7 +68,9 @@ struct EvalIn {
   const float4 *pts;
   const float *img;
   int n, w, h;
-  int ppt, pad0, pad1, pad2; // points per thread of a chunk of this evaluation (pts_per_thread of n under the tracker's table); the struct stays a multiple of 16 bytes
+  int ppt;   // points per thread of a chunk of this evaluation (pts_per_thread of n under the tracker's table)
+  int plain; // the level's template fact and the target plane's image fact both hold (eval_facts.hpp); 0: the general per-point code
+  float bx0, bx1, by0, by1, bid, pad0; // the template list's bounds xmin, xmax, ymin, ymax, idmax (read when plain); the struct stays a multiple of 16 bytes
   int residual_only; // the LM loop ends after this evaluation whatever it yields (:588, the iteration bound): only the
                      // residual side (calcResPose / calcResScale) is needed -- the normal equations calcGSSSE* would build
                      // from it are never read by the reference either

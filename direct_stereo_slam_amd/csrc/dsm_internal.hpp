@@ -142,6 +142,32 @@ struct dsm_tracker {
   bool have_k = false, have_ref = false, have_frame[2] = {false, false};
   int ref_frame_id = -1;
   bool desc_dirty = true;
+  // The facts of the template lists and frame buffers above (eval_facts.hpp): device words the kernels that produce a list or a plane
+  // write, read by the LM step when a level begins.  A stale 1 is the one way they can make a result wrong, so every path that writes
+  // a list or a plane -- a kernel, a copy, whatever comes later -- announces it HERE first, on the stream its writes are ordered on:
+  //   kFactClear  the fact is 0 from there on (the general per-point code);
+  //   kFactArm    for the producers named in eval_facts.hpp, whose kernels look at every value they write and store 0 on failure.
+  // Nothing else writes the words (dsm_diag_tracker_force_general writes its own).
+  struct Facts {
+    dsm::TrackerFacts *d = nullptr; // zeroed at creation: nothing established
+    int set[2] = {0, 1};            // the buffer set behind each frame slot ...
+    int back_set[2] = {2, 3};       // ... and behind its back buffers; swapped with the buffers (swap_frames)
+    int set_of(int slot) const { return slot >= 2 ? back_set[slot & 1] : set[slot & 1]; } // slot: 0, 1 or DSM_SLOT_NEXT_*
+  } facts;
+  enum FactUse { kFactClear = 0, kFactArm = 1 };
+  // before the lists of every level are written on stream s
+  int announce_template_write(hipStream_t s, FactUse use);
+  // before the planes of every level behind `slot` (0, 1 or DSM_SLOT_NEXT_*) are written on stream s
+  int announce_plane_write(int slot, hipStream_t s, FactUse use);
+  // the same for a batched producer whose own first launch arms the words of all its jobs (launch_pyr_facts_arm): no launch here
+  int *plane_fact_words(int slot) const { return facts.d ? facts.d->img_plain[facts.set_of(slot)] : nullptr; }
+  dsm::LevelFacts *template_fact_words() const { return facts.d ? facts.d->lv : nullptr; }
+  // dsm_frames_advance: the facts follow the buffers
+  void swap_frame_facts(int s) {
+    const int f = facts.set[s];
+    facts.set[s] = facts.back_set[s], facts.back_set[s] = f;
+    desc.img_set[s] = facts.set[s];
+  }
 };
 
 // dsm_undistorter_create: the device copy of one camera's undistortion

@@ -211,6 +211,10 @@ void launch_diag_tick_fill(hipStream_t s, int mode, int lvl, const TrackerDev *t
 void launch_diag_tick_unpack(hipStream_t s, int n, const LMState *states, const TrackerDev *const *trackers, const TrackerDev *tracker,
                              const unsigned long long *slot_ticket, ::dsm_lm_step_state *state_out, ::dsm_tick_slot_out *slot_out);
 
+// dsm_diag_eval_facts: {template fact, image fact, pose fact, fast, the bits of the five bounds} of a pose evaluation of level lvl at
+// d_pose (7 doubles) into d_out (9 ints)
+void launch_diag_eval_facts(hipStream_t s, const TrackerDev *tracker, int lvl, const double *d_pose, int *d_out);
+
 // -- tracker_kernels.hip itself --
 // descriptors of many trackers in one launch (sync_descs): d_dst[i] <- d_src[i]
 void launch_desc_scatter(hipStream_t s, int n, const TrackerDev *d_src, TrackerDev *const *d_dst);
@@ -230,12 +234,16 @@ struct TplJob {
   const float *ref[DSM_MAX_LEVELS];
   float4 *pts[DSM_MAX_LEVELS];
   int *d_n; // nlevels + 1 ints: template points per level, then the out-of-bounds flag
+  LevelFacts *facts; // the armed template-fact words of pts[] (eval_facts.hpp), one per level; null: none kept
 };
 size_t make_coarse_depth_workspace_floats(int w, int h, int nlevels, int npts);
 void launch_make_coarse_depth(hipStream_t s, int w, int h, int nlevels, const TplJob *jobs, int njobs, int max_npts, int texel_floats);
 
+// facts (eval_facts.hpp): the level's armed words, cleared / tightened from the entries as they are written; null: none kept
 void launch_interleave_template(hipStream_t s, int n, const float *u, const float *v, const float *id,
-                                const float *c, float4 *out);
+                                const float *c, float4 *out, LevelFacts *facts = nullptr);
+// the words behind dsm_tracker::announce_*: value 0 clears, 1 arms (flag 1, bounds empty); level bit masks; img_set < 0: no plane
+void launch_facts_set(hipStream_t s, TrackerFacts *f, int tpl_levels, int img_set, int img_levels, int value);
 void launch_deinterleave_template(hipStream_t s, int n, const float4 *in, float *u, float *v, float *id,
                                   float *c);
 void launch_scale_depth(hipStream_t s, int n, float4 *pts, float scale);
@@ -248,7 +256,8 @@ void launch_scale_depth_levels(hipStream_t s, const ScaleDepthArgs &a, int max_n
 
 // ---- frame_kernels.hip ----
 // makeImages (upstream DSO): the intensity plane of level 0 from the float image, of level l from level l-1
-void launch_pyramid(hipStream_t s, int w, int h, int nlevels, const float *raw, float *const *img);
+// plain (eval_facts.hpp): the armed image-fact words of the levels, cleared where a written pixel fails; null: none kept
+void launch_pyramid(hipStream_t s, int w, int h, int nlevels, const float *raw, float *const *img, int *plain = nullptr);
 // the reference's (I, dx, dy) texels out of / into an intensity plane; with d_bad != nullptr import counts the texels whose
 // gradient channels are not makeImages' central differences of channel 0 (bitwise, or beyond tol) into d_bad[0] and keeps
 // the first such index in d_bad[1]
@@ -259,7 +268,10 @@ struct PyrJob {
   const void *raw;
   float *img[DSM_MAX_LEVELS];
   const void *src; // device-visible address of the caller's pinned image (kernel copy path), else null
+  int *plain;      // the image-fact words of img[] (eval_facts.hpp), armed by launch_pyr_facts_arm; null: none kept
 };
+// arms the words of every job: the first launch of a batched pyramid build
+void launch_pyr_facts_arm(hipStream_t s, const PyrJob *d_jobs, int njobs, int nlevels);
 // raw <- src for every job, rows of row_bytes at pitch `pitch` in src (tight in raw); unit: 16, 4 or 1 bytes per access
 void launch_host_rows_copy(hipStream_t s, const PyrJob *d_jobs, int njobs, int row_bytes, int rows, size_t pitch, int unit, int max_blocks);
 void launch_pyramid_batched(hipStream_t s, int w, int h, int nlevels, const PyrJob *d_jobs, int njobs, bool u8);

@@ -290,4 +290,25 @@ void launch_diag_tick_unpack(hipStream_t s, int n, const LMState *states, const 
   hipLaunchKernelGGL(diag_tick_unpack_kernel, dim3((n + 63) / 64), dim3(64), 0, s, n, states, trackers, tracker, slot_ticket, state_out, slot_out);
 }
 
+// dsm_diag_eval_facts: the facts of a pose evaluation of level lvl at `pose`, derived as the production path derives them -- the
+// level part by make_eval_level, M and t by make_eval_rot, the pose fact by eval_chunk's own rule (one thread).
+// out = {template fact, image fact of the new left frame, pose fact, eval_fast's answer: 1 fast / 0 general}, then the bits of the
+// list's bounds {xmin, xmax, ymin, ymax, idmax} as the evaluation's inputs carry them
+__global__ void diag_eval_facts_kernel(const TrackerDev *T, int lvl, const double *pose, int *out) {
+  EvalIn e;
+  make_eval_level(*T, e, 0, lvl);
+  store_eval_facts(e, load_eval_facts(*T, 0, lvl));
+  make_eval_rot(e, 0, pose, true);
+  const TrackerFacts *F = T->facts;
+  out[0] = F && F->lv[lvl].tpl_plain == 1 ? 1 : 0;
+  out[1] = F && F->img_plain[T->img_set[0] & (kFactImageSets - 1)][lvl] == 1 ? 1 : 0;
+  out[2] = pose_fact(e.M[6], e.M[7], e.M[8], e.t[2], e.bx0, e.bx1, e.by0, e.by1, e.bid) ? 1 : 0;
+  out[3] = e.plain != 0 && out[2] ? 1 : 0;
+  out[4] = __float_as_int(e.bx0), out[5] = __float_as_int(e.bx1), out[6] = __float_as_int(e.by0), out[7] = __float_as_int(e.by1);
+  out[8] = __float_as_int(e.bid);
+}
+void launch_diag_eval_facts(hipStream_t s, const TrackerDev *tracker, int lvl, const double *d_pose, int *d_out) {
+  hipLaunchKernelGGL(diag_eval_facts_kernel, dim3(1), dim3(1), 0, s, tracker, lvl, d_pose, d_out);
+}
+
 } // namespace dsm

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(ROSEL 
     if (ROSEL == 2)
       eval_chunk_impl<MODE, LVL0, true>(c, chunk, threadIdx.x, true, red, out, arr);
     else
-      eval_chunk<MODE, LVL0>(c, chunk, threadIdx.x, true, red, out, arr);
+      eval_chunk<MODE, LVL0>(c, chunk, threadIdx.x, true, red, out, arr, MODE == 0 && LVL0 ? eval_fast(c) : 0);
     if (FUSED && threadIdx.x < 64) xwg_release(); // wave 0 stored the partial: performed at device scope before the ticket
   } else if (!FUSED) {
     return;

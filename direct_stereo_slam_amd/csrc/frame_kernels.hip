@@ -16,24 +16,36 @@ static inline int grid_for(int n, int block = 256) {
 // ------------------------------------------------------------------------------------------
 // One launch per pyramid level l: the intensities of level l+1 are the 2x2 means 0.25 * (a + b + c + d) of level l.
 // Level 0 also converts the camera image (float or "mono8" bytes, exactly) into the level-0 plane.
+// The image fact (eval_facts.hpp): every pixel of a plane passes through a register here on its way into the plane, so the thread
+// that writes it also tests it; a thread that wrote a failing pixel stores 0 into the level's armed word (plain_l for out_l,
+// plain_next for out_next; null: no word kept).  Stores of the one value 0: order-independent.
 template <typename SRC>
 __device__ __forceinline__ void pyr_level_body(int wl, int hl, const SRC *__restrict__ src, float *__restrict__ out_l,
-                                               float *__restrict__ out_next, int first, int step) {
+                                               float *__restrict__ out_next, int first, int step, int *plain_l, int *plain_next) {
   const int wn = wl >> 1, hn = hl >> 1;
   const int npx = out_l ? wl * hl : wn * hn;
+  bool ok_l = true, ok_next = true;
   for (int idx = first; idx < npx; idx += step) {
-    if (out_l) out_l[idx] = (float)src[idx];
+    if (out_l) {
+      const float v = (float)src[idx];
+      out_l[idx] = v;
+      ok_l = ok_l && pixel_plain(v);
+    }
     if (out_next && idx < wn * hn) {
       const int x = idx % wn, y = idx / wn;
       const int b = 2 * x + 2 * y * wl;
-      out_next[idx] = 0.25f * ((float)src[b] + (float)src[b + 1] + (float)src[b + wl] + (float)src[b + 1 + wl]);
+      const float v = 0.25f * ((float)src[b] + (float)src[b + 1] + (float)src[b + wl] + (float)src[b + 1 + wl]);
+      out_next[idx] = v;
+      ok_next = ok_next && pixel_plain(v);
     }
   }
+  if (!ok_l && plain_l) *plain_l = 0;
+  if (!ok_next && plain_next) *plain_next = 0;
 }
 // out_l != nullptr: level 0 (src = the camera image); else src = the plane of level l
 __global__ void pyr_level_fused_kernel(int wl, int hl, const float *__restrict__ src, float *__restrict__ out_l,
-                                       float *__restrict__ out_next) {
-  pyr_level_body<float>(wl, hl, src, out_l, out_next, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+                                       float *__restrict__ out_next, int *plain_l, int *plain_next) {
+  pyr_level_body<float>(wl, hl, src, out_l, out_next, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, plain_l, plain_next);
 }
 // the same for a batch of images (dsm_upload_images): blockIdx.y = image; U8: the level-0 source holds camera bytes
 // (main.cpp:216-217 "mono8"), converted exactly
@@ -42,14 +54,25 @@ __global__ void pyr_level_batched_kernel(int l, int nlevels, int wl, int hl, con
   const PyrJob &j = jobs[blockIdx.y];
   float *out_next = l + 1 < nlevels ? j.img[l + 1] : nullptr;
   const int first = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+  int *const plain_l = j.plain ? j.plain + l : nullptr, *const plain_next = j.plain ? j.plain + l + 1 : nullptr;
   if (l == 0) {
     if (U8)
-      pyr_level_body<unsigned char>(wl, hl, (const unsigned char *)j.raw, j.img[0], out_next, first, step);
+      pyr_level_body<unsigned char>(wl, hl, (const unsigned char *)j.raw, j.img[0], out_next, first, step, plain_l, plain_next);
     else
-      pyr_level_body<float>(wl, hl, (const float *)j.raw, j.img[0], out_next, first, step);
+      pyr_level_body<float>(wl, hl, (const float *)j.raw, j.img[0], out_next, first, step, plain_l, plain_next);
   } else {
-    pyr_level_body<float>(wl, hl, j.img[l], nullptr, out_next, first, step);
+    pyr_level_body<float>(wl, hl, j.img[l], nullptr, out_next, first, step, nullptr, plain_next);
   }
+}
+// the first launch of a batched build: every job's words read 1 until a pixel fails
+__global__ void pyr_facts_arm_kernel(const PyrJob *__restrict__ jobs, int njobs, int nlevels) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= njobs * nlevels) return;
+  int *const plain = jobs[i / nlevels].plain;
+  if (plain) plain[i % nlevels] = 1;
+}
+void launch_pyr_facts_arm(hipStream_t s, const PyrJob *d_jobs, int njobs, int nlevels) {
+  if (njobs > 0) hipLaunchKernelGGL(pyr_facts_arm_kernel, dim3(grid_for(njobs * nlevels)), dim3(256), 0, s, d_jobs, njobs, nlevels);
 }
 // The reference's texels from / against an intensity plane.  Gradients: central differences on the flat index for
 // idx in [w, w (h - 1)), zero elsewhere and where the difference is not finite (upstream DSO makeImages).
@@ -135,15 +158,17 @@ void launch_host_rows_copy(hipStream_t s, const PyrJob *d_jobs, int njobs, int r
     hipLaunchKernelGGL(host_rows_copy_kernel<unsigned char>, grid, dim3(256), 0, s, d_jobs, njobs, row_units, rows, pitch);
 }
 // raw: the level-0 float image; img[l]: the intensity planes of the pyramid levels
-void launch_pyramid(hipStream_t s, int w, int h, int nlevels, const float *raw, float *const *img) {
+void launch_pyramid(hipStream_t s, int w, int h, int nlevels, const float *raw, float *const *img, int *plain) {
   for (int l = 0; l < nlevels; l++) {
     const int wl = w >> l, hl = h >> l;
     if (l > 0 && l + 1 >= nlevels) break; // the coarsest level has nothing to produce
     hipLaunchKernelGGL(pyr_level_fused_kernel, dim3(grid_for(l == 0 ? wl * hl : (wl >> 1) * (hl >> 1))), dim3(256), 0, s, wl, hl,
-                       l == 0 ? raw : img[l], l == 0 ? img[0] : nullptr, l + 1 < nlevels ? img[l + 1] : nullptr);
+                       l == 0 ? raw : img[l], l == 0 ? img[0] : nullptr, l + 1 < nlevels ? img[l + 1] : nullptr,
+                       plain && l == 0 ? plain : nullptr, plain && l + 1 < nlevels ? plain + l + 1 : nullptr);
   }
 }
 void launch_pyramid_batched(hipStream_t s, int w, int h, int nlevels, const PyrJob *d_jobs, int njobs, bool u8) {
+  launch_pyr_facts_arm(s, d_jobs, njobs, nlevels);
   for (int l = 0; l < nlevels; l++) {
     const int wl = w >> l, hl = h >> l;
     if (l > 0 && l + 1 >= nlevels) break;
@@ -195,6 +220,7 @@ __global__ __launch_bounds__(256) void undistort_pyr_kernel(UndistortTables u, i
   const unsigned char *raw = (const unsigned char *)j.raw;
   float *out0 = j.img[0], *out1 = nlevels > 1 ? j.img[1] : nullptr;
   const int w = u.w_out, h = u.h_out, wq = (w + 1) >> 1, hq = (h + 1) >> 1, wn = w >> 1, hn = h >> 1;
+  bool ok0 = true, ok1 = true; // the image fact of levels 0 and 1, as pyr_level_body keeps it
   for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < wq * hq; q += gridDim.x * blockDim.x) {
     const int qx = q % wq, qy = q / wq, x = 2 * qx, y = 2 * qy, i = x + y * w;
     const bool right = x + 1 < w, below = y + 1 < h;
@@ -206,8 +232,15 @@ __global__ __launch_bounds__(256) void undistort_pyr_kernel(UndistortTables u, i
     if (right) out0[i + 1] = b;
     if (below) out0[i + w] = c;
     if (right && below) out0[i + w + 1] = d;
-    if (out1 && qx < wn && qy < hn) out1[qx + qy * wn] = 0.25f * (a + b + c + d);
+    ok0 = ok0 && pixel_plain(a) && pixel_plain(b) && pixel_plain(c) && pixel_plain(d); // (an absent neighbour is 0)
+    if (out1 && qx < wn && qy < hn) {
+      const float v = 0.25f * (a + b + c + d);
+      out1[qx + qy * wn] = v;
+      ok1 = ok1 && pixel_plain(v);
+    }
   }
+  if (!ok0 && j.plain) j.plain[0] = 0;
+  if (!ok1 && j.plain) j.plain[1] = 0;
 }
 template <bool HAS_G, bool HAS_VIG>
 static void launch_undistort_l0(hipStream_t s, const UndistortTables &u, int nlevels, const PyrJob *d_jobs, const dim3 &grid) {
@@ -217,6 +250,7 @@ static void launch_undistort_l0(hipStream_t s, const UndistortTables &u, int nle
     hipLaunchKernelGGL((undistort_pyr_kernel<HAS_G, HAS_VIG, false>), grid, dim3(256), 0, s, u, nlevels, d_jobs);
 }
 void launch_undistort_pyramid_batched(hipStream_t s, const UndistortTables &u, int nlevels, const PyrJob *d_jobs, int njobs) {
+  launch_pyr_facts_arm(s, d_jobs, njobs, nlevels);
   const dim3 grid0(grid_for(((u.w_out + 1) >> 1) * ((u.h_out + 1) >> 1)), njobs);
   if (u.G && u.vig)
     launch_undistort_l0<true, true>(s, u, nlevels, d_jobs, grid0);

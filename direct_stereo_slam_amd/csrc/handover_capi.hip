@@ -137,6 +137,7 @@ static int upload_images_impl(dsm_context *ctx, int n, dsm_tracker *const *track
     if (rc) return rc;
     ctx->handover.h_pyr_jobs[i].raw = raw;
     ctx->handover.h_pyr_jobs[i].src = nullptr;
+    ctx->handover.h_pyr_jobs[i].plain = trackers[i]->plane_fact_words(slots[i]); // armed by the build's first launch (launch_pyr_facts_arm)
     if (all_pinned) {
       hipPointerAttribute_t attr{};
       if (hipPointerGetAttributes(&attr, images[i]) == hipSuccess && attr.type == hipMemoryTypeHost && attr.devicePointer) {
@@ -347,6 +348,7 @@ int dsm_frames_advance(dsm_context *ctx, int n, dsm_tracker *const *trackers, co
     const size_t rb = t->raw_bytes[s];
     t->raw_bytes[s] = t->raw_back_bytes[s];
     t->raw_back_bytes[s] = rb;
+    t->swap_frame_facts(s);
     t->desc.exposure[s] = t->back_exposure[s];
     t->have_frame[s] = true;
     t->have_back[s] = false;

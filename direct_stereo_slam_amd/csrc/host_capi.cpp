@@ -10,9 +10,37 @@
 #include <string>
 #include <vector>
 
+#include "eval_facts.hpp"
 #include "loopdet_internal.hpp"
 
 extern "C" {
+
+// The rules of eval_facts.hpp as the host compiles them from the same inline functions the kernels run (-ffp-contract=off here too):
+// the pose fact of n (pose, box) pairs -- rows {M6, M7, M8, t2, xmin, xmax, ymin, ymax, idmax} -- into out[n] as 0 / 1 ...
+int dsm_pose_fact_host(int n, const float *rows9, int *out) {
+  if (n < 0 || (n && (!rows9 || !out))) return DSM_ERR_INVALID;
+  for (int i = 0; i < n; i++) {
+    const float *r = rows9 + 9 * (size_t)i;
+    out[i] = dsm::pose_fact(r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8]) ? 1 : 0;
+  }
+  return DSM_OK;
+}
+// ... and, per value v[i]: the order-preserving key, the bits of the value the key turns back into, and whether v[i] passes as an
+// inverse depth / coordinate of a template entry and as a pixel: out[4 i ..] = {key, bits, entry_plain(0, 0, v) | 2 entry_plain(v, v, 1), pixel_plain(v)}
+int dsm_fact_rules_host(int n, const float *v, int *out) {
+  if (n < 0 || (n && (!v || !out))) return DSM_ERR_INVALID;
+  for (int i = 0; i < n; i++) {
+    const int k = dsm::ordered_key(v[i]);
+    const float back = dsm::ordered_value(k);
+    int bits;
+    memcpy(&bits, &back, sizeof bits);
+    out[4 * (size_t)i] = k;
+    out[4 * (size_t)i + 1] = bits;
+    out[4 * (size_t)i + 2] = (dsm::entry_plain(0.f, 0.f, v[i]) ? 1 : 0) | (dsm::entry_plain(v[i], v[i], 1.f) ? 2 : 0);
+    out[4 * (size_t)i + 3] = dsm::pixel_plain(v[i]) ? 1 : 0;
+  }
+  return DSM_OK;
+}
 
 // LoopHandler::savePose, LoopHandler.cpp:59-80: one line per loop frame, "incoming_id x y z", std::setprecision(6) on a default
 // (%g-style) stream -- the dslam.txt / sodso.txt trajectory files the evaluation scripts of the reference read

@@ -32,7 +32,8 @@ __device__ __forceinline__ void make_eval_level(const TrackerDev &T, EvalIn &e, 
   e.pts = L.pts;
   e.img = L.img[mode == 1 ? 1 : 0]; // new left frame (:709) / right frame fh1_ (:1016)
   e.n = L.n;
-  e.ppt = pts_per_thread(L.n, T.p.geometry), e.pad0 = e.pad1 = e.pad2 = 0;
+  e.ppt = pts_per_thread(L.n, T.p.geometry), e.pad0 = 0.f;
+  e.plain = 0, e.bx0 = e.bx1 = e.by0 = e.by1 = e.bid = 0.f; // no fact established (make_eval_facts)
   e.w = L.w;
   e.h = L.h;
   if (mode == 1) { // cam-1 intrinsics (:1017-1020)
@@ -59,6 +60,29 @@ __device__ __forceinline__ void make_eval_level(const TrackerDev &T, EvalIn &e, 
     e.aff0 = 1.0f;
     e.aff1 = 0.0f;
   }
+}
+// The facts the producers of this level's list and plane left behind (eval_facts.hpp), pose mode only: the one part of the level's
+// inputs that is read through a pointer -- a round trip to memory in the step's chain, so it is asked for ONCE per level and copied to
+// the other candidate's block (begin_level).  (Held across make_eval_rot's double-precision work, which would hide the round trip,
+// the six values take tick_lm_kernel<0> from 96 to 98 registers: one wave per SIMD less.)
+struct EvalFacts {
+  int plain;
+  float bx0, bx1, by0, by1, bid;
+};
+__device__ __forceinline__ EvalFacts load_eval_facts(const TrackerDev &T, int mode, int lvl) {
+  const TrackerFacts *F = T.facts;
+  const bool known = mode == 0 && F != nullptr;
+  const LevelFacts lf = known ? F->lv[lvl] : LevelFacts{};
+  const int img_ok = known ? F->img_plain[T.img_set[0] & (kFactImageSets - 1)][lvl] : 0;
+  const int general = known ? F->force_general : 1;
+  EvalFacts f;
+  f.plain = (lf.tpl_plain == 1 && img_ok == 1 && !general) ? 1 : 0;
+  f.bx0 = ordered_value(lf.xmin), f.bx1 = ordered_value(lf.xmax), f.by0 = ordered_value(lf.ymin), f.by1 = ordered_value(lf.ymax);
+  f.bid = ordered_value(lf.idmax);
+  return f;
+}
+__device__ __forceinline__ void store_eval_facts(EvalIn &e, const EvalFacts &f) {
+  e.plain = f.plain, e.bx0 = f.bx0, e.bx1 = f.bx1, e.by0 = f.by0, e.by1 = f.by1, e.bid = f.bid;
 }
 // pose (mode 0): M = R K^-1 (:715), t (:716); loop-closure pose (mode 2, PoseEstimator.cpp:155-163): M = R.  e.Ki holds the level's K^-1.
 __device__ __forceinline__ void make_eval_rot(EvalIn &e, int mode, const double pose[7], bool st) {
@@ -109,7 +133,9 @@ __device__ __forceinline__ void make_eval_cutoff(const TrackerDev &T, EvalIn &e,
 __device__ __forceinline__ void make_eval_any(const TrackerDev &T, LMState &S, int mode, int lvl, const double pose[7], const double aff[2],
                               float scale, float cutoff, bool residual_only = false) {
   EvalIn &e = S.in;
+  const EvalFacts facts = load_eval_facts(T, mode, lvl); // (asked for in front of the level's own copies)
   make_eval_level(T, e, mode, lvl);
+  store_eval_facts(e, facts);
   if (mode == 1) {
     e.scale = scale;
   } else {
@@ -129,6 +155,8 @@ __device__ __forceinline__ void begin_level(const TrackerDev &T, LMState &S, int
   const float cutoff = T.p.coarse_cutoff_th * S.level_cutoff_repeat;
   make_eval_any(T, S, S.is_scale, lvl, S.cur, S.aff_cur, S.scale_cur, cutoff);
   make_eval_level(T, S.spec_in, S.is_scale, lvl); // (the speculative candidate's block: a proposal writes its own part only)
+  S.spec_in.plain = S.in.plain, S.spec_in.bx0 = S.in.bx0, S.spec_in.bx1 = S.in.bx1, S.spec_in.by0 = S.in.by0, S.spec_in.by1 = S.in.by1;
+  S.spec_in.bid = S.in.bid; // (the level's facts: the same for both candidates)
 }
 
 // iteration bound of a level: maxIterations[lvl] (:463,:505 / :862,:897), or the benchmark schedule's K (dsm_params.fixed_schedule)

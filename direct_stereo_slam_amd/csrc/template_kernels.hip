@@ -185,6 +185,51 @@ __global__ __launch_bounds__(1024) void tpl_emit_scan_kernel(const TplJob *__res
   if (threadIdx.x == 0) J.d_n[lvl] = carry;
 }
 
+// The template fact (eval_facts.hpp) of the entries a thread writes, kept where the entry is in registers: note() per written entry,
+// commit() once at the end of the kernel by EVERY thread of the workgroup (full waves, at most 1024 threads: it exchanges across the
+// wave, then across the waves through LDS behind a barrier).  The flag is stored as 0 on failure into the armed word; the bounds tighten
+// by integer atomics on order-preserving keys: exact, whatever the order of arrival.  One thread per workgroup issues them, and only
+// where its value would move the bound it reads (a bound only ever tightens, so a value that does not beat what is read -- however
+// stale -- cannot beat the final one either): without both, a level-0 list's 7 k waves queued 37 k atomics on one cache line, 95 us
+// for a 4 us kernel.  F null (workgroup-uniform): nothing is kept.
+struct EntryFacts {
+  bool ok = true;
+  int x0 = kKeyMinInit, x1 = kKeyMaxInit, y0 = kKeyMinInit, y1 = kKeyMaxInit, id1 = kKeyMaxInit;
+  __device__ __forceinline__ void note(float x, float y, float id) {
+    ok = ok && entry_plain(x, y, id);
+    const int kx = ordered_key(x), ky = ordered_key(y), ki = ordered_key(id);
+    x0 = kx < x0 ? kx : x0, x1 = kx > x1 ? kx : x1, y0 = ky < y0 ? ky : y0, y1 = ky > y1 ? ky : y1, id1 = ki > id1 ? ki : id1;
+  }
+  __device__ __forceinline__ void commit(LevelFacts *F) {
+    if (!F) return;
+    __shared__ int part[16][6]; // per wave: {failed, x0, x1, y0, y1, id1}
+    const int bad = __any(!ok) ? 1 : 0;
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int a0 = __shfl_xor(x0, d), a1 = __shfl_xor(x1, d), b0 = __shfl_xor(y0, d), b1 = __shfl_xor(y1, d), c1 = __shfl_xor(id1, d);
+      x0 = a0 < x0 ? a0 : x0, x1 = a1 > x1 ? a1 : x1, y0 = b0 < y0 ? b0 : y0, y1 = b1 > y1 ? b1 : y1, id1 = c1 > id1 ? c1 : id1;
+    }
+    const int wave = threadIdx.x >> 6, nwaves = (blockDim.x + 63) >> 6;
+    if ((threadIdx.x & 63) == 0) part[wave][0] = bad, part[wave][1] = x0, part[wave][2] = x1, part[wave][3] = y0, part[wave][4] = y1, part[wave][5] = id1;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    int any_bad = 0;
+    for (int w = 0; w < nwaves; w++) {
+      any_bad |= part[w][0];
+      x0 = part[w][1] < x0 ? part[w][1] : x0, x1 = part[w][2] > x1 ? part[w][2] : x1;
+      y0 = part[w][3] < y0 ? part[w][3] : y0, y1 = part[w][4] > y1 ? part[w][4] : y1, id1 = part[w][5] > id1 ? part[w][5] : id1;
+    }
+    if (any_bad) F->tpl_plain = 0;
+    if (x0 <= x1) { // the workgroup wrote an entry
+      const volatile LevelFacts *R = F;
+      if (x0 < R->xmin) atomicMin(&F->xmin, x0);
+      if (x1 > R->xmax) atomicMax(&F->xmax, x1);
+      if (y0 < R->ymin) atomicMin(&F->ymin, y0);
+      if (y1 > R->ymax) atomicMax(&F->ymax, y1);
+      if (id1 > R->idmax) atomicMax(&F->idmax, id1);
+    }
+  }
+};
+
 __global__ __launch_bounds__(kEmitThreads) void tpl_emit_write_kernel(const TplJob *__restrict__ jobs, int w, int h, int px_total, int lvl,
                                                                       int nitems, int wi, int wl, int off, int texel_floats) {
   const TplJob J = jobs[blockIdx.y];
@@ -208,13 +253,15 @@ __global__ __launch_bounds__(kEmitThreads) void tpl_emit_write_kernel(const TplJ
   }
   __syncthreads();
   int pos = block_offset[blockIdx.x];
+  EntryFacts ef;
 #pragma unroll
   for (int j = 0; j < kEmitItems; j++) {
     int off2 = pos;
     for (int w2 = 0; w2 < wave; w2++) off2 += wave_cnt[j][w2];
-    if (v[j]) pts[off2 + before[j]] = e[j];
+    if (v[j]) pts[off2 + before[j]] = e[j], ef.note(e[j].x, e[j].y, e[j].z);
     pos += wave_cnt[j][0] + wave_cnt[j][1] + wave_cnt[j][2] + wave_cnt[j][3];
   }
+  ef.commit(J.facts ? J.facts + lvl : nullptr);
 }
 
 // floats of a job's workspace (everything but its points, which live in the call's point region)
@@ -264,9 +311,28 @@ void launch_make_coarse_depth(hipStream_t s, int w, int h, int nlevels, const Tp
 // ------------------------------------------------------------------------------------------
 __global__ void interleave_kernel(int n, const float *__restrict__ u, const float *__restrict__ v,
                                   const float *__restrict__ id, const float *__restrict__ c,
-                                  float4 *__restrict__ out) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    out[i] = make_float4(u[i], v[i], id[i], c[i]);
+                                  float4 *__restrict__ out, LevelFacts *facts) {
+  EntryFacts ef;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float4 e = make_float4(u[i], v[i], id[i], c[i]);
+    out[i] = e;
+    ef.note(e.x, e.y, e.z);
+  }
+  ef.commit(facts);
+}
+// the words behind dsm_tracker::announce_template_write / announce_plane_write (one thread)
+__global__ void facts_set_kernel(TrackerFacts *f, int tpl_levels, int img_set, int img_levels, int value) {
+  for (int l = 0; l < kFactLevels; l++) {
+    if (tpl_levels >> l & 1) {
+      LevelFacts &L = f->lv[l];
+      L.tpl_plain = value;
+      L.xmin = L.ymin = kKeyMinInit, L.xmax = L.ymax = L.idmax = kKeyMaxInit;
+    }
+    if (img_set >= 0 && (img_levels >> l & 1)) f->img_plain[img_set][l] = value;
+  }
+}
+void launch_facts_set(hipStream_t s, TrackerFacts *f, int tpl_levels, int img_set, int img_levels, int value) {
+  if (f) hipLaunchKernelGGL(facts_set_kernel, dim3(1), dim3(1), 0, s, f, tpl_levels, img_set < kFactImageSets ? img_set : -1, img_levels, value);
 }
 __global__ void deinterleave_kernel(int n, const float4 *__restrict__ in, float *u, float *v, float *id,
                                     float *c) {
@@ -288,8 +354,8 @@ static inline int grid_for(int n, int block = 256) {
 }
 
 void launch_interleave_template(hipStream_t s, int n, const float *u, const float *v, const float *id,
-                                const float *c, float4 *out) {
-  if (n > 0) hipLaunchKernelGGL(interleave_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, u, v, id, c, out);
+                                const float *c, float4 *out, LevelFacts *facts) {
+  if (n > 0) hipLaunchKernelGGL(interleave_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, u, v, id, c, out, facts);
 }
 void launch_deinterleave_template(hipStream_t s, int n, const float4 *in, float *u, float *v, float *id,
                                   float *c) {

@@ -179,6 +179,18 @@ int check_ready(dsm_tracker *t, int mode) {
 
 } // namespace dsm
 
+// ---- the owner of the facts (dsm_internal.hpp): the only writers of the words from the host side ----
+int dsm_tracker::announce_template_write(hipStream_t s, FactUse use) {
+  dsm::launch_facts_set(s, facts.d, (1 << nlevels) - 1, -1, 0, use == kFactArm ? 1 : 0);
+  DSM_HIP(hipGetLastError());
+  return DSM_OK;
+}
+int dsm_tracker::announce_plane_write(int slot, hipStream_t s, FactUse use) {
+  dsm::launch_facts_set(s, facts.d, 0, facts.set_of(slot), (1 << nlevels) - 1, use == kFactArm ? 1 : 0);
+  DSM_HIP(hipGetLastError());
+  return DSM_OK;
+}
+
 using namespace dsm;
 
 extern "C" {
@@ -234,6 +246,10 @@ static int tracker_create_fill(dsm_tracker *t, dsm_context *ctx, int w, int h, i
     D.lv[l].n = 0;
   }
   desc_cam1(D, nlevels, K1);
+  DSM_HIP(hipMalloc(&t->facts.d, sizeof(TrackerFacts)));
+  DSM_HIP(hipMemsetAsync(t->facts.d, 0, sizeof(TrackerFacts), ctx->stream)); // nothing established
+  D.facts = t->facts.d;
+  D.img_set[0] = t->facts.set[0], D.img_set[1] = t->facts.set[1];
   DSM_HIP(hipMalloc(&t->d_desc, sizeof(TrackerDev)));
   t->desc_dirty = true;
   DSM_HIP(hipStreamSynchronize(ctx->stream)); // the zero fills are through before any other stream may write these buffers
@@ -256,6 +272,7 @@ int dsm_tracker_destroy(dsm_tracker *t) {
     for (int l = 0; l < DSM_MAX_LEVELS; l++) hipFree(t->d_img_back[s][l]);
   }
   hipFree(t->d_desc);
+  hipFree(t->facts.d);
   delete t;
   return DSM_OK;
 }
@@ -281,6 +298,7 @@ int dsm_tracker_set_ref(dsm_tracker *t, int ref_frame_id, double ref_aff_a, doub
   A.work.take(sizeof(float) * 4 * (size_t)t->w * t->h);
   int rc = A.bind(ctx);
   if (rc) return rc;
+  if ((rc = t->announce_template_write(ctx->stream, dsm_tracker::kFactArm))) return rc; // interleave_kernel sees every entry it writes
   for (int l = 0; l < t->nlevels; l++) {
     const size_t nl = n[l];
     float *su = A.dev_work<float>(), *sv = su + nl, *si = sv + nl, *sc = si + nl;
@@ -289,7 +307,7 @@ int dsm_tracker_set_ref(dsm_tracker *t, int ref_frame_id, double ref_aff_a, doub
       DSM_HIP(hipMemcpyAsync(sv, pc_v[l], nl * 4, hipMemcpyHostToDevice, ctx->stream));
       DSM_HIP(hipMemcpyAsync(si, pc_idepth[l], nl * 4, hipMemcpyHostToDevice, ctx->stream));
       DSM_HIP(hipMemcpyAsync(sc, pc_color[l], nl * 4, hipMemcpyHostToDevice, ctx->stream));
-      launch_interleave_template(ctx->stream, (int)nl, su, sv, si, sc, t->d_pts[l]);
+      launch_interleave_template(ctx->stream, (int)nl, su, sv, si, sc, t->d_pts[l], t->template_fact_words() ? t->template_fact_words() + l : nullptr);
     }
     DSM_HIP(hipStreamSynchronize(ctx->stream)); // staging buffer is reused by the next level
     t->desc.lv[l].n = (int)nl;
@@ -371,6 +389,8 @@ int dsm_set_refs_from_points(dsm_context *ctx, int n_jobs, const dsm_ref_job *jo
     T.ws = d_ws + off[j];
     T.d_n = d_cnt + (size_t)j * (DSM_MAX_LEVELS + 2);
     for (int l = 0; l < t->nlevels; l++) T.ref[l] = J.frame_owner->d_img[J.slot][l], T.pts[l] = t->d_pts[l];
+    if ((rc = t->announce_template_write(ctx->stream, dsm_tracker::kFactArm))) return rc; // tpl_emit_write_kernel sees every entry it writes
+    T.facts = t->template_fact_words();
   }
   if ((rc = A.upload())) return rc;
   launch_make_coarse_depth(ctx->stream, t0->w, t0->h, t0->nlevels, d_tab, n_jobs, max_npts, kTexel);
@@ -381,8 +401,10 @@ int dsm_set_refs_from_points(dsm_context *ctx, int n_jobs, const dsm_ref_job *jo
   for (int j = 0; j < n_jobs; j++)
     for (int l = 0; l <= jobs[j].t->nlevels; l++) h_n[(size_t)j * (DSM_MAX_LEVELS + 1) + l] = h_cnt[(size_t)j * (DSM_MAX_LEVELS + 2) + l];
   for (int j = 0; j < n_jobs; j++)
-    if (h_n[(size_t)j * (DSM_MAX_LEVELS + 1) + jobs[j].t->nlevels]) // a point projected outside the image: the reference would corrupt memory (:160)
+    if (h_n[(size_t)j * (DSM_MAX_LEVELS + 1) + jobs[j].t->nlevels]) { // a point projected outside the image: the reference would corrupt memory (:160)
+      for (int k = 0; k < n_jobs; k++) (void)jobs[k].t->announce_template_write(ctx->stream, dsm_tracker::kFactClear); // (the counts are not taken over)
       return invalid("dsm_tracker_set_ref_from_points: point outside the level-0 image");
+    }
   for (int j = 0; j < n_jobs; j++) {
     const dsm_ref_job &J = jobs[j];
     dsm_tracker *t = J.t;
@@ -421,6 +443,9 @@ int dsm_tracker_scale_depth(dsm_tracker *t, float scale) {
   // one launch over all levels, enqueued on the context's stream and NOT waited for: everything that reads the template afterwards --
   // evaluations, the streaming form's advances (their stream groups fork from this stream), dsm_tracker_get_template -- is ordered
   // behind it there (eight keyframes' calls were 0.24 of the 1.9 ms between two advances of 128 concurrent sequences)
+  // (the new inverse depths need not keep the template fact: cleared; the next reference establishes it again)
+  const int frc = t->announce_template_write(t->ctx->stream, dsm_tracker::kFactClear);
+  if (frc) return frc;
   ScaleDepthArgs a;
   a.nlevels = t->nlevels;
   int max_n = 0;
@@ -475,6 +500,7 @@ int dsm_tracker_upload_frame(dsm_tracker *t, int slot, const float *const *dIp, 
   for (int l = 0; l < DSM_MAX_LEVELS; l++) h_bad[2 * l] = 0, h_bad[2 * l + 1] = 0x7FFFFFFF;
   const bool check = t->params.frame_check != 0;
   if (check) DSM_HIP(hipMemcpyAsync(d_bad, h_bad, sizeof h_bad, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = t->announce_plane_write(slot, ctx->stream, dsm_tracker::kFactClear))) return rc; // dip_import_kernel keeps no fact
   for (int l = 0; l < t->nlevels; l++) {
     const int wl = t->w >> l, hl = t->h >> l;
     DSM_HIP(hipMemcpyAsync(d_stage, dIp[l], (size_t)wl * hl * 12, hipMemcpyHostToDevice, ctx->stream));
@@ -503,6 +529,8 @@ int dsm_tracker_upload_intensity(dsm_tracker *t, int slot, const float *const *I
   if (!t || !I || slot < 0 || slot > 1) return invalid("dsm_tracker_upload_intensity: bad argument");
   dsm_context *ctx = t->ctx;
   DSM_HIP(hipSetDevice(ctx->device));
+  const int frc = t->announce_plane_write(slot, ctx->stream, dsm_tracker::kFactClear); // raw copies: nobody looks at the pixels
+  if (frc) return frc;
   for (int l = 0; l < t->nlevels; l++) {
     if (!I[l]) return invalid("dsm_tracker_upload_intensity: null level");
     DSM_HIP(hipMemcpyAsync(t->d_img[slot][l], I[l], sizeof(float) * (size_t)(t->w >> l) * (t->h >> l), hipMemcpyHostToDevice, ctx->stream));
@@ -525,7 +553,9 @@ int dsm_tracker_upload_image(dsm_tracker *t, int slot, const float *image, float
   if (!t->d_raw[slot]) DSM_HIP(hipMalloc(&t->d_raw[slot], npx0 * sizeof(float)));
   DSM_HIP(hipMemcpyAsync(t->d_raw[slot], image, npx0 * 4, hipMemcpyHostToDevice, ctx->stream));
   DSM_HIP(hipEventRecord(ctx->handover.copy_event, ctx->stream));
-  launch_pyramid(ctx->stream, t->w, t->h, t->nlevels, t->d_raw[slot], t->d_img[slot]);
+  const int frc = t->announce_plane_write(slot, ctx->stream, dsm_tracker::kFactArm); // pyr_level_fused_kernel sees every pixel it writes
+  if (frc) return frc;
+  launch_pyramid(ctx->stream, t->w, t->h, t->nlevels, t->d_raw[slot], t->d_img[slot], t->plane_fact_words(slot));
   DSM_HIP(hipGetLastError());
   DSM_HIP(hipEventSynchronize(ctx->handover.copy_event));
   t->desc.exposure[slot] = ab_exposure;

@@ -158,6 +158,8 @@ struct EvalConsts {
   float t[3];
   float aff0, aff1, b0, scale, cutoff, max_energy;
   int residual_only; // EvalIn::residual_only
+  int plain;         // EvalIn::plain
+  float bx0, bx1, by0, by1, bid; // EvalIn's template bounds
 };
 // wave-uniform evaluation inputs: global memory (`in`: a const DSM_GLOBAL EvalIn, scalar loads) -> SGPRs.  A macro: as a function that
 // takes the address-space-qualified reference the same statements compile to other code in eval_kernel and tick_eval_kernel
@@ -170,6 +172,7 @@ struct EvalConsts {
     c.t[0] = in.t[0], c.t[1] = in.t[1], c.t[2] = in.t[2];                                                                      \
     c.aff0 = in.aff0, c.aff1 = in.aff1, c.b0 = in.b0, c.scale = in.scale, c.cutoff = in.cutoff, c.max_energy = in.max_energy; \
     c.residual_only = in.residual_only;                                                                                        \
+    c.plain = in.plain, c.bx0 = in.bx0, c.bx1 = in.bx1, c.by0 = in.by0, c.by1 = in.by1, c.bid = in.bid;                         \
   } while (0)
 // wave-uniform evaluation inputs: LDS -> SGPRs
 __device__ __forceinline__ void eval_consts_from_lds(const EvalIn &in, EvalConsts &c) {
@@ -190,6 +193,8 @@ __device__ __forceinline__ void eval_consts_from_lds(const EvalIn &in, EvalConst
   c.aff0 = rf(in.aff0), c.aff1 = rf(in.aff1), c.b0 = rf(in.b0), c.scale = rf(in.scale);
   c.cutoff = rf(in.cutoff), c.max_energy = rf(in.max_energy);
   c.residual_only = __builtin_amdgcn_readfirstlane(in.residual_only);
+  c.plain = __builtin_amdgcn_readfirstlane(in.plain);
+  c.bx0 = rf(in.bx0), c.bx1 = rf(in.bx1), c.by0 = rf(in.by0), c.by1 = rf(in.by1), c.bid = rf(in.bid);
 }
 
 // One chunk of one evaluation by 256 threads (tid = 0..255 inside the chunk's thread group):
@@ -212,7 +217,10 @@ __device__ __forceinline__ void eval_consts_from_lds(const EvalIn &in, EvalConst
 // arithmetic between them -- and the same A/B now gives + 1.3 % frames/s, the kernel 0.61 -> 0.63 of peak: profiles/r06_ab_deep_all_levels.log)
 // It also keeps the warp's twelve wave-uniform constants in VGPRs (pose mode; see where they are pinned below); the one-point loop's
 // kernels of five waves per SIMD have no registers for that.
-template <int MODE, bool LVL0, bool RO, bool DEEP = LVL0>
+// FAST (mode 0; eval_chunk decides, wave-uniform): the template, image and pose facts of eval_facts.hpp hold for this evaluation, so
+// the tests they settle are not made -- the quotients' range test with its IEEE-division path, new_idepth > 0, the finiteness tests of
+// g1, g2 and h0 with the tap refetch.  Each of them is all-true on every listed lane under the facts: the same masks, the same bits.
+template <int MODE, bool LVL0, bool RO, bool DEEP = LVL0, bool FAST = false>
 __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, int tid, bool active, float (*red)[kNumSlots],
                                                 float *out, int *arrive = nullptr) {
   const int n = c.n;
@@ -282,7 +290,7 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
         const float apt2 = __builtin_fabsf(pt2);
         lmask ordinary = DSM_FCMP(apt2, 0x1p-33f, kOGE) & DSM_FCMP(apt2, 0x1p32f, kOLT);
         if (MODE != 2) ordinary &= DSM_FCMP(__builtin_fabsf(id), 0x1p-64f, kOGE) | DSM_FCMP(id, 0.0f, kOEQ);
-        if (__builtin_expect(ordinary != full, 0)) {
+        if (!FAST && __builtin_expect(ordinary != full, 0)) {
           W.u = pt0 / pt2;
           W.v = pt1 / pt2;
           W.new_idepth = (MODE == 2 ? 1.0f : id) / pt2; // PoseEstimator.cpp:197: 1 / pt[2]
@@ -303,8 +311,8 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
       W.refColor = p.w;
       W.x = x, W.y = y, W.id = id;
       // :786 / :1102 (every comparison is false for a NaN, as in the reference)
-      W.inb = in_list & DSM_FCMP(Ku, 2.0f, kOGT) & DSM_FCMP(Kv, 2.0f, kOGT) & DSM_FCMP(Ku, wm3, kOLT) & DSM_FCMP(Kv, hm3, kOLT) &
-              DSM_FCMP(W.new_idepth, 0.0f, kOGT);
+      W.inb = in_list & DSM_FCMP(Ku, 2.0f, kOGT) & DSM_FCMP(Kv, 2.0f, kOGT) & DSM_FCMP(Ku, wm3, kOLT) & DSM_FCMP(Kv, hm3, kOLT);
+      if (!FAST) W.inb &= DSM_FCMP(W.new_idepth, 0.0f, kOGT); // (FAST: id >= 2^-64 and 2^-21 <= pt2 < 2^31, the product is positive or +inf)
       taps_load<!RO>(img, Ku, Kv, pitch, W.inb, safe_off, T); // (unusable lanes fetch around texel (2, 2))
     };
     auto stage_b = [&](const Warped &W, const Taps &T) {
@@ -312,13 +320,13 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
       taps_interp<false, !RO>(T, h0, g1, g2);
       // makeImages' "non-finite gradient -> 0", the rare path: the taps are fetched again (so that the common path
       // does not keep twelve registers alive for it) and the replacement is applied tap by tap
-      if (!RO && __builtin_expect((W.inb & ~(lanes_finite(g1) & lanes_finite(g2))) != 0ull, 0)) {
+      if (!FAST && !RO && __builtin_expect((W.inb & ~(lanes_finite(g1) & lanes_finite(g2))) != 0ull, 0)) {
         Taps Tx;
         taps_load(img, fxl * W.u + cxl, fyl * W.v + cyl, wl, W.inb, safe_off, Tx);
         taps_interp<true>(Tx, h0, g1, g2);
       }
       const float refColor = W.refColor;
-      const lmask fin = W.inb & lanes_finite(h0); // :791
+      const lmask fin = FAST ? W.inb : W.inb & lanes_finite(h0); // :791 (FAST: a bilinear sum of pixels of magnitude <= 2^100)
       const float residual = MODE != 1 ? h0 - (aff0 * refColor + aff1) : h0 - refColor; // :793 / :1109
       const float ar = __builtin_fabsf(residual);
       // Huber weight (:794-795): 1 for |r| < huber, huber / |r| beyond.  It is off the per-point decision path (in/out, cut-off):
@@ -610,13 +618,32 @@ __device__ __forceinline__ void eval_chunk_impl(const EvalConsts &c, int chunk, 
   }
 }
 
+// The three facts of a pose evaluation (eval_facts.hpp), once per chunk: the template and image facts travel with the evaluation's
+// inputs (EvalIn::plain and the list's bounds), the pose fact is derived here from this evaluation's M and t -- a dozen vector
+// instructions on wave-uniform values, the result an SGPR.  Depends on the problem's own data alone: every form, every chunk of an
+// evaluation decides alike.
+__device__ __forceinline__ int eval_fast(const EvalConsts &c) {
+  const bool fast = c.plain != 0 && pose_fact(c.M[6], c.M[7], c.M[8], c.t[2], c.bx0, c.bx1, c.by0, c.by1, c.bid);
+  return __builtin_amdgcn_readfirstlane((int)fast);
+}
+// fast: eval_fast(c) from the callers that have the FAST instantiation built in (mode 0, the two-point loop: the tick engine's kernel and
+// the chains on every level, the launch form's level-0 kernel), 0 = the general instantiation (everything else; queue_kernel, whose
+// spill budget has no room for two more loops).  Where the decision is taken matters to the register allocator: with eval_fast inside
+// this function tick_eval_kernel<0, false> spilled two registers in the general loop's tap-refetch block (12 bytes of scratch).
 template <int MODE, bool LVL0, bool DEEP = LVL0>
 __device__ __forceinline__ void eval_chunk(const EvalConsts &c, int chunk, int tid, bool active, float (*red)[kNumSlots],
-                                           float *out, int *arrive = nullptr) {
-  if (c.residual_only) // wave-uniform
-    eval_chunk_impl<MODE, LVL0, true, DEEP>(c, chunk, tid, active, red, out, arrive);
-  else
-    eval_chunk_impl<MODE, LVL0, false, DEEP>(c, chunk, tid, active, red, out, arrive);
+                                           float *out, int *arrive = nullptr, int fast = 0) {
+  const bool take_fast = MODE == 0 && DEEP && fast != 0; // wave-uniform
+  if (!take_fast) {
+    if (c.residual_only) // wave-uniform
+      eval_chunk_impl<MODE, LVL0, true, DEEP>(c, chunk, tid, active, red, out, arrive);
+    else
+      eval_chunk_impl<MODE, LVL0, false, DEEP>(c, chunk, tid, active, red, out, arrive);
+  } else if (c.residual_only) {
+    eval_chunk_impl<MODE, LVL0, true, DEEP, MODE == 0 && DEEP>(c, chunk, tid, active, red, out, arrive);
+  } else {
+    eval_chunk_impl<MODE, LVL0, false, DEEP, MODE == 0 && DEEP>(c, chunk, tid, active, red, out, arrive);
+  }
 }
 
 // a chunk of whatever level inside the kernels that run at four waves per SIMD (tick_eval_kernel, the chains): the two-point loop on
@@ -624,10 +651,11 @@ __device__ __forceinline__ void eval_chunk(const EvalConsts &c, int chunk, int t
 // compile to other code in all ten kernels that use it (tools/experiments/README.md, "Kernel source tidy-ups").
 #define DSM_EVAL_CHUNK_DEEP(MODE, c, lvl, chunk, tid, red, out)          \
   do {                                                                   \
+    const int fast_ = MODE == 0 ? eval_fast(c) : 0;                      \
     if (lvl == 0)                                                        \
-      eval_chunk<MODE, true>(c, chunk, tid, true, red, out);             \
+      eval_chunk<MODE, true>(c, chunk, tid, true, red, out, nullptr, fast_);             \
     else                                                                 \
-      eval_chunk<MODE, false, true>(c, chunk, tid, true, red, out);      \
+      eval_chunk<MODE, false, true>(c, chunk, tid, true, red, out, nullptr, fast_);      \
   } while (0)
 
 // Host side, for the launchers of the forms: a run-time selector as a compile-time constant.  Calls f(Const<I>{}) with I = v for

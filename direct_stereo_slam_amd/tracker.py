@@ -651,6 +651,20 @@ class TrackerAndScaler:
                                           None, None, C.byref(n)))
         return rs, H.reshape(8, 8), b, n.value
 
+    def diagEvalFacts(self, lvl, pose, with_bounds=False):
+        """the facts that pick the instantiation of a pose evaluation of level lvl at pose (dsm_diag_eval_facts), derived on the
+        device by the production code; returns (template fact, image fact, pose fact, fast) as 0 / 1 -- with_bounds: and the
+        list's bounds (umin, umax, vmin, vmax, idepth max) as a float32 array"""
+        pose = np.ascontiguousarray(pose, np.float64)
+        out, bounds = np.zeros(4, np.int32), np.zeros(5, np.float32)
+        check(self.L.dsm_diag_eval_facts(self.h, lvl, _dp(pose), out.ctypes.data_as(c_int_p), _fp(bounds)))
+        facts = tuple(int(v) for v in out)
+        return (facts, bounds) if with_bounds else facts
+
+    def diagForceGeneral(self, on=True):
+        """evaluations of this tracker take the general per-point code whatever the facts say (dsm_diag_tracker_force_general)"""
+        check(self.L.dsm_diag_tracker_force_general(self.h, int(bool(on))))
+
     def diagEvalScale(self, lvl, scale, cutoff, form=0, residual_only=False):
         """calcResScale likewise; returns (rs[6], h00, h01, n_warped)"""
         rs, H, b, n = np.zeros(6), C.c_float(), C.c_float(), C.c_int()

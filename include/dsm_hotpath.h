@@ -383,6 +383,28 @@ int dsm_tracker_calc_res_scale(dsm_tracker *t, int lvl, float scale, float cutof
  * (H, b, Hs, bs come back as zeros).  A bad mode, form or level is DSM_ERR_INVALID with nothing written.  No production path calls this. */
 int dsm_diag_single_eval(dsm_tracker *t, int mode, int lvl, const double pose[7], const double aff[2], float scale, float cutoff_th,
                          int form, int residual_only, double rs[6], double H[64], double b[8], float *Hs, float *bs, int *n_warped);
+/* test aid (no reference counterpart): the facts that decide which instantiation of the per-point stages a pose evaluation (mode 0)
+ * of level lvl at pose {qx,qy,qz,qw,tx,ty,tz} runs, derived on the device by the code the production path runs (one thread):
+ *   out[0]  the template fact of the level's list: every entry has 2^-64 <= idepth and finite u, v;
+ *   out[1]  the image fact of the new left frame's plane of that level: every pixel has |I| <= 2^100;
+ *   out[2]  the pose fact: 2^-21 <= pt2 < 2^31 for every point inside the list's bounds (meaningful while out[0] is 1);
+ *   out[3]  1 if the evaluation takes the instantiation without the settled checks where its kernel has one (all three facts, the
+ *           tracker not forced general; the tick engine's kernel and the chains have one on every level, the launch form's kernel on
+ *           level 0, the work-queue kernel none), else 0.
+ * bounds (may be NULL): the list's {umin, umax, vmin, vmax, idepth max} as the evaluation's inputs carry them (meaningful while out[0]
+ * is 1; an empty list's are {+inf, -inf, +inf, -inf, -inf}).
+ * DSM_ERR_INVALID with nothing written for a NULL t, pose or out or a bad level.  No production path calls this. */
+int dsm_diag_eval_facts(dsm_tracker *t, int lvl, const double pose[7], int out[4], float bounds[5]);
+/* host forms of the rules behind those facts, compiled from the inline functions the kernels run (no device needed):
+ * dsm_pose_fact_host: the pose fact of n rows {M6, M7, M8, t2, xmin, xmax, ymin, ymax, idmax} into out[n] (0 / 1);
+ * dsm_fact_rules_host: per value v[i], out[4 i ..] = {the order-preserving integer key the bounds are kept as, the bits of the value that
+ * key turns back into, bit 0: v passes as a template entry's inverse depth, bit 1: as its coordinate, whether v passes as a pixel}.
+ * DSM_ERR_INVALID for a negative n or a NULL array with n > 0. */
+int dsm_pose_fact_host(int n, const float *rows9, int *out);
+int dsm_fact_rules_host(int n, const float *v, int *out);
+/* test aid: on != 0 makes every evaluation of this tracker whose level begins from here on take the general instantiation whatever the
+ * facts say (the facts themselves are left alone); on = 0 ends that.  Waits for the context's stream.  No production path calls this. */
+int dsm_diag_tracker_force_general(dsm_tracker *t, int on);
 /* test aid (no reference counterpart): ONE evaluation of the loop-closure alignment (mode 2: PoseEstimator::calcRes + calcGSSSE,
  * PoseEstimator.cpp:84-296) at level lvl, pose {qx,qy,qz,qw,tx,ty,tz} and affine pair aff.  The inputs are those of
  * dsm_pose_estimator_estimate and are loaded by the same function (makeK(new_cam), the points narrowed to float, the reference with
