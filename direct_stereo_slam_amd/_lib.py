@@ -252,6 +252,21 @@ class StepJob(C.Structure):
     ]
 
 
+class OptimizeParams(C.Structure):
+    _fields_ = [
+        ("lambda_init", C.c_double), ("lambda_accept_fac", C.c_double), ("lambda_reject_fac", C.c_double), ("fixed_lambda", C.c_double),
+        ("min_iterations", C.c_int), ("force_accept", C.c_int), ("step_momentum", C.c_int),
+    ]
+
+
+class OptimizeJob(C.Structure):
+    _fields_ = [
+        ("step", StepJob), ("max_iterations", C.c_int), ("n_iterations", c_int_p), ("n_passes", c_int_p), ("pattern", C.POINTER(C.c_ubyte)),
+        ("pass_energy", c_double_p), ("pass_lambda", c_double_p), ("iter_stepsize", c_float_p), ("iter_can_break", C.POINTER(C.c_ubyte)),
+        ("last_energy", c_double_p), ("lambda_out", c_double_p), ("frame_energy_th_out", c_float_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -514,6 +529,11 @@ SYMBOLS = {
     "dsm_step_params_default": (C.c_int, [C.POINTER(StepParams)]),
     "dsm_window_step_batch": (C.c_int, [_vp, C.c_int, C.POINTER(StepJob), C.POINTER(LinearizeParams), C.POINTER(StepParams)]),
     "dsm_window_step_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(StepJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams), C.POINTER(StepParams)]),
+    "dsm_optimize_params_default": (C.c_int, [C.POINTER(OptimizeParams)]),
+    "dsm_window_optimize_batch": (C.c_int, [_vp, C.c_int, C.POINTER(OptimizeJob), C.POINTER(LinearizeParams), C.POINTER(StepParams),
+                                            C.POINTER(OptimizeParams)]),
+    "dsm_window_optimize_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(OptimizeJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams),
+                                           C.POINTER(StepParams), C.POINTER(OptimizeParams)]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

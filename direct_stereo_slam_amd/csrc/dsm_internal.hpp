@@ -221,6 +221,11 @@ const char *solve_job_error(const dsm_solve_job &J);
 // 
 const char *step_params_error(const dsm_step_params *p);
 const char *step_job_error(const dsm_step_job &J);
+// optimize_host.cpp: what both forms of the optimize call refuse on top of that, and the job of pass 0 as
+// the step call's rules and pieces see it: zeros (n_frames * 8, 4 and n_pts of them) for the three steps, zero factors, `lambda`
+const char *optimize_params_error(const dsm_optimize_params *p);
+const char *optimize_job_error(const dsm_optimize_job &J);
+dsm_step_job optimize_first_pass(const dsm_optimize_job &J, const double *zeros, double lambda);
 // points_host.cpp: the copies of the optional raw accumulators alone
 void hessian_copy_raw(const dsm_hessian_job &J, const double *top, const double *D, const double *E, const double *EB, const double *Hcc,
                       const double *bc);

@@ -18,6 +18,7 @@
 // Every result is ONE sequential chain in one lane, in the stated order: it does not depend on the launch geometry or on the other
 // jobs of the call.  No kernel waits for another workgroup; barriers are workgroup-local.  No MFMA, no scratch.
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -338,6 +339,7 @@ void solve_layout(SolPlan &P, CallArena &A) {
     P.max_N = std::max(P.max_N, (int)N);
   }
   P.o_sol = A.in.take(sizeof(SolJob) * n_jobs), P.o_sd = A.in.take(8 * doubles);
+  P.sol_stride = sizeof(SolJob), P.sol_lambda = offsetof(SolJob, lambda);
 }
 
 void solve_stage(SolPlan &P, CallArena &A) {

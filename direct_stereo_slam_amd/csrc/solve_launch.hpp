@@ -24,6 +24,7 @@ struct SolPlan {
   std::vector<const dsm_solve_job *> jobs;
   HesPlan hes;
   size_t o_sol = 0, o_sd = 0;
+  size_t sol_stride = 0, sol_lambda = 0; // bytes: one entry of the device job table at o_sol, and its double `lambda` within it
   std::vector<SolWhere> at;
   std::vector<SolView> view;
   int max_N = 12;

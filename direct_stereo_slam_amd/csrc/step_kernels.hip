@@ -17,12 +17,14 @@
 //                     can_break: the chains feed nothing else, so they run beside the point lanes and add no launch.
 // After the upload the arena's input part is ordinary device memory: the kernels of sections 16-18 see other values at the same
 // offsets and are unchanged.  Every result is one sequential chain in one lane; no kernel waits for another workgroup; no scratch.
+// The call's host side is the pieces of step_launch.hpp, which dsm_window_optimize_batch (optimize_kernels.hip) runs too.
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "solve_launch.hpp"
+#include "step_launch.hpp"
 
 #include "step_math.hpp"
 
@@ -182,7 +184,25 @@ __global__ __launch_bounds__(kPointBlock) void stp_point_kernel(const StpJob *jo
 } // namespace
 
 extern "C" int dsm_window_step_batch(dsm_context *ctx, int n_jobs, const dsm_step_job *jobs, const dsm_linearize_params *lp, const dsm_step_params *sp) {
-  auto bad = [](const char *msg) { return invalid((std::string("dsm_window_step_batch: ") + msg).c_str()); };
+  StpPlan P;
+  int rc = step_check("dsm_window_step_batch", ctx, n_jobs, jobs, lp, sp, P);
+  if (rc) return rc;
+  CallArena A;
+  step_layout(P, A);
+  if ((rc = A.bind(ctx))) return rc;
+  step_stage(P, A);
+  if ((rc = A.upload())) return rc;
+  if ((rc = step_launch(ctx, P, A, *lp, *sp))) return rc;
+  if ((rc = A.fetch(A.out.used))) return rc;
+  step_unpack(P, A, *lp);
+  return DSM_OK;
+}
+
+namespace dsm {
+
+int step_check(const char *call, dsm_context *ctx, int n_jobs, const dsm_step_job *jobs, const dsm_linearize_params *lp, const dsm_step_params *sp,
+               StpPlan &P) {
+  auto bad = [call](const char *msg) { return invalid((std::string(call) + ": " + msg).c_str()); };
   if (!ctx || n_jobs < 1 || !jobs) return bad("bad argument");
   if (const char *e = linearize_params_error(lp)) return bad(e);
   if (const char *e = step_params_error(sp)) return bad(e);
@@ -194,9 +214,11 @@ extern "C" int dsm_window_step_batch(dsm_context *ctx, int n_jobs, const dsm_ste
   }
   // the solve call's rules and pieces see the job completed with placeholders of the right size for what the device forms: the staged
   // zeros are overwritten by stp_frame_kernel and stp_point_kernel before any kernel reads them
-  const std::vector<double> zero(zeros, 0.0);
-  const float *zf = reinterpret_cast<const float *>(zero.data());
-  std::vector<dsm_solve_job> T(n_jobs);
+  P.n_jobs = n_jobs, P.jobs = jobs;
+  P.zero.assign(zeros, 0.0);
+  const float *zf = reinterpret_cast<const float *>(P.zero.data());
+  std::vector<dsm_solve_job> &T = P.T;
+  T.resize(n_jobs);
   std::vector<const dsm_linearize_job *> lin;
   for (int j = 0; j < n_jobs; j++) {
     T[j] = jobs[j].sol;
@@ -204,36 +226,33 @@ extern "C" int dsm_window_step_batch(dsm_context *ctx, int n_jobs, const dsm_ste
     L.cam[0] = L.cam[1] = L.cam_inv[0] = L.cam_inv[1] = 1.0f, L.cam[2] = L.cam[3] = 0.0f;
     L.pre_RTll_0 = L.pre_tTll_0 = L.pre_KRKiTll = L.pre_KtTll = L.pre_aff_mode = L.pre_b0_mode = zf;
     L.idepth_scaled = L.idepth_zero_scaled = zf;
-    T[j].delta_x = zero.data();
+    T[j].delta_x = P.zero.data();
     lin.push_back(&L);
   }
   size_t res = 0;
-  int rc = linearize_check_jobs("dsm_window_step_batch", ctx, n_jobs, lin.data(), lp, &res);
+  int rc = linearize_check_jobs(call, ctx, n_jobs, lin.data(), lp, &res);
   if (rc) return rc;
   for (int j = 0; j < n_jobs; j++) {
     if (const char *e = hessian_job_error(T[j].hes, false)) return bad(e);
     if (const char *e = solve_job_error(T[j])) return bad(e);
   }
-  // on top of the solve call's parts: staged [job table | doubles: eval, state_zero, state_backup, frame_step, the calibration's three,
-  // the priors | floats: idepth_backup, idepth_step, exposure], read back [per job: state, calib, W, energy_m, sums, can_break, idepth,
-  // as asked for: C, cam, the six tables, delta_x, H_L, b_L]
-  CallArena A;
-  SolPlan P;
-  for (int j = 0; j < n_jobs; j++) P.jobs.push_back(&T[j]);
-  solve_layout(P, A);
-  struct Where {
-    size_t state, calib, idepth, W, can, sums, em;
-    long long C = -1, cam = -1, pre = -1, dx = -1, HL = -1, bL = -1;
-  };
-  std::vector<Where> at(n_jobs);
-  size_t doubles = 0, floats = 0;
-  int max_pts = 0;
+  return DSM_OK;
+}
+
+// on top of the solve call's parts: staged [job table | doubles: eval, state_zero, state_backup, frame_step, the calibration's three,
+// the priors | floats: idepth_backup, idepth_step, exposure], read back [per job: state, calib, W, energy_m, sums, can_break, idepth,
+// as asked for: C, cam, the six tables, delta_x, H_L, b_L]
+void step_layout(StpPlan &P, CallArena &A) {
+  const int n_jobs = P.n_jobs;
+  for (int j = 0; j < n_jobs; j++) P.sol.jobs.push_back(&P.T[j]);
+  solve_layout(P.sol, A);
+  P.at.assign(n_jobs, StpWhere());
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_step_job &S = jobs[j];
+    const dsm_step_job &S = P.jobs[j];
     const size_t n = S.sol.hes.lin.n_frames, np = S.sol.hes.lin.n_pts, N = 4 + 8 * n;
-    Where &w = at[j];
-    doubles += 7 * n + 3 * 8 * n + 12 + (S.prior ? 2 * N : 0);
-    floats += 2 * np + n;
+    StpWhere &w = P.at[j];
+    P.doubles += 7 * n + 3 * 8 * n + 12 + (S.prior ? 2 * N : 0);
+    P.floats += 2 * np + n;
     w.state = A.out.take(64 * n), w.calib = A.out.take(32), w.W = A.out.take(56 * n), w.em = A.out.take(8), w.sums = A.out.take(24), w.can = A.out.take(4);
     w.idepth = A.out.take(4 * np);
     if (S.cam_to_world_out) w.C = (long long)A.out.take(56 * n);
@@ -243,27 +262,32 @@ extern "C" int dsm_window_step_batch(dsm_context *ctx, int n_jobs, const dsm_ste
     if (S.delta_x_out) w.dx = (long long)A.out.take(8 * N);
     if (S.H_L_out) w.HL = (long long)A.out.take(8 * N * N);
     if (S.b_L_out) w.bL = (long long)A.out.take(8 * N);
-    max_pts = std::max(max_pts, (int)np);
+    P.max_pts = std::max(P.max_pts, (int)np);
   }
-  const size_t o_stp = A.in.take(sizeof(StpJob) * n_jobs), o_sq = A.in.take(8 * doubles), o_sf = A.in.take(4 * floats);
-  if ((rc = A.bind(ctx))) return rc;
-  solve_stage(P, A);
-  StpJob *hj = A.host_in<StpJob>(o_stp);
-  double *hq = A.host_in<double>(o_sq);
-  WordPacker F{A.host_in<float>(o_sf)};
+  P.o_stp = A.in.take(sizeof(StpJob) * n_jobs), P.o_sq = A.in.take(8 * P.doubles), P.o_sf = A.in.take(4 * P.floats);
+  P.stp_stride = sizeof(StpJob), P.stp_stepfac = offsetof(StpJob, stepfac);
+}
+
+void step_stage(StpPlan &P, CallArena &A) {
+  const int n_jobs = P.n_jobs;
+  solve_stage(P.sol, A);
+  StpJob *hj = A.host_in<StpJob>(P.o_stp);
+  double *hq = A.host_in<double>(P.o_sq);
+  WordPacker F{A.host_in<float>(P.o_sf)};
   size_t used = 0;
   auto put = [&](const double *a, size_t m) {
     memcpy(hq + used, a, 8 * m);
     used += m;
     return (int)(used - m);
   };
-  const long long out0 = P.hes.out0;
+  const long long out0 = P.sol.hes.out0;
   auto word = [out0](long long bytes) { return bytes < 0 ? -1ll : out0 + bytes / 4; };
+  P.view.assign(n_jobs, StpView());
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_step_job &S = jobs[j];
+    const dsm_step_job &S = P.jobs[j];
     const size_t n = S.sol.hes.lin.n_frames, np = S.sol.hes.lin.n_pts, N = 4 + 8 * n;
-    const Where &w = at[j];
-    const SolView &V = P.view[j];
+    const StpWhere &w = P.at[j];
+    const SolView &V = P.sol.view[j];
     StpJob &G = hj[j];
     memset(&G, 0, sizeof G);
     G.n = (int)n, G.n_pts = (int)np, G.N = (int)N;
@@ -276,25 +300,30 @@ extern "C" int dsm_window_step_batch(dsm_context *ctx, int n_jobs, const dsm_ste
     G.o_state = word((long long)w.state), G.o_calib = word((long long)w.calib), G.o_idepth = word((long long)w.idepth), G.o_W = word((long long)w.W);
     G.o_can = word((long long)w.can), G.o_sums = word((long long)w.sums), G.o_em = word((long long)w.em);
     G.o_C = word(w.C), G.o_cam = word(w.cam), G.o_pre = word(w.pre), G.o_dx = word(w.dx), G.o_HL = word(w.HL), G.o_bL = word(w.bL);
+    P.view[j] = StpView{G.q_backup, G.q_step, G.q_cbackup, G.q_cstep, G.q_prior, G.f_idb, G.f_ids, G.o_state, G.o_calib, G.o_idepth, G.o_em, G.o_can};
   }
-  if ((rc = A.upload())) return rc;
-  const stp::Scales Sc{sp->scale_xi_trans, sp->scale_xi_rot, sp->scale_a, sp->scale_b, sp->th_opt_iterations, lp->scale_f, lp->scale_c, lp->scale_idepth};
-  const StpJob *dj = A.dev_in<const StpJob>(o_stp);
-  LinJob *dl = A.dev_in<LinJob>(P.hes.o_lin);
-  float *dstage = A.dev_in<float>(P.hes.o_stage);
-  hipLaunchKernelGGL(stp_frame_kernel, dim3(n_jobs), dim3(kFrameBlock), 0, ctx->stream, dj, dl, dstage, A.dev_in<double>(P.o_sd),
-                     A.dev_in<const double>(o_sq), A.dev_in<const float>(o_sf), P.hes.dev_base, Sc);
-  hipLaunchKernelGGL(stp_point_kernel, dim3((max_pts + kPointBlock - 1) / kPointBlock + 1, n_jobs), dim3(kPointBlock), 0, ctx->stream, dj, dl, dstage,
-                     A.dev_in<const float>(o_sf), P.hes.dev_base, Sc);
+}
+
+int step_launch(dsm_context *ctx, StpPlan &P, CallArena &A, const dsm_linearize_params &lp, const dsm_step_params &sp) {
+  const stp::Scales Sc{sp.scale_xi_trans, sp.scale_xi_rot, sp.scale_a, sp.scale_b, sp.th_opt_iterations, lp.scale_f, lp.scale_c, lp.scale_idepth};
+  const StpJob *dj = A.dev_in<const StpJob>(P.o_stp);
+  LinJob *dl = A.dev_in<LinJob>(P.sol.hes.o_lin);
+  float *dstage = A.dev_in<float>(P.sol.hes.o_stage);
+  hipLaunchKernelGGL(stp_frame_kernel, dim3(P.n_jobs), dim3(kFrameBlock), 0, ctx->stream, dj, dl, dstage, A.dev_in<double>(P.sol.o_sd),
+                     A.dev_in<const double>(P.o_sq), A.dev_in<const float>(P.o_sf), P.sol.hes.dev_base, Sc);
+  hipLaunchKernelGGL(stp_point_kernel, dim3((P.max_pts + kPointBlock - 1) / kPointBlock + 1, P.n_jobs), dim3(kPointBlock), 0, ctx->stream, dj, dl, dstage,
+                     A.dev_in<const float>(P.o_sf), P.sol.hes.dev_base, Sc);
   DSM_HIP(hipGetLastError());
-  if ((rc = solve_launch(ctx, P, A, *lp))) return rc;
-  if ((rc = A.fetch(A.out.used))) return rc;
-  solve_unpack(P, A, *lp);
+  return solve_launch(ctx, P.sol, A, lp);
+}
+
+void step_unpack(const StpPlan &P, const CallArena &A, const dsm_linearize_params &lp) {
+  solve_unpack(P.sol, A, lp);
   const unsigned char *ho = A.host_out<unsigned char>(0);
-  for (int j = 0; j < n_jobs; j++) {
-    const dsm_step_job &S = jobs[j];
+  for (int j = 0; j < P.n_jobs; j++) {
+    const dsm_step_job &S = P.jobs[j];
     const size_t n = S.sol.hes.lin.n_frames, np = S.sol.hes.lin.n_pts, N = 4 + 8 * n, n2 = n * n;
-    const Where &w = at[j];
+    const StpWhere &w = P.at[j];
     memcpy(S.state_out, ho + w.state, 64 * n), memcpy(S.calib_out, ho + w.calib, 32), memcpy(S.world_to_cam_out, ho + w.W, 56 * n);
     if (np) memcpy(S.idepth_out, ho + w.idepth, 4 * np);
     memcpy(S.can_break, ho + w.can, 4), memcpy(S.step_sums, ho + w.sums, 24), memcpy(S.energy_m, ho + w.em, 8);
@@ -311,5 +340,7 @@ extern "C" int dsm_window_step_batch(dsm_context *ctx, int n_jobs, const dsm_ste
     if (S.H_L_out) memcpy(S.H_L_out, ho + w.HL, 8 * N * N);
     if (S.b_L_out) memcpy(S.b_L_out, ho + w.bL, 8 * N);
   }
-  return DSM_OK;
 }
+
+} // namespace dsm
+

@@ -94,6 +94,7 @@ public:
   bool stepValid() const { return step_valid_; }
 
 private:
+  friend class WindowOptimize; // WindowOptimize.hpp: the whole loop in one call, on the same members
   struct Params {
     dsm_linearize_params l;
     dsm_step_params s;

@@ -1577,6 +1577,76 @@ int dsm_window_step_batch(dsm_context *ctx, int n_jobs, const dsm_step_job *jobs
 int dsm_window_step_host(int w, int h, const dsm_step_job *job, const float *const *frame_I, const dsm_linearize_params *lp,
                          const dsm_step_params *sp);
 
+/* ---- The accept / reject loop of the window optimisation in one call -------------------------------------------
+ * replaces, together with the four sections above, the loop of FrontEnd::optimize (dso_helpers/FrontEndOptimize.cpp:332-486): the
+ * linearizeAll and applyRes before it (:362-371), and per iteration (:382-453) backupState, the step-size heuristic (:390-405),
+ * doStepFromBackup, linearizeAll, the accept test (:427-429), applyRes or loadSateBackup with its linearizeAll (:444-448), the lambda
+ * schedule and the break (:451).  A PASS is what one dsm_window_step_batch call does.  Every job carries its own lambda, factors,
+ * iteration count and break:
+ *   pass 0:      zero factors, lambda = lambda_init                      -> always committed; last = E + E_M
+ *   iteration i: trial pass, factors = stepsize, lambda_trial = lambda * lambda_accept_fac
+ *                accept (force_accept, or E + E_M < last, in double): commit; lambda = lambda_trial
+ *                reject: lambda = lambda * lambda_reject_fac; re-pass with zero factors at the backed-up state with that lambda; commit it
+ *                break after the iteration if the TRIAL's can_break && i >= min_iterations
+ * Commit: the returned state, calibration and depths become the backup, new_state / new_energy become state_in / energy_in (applyRes),
+ * frame_step = -x[4..], calib_step = -x[0..3], idepth_step = step.  frame_energy_th[n - 1] takes new_frame_energy_th after EVERY pass.
+ * The rules are the project's statement; parity with the parts of DSO that are not under the reference tree is
+ * unpinned.  NOT here: accumulateLF_MT, the nullspaces, setEvalPT after the loop, marginalisation, SOLVER_MOMENTUM.
+ * The struct defaults reproduce the loop of host/step_demo.cpp (lambda 0.1, x 0.25, x 100, setting_minOptIterations = 1, the energy
+ * test, step size 1).  The recalled upstream defaults are setting_forceAceptStep = true and SOLVER_FIX_LAMBDA set (the solve then
+ * always gets 1e-5): force_accept = 1, fixed_lambda = 1e-5; they are not citable under the reference tree. */
+#define DSM_OPTIMIZE_MAX_ITERATIONS 20
+
+typedef struct dsm_optimize_params {
+  double lambda_init;        /* 0.1   :382 */
+  double lambda_accept_fac;  /* 0.25  :442 */
+  double lambda_reject_fac;  /* 100   :448 */
+  double fixed_lambda;       /* -1    >= 0: every solve gets this value; the schedule still runs and is logged */
+  int min_iterations;        /* 1     setting_minOptIterations */
+  int force_accept;          /* 0     setting_forceAceptStep */
+  int step_momentum;         /* 0     SOLVER_STEPMOMENTUM: the step-size heuristic of :390-405; otherwise the step size is 1 */
+} dsm_optimize_params;
+
+/* One window.  step describes the window at its current state: state_backup, calib_backup and idepth_backup are the current values,
+ * sol.hes.lin.state_in / energy_in the committed residual states.  step.frame_step, step.calib_step and step.idepth_step MUST be NULL
+ * (the loop forms them); step.stepfac and step.sol.lambda are not read.  Every output of step receives the values of THE JOB'S LAST
+ * PASS: in both branches they describe the committed state, with the solve (x, step, flags) computed as for a next iteration.
+ * P = 1 + 2 * max_iterations bounds the passes. */
+typedef struct dsm_optimize_job {
+  dsm_step_job step;
+  int max_iterations;            /* 0 .. DSM_OPTIMIZE_MAX_ITERATIONS; 0: pass 0 only */
+  int *n_iterations;             /* iterations run */
+  int *n_passes;                 /* passes run: 1 + iterations + rejected iterations */
+  unsigned char *pattern;        /* max_iterations: 'A' or 'R' per iteration run, 0 behind them */
+  double *pass_energy;           /* P * 2: E and E_M of every pass, 0 behind them */
+  double *pass_lambda;           /* P: the schedule's lambda of every pass (what the solve gets unless fixed_lambda >= 0), 0 behind them */
+  float *iter_stepsize;          /* max_iterations: the factor of every trial, 0 behind them */
+  unsigned char *iter_can_break; /* max_iterations: the trial's can_break, 0 behind them */
+  double *last_energy;           /* 2: E and E_M of the last committed pass */
+  double *lambda_out;            /* the schedule's lambda after the last iteration */
+  float *frame_energy_th_out;    /* frame_energy_th[n - 1] after the last pass */
+} dsm_optimize_job;
+
+/* the defaults listed above */
+int dsm_optimize_params_default(dsm_optimize_params *p);
+/* The loop for every job: ONE staged copy (that of dsm_window_step_batch with the loop's state on top), then the passes back to back on
+ * the context's stream with no host wait between them: the ten launches of dsm_window_step_batch and two more (opt_decide_kernel: the
+ * ordered energy sum and the order statistic of new_frame_energy_th, the decision, the lambda schedule, the heuristic and the frames'
+ * part of the commit; opt_commit_kernel: the points' and residuals' part) that write the next pass's inputs where the ten read them.
+ * 1 + max over the jobs of max_iterations passes are enqueued and read back; only if a job is then unfinished (it rejected a step), the
+ * remaining passes follow: at most two host waits per call.  A finished job is frozen: its later passes recompute the same bytes.  A
+ * job's results do not depend on the other jobs of the call or on the launch geometry.  Validation is all or nothing, before anything
+ * is enqueued: DSM_ERR_INVALID for everything dsm_window_step_batch refuses (except the NULLs this call requires), frame_step,
+ * calib_step or idepth_step given, a NULL output of this struct, parameters that are not finite, lambda_init <= -1, a factor <= 0,
+ * min_iterations < 0, max_iterations outside [0, DSM_OPTIMIZE_MAX_ITERATIONS]. */
+int dsm_window_optimize_batch(dsm_context *ctx, int n_jobs, const dsm_optimize_job *jobs, const dsm_linearize_params *lp,
+                              const dsm_step_params *sp, const dsm_optimize_params *op);
+/* The same for one job on the host: the loop over dsm_window_step_host.  A checker that needs no device.  (A state that stops being
+ * finite in the middle of the loop is refused by the pass that would read it: DSM_ERR_INVALID, the outputs of step then hold the last
+ * completed pass and the outputs of this struct are not written; the device form carries the NaNs through.) */
+int dsm_window_optimize_host(int w, int h, const dsm_optimize_job *job, const float *const *frame_I, const dsm_linearize_params *lp,
+                             const dsm_step_params *sp, const dsm_optimize_params *op);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.
