@@ -267,6 +267,23 @@ class OptimizeJob(C.Structure):
     ]
 
 
+class MarginalizeParams(C.Structure):
+    _fields_ = [
+        ("min_good_active_res_for_marg", C.c_int), ("min_good_res_for_marg", C.c_int), ("min_idepth_h_marg", C.c_float),
+        ("marg_weight_fac", C.c_float), ("idepth_fix_prior_marg_fac", C.c_float),
+    ]
+
+
+class MarginalizeJob(C.Structure):
+    _fields_ = [
+        ("hes", HessianJob), ("flagged", C.POINTER(C.c_ubyte)), ("n_good_residuals", c_int_p), ("last_state", C.POINTER(C.c_ubyte)),
+        ("idepth_hessian", c_float_p), ("ad_ht_delta", c_float_p), ("c_delta", c_float_p), ("H_M", c_double_p), ("b_M", c_double_p),
+        ("n_marg_frames", C.c_int), ("marg_frames", c_int_p), ("frame_prior", c_double_p), ("frame_delta_prior", c_double_p),
+        ("verdict", C.POINTER(C.c_ubyte)), ("H_M_out", c_double_p), ("b_M_out", c_double_p), ("n_res_marg", c_int_p),
+        ("H_M_points", c_double_p), ("b_M_points", c_double_p), ("res_to_zero", c_float_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -534,6 +551,10 @@ SYMBOLS = {
                                             C.POINTER(OptimizeParams)]),
     "dsm_window_optimize_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(OptimizeJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams),
                                            C.POINTER(StepParams), C.POINTER(OptimizeParams)]),
+    "dsm_marginalize_params_default": (C.c_int, [C.POINTER(MarginalizeParams)]),
+    "dsm_window_marginalize_batch": (C.c_int, [_vp, C.c_int, C.POINTER(MarginalizeJob), C.POINTER(LinearizeParams), C.POINTER(MarginalizeParams)]),
+    "dsm_window_marginalize_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(MarginalizeJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams),
+                                              C.POINTER(MarginalizeParams)]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

@@ -233,6 +233,10 @@ void hessian_copy_raw(const dsm_hessian_job &J, const double *top, const double 
 // the optional raw accumulators
 void hessian_stitch(const dsm_hessian_job &J, const double *top, const double *D, const double *E, const double *EB, const double *Hcc,
                     const double *bc);
+// points_host.cpp: dsm_window_hessian_host with a hook between the linearisation and the accumulation: after_lin (or null) sees the
+// linearised job (its J_out holds the rows, the host form's own room where the caller gave none) and may rewrite the rows
+int hessian_host_run(int w, int h, const dsm_hessian_job *job, const float *const *frame_I, const dsm_linearize_params *params,
+                     void (*after_lin)(void *user, const dsm_linearize_job &L, float *rows), void *user);
 // context_capi.hip: the device-visible address of a caller's array if it lies in page-locked memory, else null
 const void *pinned_device_pointer(const void *p);
 int take_params(const dsm_params *params, dsm_params *out); // the caller's parameters, checked, or the defaults

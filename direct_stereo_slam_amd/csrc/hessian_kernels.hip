@@ -323,14 +323,23 @@ void hessian_stage(HesPlan &P, CallArena &A) {
 }
 
 int hessian_launch(dsm_context *ctx, HesPlan &P, CallArena &A, const dsm_linearize_params &params) {
+  if (int rc = hessian_launch_linearize(ctx, P, A, params)) return rc;
+  return hessian_launch_accumulate(ctx, P, A);
+}
+
+int hessian_launch_linearize(dsm_context *ctx, HesPlan &P, CallArena &A, const dsm_linearize_params &params) {
+  if (!P.max_res) return DSM_OK;
+  const dsm_window *win = P.jobs[0]->lin.window;
+  return linearize_launch(ctx, (int)P.jobs.size(), P.max_res, A.dev_in<const LinJob>(P.o_lin), P.dev_stage, P.dev_base, win->w, win->h, params);
+}
+
+int hessian_launch_accumulate(dsm_context *ctx, HesPlan &P, CallArena &A) {
   const int n_jobs = (int)P.jobs.size(), max_res = P.max_res, max_pts = P.max_pts, max_nf = P.max_nf;
   const LinJob *dl = A.dev_in<const LinJob>(P.o_lin);
   const HesJob *dh = A.dev_in<const HesJob>(P.o_hes);
   const float *ds = P.dev_stage;
   float *base = P.dev_base;
   if (max_res) {
-    const dsm_window *win = P.jobs[0]->lin.window;
-    if (int rc = linearize_launch(ctx, n_jobs, max_res, dl, ds, base, win->w, win->h, params)) return rc;
     hipLaunchKernelGGL(hes_residual_kernel, dim3((max_res + kResBlock - 1) / kResBlock, n_jobs), dim3(kResBlock), 0, ctx->stream, dl, dh, ds, base);
   }
   if (max_pts)

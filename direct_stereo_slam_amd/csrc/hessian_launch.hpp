@@ -52,6 +52,9 @@ void hessian_layout(HesPlan &P, CallArena &A);
 void hessian_stage(HesPlan &P, CallArena &A);
 // linearize_kernel and the four accumulation kernels on the context's stream
 int hessian_launch(dsm_context *ctx, HesPlan &P, CallArena &A, const dsm_linearize_params &params);
+// its two halves, for a call that rewrites the rows between them (dsm_window_marginalize_batch): linearize_kernel; the four others
+int hessian_launch_linearize(dsm_context *ctx, HesPlan &P, CallArena &A, const dsm_linearize_params &params);
+int hessian_launch_accumulate(dsm_context *ctx, HesPlan &P, CallArena &A);
 // every output of the jobs from the read-back; after A.fetch()
 void hessian_unpack(const HesPlan &P, const CallArena &A, const dsm_linearize_params &params);
 

@@ -797,6 +797,13 @@ extern "C" int dsm_linearize_residuals_host(int w, int h, const dsm_linearize_jo
 // are hessian_math.hpp, shared with the device kernels.
 // ---------------------------------------------------------------------------------------------
 extern "C" int dsm_window_hessian_host(int w, int h, const dsm_hessian_job *job, const float *const *frame_I, const dsm_linearize_params *params) {
+  return dsm::hessian_host_run(w, h, job, frame_I, params, nullptr, nullptr);
+}
+
+// the host form above; after_lin (or null) sees the linearisation's result and may rewrite the rows before anything accumulates
+// (dsm_window_marginalize_host: X1 of section 21)
+int dsm::hessian_host_run(int w, int h, const dsm_hessian_job *job, const float *const *frame_I, const dsm_linearize_params *params,
+                          void (*after_lin)(void *user, const dsm_linearize_job &L, float *rows), void *user) {
   using namespace dsm::hes;
   auto fail = [](const char *msg) { return refuse("dsm_window_hessian_host", msg); };
   if (w < 8 || h < 8 || !job || !frame_I) return fail("bad argument");
@@ -812,6 +819,7 @@ extern "C" int dsm_window_hessian_host(int w, int h, const dsm_hessian_job *job,
   if (!L.J_out) rows.resize((size_t)nr * dsm::lin::J_FLOATS), L.J_out = rows.data();
   const int rc = dsm_linearize_residuals_host(w, h, &L, frame_I, params);
   if (rc) return rc;
+  if (after_lin) after_lin(user, L, L.J_out);
   const size_t n2 = (size_t)nf * nf;
   std::vector<double> top(n2 * 169, 0.0), D(n2 * nf * 64, 0.0), E(n2 * 32, 0.0), EB(n2 * 8, 0.0), Hcc(16, 0.0), bc(4, 0.0);
   std::vector<float> rec((size_t)nr * R_FLOATS), prec((size_t)np * P_FLOATS, 0.0f);

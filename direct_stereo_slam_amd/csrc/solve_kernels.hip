@@ -313,7 +313,9 @@ extern "C" int dsm_window_solve_batch(dsm_context *ctx, int n_jobs, const dsm_so
 namespace dsm {
 
 // on top of the Hessian call's parts: staged [job table | doubles: ad_host, ad_target, H_L, b_L and the optional inputs], device only
-// or read back (a job that asks for one of them) [H_A, b_A, H_sc, b_sc], read back [x, steps, flags, as asked for: last_HS, last_bS]
+// or read back (a job that asks for one of them) [H_A, b_A, H_sc, b_sc], read back [x, steps, flags, as asked for: last_HS, last_bS].
+// A stitch_only plan (dsm_window_marginalize_batch) has jobs without H_L / b_L (counted only where given; every other caller's
+// validation refuses a NULL one) and takes no room for x, the steps and the flags: only sol_stitch_kernel runs on it.
 void solve_layout(SolPlan &P, CallArena &A) {
   const int n_jobs = (int)P.jobs.size();
   P.hes.lean = true;
@@ -325,7 +327,8 @@ void solve_layout(SolPlan &P, CallArena &A) {
     const dsm_solve_job &S = *P.jobs[j];
     const size_t nf = S.hes.lin.n_frames, N = 4 + 8 * nf;
     SolWhere &w = P.at[j];
-    doubles += 2 * nf * nf * 64 + N * N + N + (S.H_M ? N * N : 0) + (S.b_M ? N : 0) + (S.delta_x ? N : 0) + 2 * N * (size_t)S.n_null;
+    doubles += 2 * nf * nf * 64 + (S.H_L ? N * N : 0) + (S.b_L ? N : 0) + (S.H_M ? N * N : 0) + (S.b_M ? N : 0) + (S.delta_x ? N : 0) +
+               2 * N * (size_t)S.n_null;
     const bool out = S.hes.H_A || S.hes.b_A || S.hes.H_sc || S.hes.b_sc;
     auto take = [&A, out](size_t bytes) {
       HesSpot s;
@@ -333,7 +336,7 @@ void solve_layout(SolPlan &P, CallArena &A) {
       return s;
     };
     w.HA = take(8 * N * N), w.bA = take(8 * N), w.HS = take(8 * N * N), w.bS = take(8 * N);
-    w.x = A.out.take(8 * N), w.step = A.out.take(4 * (size_t)S.hes.lin.n_pts), w.flags = A.out.take(4);
+    if (!P.stitch_only) w.x = A.out.take(8 * N), w.step = A.out.take(4 * (size_t)S.hes.lin.n_pts), w.flags = A.out.take(4);
     if (S.last_HS) w.lastH = (long long)A.out.take(8 * N * N);
     if (S.last_bS) w.lastb = (long long)A.out.take(8 * N);
     P.max_N = std::max(P.max_N, (int)N);
@@ -368,9 +371,17 @@ void solve_stage(SolPlan &P, CallArena &A) {
     G.d_basis = put(S.n_null ? S.null_basis : nullptr, N * S.n_null), G.d_pinv = put(S.n_null ? S.null_pinv : nullptr, N * S.n_null);
     G.o_HA = w.HA.word(out0), G.o_bA = w.bA.word(out0), G.o_HS = w.HS.word(out0), G.o_bS = w.bS.word(out0);
     G.o_x = out0 + (long long)(w.x / 4), G.o_step = out0 + (long long)(w.step / 4), G.o_flags = out0 + (long long)(w.flags / 4);
+    if (P.stitch_only) G.o_x = G.o_step = G.o_flags = -1; // no room was taken: sol_solve_kernel and sol_step_kernel do not run
     G.o_lastH = w.lastH < 0 ? -1 : out0 + w.lastH / 4, G.o_lastb = w.lastb < 0 ? -1 : out0 + w.lastb / 4;
     P.view[j] = SolView{(int)N, G.d_HL, G.d_bL, G.d_HM, G.d_bM, G.d_dx};
   }
+}
+
+int solve_launch_stitch(dsm_context *ctx, SolPlan &P, CallArena &A) {
+  const int n_jobs = (int)P.jobs.size(), nf = P.hes.max_nf;
+  hipLaunchKernelGGL(sol_stitch_kernel, dim3(nf * (nf + 1) / 2 + nf + 1, n_jobs), dim3(64), 0, ctx->stream, A.dev_in<const SolJob>(P.o_sol),
+                     A.dev_in<const double>(P.o_sd), P.hes.dev_base);
+  return DSM_OK;
 }
 
 int solve_launch(dsm_context *ctx, SolPlan &P, CallArena &A, const dsm_linearize_params &params) {
@@ -378,10 +389,9 @@ int solve_launch(dsm_context *ctx, SolPlan &P, CallArena &A, const dsm_linearize
   if (int rc = hessian_launch(ctx, P.hes, A, params)) return rc;
   const SolJob *ds = A.dev_in<const SolJob>(P.o_sol);
   const double *dd = A.dev_in<const double>(P.o_sd);
-  const int nf = P.hes.max_nf;
   const size_t lds = solve_lds_bytes(P.max_N);
   if (lds > 64 * 1024) DSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sol_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(sol_stitch_kernel, dim3(nf * (nf + 1) / 2 + nf + 1, n_jobs), dim3(64), 0, ctx->stream, ds, dd, P.hes.dev_base);
+  if (int rc = solve_launch_stitch(ctx, P, A)) return rc;
   hipLaunchKernelGGL(sol_solve_kernel, dim3(n_jobs), dim3(kSolveBlock), lds, ctx->stream, ds, dd, P.hes.dev_base);
   if (P.hes.max_pts)
     hipLaunchKernelGGL(sol_step_kernel, dim3((P.hes.max_pts + kStepBlock - 1) / kStepBlock, n_jobs), dim3(kStepBlock), 0, ctx->stream, ds, dd,
@@ -402,6 +412,7 @@ void solve_unpack(const SolPlan &P, const CallArena &A, const dsm_linearize_para
     if (S.hes.b_A) memcpy(S.hes.b_A, ho + w.bA.at, 8 * N);
     if (S.hes.H_sc) memcpy(S.hes.H_sc, ho + w.HS.at, 8 * N * N);
     if (S.hes.b_sc) memcpy(S.hes.b_sc, ho + w.bS.at, 8 * N);
+    if (P.stitch_only) continue;
     memcpy(S.x, ho + w.x, 8 * N);
     if (S.hes.lin.n_pts) memcpy(S.step, ho + w.step, 4 * (size_t)S.hes.lin.n_pts);
     memcpy(S.flags, ho + w.flags, 4);

@@ -28,6 +28,9 @@ struct SolPlan {
   std::vector<SolWhere> at;
   std::vector<SolView> view;
   int max_N = 12;
+  // the jobs hold hes alone and the call runs the stitch alone (dsm_window_marginalize_batch): no room for the solve's inputs and
+  // outputs is taken, and solve_unpack leaves them alone
+  bool stitch_only = false;
 };
 
 // takes the call's parts of A.in, A.work and A.out (the Hessian pieces' among them); before A.bind()
@@ -36,6 +39,8 @@ void solve_layout(SolPlan &P, CallArena &A);
 void solve_stage(SolPlan &P, CallArena &A);
 // the five launches of hessian_launch and the three of the solve on the context's stream
 int solve_launch(dsm_context *ctx, SolPlan &P, CallArena &A, const dsm_linearize_params &params);
+// its pieces: hessian_launch is the first; the stitch (T1d) of the raw accumulators into H_A, b_A, H_sc, b_sc where the plan put them
+int solve_launch_stitch(dsm_context *ctx, SolPlan &P, CallArena &A);
 // every output of the jobs from the read-back; after A.fetch()
 void solve_unpack(const SolPlan &P, const CallArena &A, const dsm_linearize_params &params);
 

@@ -2,7 +2,8 @@
 // 382-453): backupState, then doStepFromBackup (:182-262) with setPrecalcValues (:300-323), linearizeAll, calcMEnergy and the
 // solveSystem of the NEXT iteration as ONE call, for one window or for the windows of many sequences, on top of the C ABI
 // (include/dsm_hotpath.h).  The adaptor holds what optimize holds across iterations: the committed state of the frames, the calibration
-// and the points, state_state / state_energy of the residuals, frameEnergyTH and the step.  The accept decision and the step-size
+// and the points, state_state / state_energy of the residuals, frameEnergyTH and the step, and the precalc tables and calibration the
+// call formed at the committed state (for host/WindowMarginalize.hpp).  The accept decision and the step-size
 // heuristic stay the caller's.  Header-only, plain C++11.  Semantics: DESIGN.md section 19 (D1-D4, Q1-Q4, E1-E3).
 //
 //   WindowStep w;  ... fill w.req (no precalc, deltaF or deltaX), the poses, states, priors ...
@@ -44,6 +45,10 @@ public:
   double trialCalib[4] = {0, 0, 0, 0};
   std::vector<float> trialIdepth;
   float stepSums[6] = {0, 0, 0, 0, 0, 0};
+  // what the call formed at the committed state (set by accept(), from the trial's): the FrameFramePrecalc tables and fxl, fyl, cxl,
+  // cyl, fxli, fyli, as a caller of the other window calls passes them (host/WindowMarginalize.hpp reads them)
+  std::vector<LinearizePrecalc> precalc;
+  float cam[6] = {0, 0, 0, 0, 0, 0};
 
   void backupState() {
     stateBackup_ = state, idepthBackup_ = idepth;
@@ -85,6 +90,14 @@ public:
     for (size_t i = 0; i < frameStep.size(); i++) frameStep[i] = -req.lastX[4 + i];
     for (int c = 0; c < 4; c++) calibStep[c] = -req.lastX[c];
     idepthStep = req.pointStep;
+    const size_t n2 = pre_[5].size();
+    precalc.assign(n2, LinearizePrecalc());
+    for (size_t p = 0; p < n2; p++) {
+      LinearizePrecalc &P = precalc[p];
+      memcpy(P.PRE_RTll_0, &pre_[0][9 * p], 36), memcpy(P.PRE_tTll_0, &pre_[1][3 * p], 12), memcpy(P.PRE_KRKiTll, &pre_[2][9 * p], 36);
+      memcpy(P.PRE_KtTll, &pre_[3][3 * p], 12), memcpy(P.PRE_aff_mode, &pre_[4][2 * p], 8), P.PRE_b0_mode = pre_[5][p];
+    }
+    memcpy(cam, trialCam_, sizeof cam);
     step_valid_ = true;
   }
   // the trial is discarded (loadSateBackup): the committed state stays and the step is void until an iterate with zero factors at
@@ -112,6 +125,8 @@ private:
   solve_detail::Flat flat_;
   int can_break_ = 0;
   double energy_m_ = 0;
+  std::vector<float> pre_[6]; // the trial's pre_RTll_0, pre_tTll_0, pre_KRKiTll, pre_KtTll, pre_aff_mode, pre_b0_mode
+  float trialCam_[6] = {0, 0, 0, 0, 0, 0};
 
   dsm_step_job fill(const float stepfac[5], double lambda) {
     const size_t n = req.hes.lin.frame_ids.size(), N = 4 + 8 * n, np = idepth.size();
@@ -141,6 +156,10 @@ private:
     trialState.assign(8 * n, 0.0), trialWorldToCam.assign(7 * n, 0.0), trialIdepth.assign(np + 1, 0.f);
     j.state_out = trialState.data(), j.calib_out = trialCalib, j.idepth_out = trialIdepth.data(), j.world_to_cam_out = trialWorldToCam.data();
     j.can_break = &can_break_, j.step_sums = stepSums, j.energy_m = &energy_m_;
+    const size_t width[6] = {9, 3, 9, 3, 2, 1};
+    for (int k = 0; k < 6; k++) pre_[k].assign(n * n * width[k], 0.f);
+    j.cam_out = trialCam_, j.pre_RTll_0_out = pre_[0].data(), j.pre_tTll_0_out = pre_[1].data(), j.pre_KRKiTll_out = pre_[2].data();
+    j.pre_KtTll_out = pre_[3].data(), j.pre_aff_mode_out = pre_[4].data(), j.pre_b0_mode_out = pre_[5].data();
     return j;
   }
   StepResult finish() {

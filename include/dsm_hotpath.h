@@ -1519,7 +1519,8 @@ int dsm_window_solve_host(int w, int h, const dsm_solve_job *job, const float *c
  * step) to the next call.  Reject: call again with all five factors 0 and lambda * 100.
  * NOT here: SOLVER_MOMENTUM; the step-size heuristic (:390-405; the caller passes the factors); calcLEnergy and accumulateLF_MT (zero
  * while no residual is linearised, which is all of optimize); setAdjointsF (ad_host / ad_target stay the caller's: the evaluation point
- * does not move inside optimize); the nullspaces; setEvalPT after the loop (:455-464); applyRes; the accept decision; marginalisation.
+ * does not move inside optimize); the nullspaces; setEvalPT after the loop (:455-464); applyRes; the accept decision.  (Marginalisation, which produces H_M / b_M, is
+ * dsm_window_marginalize_batch below.)
  * All arithmetic is IEEE, left to right as written, without contraction. */
 typedef struct dsm_step_params {
   double scale_xi_trans;     /* 0.5   SCALE_XI_TRANS */
@@ -1591,7 +1592,8 @@ int dsm_window_step_host(int w, int h, const dsm_step_job *job, const float *con
  * Commit: the returned state, calibration and depths become the backup, new_state / new_energy become state_in / energy_in (applyRes),
  * frame_step = -x[4..], calib_step = -x[0..3], idepth_step = step.  frame_energy_th[n - 1] takes new_frame_energy_th after EVERY pass.
  * The rules are the project's statement; parity with the parts of DSO that are not under the reference tree is
- * unpinned.  NOT here: accumulateLF_MT, the nullspaces, setEvalPT after the loop, marginalisation, SOLVER_MOMENTUM.
+ * unpinned.  NOT here: accumulateLF_MT, the nullspaces, setEvalPT after the loop, SOLVER_MOMENTUM.  (Marginalisation, which
+ * produces the H_M / b_M this loop reads, is dsm_window_marginalize_batch below.)
  * The struct defaults reproduce the loop of host/step_demo.cpp (lambda 0.1, x 0.25, x 100, setting_minOptIterations = 1, the energy
  * test, step size 1).  The recalled upstream defaults are setting_forceAceptStep = true and SOLVER_FIX_LAMBDA set (the solve then
  * always gets 1e-5): force_accept = 1, fixed_lambda = 1e-5; they are not citable under the reference tree. */
@@ -1646,6 +1648,73 @@ int dsm_window_optimize_batch(dsm_context *ctx, int n_jobs, const dsm_optimize_j
  * completed pass and the outputs of this struct are not written; the device form carries the NaNs through.) */
 int dsm_window_optimize_host(int w, int h, const dsm_optimize_job *job, const float *const *frame_I, const dsm_linearize_params *lp,
                              const dsm_step_params *sp, const dsm_optimize_params *op);
+
+/* ---- Marginalising points and frames of the window ---------------------------------------------------------------
+ * replaces what FrontEnd::makeKeyFrame does right after optimize (FrontEnd.cpp:816-839): flagPointsForRemoval (FrontEnd.cpp:504-583),
+ * EnergyFunctional::marginalizePointsF and, per frame that leaves, EnergyFunctional::marginalizeFrame (FrontEndMarginalize.cpp:148-153
+ * calls it).  isOOB, isInlierNew, fixLinearizationF, addPoint<2>, marginalizePointsF and marginalizeFrame are UPSTREAM-DSO and not under
+ * the reference tree: parity is unpinned, and the rules C, M1, X1, A1', M2, G1-G7, Z and V of DESIGN.md section 21 are the project's
+ * statement.  The call produces the H_M / b_M that the next keyframe's dsm_window_solve_batch / _step_batch / _optimize_batch reads.
+ * NOT here: the SOLVER_ORTHOGONALIZE_* projections, connectivityMap, the bookkeeping that erases points, residuals and frames (the
+ * verdicts and marg_frames tell the caller what to erase), flagFramesForMarginalization, the nullspaces, setEvalPT.
+ * All arithmetic is IEEE, left to right as written, without contraction. */
+typedef struct dsm_marginalize_params {
+  int min_good_active_res_for_marg; /* 3       setting_minGoodActiveResForMarg */
+  int min_good_res_for_marg;        /* 4       setting_minGoodResForMarg */
+  float min_idepth_h_marg;          /* 50      setting_minIdepthH_marg */
+  float marg_weight_fac;            /* 0.25    setting_margWeightFac */
+  float idepth_fix_prior_marg_fac;  /* 360000  setting_idepthFixPriorMargFac (600 * 600) */
+} dsm_marginalize_params;           /* the defaults are the recalled upstream settings; they are not citable under the reference tree */
+
+/* One window as optimize left it; n = hes.lin.n_frames, N = 4 + 8 n, n_pts = hes.lin.n_pts, n_res = hes.lin.n_res.
+ * hes describes the WHOLE window: lin.state_in the committed state of every residual, the precalc tables at the committed state,
+ * frame_energy_th, ad_host, ad_target, per point prior and delta.  Not read: lin.energy_in's values, lin.is_new, hes.hdd_lin,
+ * hes.bd_lin, hes.hcd_lin, hes.shift_prior_to_zero (M1 and A1' fix them).  MUST be NULL / 0: lin.J_out, lin.keep, lin.rel_bs,
+ * lin.fix_linearization.  H_A, b_A, H_sc, b_sc are optional here.  Every per-residual and per-point output of hes (lin.new_state,
+ * new_energy, new_energy_with_outlier, center_projected_to, projected_to, active, JpJdF, hdd_acc ... idepth_hessian) is indexed as
+ * the window's residuals and points are and is written for the residuals and points of the sub-window (M1) only; the rest keeps the
+ * caller's bytes.  lin.energy_out and lin.new_frame_energy_th_out take the sub-window's values (B1, B2 over its residuals); H_A, b_A,
+ * H_sc, b_sc and the raw accumulators are those of the sub-window. */
+typedef struct dsm_marginalize_job {
+  dsm_hessian_job hes;
+  const unsigned char *flagged;    /* n: flaggedForMarginalization */
+  const int *n_good_residuals;     /* n_pts: numGoodResiduals */
+  const unsigned char *last_state; /* n_pts * 2: lastResiduals[0].second, [1].second as DSM_RES_* */
+  const float *idepth_hessian;     /* n_pts: idepth_hessian as the last accumulation of optimize left it */
+  const float *ad_ht_delta;        /* n * n * 8, [host][target]: EF->adHTdeltaF */
+  const float *c_delta;            /* 4: cDeltaF */
+  const double *H_M, *b_M;         /* optional (NULL: zeros).  N * N (row-major) and N */
+  int n_marg_frames;               /* 0 .. n */
+  const int *marg_frames;          /* n_marg_frames: strictly ascending indices into frame_ids, each with flagged set */
+  const double *frame_prior;       /* n_marg_frames * 8: EFFrame::prior of each */
+  const double *frame_delta_prior; /* n_marg_frames * 8: EFFrame::delta_prior of each */
+  unsigned char *verdict;          /* n_pts: 0 keep, 1 marginalise, 2 drop (as dsm_activate_points_batch) */
+  double *H_M_out, *b_M_out;       /* N' * N' and N', N' = N - 8 n_marg_frames: the frames that stay, in order */
+  int *n_res_marg;                 /* one word: the increment of resInM */
+  double *H_M_points, *b_M_points; /* the rest: optional (NULL).  N * N and N: the prior after the points, before a frame leaves */
+  float *res_to_zero;              /* n_res * 8, written for the active residuals of the sub-window only (X1) */
+} dsm_marginalize_job;
+
+/* the defaults listed above */
+int dsm_marginalize_params_default(dsm_marginalize_params *p);
+/* flagPointsForRemoval's verdicts, marginalizePointsF and marginalizeFrame for every job: the verdicts (C) during staging on the host,
+ * ONE staged copy of the sub-window (the points of verdict 1 with all their residuals), the five launches of dsm_window_hessian_batch
+ * with mrg_fix_kernel (X1) between the linearisation and the accumulation, the stitch of dsm_window_solve_batch, mrg_fold_kernel (M2)
+ * and mrg_frame_kernel (G1-G7 for the job's frames, one workgroup per job), one read-back.  A job's results do not depend on the other
+ * jobs of the call or on the launch geometry.  Validation is all or nothing, before anything is enqueued and with no output touched:
+ * DSM_ERR_INVALID for everything dsm_window_hessian_batch refuses (except a NULL H_A, b_A, H_sc or b_sc), one of the must-be-NULL
+ * fields given, a NULL flagged, n_good_residuals, last_state, idepth_hessian, ad_ht_delta, c_delta, verdict, H_M_out, b_M_out or
+ * n_res_marg, a last_state other than DSM_RES_IN / _OOB / _OUTLIER, a non-finite idepth_hessian, ad_ht_delta, c_delta, H_M, b_M,
+ * frame_prior or frame_delta_prior, n_marg_frames outside [0, n] or, when it is not 0, a NULL marg_frames, frame_prior or
+ * frame_delta_prior, marg_frames that are not strictly ascending, out of range or not flagged, a marginalised frame that still hosts
+ * a point of verdict 0, parameters that are not finite, or a negative count among them.  n_res == 0, n_pts == 0, a job of one frame
+ * and a job whose every frame leaves (N' = 4) are valid. */
+int dsm_window_marginalize_batch(dsm_context *ctx, int n_jobs, const dsm_marginalize_job *jobs, const dsm_linearize_params *lin_params,
+                                 const dsm_marginalize_params *marg_params);
+/* The same for one job on the host planes frame_I (as dsm_window_hessian_host; job->hes.lin.window is ignored): plain loops over the
+ * same marginalize_math.hpp.  A checker that needs no device. */
+int dsm_window_marginalize_host(int w, int h, const dsm_marginalize_job *job, const float *const *frame_I,
+                                const dsm_linearize_params *lin_params, const dsm_marginalize_params *marg_params);
 
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],

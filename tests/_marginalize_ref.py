@@ -1,0 +1,571 @@
+"""Independent checker of the marginalisation of points and frames: the rules C, M1, X1, A1', M2, G1-G7 and Z as
+the project states them, layered on the checkers of the linearisation (tests/_linearize_ref.py), the accumulation
+(tests/_hessian_ref.py) and the solve (tests/_solve_ref.py), which are imported and not edited.  float32 scalars where the rules say
+float (every operation rounds once), float64 sums as loops over ascending index from 0.0.  Written from the statement, not from the
+C code.
+
+marginalize(w, h, job, frames, marg) returns every output of direct_stereo_slam_amd.marginalize for the job, indexed as the window's
+residuals and points are, with the mirror's fill values wherever Z leaves the caller's bytes; with a `drop` it returns a mutant, for
+the tests that show a bound has teeth."""
+import numpy as np
+
+import _hessian_ref as HR
+import _linearize_ref as R
+import _solve_ref as SR
+
+f32, f64 = np.float32, np.float64
+KEEP, MARGINALIZE, DROP = 0, 1, 2
+PARAMS = dict(min_good_active_res_for_marg=3, min_good_res_for_marg=4, min_idepth_h_marg=50.0, marg_weight_fac=0.25,
+              idepth_fix_prior_marg_fac=360000.0)
+MARG_KEYS = ("flagged", "n_good_residuals", "last_state", "idepth_hessian", "ad_ht_delta", "c_delta", "H_M", "b_M", "marg_frames",
+             "frame_prior", "frame_delta_prior")
+OWN = ("verdict", "H_M_out", "b_M_out", "n_res_marg", "H_M_points", "b_M_points", "res_to_zero")
+PER_RESIDUAL = ("new_state", "new_energy", "new_energy_with_outlier", "center_projected_to", "projected_to", "active", "JpJdF", "res_to_zero")
+POINT_KEYS = ("host", "u", "v", "idepth_scaled", "idepth_zero_scaled", "color", "weights")
+FILL = -7.0
+
+
+# ---- C -----------------------------------------------------------------------------------------------------------------------------
+
+def classify(job, marg=None):
+    """C: (verdict, why) per point; `why` names the rule that decided and, for a point that is not kept, what made it a candidate"""
+    P = dict(PARAMS, **(marg or {}))
+    mga, mgr, mih = int(P["min_good_active_res_for_marg"]), int(P["min_good_res_for_marg"]), f32(P["min_idepth_h_marg"])
+    host, point, target, state_in = (np.asarray(job[k]) for k in ("host", "point", "target", "state_in"))
+    flagged = np.asarray(job["flagged"]).astype(bool)
+    last = np.asarray(job["last_state"]).reshape(-1, 2)
+    verdict, why = np.zeros(len(host), np.uint8), []
+    for p in range(len(host)):
+        rs = np.flatnonzero(point == p)
+        k = len(rs)
+        vis = int(sum(1 for r in rs if state_in[r] == R.IN and flagged[target[r]]))
+        n_good = int(job["n_good_residuals"][p])
+        if f32(job["idepth_scaled"][p]) < 0 or k == 0:  # C1
+            verdict[p] = DROP
+            why.append(("c1_idepth" if f32(job["idepth_scaled"][p]) < 0 else "c1_no_residuals", ()))
+            continue
+        clauses = (k >= mga and n_good > mgr + 10 and k - vis < mga, last[p, 0] == R.OOB, k >= 2 and last[p, 0] == R.OUTLIER and last[p, 1] == R.OUTLIER)
+        cand = tuple(name for name, on in zip(("oob1", "oob2", "oob3", "host_flagged"), clauses + (bool(flagged[host[p]]),)) if on)
+        if not cand:  # C2
+            verdict[p] = KEEP
+            why.append(("keep", cand))
+        elif not (k >= mga and n_good >= mgr):  # C3
+            verdict[p] = DROP
+            why.append(("c3_few_residuals" if k < mga else "c3_few_good", cand))
+        elif f32(job["idepth_hessian"][p]) > mih:  # C4
+            verdict[p] = MARGINALIZE
+            why.append(("c4_marginalize", cand))
+        else:
+            verdict[p] = DROP
+            why.append(("c4_drop", cand))
+    return verdict, why
+
+
+# ---- M1, X1 ------------------------------------------------------------------------------------------------------------------------
+
+def sub_window(job, verdict, marg=None):
+    """M1: (sub job with its Hessian extras, the window's indices of its points, of its residuals)"""
+    P = dict(PARAMS, **(marg or {}))
+    pts = np.flatnonzero(np.asarray(verdict) == MARGINALIZE)
+    new_index = -np.ones(len(verdict), int)
+    new_index[pts] = np.arange(len(pts))
+    res = np.array([r for r in range(len(job["point"])) if new_index[job["point"][r]] >= 0], int)
+    sub = R.subset(job, res)
+    sub["point"] = new_index[np.asarray(job["point"])[res]].astype(np.int32)
+    sub["state_in"] = np.full(len(res), R.IN, np.uint8)  # resetOOB
+    sub["energy_in"] = np.zeros(len(res), f32)
+    sub["fix_linearization"] = 0
+    for k in POINT_KEYS:
+        sub[k] = np.asarray(job[k])[pts].copy()
+    n = len(job["host"])
+    prior = np.asarray(job["prior"], f32) if job.get("prior") is not None else np.zeros(n, f32)
+    delta = np.asarray(job["delta"], f32) if job.get("delta") is not None else np.zeros(n, f32)
+    sub.update(prior=(prior[pts] * f32(P["idepth_fix_prior_marg_fac"])).astype(f32), delta=delta[pts].copy(), hdd_lin=None, bd_lin=None, hcd_lin=None,
+               shift_prior_to_zero=0)
+    return sub, pts, res
+
+
+def res_to_zero(row, dp, cd, delta):
+    """X1 for one row: the eight floats"""
+    row, dp, cd, delta = np.asarray(row, f32), np.asarray(dp, f32), np.asarray(cd, f32), f32(delta)
+    j = []
+    for a in range(2):
+        sx, sc = f32(0.0), f32(0.0)
+        for k in range(6):
+            sx = f32(sx + f32(row[HR.PDXI + 6 * a + k] * dp[k]))
+        for c in range(4):
+            sc = f32(sc + f32(row[HR.PDC + 4 * a + c] * cd[c]))
+        j.append(f32(f32(sx + sc) + f32(row[HR.PDD + a] * delta)))
+    out = np.zeros(8, f32)
+    for i in range(8):
+        v = f32(row[HR.RESF + i] - f32(row[HR.IDX + i] * j[0]))
+        v = f32(v - f32(row[HR.IDX + 8 + i] * j[1]))
+        v = f32(v - f32(row[HR.ABF + i] * dp[6]))
+        out[i] = f32(v - f32(row[HR.ABF + 8 + i] * dp[7]))
+    return out
+
+
+def res_to_zero_f64(row, dp, cd, delta):
+    """(value, sum of the magnitudes of the terms) of X1 in float64"""
+    row, dp, cd, delta = np.asarray(row, f64), np.asarray(dp, f64), np.asarray(cd, f64), float(delta)
+    val, mag = np.zeros(8), np.zeros(8)
+    j, jm = [], []
+    for a in range(2):
+        terms = np.concatenate([row[HR.PDXI + 6 * a:HR.PDXI + 6 * a + 6] * dp[:6], row[HR.PDC + 4 * a:HR.PDC + 4 * a + 4] * cd, [row[HR.PDD + a] * delta]])
+        j.append(terms.sum()), jm.append(np.abs(terms).sum())
+    for i in range(8):
+        terms = [row[HR.RESF + i], -row[HR.IDX + i] * j[0], -row[HR.IDX + 8 + i] * j[1], -row[HR.ABF + i] * dp[6], -row[HR.ABF + 8 + i] * dp[7]]
+        val[i] = sum(terms)
+        mag[i] = abs(terms[0]) + abs(row[HR.IDX + i]) * jm[0] + abs(row[HR.IDX + 8 + i]) * jm[1] + abs(terms[3]) + abs(terms[4])
+    return val, mag
+
+
+# ---- G -----------------------------------------------------------------------------------------------------------------------------
+
+def lu_inverse(A_in, xp=f64):
+    """G5: the inverse of an 8 x 8 matrix by LU with row partial pivoting, operation for operation"""
+    n = A_in.shape[0]
+    a = np.array(A_in, xp).copy()
+    piv = list(range(n))
+    with np.errstate(all="ignore"):
+        for k in range(n):
+            big, bigv = k, abs(a[k, k])
+            for i in range(k + 1, n):
+                if abs(a[i, k]) > bigv:  # false for a NaN on either side
+                    bigv, big = abs(a[i, k]), i
+            if big != k:
+                a[[k, big]] = a[[big, k]]
+                piv[k], piv[big] = piv[big], piv[k]
+            for i in range(k + 1, n):
+                m = a[i, k] / a[k, k]
+                a[i, k] = m
+                for j in range(k + 1, n):
+                    a[i, j] = a[i, j] - m * a[k, j]
+        P = np.zeros((n, n), xp)
+        for c in range(n):
+            y = np.zeros(n, xp)
+            for i in range(n):
+                s = xp(0.0)
+                for j in range(i):
+                    s = s + a[i, j] * y[j]
+                y[i] = xp(1.0 if piv[i] == c else 0.0) - s
+            for i in range(n - 1, -1, -1):
+                s = xp(0.0)
+                for j in range(i + 1, n):
+                    s = s + a[i, j] * P[j, c]
+                P[i, c] = (y[i] - s) / a[i, i]
+    return P
+
+
+def marginalize_frame(H, b, f, prior, delta_prior, drop=(), xp=f64):
+    """G1-G7 for the frame at index f of the system (H, b): the system without it.  xp: the type of every operation (float64 as the
+    rules say; numpy.longdouble measures what the roundings of the float64 evaluation amount to)"""
+    H, b = np.asarray(H, xp), np.asarray(b, xp)
+    N = len(b)
+    nd = N - 8
+    at = 4 + 8 * f
+    order = list(range(at)) + list(range(at + 8, N)) + list(range(at, at + 8))  # G1
+    if "perm" in drop:
+        order = list(range(N))
+    Hp, bp = H[np.ix_(order, order)].copy(), b[order].copy()
+    if "G2" not in drop:
+        for k in range(8):
+            Hp[nd + k, nd + k] = Hp[nd + k, nd + k] + xp(prior[k])
+            bp[nd + k] = bp[nd + k] + xp(prior[k]) * xp(delta_prior[k])
+    with np.errstate(all="ignore"):
+        S = np.sqrt(np.abs(np.diag(Hp)) + xp(10.0))  # G3
+        SI = xp(1.0) / S
+        Hs = (SI[:, None] * Hp) * SI[None, :]  # G4
+        bs = SI * bp
+        P = lu_inverse(Hs[nd:, nd:], xp)  # G5
+        bli = np.zeros((nd, 8), xp)  # G6
+        for j in range(8):
+            bli = bli + Hs[nd + j, :nd][:, None] * P[j, :][None, :]
+        if "bli_T" in drop:  # the nd x 8 array read as if it were stored 8 x nd (the system is symmetric: transposing P changes nothing)
+            bli = np.ascontiguousarray(bli).reshape(8, nd).T
+        accH, accb = np.zeros((nd, nd), xp), np.zeros(nd, xp)
+        for k in range(8):
+            accH = accH + bli[:, k][:, None] * Hs[nd + k, :nd][None, :]
+            accb = accb + bli[:, k] * bs[nd + k]
+        Hn, bn = Hs[:nd, :nd] - accH, bs[:nd] - accb
+        Hu = (S[:nd, None] * Hn) * S[None, :nd]  # G7
+        return xp(0.5) * (Hu + Hu.T), S[:nd] * bn
+
+
+def marginalize_frames(H, b, marg_frames, priors, delta_priors, drop=(), xp=f64):
+    """G for every entry of marg_frames on the previous result, the indices renumbered"""
+    for m, f in enumerate(marg_frames):
+        H, b = marginalize_frame(H, b, int(f) - m, priors[m], delta_priors[m], drop, xp)
+    return H, b
+
+
+# ---- the whole call ----------------------------------------------------------------------------------------------------------------
+
+def marginalize(w, h, job, frames, marg=None, params=None, drop=()):
+    """every output of a marginalize job; drop: a sub-window residual index left out of the accumulation ("residual", i), or the names
+    marginalize_frame takes"""
+    P = dict(PARAMS, **(marg or {}))
+    nf, n, nr = len(job["frame_ids"]), len(job["host"]), len(job["point"])
+    N = 4 + 8 * nf
+    verdict, why = classify(job, marg)
+    sub, pts, res = sub_window(job, verdict, marg)
+    lin = R.linearize(w, h, sub, frames, params)  # L1-L8 with fix_linearization = 0
+    active = HR.active_of(sub, lin)
+    dp = np.asarray(job["ad_ht_delta"], f32).reshape(nf, nf, 8)
+    cd = np.asarray(job["c_delta"], f32).reshape(4)
+    rows = lin["J"].copy()
+    rtz = np.full((nr, 8), FILL, f32)
+    for i in np.flatnonzero(active):  # X1
+        p = int(sub["point"][i])
+        rows[i, HR.RESF:HR.RESF + 8] = res_to_zero(lin["J"][i], dp[int(sub["host"][p]), int(sub["target"][i])], cd, sub["delta"][p])
+        rtz[res[i]] = rows[i, HR.RESF:HR.RESF + 8]
+    dropped = tuple(d[1] for d in drop if isinstance(d, tuple) and d[0] == "residual")
+    hes = HR.hessian(sub, dict(lin, J=rows), sub, drop=dropped)  # A1' with A2, A3, P1, S1-S3, T1
+    HM = np.asarray(job["H_M"], f64).reshape(N, N) if job.get("H_M") is not None else np.zeros((N, N))
+    bM = np.asarray(job["b_M"], f64).reshape(N) if job.get("b_M") is not None else np.zeros(N)
+    wt = float(f32(P["marg_weight_fac"]))
+    Hp, bp = HM + wt * (hes["H_A"] - hes["H_sc"]), bM + wt * (hes["b_A"] - hes["b_sc"])  # M2
+    marg_frames = [int(f) for f in np.asarray(job.get("marg_frames", ()), int).reshape(-1)]
+    priors = np.asarray(job["frame_prior"], f64).reshape(-1, 8) if marg_frames else ()
+    dpriors = np.asarray(job["frame_delta_prior"], f64).reshape(-1, 8) if marg_frames else ()
+    Ho, bo = marginalize_frames(Hp, bp, marg_frames, priors, dpriors, tuple(d for d in drop if isinstance(d, str)))
+    out = dict(verdict=verdict, why=why, H_M_out=np.ascontiguousarray(Ho), b_M_out=bo, n_res_marg=int(active.sum()), H_M_points=Hp, b_M_points=bp,
+               res_to_zero=rtz, sub_points=pts, sub_residuals=res, sub=sub, sub_lin=lin, sub_rows=rows, sub_hes=hes)
+    # Z: the sub-window's results at the window's indices, the mirror's fill values everywhere else
+    out.update(new_state=np.full(nr, 77, np.uint8), new_energy=np.full(nr, FILL, f32), new_energy_with_outlier=np.full(nr, FILL, f32),
+               center_projected_to=np.full((nr, 3), FILL, f32), projected_to=np.full((nr, 16), FILL, f32), active=np.full(nr, 77, np.uint8),
+               JpJdF=np.full((nr, 8), FILL, f32))
+    for i, r in enumerate(res):
+        out["new_state"][r], out["new_energy"][r], out["new_energy_with_outlier"][r] = lin["new_state"][i], lin["new_energy"][i], lin["new_energy_with_outlier"][i]
+        out["active"][r] = hes["active"][i]
+        if lin["defined"][i]:
+            out["center_projected_to"][r], out["projected_to"][r] = lin["center_projected_to"][i], lin["projected_to"][i]
+        if hes["active"][i]:
+            out["JpJdF"][r] = hes["JpJdF"][i]
+    for k in HR.PER_POINT:
+        out[k] = np.full((n, 4) if k == "hcd_acc" else n, FILL, f32)
+        out[k][pts] = hes[k]
+    for k in HR.STITCHED + HR.RAW:
+        out[k] = hes[k]
+    out["energy"], out["new_frame_energy_th"] = lin["energy"], lin["new_frame_energy_th"]
+    return out
+
+
+# ---- the shared scenes -------------------------------------------------------------------------------------------------------------
+
+def make_marg_extra(job, seed, flagged, marg_frames, priors=True):
+    """what a marginalize job holds on top of its hessian job, seeded: the frames' flags, per point numGoodResiduals (0 .. 24), the two
+    last states (IN 60 %, OOB 15 %, OUTLIER 25 %), idepth_hessian either side of 50, three points behind the camera; small adHTdeltaF
+    and cDeltaF; a symmetric positive definite prior (J^T J + diagonal, _solve_ref's); per marginalised frame a prior and a delta"""
+    rng = np.random.default_rng(3000 + seed)
+    nf, n = len(job["frame_ids"]), len(job["host"])
+    N = 4 + 8 * nf
+    fl = np.zeros(nf, np.uint8)
+    fl[list(flagged)] = 1
+    ex = dict(flagged=fl, n_good_residuals=rng.integers(0, 25, n).astype(np.int32),
+              last_state=rng.choice([R.IN, R.OOB, R.OUTLIER], (n, 2), p=[0.6, 0.15, 0.25]).astype(np.uint8),
+              idepth_hessian=rng.uniform(0, 150, n).astype(f32), ad_ht_delta=rng.normal(0, 0.01, (nf, nf, 8)).astype(f32),
+              c_delta=rng.normal(0, 0.01, 4).astype(f32), marg_frames=np.array(marg_frames, np.int32).reshape(-1), fix_linearization=0)
+    nm = len(marg_frames)
+    ex["frame_prior"] = np.where(rng.uniform(size=(nm, 8)) < 0.7, rng.uniform(0, 1e3, (nm, 8)), 0.0)
+    ex["frame_delta_prior"] = rng.normal(0, 0.01, (nm, 8))
+    idepth = np.asarray(job["idepth_scaled"], f32).copy()
+    if n:
+        idepth[rng.choice(n, min(3, n), replace=False)] *= f32(-1.0)
+    ex["idepth_scaled"] = idepth
+    if priors:
+        sol = SR.make_solve_extra(job, 40 + seed)
+        ex.update(H_M=sol["H_M"], b_M=sol["b_M"])
+    return ex
+
+
+def without_residuals_of(job, points):
+    """the job without the residuals of `points`"""
+    keep = [r for r in range(len(job["point"])) if int(job["point"][r]) not in points]
+    return R.subset(job, keep)
+
+
+# name -> (the hessian case it sits on, flagged, marg_frames)
+SCENES = {
+    "scene": ("scene", (1, 3), (1,)),                 # 5 frames, a middle frame leaves, another is flagged and stays
+    "nine_frames": ("nine_frames", (0, 4, 8), (0, 8)),  # two frames in one job: the first and the last
+    "two_frames": ("two_frames", (1,), (1,)),          # the last
+    "one_frame": ("one_frame", (0,), (0,)),            # every frame leaves: N' = 4
+    "three_frames_no_residuals": ("three_frames_no_residuals", (0, 2), ()),  # flagged frames, none leaves
+    "no_points": ("no_points", (0,), (0,)),            # the first
+    "sixteen_frames": ("sixteen_frames", (2, 15), (2,)),
+    "wide": ("wide", (0,), (0,)),                      # two frames and 140 points: the first
+}
+_cache = {}
+
+
+def scene_job(name, marg_frames=None, flagged=None, priors=True):
+    """(job, frames) of a scene; two points of the larger scenes lose all their residuals (C1's second clause)"""
+    base, fl, mf = SCENES[name]
+    job, frames, _ = HR.case(base)
+    if len(job["host"]) > 30:
+        job = without_residuals_of(job, (4, 9))
+    mf = mf if marg_frames is None else tuple(marg_frames)
+    fl = tuple(sorted(set(fl if flagged is None else flagged) | set(mf)))
+    return dict(job, **make_marg_extra(job, list(SCENES).index(name), fl, mf, priors)), frames
+
+
+def case(name, marg=None, **kw):
+    """(job, frames, expected) at _linearize_ref's geometry, computed once per variant"""
+    key = (name, tuple(sorted((marg or {}).items())), tuple(sorted(kw.items())))
+    if key not in _cache:
+        job, frames = scene_job(name, **kw)
+        _cache[key] = (job, frames, marginalize(R.W, R.H, job, frames, marg))
+    return _cache[key]
+
+
+def frames_case(nf, marg_frames, marg=None):
+    """(job, frames, expected) of a window of nf frames and 40 points (_solve_ref.frames_case), for the frame counts the scenes lack"""
+    key = ("frames", nf, tuple(marg_frames), tuple(sorted((marg or {}).items())))
+    if key not in _cache:
+        job, frames, _ = SR.frames_case(nf)
+        job = {k: v for k, v in job.items() if k not in SR.SOLVE_KEYS}
+        job = dict(job, **make_marg_extra(job, 100 + nf, tuple(marg_frames), tuple(marg_frames)))
+        _cache[key] = (job, frames, marginalize(R.W, R.H, job, frames, marg))
+    return _cache[key]
+
+
+def geometry_case():
+    """(job, frames, expected) at _linearize_ref.GEOMETRY (101 x 53) with nine frames moving towards every side; frames 2 and 6 leave"""
+    if "geometry" not in _cache:
+        w, h = R.GEOMETRY
+        job, frames = R.make_case(seed=8, n_frames=9, n_pts=70, w=w, h=h, around=True)
+        job = dict(job, **HR.make_extra(job, seed=8))
+        job = dict(job, **make_marg_extra(job, 8, (2, 5, 6), (2, 6)))
+        _cache["geometry"] = (job, frames, marginalize(w, h, job, frames))
+    return _cache["geometry"]
+
+
+LOOSE = dict(min_good_active_res_for_marg=1, min_good_res_for_marg=0)  # a point of one residual may be marginalised
+
+
+def forced_case(base, n_points=None, n_residuals=None):
+    """(job, frames, expected, marg): a scene whose per-point inputs are set so that the sub-window holds exactly n_points points, or
+    points with exactly n_residuals residuals in all (chosen greedily in ascending index), under LOOSE; every other point is kept"""
+    key = ("forced", base, n_points, n_residuals)
+    if key not in _cache:
+        job, frames = scene_job(base, marg_frames=(), flagged=())
+        n = len(job["host"])
+        k = np.bincount(np.asarray(job["point"], int), minlength=n)
+        chosen, total, cut = [], 0, []
+        for p in range(n):
+            if k[p] == 0 or f32(job["idepth_scaled"][p]) < 0:
+                continue
+            if n_points is not None and len(chosen) < n_points:
+                chosen.append(p)
+            if n_residuals is not None and total < n_residuals:
+                chosen.append(p)
+                own = np.flatnonzero(np.asarray(job["point"]) == p)
+                cut += list(own[n_residuals - total:])  # the last chosen point loses the residuals beyond the count
+                total += min(int(k[p]), n_residuals - total)
+        job = R.subset(job, [r for r in range(len(job["point"])) if r not in set(cut)])
+        last = np.full((n, 2), R.IN, np.uint8)
+        last[chosen, 0] = R.OOB
+        job = dict(job, last_state=last, n_good_residuals=np.full(n, 9, np.int32), idepth_hessian=np.full(n, 100.0, f32))
+        _cache[key] = (job, frames, marginalize(R.W, R.H, job, frames, LOOSE), LOOSE)
+    return _cache[key]
+
+
+def next_keyframe(job, exp):
+    """the solve job of the next keyframe on the shrunken window: the frames that stay, the points of verdict 0 with their residuals,
+    every residual state as committed, the returned prior as H_M / b_M"""
+    nf = len(job["frame_ids"])
+    stay = [f for f in range(nf) if f not in set(int(x) for x in job["marg_frames"])]
+    new_frame = -np.ones(nf, int)
+    new_frame[stay] = np.arange(len(stay))
+    pts = np.flatnonzero(exp["verdict"] == KEEP)
+    new_point = -np.ones(len(job["host"]), int)
+    new_point[pts] = np.arange(len(pts))
+    res = [r for r in range(len(job["point"])) if new_point[job["point"][r]] >= 0 and new_frame[job["target"][r]] >= 0]
+    nxt = R.subset(job, res)
+    nxt["point"] = new_point[np.asarray(job["point"])[res]].astype(np.int32)
+    nxt["target"] = new_frame[np.asarray(job["target"])[res]].astype(np.int32)
+    for k in POINT_KEYS:
+        nxt[k] = np.asarray(job[k])[pts].copy()
+    nxt["host"] = new_frame[nxt["host"]].astype(np.int32)
+    for k in ("prior", "delta", "hdd_lin", "bd_lin", "hcd_lin"):
+        if job.get(k) is not None:
+            nxt[k] = np.asarray(job[k])[pts].copy()
+    ns = len(stay)
+    for k, m in R.PRE:
+        nxt[k] = np.asarray(job[k], f32).reshape(nf, nf, m)[np.ix_(stay, stay)].copy()
+    for k in ("ad_host", "ad_target"):
+        nxt[k] = np.asarray(job[k], f64).reshape(nf, nf, 8, 8)[np.ix_(stay, stay)].copy()
+    nxt["frame_ids"], nxt["frame_energy_th"] = np.asarray(job["frame_ids"])[stay].copy(), np.asarray(job["frame_energy_th"])[stay].copy()
+    for k in MARG_KEYS:
+        nxt.pop(k, None)
+    Nn = 4 + 8 * ns
+    rng = np.random.default_rng(5)
+    G = rng.normal(0, 3.0, (Nn, Nn))
+    nxt.update(H_L=np.tril(G @ G.T) + np.tril(G @ G.T, -1).T, b_L=rng.normal(0, 30.0, Nn), H_M=exp["H_M_out"], b_M=exp["b_M_out"],
+               delta_x=rng.normal(0, 0.05, Nn), **{"lambda": 1e-5})
+    return nxt, stay
+
+
+# ---- two keyframes: optimize, marginalise, shrink, optimize (host/marginalize_demo.cpp's chain) -------------------------------------
+
+def set_delta(delta_f, c_delta, ad_host, ad_target):
+    """adHTdeltaF as MarginalizeRequest::setDeltaF forms it from delta_f = state - state_zero (n x 8 doubles): float products and sums
+    over ascending k from 0, the host's part and the target's part added last"""
+    nf = len(delta_f)
+    adh, adt = (np.asarray(a, f64).reshape(nf, nf, 8, 8).astype(f32) for a in (ad_host, ad_target))
+    d = np.asarray(delta_f, f64).astype(f32)
+    out = np.zeros((nf, nf, 8), f32)
+    for h in range(nf):
+        for t in range(nf):
+            if h == t:
+                continue
+            a, b = np.zeros(8, f32), np.zeros(8, f32)
+            for k in range(8):
+                a = a + d[h, k] * adh[h, t, k]
+                b = b + d[t, k] * adt[h, t, k]
+            out[h, t] = a + b
+    return out, np.asarray(c_delta, f64).astype(f32)
+
+
+def keyframe_chain(name="scene", max_iterations=6, leaves=1):
+    """The checkers' chain on a _step_ref scene: _optimize_ref's loop; the marginalize job of the committed window (frame `leaves`
+    flagged and marginalised, every point with 9 good residuals and last states IN, the frame's prior 100 (k + 1) and delta prior
+    0.001 (k + 1)); the window shrunk to the frames that stay and the points of verdict 0; _optimize_ref's loop on the returned prior.
+    Returns (first result, marginalize job, its result, second job, second frames, second result), computed once."""
+    import _optimize_ref as O
+
+    key = ("chain", name, max_iterations, leaves)
+    if key in _cache:
+        return _cache[key]
+    job, frames, one = O.expected(name, max_iterations)
+    nf, n = len(job["frame_ids"]), len(job["host"])
+    N = 4 + 8 * nf
+    d = lambda k, shape: np.asarray(job[k], f64).reshape(shape)  # noqa: E731
+    state, calib, idepth = np.asarray(one["state"], f64).reshape(nf, 8), np.asarray(one["calib"], f64), np.asarray(one["idepth"], f32)
+    dp, cd = set_delta(state - d("state_zero", (nf, 8)), calib - d("calib_zero", 4), job["ad_host"], job["ad_target"])
+    flagged = np.zeros(nf, np.uint8)
+    flagged[leaves] = 1
+    mjob = {k: job[k] for k in ("frame_ids", "host", "u", "v", "color", "weights", "point", "target", "is_new", "ad_host", "ad_target", "prior")}
+    mjob.update({k: one[k] for k, _ in R.PRE})
+    mjob.update(cam=tuple(one["cam"][:4]), cam_inv=tuple(one["cam"][4:]), frame_energy_th=one["committed"]["frame_energy_th"], idepth_scaled=idepth,
+                idepth_zero_scaled=idepth, state_in=one["new_state"], energy_in=one["new_energy"], fix_linearization=0, delta=None,
+                flagged=flagged, n_good_residuals=np.full(n, 9, np.int32), last_state=np.zeros((n, 2), np.uint8), idepth_hessian=one["idepth_hessian"],
+                ad_ht_delta=dp, c_delta=cd, H_M=job.get("H_M"), b_M=job.get("b_M"), marg_frames=np.array([leaves], np.int32),
+                frame_prior=100.0 * np.arange(1, 9, dtype=f64).reshape(1, 8), frame_delta_prior=0.001 * np.arange(1, 9, dtype=f64).reshape(1, 8))
+    marg = marginalize(R.W, R.H, mjob, frames)
+    stay = [f for f in range(nf) if f != leaves]
+    new_frame, new_point = -np.ones(nf, int), -np.ones(n, int)
+    new_frame[stay] = np.arange(len(stay))
+    pts = np.flatnonzero(marg["verdict"] == KEEP)
+    new_point[pts] = np.arange(len(pts))
+    res = [r for r in range(len(job["point"])) if new_point[job["point"][r]] >= 0 and new_frame[job["target"][r]] >= 0]
+    idx = list(range(4)) + [4 + 8 * f + k for f in stay for k in range(8)]
+    two = dict(job)
+    two.update(frame_ids=np.asarray(job["frame_ids"])[stay], frame_energy_th=np.asarray(one["committed"]["frame_energy_th"], f32)[stay],
+               host=new_frame[np.asarray(job["host"])[pts]].astype(np.int32), point=new_point[np.asarray(job["point"])[res]].astype(np.int32),
+               target=new_frame[np.asarray(job["target"])[res]].astype(np.int32), state_in=np.asarray(one["new_state"])[res],
+               energy_in=np.asarray(one["new_energy"], f32)[res], is_new=np.asarray(job["is_new"])[res])
+    for k in ("u", "v", "color", "weights", "prior", "hdd_lin", "bd_lin", "hcd_lin"):
+        two[k] = np.asarray(job[k])[pts]
+    for k in ("ad_host", "ad_target"):
+        two[k] = d(k, (nf, nf, 8, 8))[np.ix_(stay, stay)].copy()
+    two.update(H_L=d("H_L", (N, N))[np.ix_(idx, idx)].copy(), b_L=d("b_L", N)[idx], H_M=marg["H_M_out"], b_M=marg["b_M_out"], n_null=0, null_basis=None,
+               null_pinv=None, world_to_cam_eval=d("world_to_cam_eval", (nf, 7))[stay], state_zero=d("state_zero", (nf, 8))[stay],
+               state_backup=state[stay], calib_backup=calib, idepth_backup=idepth[pts], exposure=np.asarray(job["exposure"], f32)[stay])
+    if job.get("state_prior") is not None:
+        two.update(state_prior=d("state_prior", N)[idx], state_prior_zero=d("state_prior_zero", N)[idx])
+    frames2 = [frames[f] for f in stay]
+    _cache[key] = (one, mjob, marg, two, frames2, O.run(two, frames2, max_iterations))
+    return _cache[key]
+
+
+# ---- for tools/marginalize_host_standalone.cpp -------------------------------------------------------------------------------------
+
+HASHED = ("verdict", "H_M_out", "b_M_out", "H_M_points", "b_M_points", "res_to_zero", "new_state", "new_energy", "new_energy_with_outlier",
+          "center_projected_to", "projected_to", "active", "JpJdF") + HR.STITCHED + HR.RAW + HR.PER_POINT
+
+
+def write_case(path, w, h, job, frames):
+    """the marginalize file: the window file of host/linearize_demo.cpp, then the Hessian job's ad_host, ad_target, prior and delta,
+    then what a marginalize job holds on top"""
+    import struct
+
+    from test_linearize_demo import write_case as write_window
+
+    n, m = len(job["frame_ids"]), len(job["host"])
+    write_window(path, w, h, job, frames)
+    pin = np.stack([np.asarray(job[k] if job.get(k) is not None else np.zeros(m), f32).reshape(m) for k in ("prior", "delta")], axis=1)
+    d = lambda k: np.ascontiguousarray(job[k], f64).tobytes()  # noqa: E731
+    s = lambda k: np.ascontiguousarray(job[k], f32).tobytes()  # noqa: E731
+    marg = np.asarray(job.get("marg_frames", ()), np.int32).reshape(-1)
+    with open(path, "ab") as f:
+        f.write(d("ad_host") + d("ad_target") + np.ascontiguousarray(pin, f32).tobytes())
+        f.write(np.ascontiguousarray(job["flagged"], np.uint8).tobytes() + np.ascontiguousarray(job["n_good_residuals"], np.int32).tobytes())
+        f.write(np.ascontiguousarray(job["last_state"], np.uint8).tobytes() + s("idepth_hessian") + s("ad_ht_delta") + s("c_delta"))
+        f.write(struct.pack("i", int(job.get("H_M") is not None)))
+        if job.get("H_M") is not None:
+            f.write(d("H_M") + d("b_M"))
+        f.write(struct.pack("i", len(marg)) + marg.tobytes() + d("frame_prior") + d("frame_delta_prior"))
+
+
+def hashes(exp):
+    """what tools/marginalize_host_standalone.cpp prints, from a checker result"""
+    from test_linearize_demo import fnv1a
+
+    hx = lambda a: f"{fnv1a(np.ascontiguousarray(a).tobytes()):016x}"  # noqa: E731
+    out = {k: hx(exp[k]) for k in HASHED}
+    out.update(n_res=len(exp["new_state"]), n_res_marg=int(exp["n_res_marg"]), energy=hx(np.array([exp["energy"]], f64)),
+               new_frame_energy_th=hx(np.array([exp["new_frame_energy_th"]], f32)), lean_equal=1)
+    return out
+
+
+def assert_equal(got, exp, outputs=OWN + HR.STITCHED + HR.RAW + HR.PER_POINT + PER_RESIDUAL, fills=()):
+    """every output bit for bit (a NaN where the checker has a NaN: _solve_ref.assert_equal has the reason); `fills`: outputs that
+    were not asked for and must hold the mirror's fill value"""
+    for k in tuple(dict.fromkeys(outputs)) + ("energy", "new_frame_energy_th"):
+        if k in fills:
+            continue
+        if k == "n_res_marg":
+            assert int(got[k]) == int(exp[k]), (k, got[k], exp[k])
+            continue
+        a, b = np.asarray(got[k]), np.asarray(exp[k])
+        assert a.dtype == b.dtype and a.shape == b.shape, (k, a.dtype, b.dtype, a.shape, b.shape)
+        assert (np.isnan(a) == np.isnan(b)).all(), (k, np.argwhere(np.isnan(a) != np.isnan(b))[:6])
+        if a.dtype.kind == "f":
+            a, b = np.where(np.isnan(a), a.dtype.type(0), a), np.where(np.isnan(b), b.dtype.type(0), b)
+        assert a.tobytes() == b.tobytes(), (k, np.argwhere(a != b)[:6], a[a != b][:3], b[a != b][:3])
+    for k in fills:
+        assert (np.asarray(got[k]) == FILL).all(), k
+
+
+def invalid_jobs(job):
+    """(what, job) of the calls the marginalize call refuses on top of the Hessian call's"""
+    def with_(key, at, value, dtype=None):
+        a = np.array(job[key], dtype, copy=True)
+        a[at] = value
+        return dict(job, **{key: a})
+
+    nf = len(job["frame_ids"])
+    N = 4 + 8 * nf
+    mf = [int(f) for f in job["marg_frames"]]
+    unflagged = next(f for f in range(nf) if not job["flagged"][f])
+    out =[(f"no {k}", dict(job, **{k: None})) for k in ("flagged", "n_good_residuals", "last_state", "idepth_hessian", "ad_ht_delta", "c_delta")]
+    out += [("last_state 3", with_("last_state", (2, 1), 3)), ("idepth_hessian NaN", with_("idepth_hessian", 1, np.nan)),
+            ("ad_ht_delta inf", with_("ad_ht_delta", (1, 0, 7), np.inf)), ("c_delta NaN", with_("c_delta", 2, np.nan)),
+            ("H_M NaN", with_("H_M", (3, 4), np.nan)), ("b_M inf", with_("b_M", N - 1, -np.inf)),
+            ("frame_prior NaN", with_("frame_prior", (0, 5), np.nan)), ("frame_delta_prior inf", with_("frame_delta_prior", (0, 0), np.inf)),
+            ("marg_frames descending", dict(job, marg_frames=np.array([3, 1], np.int32), frame_prior=np.zeros((2, 8)), frame_delta_prior=np.zeros((2, 8)))),
+            ("marg_frames repeated", dict(job, marg_frames=np.array([1, 1], np.int32), frame_prior=np.zeros((2, 8)), frame_delta_prior=np.zeros((2, 8)))),
+            ("marg_frames past the end", dict(job, marg_frames=np.array([nf], np.int32))), ("marg_frames below 0", dict(job, marg_frames=np.array([-1], np.int32))),
+            ("a marginalised frame that is not flagged", dict(job, marg_frames=np.array([unflagged], np.int32))),
+            ("n_marg_frames -1", dict(job, n_marg_frames=-1)), ("n_marg_frames past n", dict(job, n_marg_frames=nf + 1)),
+            ("no frame_prior", dict(job, frame_prior=None)), ("no frame_delta_prior", dict(job, frame_delta_prior=None)),
+            ("fix_linearization", dict(job, fix_linearization=1))]
+    assert mf == [1] and nf == 5, "invalid_jobs is written for the scene"
+    return out
+
+
+def invalid_params():
+    return [dict(min_idepth_h_marg=float("nan")), dict(marg_weight_fac=float("inf")), dict(idepth_fix_prior_marg_fac=float("nan")),
+            dict(min_good_active_res_for_marg=-1), dict(min_good_res_for_marg=-2)]
