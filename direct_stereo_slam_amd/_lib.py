@@ -267,6 +267,23 @@ class OptimizeJob(C.Structure):
     ]
 
 
+class FinishJob(C.Structure):
+    _fields_ = [
+        ("opt", OptimizeJob), ("n_good_residuals_in", c_int_p), ("max_rel_baseline_in", c_float_p), ("last_res", c_int_p),
+        ("last_state_in", C.POINTER(C.c_ubyte)),
+        ("world_to_cam_eval_out", c_double_p), ("state_zero_out", c_double_p), ("state_out", c_double_p),
+        ("ad_host_out", c_double_p), ("ad_target_out", c_double_p), ("ad_ht_delta_out", c_float_p), ("c_delta_out", c_float_p),
+        ("delta_x_out", c_double_p), ("pre_RTll_0_out", c_float_p), ("pre_tTll_0_out", c_float_p), ("pre_KRKiTll_out", c_float_p),
+        ("pre_KtTll_out", c_float_p), ("pre_aff_mode_out", c_float_p), ("pre_b0_mode_out", c_float_p), ("cam_out", c_float_p),
+        ("new_state", C.POINTER(C.c_ubyte)), ("new_energy", c_float_p), ("new_energy_with_outlier", c_float_p),
+        ("keep", C.POINTER(C.c_ubyte)), ("rel_bs", c_float_p), ("energy", c_double_p), ("frame_energy_th_out", c_float_p),
+        ("n_good_residuals_out", c_int_p), ("max_rel_baseline_out", c_float_p), ("last_res_out", c_int_p),
+        ("last_state_out", C.POINTER(C.c_ubyte)), ("n_res_kept", c_int_p), ("point_dropped", C.POINTER(C.c_ubyte)),
+        ("res_index_out", c_int_p), ("point_index_out", c_int_p), ("n_res_out", c_int_p), ("n_pts_out", c_int_p),
+        ("rmse", c_float_p), ("lost", c_int_p), ("cam_to_world_out", c_double_p), ("J_out", c_float_p),
+    ]
+
+
 class MarginalizeParams(C.Structure):
     _fields_ = [
         ("min_good_active_res_for_marg", C.c_int), ("min_good_res_for_marg", C.c_int), ("min_idepth_h_marg", C.c_float),
@@ -551,6 +568,13 @@ SYMBOLS = {
                                             C.POINTER(OptimizeParams)]),
     "dsm_window_optimize_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(OptimizeJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams),
                                            C.POINTER(StepParams), C.POINTER(OptimizeParams)]),
+    "dsm_window_finish_batch": (C.c_int, [_vp, C.c_int, C.POINTER(FinishJob), C.POINTER(LinearizeParams), C.POINTER(StepParams),
+                                          C.POINTER(OptimizeParams)]),
+    "dsm_window_finish_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(FinishJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams),
+                                         C.POINTER(StepParams), C.POINTER(OptimizeParams)]),
+    "dsm_diag_finish_prepare_host": (C.c_int, [C.POINTER(FinishJob), C.POINTER(LinearizeParams), C.POINTER(StepParams), c_float_p,
+                                                 C.POINTER(LinearizeJob)]),
+    "dsm_diag_finish_book_host": (C.c_int, [C.POINTER(FinishJob)]),
     "dsm_marginalize_params_default": (C.c_int, [C.POINTER(MarginalizeParams)]),
     "dsm_window_marginalize_batch": (C.c_int, [_vp, C.c_int, C.POINTER(MarginalizeJob), C.POINTER(LinearizeParams), C.POINTER(MarginalizeParams)]),
     "dsm_window_marginalize_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(MarginalizeJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams),

@@ -226,6 +226,8 @@ const char *step_job_error(const dsm_step_job &J);
 const char *optimize_params_error(const dsm_optimize_params *p);
 const char *optimize_job_error(const dsm_optimize_job &J);
 dsm_step_job optimize_first_pass(const dsm_optimize_job &J, const double *zeros, double lambda);
+// finish_host.cpp: what both forms of the finish call refuse on top of that
+const char *finish_job_error(const dsm_finish_job &J);
 // points_host.cpp: the copies of the optional raw accumulators alone
 void hessian_copy_raw(const dsm_hessian_job &J, const double *top, const double *D, const double *E, const double *EB, const double *Hcc,
                       const double *bc);

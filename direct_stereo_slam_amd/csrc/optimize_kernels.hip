@@ -17,14 +17,13 @@
 // A finished job is FROZEN: opt_decide_kernel restores H_L / b_L and returns, nothing else of its inputs is written, and every later
 // pass recomputes the same bytes.  After the upload the arena's input part is ordinary device memory: the kernels of sections 16-19
 // see other values at the same offsets and are unchanged.  No kernel waits for another workgroup; no scratch.
+// The call's host side is the pieces of optimize_launch.hpp, which dsm_window_finish_batch (finish_kernels.hip) runs too.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "step_launch.hpp"
-
-#include "optimize_math.hpp"
+#include "optimize_launch.hpp"
 
 using namespace dsm;
 
@@ -191,59 +190,89 @@ __global__ __launch_bounds__(kBlock) void opt_commit_kernel(const OptJob *jobs, 
 
 extern "C" int dsm_window_optimize_batch(dsm_context *ctx, int n_jobs, const dsm_optimize_job *jobs, const dsm_linearize_params *lp,
                                          const dsm_step_params *sp, const dsm_optimize_params *op) {
-  auto bad = [](const char *msg) { return invalid((std::string("dsm_window_optimize_batch: ") + msg).c_str()); };
+  std::vector<const dsm_optimize_job *> list;
+  for (int j = 0; jobs && j < n_jobs; j++) list.push_back(jobs + j);
+  OptPlan P;
+  int rc = optimize_check("dsm_window_optimize_batch", ctx, n_jobs, jobs ? list.data() : nullptr, lp, sp, op, P);
+  if (rc) return rc;
+  CallArena A;
+  optimize_layout(P, A);
+  if ((rc = A.bind(ctx))) return rc;
+  optimize_stage(P, A, *op);
+  if ((rc = A.upload())) return rc;
+  // enough when nothing is rejected; a rejected iteration costs one more pass
+  if ((rc = optimize_passes(ctx, P, A, *lp, *sp, 1 + P.max_it))) return rc;
+  if ((rc = A.fetch(A.out.used))) return rc;
+  if (optimize_unfinished(P, A)) {
+    if ((rc = optimize_passes(ctx, P, A, *lp, *sp, P.max_it))) return rc;
+    if ((rc = A.fetch(A.out.used))) return rc;
+  }
+  optimize_unpack(P, A, *lp);
+  return DSM_OK;
+}
+
+namespace dsm {
+
+int optimize_check(const char *call, dsm_context *ctx, int n_jobs, const dsm_optimize_job *const *jobs, const dsm_linearize_params *lp,
+                   const dsm_step_params *sp, const dsm_optimize_params *op, OptPlan &P) {
+  auto bad = [call](const char *msg) { return invalid((std::string(call) + ": " + msg).c_str()); };
   if (!ctx || n_jobs < 1 || !jobs) return bad("bad argument");
   if (const char *e = optimize_params_error(op)) return bad(e);
   size_t zeros = 4;
   int max_it = 0;
   for (int j = 0; j < n_jobs; j++) {
-    if (const char *e = optimize_job_error(jobs[j])) return bad(e);
-    const dsm_linearize_job &L = jobs[j].step.sol.hes.lin;
+    if (const char *e = optimize_job_error(*jobs[j])) return bad(e);
+    const dsm_linearize_job &L = jobs[j]->step.sol.hes.lin;
     zeros = std::max(zeros, std::max((size_t)8 * L.n_frames, (size_t)L.n_pts / 2 + 1));
-    max_it = std::max(max_it, jobs[j].max_iterations);
+    max_it = std::max(max_it, jobs[j]->max_iterations);
   }
-  const opt::Rules R{op->lambda_accept_fac, op->lambda_reject_fac, op->fixed_lambda, op->min_iterations, op->force_accept != 0, op->step_momentum != 0};
   const double lambda0 = op->fixed_lambda >= 0.0 ? op->fixed_lambda : op->lambda_init;
   // the step call's rules and pieces see pass 0: zero steps, zero factors, the first lambda
-  const std::vector<double> zero(zeros, 0.0);
-  std::vector<dsm_step_job> first(n_jobs);
-  for (int j = 0; j < n_jobs; j++) first[j] = optimize_first_pass(jobs[j], zero.data(), lambda0);
-  StpPlan P;
-  int rc = step_check("dsm_window_optimize_batch", ctx, n_jobs, first.data(), lp, sp, P);
-  if (rc) return rc;
+  P.n_jobs = n_jobs, P.max_it = max_it;
+  P.jobs.assign(jobs, jobs + n_jobs);
+  P.zero.assign(zeros, 0.0);
+  P.first.resize(n_jobs);
+  for (int j = 0; j < n_jobs; j++) P.first[j] = optimize_first_pass(*jobs[j], P.zero.data(), lambda0);
+  return step_check(call, ctx, n_jobs, P.first.data(), lp, sp, P.stp);
+}
 
-  // on top of the step call's parts: staged [job table | the jobs' states | doubles: per job with a prior the diagonal of H_L and
-  // b_L as given], device only [per job: the select's list of keys], read back [per job: its state, mirrored after every pass]
-  CallArena A;
-  step_layout(P, A);
-  size_t doubles = 0, max_lanes = 0;
-  std::vector<size_t> log(n_jobs), keys(n_jobs);
+// on top of the step call's parts: staged [job table | the jobs' states | doubles: per job with a prior the diagonal of H_L and
+// b_L as given], device only [per job: the select's list of keys], read back [per job: its state, mirrored after every pass]
+void optimize_layout(OptPlan &P, CallArena &A) {
+  const int n_jobs = P.n_jobs;
+  step_layout(P.stp, A);
+  P.log.assign(n_jobs, 0), P.keys.assign(n_jobs, 0);
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_linearize_job &L = first[j].sol.hes.lin;
-    if (first[j].prior) doubles += 2 * (4 + 8 * (size_t)L.n_frames);
-    max_lanes = std::max(max_lanes, std::max((size_t)L.n_pts, (size_t)L.n_res));
-    log[j] = A.out.take(sizeof(opt::State)), keys[j] = A.work.take(4 * (size_t)L.n_res);
+    const dsm_linearize_job &L = P.first[j].sol.hes.lin;
+    if (P.first[j].prior) P.doubles += 2 * (4 + 8 * (size_t)L.n_frames);
+    P.max_lanes = std::max(P.max_lanes, std::max((size_t)L.n_pts, (size_t)L.n_res));
+    P.log[j] = A.out.take(sizeof(opt::State)), P.keys[j] = A.work.take(4 * (size_t)L.n_res);
   }
-  const size_t o_opt = A.in.take(sizeof(OptJob) * n_jobs), o_states = A.in.take(sizeof(opt::State) * n_jobs), o_keep = A.in.take(8 * doubles);
-  if ((rc = A.bind(ctx))) return rc;
-  step_stage(P, A);
-  OptJob *hj = A.host_in<OptJob>(o_opt);
-  opt::State *hs = A.host_in<opt::State>(o_states);
-  double *hk = A.host_in<double>(o_keep);
-  const long long out0 = P.sol.hes.out0;
-  const LinJob *hl = A.host_in<LinJob>(P.sol.hes.o_lin);
+  P.o_opt = A.in.take(sizeof(OptJob) * n_jobs), P.o_states = A.in.take(sizeof(opt::State) * n_jobs), P.o_keep = A.in.take(8 * P.doubles);
+}
+
+void optimize_stage(OptPlan &P, CallArena &A, const dsm_optimize_params &op) {
+  const int n_jobs = P.n_jobs;
+  const opt::Rules R{op.lambda_accept_fac, op.lambda_reject_fac, op.fixed_lambda, op.min_iterations, op.force_accept != 0, op.step_momentum != 0};
+  StpPlan &T = P.stp;
+  step_stage(T, A);
+  OptJob *hj = A.host_in<OptJob>(P.o_opt);
+  opt::State *hs = A.host_in<opt::State>(P.o_states);
+  double *hk = A.host_in<double>(P.o_keep);
+  const long long out0 = T.sol.hes.out0;
+  const LinJob *hl = A.host_in<LinJob>(T.sol.hes.o_lin);
   size_t used = 0;
   for (int j = 0; j < n_jobs; j++) {
-    const dsm_step_job &S = first[j];
+    const dsm_step_job &S = P.first[j];
     const dsm_linearize_job &L = S.sol.hes.lin;
     const int n = L.n_frames, N = 4 + 8 * n;
-    const StpView &V = P.view[j];
+    const StpView &V = T.view[j];
     OptJob &G = hj[j];
     memset(&G, 0, sizeof G);
     G.R = R, G.n = n, G.n_pts = L.n_pts, G.n_res = L.n_res, G.N = N;
-    G.a_stepfac = (long long)(P.o_stp + P.stp_stride * j + P.stp_stepfac), G.a_lambda = (long long)(P.sol.o_sol + P.sol.sol_stride * j + P.sol.sol_lambda);
+    G.a_stepfac = (long long)(T.o_stp + T.stp_stride * j + T.stp_stepfac), G.a_lambda = (long long)(T.sol.o_sol + T.sol.sol_stride * j + T.sol.sol_lambda);
     G.q_backup = V.q_backup, G.q_step = V.q_step, G.q_cbackup = V.q_cbackup, G.q_cstep = V.q_cstep, G.f_idb = V.f_idb, G.f_ids = V.f_ids;
-    G.d_HL = P.sol.view[j].d_HL, G.d_bL = P.sol.view[j].d_bL, G.d_keep = -1;
+    G.d_HL = T.sol.view[j].d_HL, G.d_bL = T.sol.view[j].d_bL, G.d_keep = -1;
     if (S.prior) {
       G.d_keep = (long long)used;
       for (int i = 0; i < N; i++) hk[used + i] = S.sol.H_L[(size_t)i * N + i], hk[used + N + i] = S.sol.b_L[i];
@@ -251,49 +280,48 @@ extern "C" int dsm_window_optimize_batch(dsm_context *ctx, int n_jobs, const dsm
     }
     G.off_eth = hl[j].off_eth, G.off_ein = hl[j].off_ein, G.off_flags = hl[j].off_flags, G.off_target = hl[j].off_target;
     G.o_head = hl[j].o_head, G.o_state = V.o_state, G.o_calib = V.o_calib, G.o_idepth = V.o_idepth, G.o_em = V.o_em, G.o_can = V.o_can;
-    G.o_x = out0 + (long long)(P.sol.at[j].x / 4), G.o_step = out0 + (long long)(P.sol.at[j].step / 4), G.o_log = out0 + (long long)(log[j] / 4);
-    G.o_keys = (long long)(keys[j] / 4);
-    opt::state_init(hs[j], op->lambda_init, jobs[j].max_iterations);
+    G.o_x = out0 + (long long)(T.sol.at[j].x / 4), G.o_step = out0 + (long long)(T.sol.at[j].step / 4), G.o_log = out0 + (long long)(P.log[j] / 4);
+    G.o_keys = (long long)(P.keys[j] / 4);
+    opt::state_init(hs[j], op.lambda_init, P.jobs[j]->max_iterations);
   }
-  if ((rc = A.upload())) return rc;
+}
 
-  const OptJob *dj = A.dev_in<const OptJob>(o_opt);
-  opt::State *ds = A.dev_in<opt::State>(o_states);
-  const Median T{lp->thn, lp->fac_median, lp->cw, lp->ow};
-  const int commit_blocks = (int)((max_lanes + kBlock - 1) / kBlock);
-  auto passes = [&](int count) {
-    for (int k = 0; k < count; k++) {
-      if (int e = step_launch(ctx, P, A, *lp, *sp)) return e;
-      hipLaunchKernelGGL(opt_decide_kernel, dim3(n_jobs), dim3(kBlock), 0, ctx->stream, dj, ds, A.dev_in<unsigned char>(0), A.dev_in<double>(P.o_sq),
-                         A.dev_in<double>(P.sol.o_sd), A.dev_in<const double>(o_keep), A.dev_in<float>(P.sol.hes.o_stage), P.sol.hes.dev_base, T);
-      if (commit_blocks)
-        hipLaunchKernelGGL(opt_commit_kernel, dim3(commit_blocks, n_jobs), dim3(kBlock), 0, ctx->stream, dj, ds, A.dev_in<float>(P.o_sf),
-                           A.dev_in<float>(P.sol.hes.o_stage), P.sol.hes.dev_base);
-      DSM_HIP(hipGetLastError());
-    }
-    return (int)DSM_OK;
-  };
-  auto unfinished = [&]() {
-    int open = 0;
-    for (int j = 0; j < n_jobs; j++) open += A.host_out<opt::State>(log[j])->phase != opt::DONE;
-    return open;
-  };
-  // enough when nothing is rejected; a rejected iteration costs one more pass
-  if ((rc = passes(1 + max_it))) return rc;
-  if ((rc = A.fetch(A.out.used))) return rc;
-  if (unfinished()) {
-    if ((rc = passes(max_it))) return rc;
-    if ((rc = A.fetch(A.out.used))) return rc;
+int optimize_passes(dsm_context *ctx, OptPlan &P, CallArena &A, const dsm_linearize_params &lp, const dsm_step_params &sp, int count) {
+  StpPlan &T = P.stp;
+  const int n_jobs = P.n_jobs;
+  const OptJob *dj = A.dev_in<const OptJob>(P.o_opt);
+  opt::State *ds = A.dev_in<opt::State>(P.o_states);
+  const Median M{lp.thn, lp.fac_median, lp.cw, lp.ow};
+  const int commit_blocks = (int)((P.max_lanes + kBlock - 1) / kBlock);
+  for (int k = 0; k < count; k++) {
+    if (int e = step_launch(ctx, T, A, lp, sp)) return e;
+    hipLaunchKernelGGL(opt_decide_kernel, dim3(n_jobs), dim3(kBlock), 0, ctx->stream, dj, ds, A.dev_in<unsigned char>(0), A.dev_in<double>(T.o_sq),
+                       A.dev_in<double>(T.sol.o_sd), A.dev_in<const double>(P.o_keep), A.dev_in<float>(T.sol.hes.o_stage), T.sol.hes.dev_base, M);
+    if (commit_blocks)
+      hipLaunchKernelGGL(opt_commit_kernel, dim3(commit_blocks, n_jobs), dim3(kBlock), 0, ctx->stream, dj, ds, A.dev_in<float>(T.o_sf),
+                         A.dev_in<float>(T.sol.hes.o_stage), T.sol.hes.dev_base);
+    DSM_HIP(hipGetLastError());
   }
-  step_unpack(P, A, *lp);
-  for (int j = 0; j < n_jobs; j++) {
-    const dsm_optimize_job &J = jobs[j];
-    const opt::State &S = *A.host_out<opt::State>(log[j]);
+  return DSM_OK;
+}
+
+int optimize_unfinished(const OptPlan &P, const CallArena &A) {
+  int open = 0;
+  for (int j = 0; j < P.n_jobs; j++) open += A.host_out<opt::State>(P.log[j])->phase != opt::DONE;
+  return open;
+}
+
+void optimize_unpack(const OptPlan &P, const CallArena &A, const dsm_linearize_params &lp) {
+  step_unpack(P.stp, A, lp);
+  for (int j = 0; j < P.n_jobs; j++) {
+    const dsm_optimize_job &J = *P.jobs[j];
+    const opt::State &S = *A.host_out<opt::State>(P.log[j]);
     const size_t its = J.max_iterations, np = 1 + 2 * its;
     *J.n_iterations = S.iteration, *J.n_passes = S.n_passes;
     memcpy(J.pass_energy, S.pass_energy, 16 * np), memcpy(J.pass_lambda, S.pass_lambda, 8 * np);
     if (its) memcpy(J.pattern, S.pattern, its), memcpy(J.iter_stepsize, S.iter_stepsize, 4 * its), memcpy(J.iter_can_break, S.iter_can, its);
     J.last_energy[0] = S.last[0], J.last_energy[1] = S.last[1], *J.lambda_out = S.lambda, *J.frame_energy_th_out = S.eth_out;
   }
-  return DSM_OK;
 }
+
+} // namespace dsm

@@ -300,7 +300,7 @@ void step_stage(StpPlan &P, CallArena &A) {
     G.o_state = word((long long)w.state), G.o_calib = word((long long)w.calib), G.o_idepth = word((long long)w.idepth), G.o_W = word((long long)w.W);
     G.o_can = word((long long)w.can), G.o_sums = word((long long)w.sums), G.o_em = word((long long)w.em);
     G.o_C = word(w.C), G.o_cam = word(w.cam), G.o_pre = word(w.pre), G.o_dx = word(w.dx), G.o_HL = word(w.HL), G.o_bL = word(w.bL);
-    P.view[j] = StpView{G.q_backup, G.q_step, G.q_cbackup, G.q_cstep, G.q_prior, G.f_idb, G.f_ids, G.o_state, G.o_calib, G.o_idepth, G.o_em, G.o_can};
+    P.view[j] = StpView{G.q_backup, G.q_step, G.q_cbackup, G.q_cstep, G.q_prior, G.f_idb, G.f_ids, G.o_state, G.o_calib, G.o_idepth, G.o_em, G.o_can, G.o_W};
   }
 }
 

@@ -18,7 +18,7 @@ struct StpWhere {
 struct StpView {
   int q_backup, q_step, q_cbackup, q_cstep, q_prior;
   int f_idb, f_ids;
-  long long o_state, o_calib, o_idepth, o_em, o_can;
+  long long o_state, o_calib, o_idepth, o_em, o_can, o_W;
 };
 
 struct StpPlan {

@@ -12,7 +12,9 @@
 //   m.verdict, m.pointsMarginalized(), m.pointsOut(): what to erase;  m.HM_out / m.bM_out: the next keyframe's SolveRequest::HM / bM
 // Erasing the points, residuals and frames and renumbering what stays (dropPointsF, removePoint, makeIDX) stay the caller's.
 #pragma once
-#include "WindowOptimize.hpp"
+#include "WindowFinish.hpp" // includes WindowOptimize.hpp
+
+#include "../csrc/delta_math.hpp"
 
 namespace dsm_host {
 
@@ -55,12 +57,8 @@ struct MarginalizeRequest {
       for (size_t t = 0; t < n; t++) {
         if (h == t) continue;
         const double *ah = &hes.adHost[(h * n + t) * 64], *at = &hes.adTarget[(h * n + t) * 64];
-        for (int c = 0; c < 8; c++) {
-          float a = 0.f, b = 0.f;
-          for (int k = 0; k < 8; k++) a += (float)(state[8 * h + k] - stateZero[8 * h + k]) * (float)ah[8 * k + c];
-          for (int k = 0; k < 8; k++) b += (float)(state[8 * t + k] - stateZero[8 * t + k]) * (float)at[8 * k + c];
-          adHTdeltaF[(h * n + t) * 8 + c] = a + b;
-        }
+        for (int c = 0; c < 8; c++)
+          adHTdeltaF[(h * n + t) * 8 + c] = dsm::ad_ht_delta_entry(ah, at, &state[8 * h], &stateZero[8 * h], &state[8 * t], &stateZero[8 * t], c);
       }
   }
   // Everything a WindowOptimize holds after optimize() (or a WindowStep after accept()): the frames, the calibration and the precalc
@@ -84,6 +82,29 @@ struct MarginalizeRequest {
     idepthHessian = H.idepth_hessian;
     HM = w.req.HM, bM = w.req.bM;
     setDeltaF(w.state, w.stateZero, w.calib, w.calibZero);
+  }
+  // Everything from a WindowFinish after finishWindow() and shrink(): the shrunken point and residual lists with
+  // the final linearisation's states, the tables, the calibration and frameEnergyTH at the new evaluation point, adHost / adTarget,
+  // adHTdeltaF and cDeltaF as the finish formed them (no setDeltaF here), numGoodResiduals, the last states, priorF, idepth_hessian,
+  // HM / bM.  What remains the caller's: flaggedForMarginalization, margFrames, framePrior, frameDeltaPrior.
+  void fromFinished(const WindowFinish &f, float scaleIdepth = DSM_LINEARIZE_SCALE_IDEPTH) {
+    const WindowStep &w = f.optimizer.window;
+    const HessianRequest &H = w.req.hes;
+    const size_t n = H.lin.frame_ids.size(), np = f.points.size();
+    if (!f.shrunk || w.precalc.size() != n * n || w.idepth.size() != np || f.idepthHessian.size() != np || f.adHTdeltaF.size() != n * n * 8)
+      throw std::logic_error("MarginalizeRequest::fromFinished: the window is not finished and shrunk");
+    hes = HessianRequest();
+    hes.lin.window = H.lin.window, hes.lin.frame_ids = H.lin.frame_ids, hes.lin.precalc = w.precalc, hes.lin.frameEnergyTH = w.frameEnergyTH;
+    hes.lin.fxl = w.cam[0], hes.lin.fyl = w.cam[1], hes.lin.cxl = w.cam[2], hes.lin.cyl = w.cam[3], hes.lin.fxli = w.cam[4], hes.lin.fyli = w.cam[5];
+    hes.lin.fixLinearization = false, hes.lin.wantJacobians = false;
+    points = f.points, residuals = w.residuals, ownsWindowData = true;
+    for (size_t i = 0; i < np; i++) points[i].idepth_scaled = points[i].idepth_zero_scaled = scaleIdepth * w.idepth[i];
+    hes.adHost = H.adHost, hes.adTarget = H.adTarget, hes.priorF = H.priorF;
+    idepthHessian = f.idepthHessian;
+    HM = w.req.HM, bM = w.req.bM;
+    adHTdeltaF = f.adHTdeltaF;
+    memcpy(cDeltaF, f.cDeltaF, sizeof cDeltaF);
+    numGoodResiduals = f.numGoodResiduals, lastResiduals = f.lastResidualStates;
   }
   // the points flagPointsForRemoval moves to pointHessiansMarginalized / pointHessiansOut
   std::vector<int> pointsMarginalized() const { return pointsOf(1); }

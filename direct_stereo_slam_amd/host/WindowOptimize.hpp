@@ -61,6 +61,7 @@ public:
   }
 
 private:
+  friend class WindowFinish; // WindowFinish.hpp: the same job with the finish on top
   int n_iterations_ = 0, n_passes_ = 0;
   std::vector<unsigned char> pattern_, can_;
   std::vector<double> energy_, lambda_;

@@ -108,6 +108,7 @@ public:
 
 private:
   friend class WindowOptimize; // WindowOptimize.hpp: the whole loop in one call, on the same members
+  friend class WindowFinish;   // WindowFinish.hpp: the loop and what follows it in one call
   struct Params {
     dsm_linearize_params l;
     dsm_step_params s;

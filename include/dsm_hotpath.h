@@ -1520,7 +1520,7 @@ int dsm_window_solve_host(int w, int h, const dsm_solve_job *job, const float *c
  * NOT here: SOLVER_MOMENTUM; the step-size heuristic (:390-405; the caller passes the factors); calcLEnergy and accumulateLF_MT (zero
  * while no residual is linearised, which is all of optimize); setAdjointsF (ad_host / ad_target stay the caller's: the evaluation point
  * does not move inside optimize); the nullspaces; setEvalPT after the loop (:455-464); applyRes; the accept decision.  (Marginalisation, which produces H_M / b_M, is
- * dsm_window_marginalize_batch below.)
+ * dsm_window_marginalize_batch below; setAdjointsF and setEvalPT after the loop are dsm_window_finish_batch)
  * All arithmetic is IEEE, left to right as written, without contraction. */
 typedef struct dsm_step_params {
   double scale_xi_trans;     /* 0.5   SCALE_XI_TRANS */
@@ -1593,7 +1593,8 @@ int dsm_window_step_host(int w, int h, const dsm_step_job *job, const float *con
  * frame_step = -x[4..], calib_step = -x[0..3], idepth_step = step.  frame_energy_th[n - 1] takes new_frame_energy_th after EVERY pass.
  * The rules are the project's statement; parity with the parts of DSO that are not under the reference tree is
  * unpinned.  NOT here: accumulateLF_MT, the nullspaces, setEvalPT after the loop, SOLVER_MOMENTUM.  (Marginalisation, which
- * produces the H_M / b_M this loop reads, is dsm_window_marginalize_batch below.)
+ * produces the H_M / b_M this loop reads, is dsm_window_marginalize_batch below; setEvalPT after the loop with what follows it is
+ * dsm_window_finish_batch, which runs this loop first: DESIGN.md section 22.)
  * The struct defaults reproduce the loop of host/step_demo.cpp (lambda 0.1, x 0.25, x 100, setting_minOptIterations = 1, the energy
  * test, step size 1).  The recalled upstream defaults are setting_forceAceptStep = true and SOLVER_FIX_LAMBDA set (the solve then
  * always gets 1e-5): force_accept = 1, fixed_lambda = 1e-5; they are not citable under the reference tree. */
@@ -1656,7 +1657,8 @@ int dsm_window_optimize_host(int w, int h, const dsm_optimize_job *job, const fl
  * the reference tree: parity is unpinned, and the rules C, M1, X1, A1', M2, G1-G7, Z and V of DESIGN.md section 21 are the project's
  * statement.  The call produces the H_M / b_M that the next keyframe's dsm_window_solve_batch / _step_batch / _optimize_batch reads.
  * NOT here: the SOLVER_ORTHOGONALIZE_* projections, connectivityMap, the bookkeeping that erases points, residuals and frames (the
- * verdicts and marg_frames tell the caller what to erase), flagFramesForMarginalization, the nullspaces, setEvalPT.
+ * verdicts and marg_frames tell the caller what to erase), flagFramesForMarginalization, the nullspaces, setEvalPT (which, with the
+ * final linearizeAll(true) whose results this call reads, is dsm_window_finish_batch: DESIGN.md section 22).
  * All arithmetic is IEEE, left to right as written, without contraction. */
 typedef struct dsm_marginalize_params {
   int min_good_active_res_for_marg; /* 3       setting_minGoodActiveResForMarg */
@@ -1715,6 +1717,82 @@ int dsm_window_marginalize_batch(dsm_context *ctx, int n_jobs, const dsm_margina
  * same marginalize_math.hpp.  A checker that needs no device. */
 int dsm_window_marginalize_host(int w, int h, const dsm_marginalize_job *job, const float *const *frame_I,
                                 const dsm_linearize_params *lin_params, const dsm_marginalize_params *marg_params);
+
+/* ---- The end of optimize in the same call as its loop ----------------------------------------------------------
+ * replaces, behind the loop of the section above, what FrontEnd::optimize does after it (dso_helpers/FrontEndOptimize.cpp:455-486):
+ * setEvalPT of the newest frame (:455-460), EnergyFunctional::setAdjointsF and setDeltaF, setPrecalcValues at the new evaluation point,
+ * linearizeAll(true) with its bookkeeping (:466, :39-72, :145-176: numGoodResiduals, maxRelBaseline, lastResiduals, the residuals that
+ * do not survive) and removeOutliers (:504-523), as the rules Z1-Z8 and V of DESIGN.md section 22 state them.  setEvalPT, setAdjointsF
+ * and setDeltaF are UPSTREAM-DSO and not under the reference tree: parity is unpinned.  What the call returns is what
+ * dsm_window_marginalize_batch reads.  NOT here: the nullspaces, flagFramesForMarginalization, erasing the residuals and points (the
+ * index maps tell the caller what to erase and how to renumber).
+ * All arithmetic is IEEE, left to right as written, without contraction. */
+
+/* One window; n, N, n_pts, n_res as in opt.  opt runs exactly as dsm_window_optimize_batch runs it and every output of opt keeps its
+ * meaning (the job's last pass).  opt.step.sol.hes.lin.is_new is read here (and only here).  A residual is REMOVED when keep is 0. */
+typedef struct dsm_finish_job {
+  dsm_optimize_job opt;
+  const int *n_good_residuals_in;      /* n_pts: numGoodResiduals */
+  const float *max_rel_baseline_in;    /* n_pts: maxRelBaseline */
+  const int *last_res;                 /* n_pts * 2: the residual index of lastResiduals[0].first, [1].first; -1: none */
+  const unsigned char *last_state_in;  /* n_pts * 2: lastResiduals[0].second, [1].second as DSM_RES_* */
+  double *world_to_cam_eval_out;       /* n * 7: worldToCam_evalPT after setEvalPT (Z1) */
+  double *state_zero_out;              /* n * 8 */
+  double *state_out;                   /* n * 8 */
+  double *ad_host_out, *ad_target_out; /* n * n * 8 * 8 each, as dsm_hessian_job reads them (Z2) */
+  float *ad_ht_delta_out;              /* n * n * 8, as dsm_marginalize_job reads it (Z3) */
+  float *c_delta_out;                  /* 4 */
+  double *delta_x_out;                 /* N */
+  float *pre_RTll_0_out, *pre_tTll_0_out, *pre_KRKiTll_out, *pre_KtTll_out, *pre_aff_mode_out, *pre_b0_mode_out; /* n * n * (9, 3, 9, 3, 2, 1) */
+  float *cam_out;                      /* 6: cam, cam_inv */
+  unsigned char *new_state;            /* the next five: n_res each, the final linearisation (Z4); a residual's state from here on */
+  float *new_energy;
+  float *new_energy_with_outlier;
+  unsigned char *keep;
+  float *rel_bs;
+  double *energy;                      /* B1 of the final linearisation */
+  float *frame_energy_th_out;          /* B2 of the final linearisation */
+  int *n_good_residuals_out;           /* n_pts (Z5) */
+  float *max_rel_baseline_out;         /* n_pts */
+  int *last_res_out;                   /* n_pts * 2, in the old numbering; -1 where the residual was removed */
+  unsigned char *last_state_out;       /* n_pts * 2 */
+  int *n_res_kept;                     /* n_pts */
+  unsigned char *point_dropped;        /* n_pts: 1 = the point lost all its residuals (Z6) */
+  int *res_index_out;                  /* n_res: the residual's index among the kept ones, -1 if removed (Z7) */
+  int *point_index_out;                /* n_pts: the point's index among those not dropped, -1 if dropped */
+  int *n_res_out, *n_pts_out;          /* one word each */
+  float *rmse;                         /* one word (Z8) */
+  int *lost;                           /* one word */
+  double *cam_to_world_out;            /* optional (NULL), n * 7: PRE_camToWorld at the new evaluation point */
+  float *J_out;                        /* optional (NULL), n_res * 74: the rows of the final linearisation (not written for a residual that ends OOB) */
+} dsm_finish_job;
+
+/* The loop of dsm_window_optimize_batch and, behind the call's last pass, four more launches on the same arena (fin_frame_kernel:
+ * Z1-Z3; linearize_kernel with the fix flag: Z4; fin_point_kernel: Z5, Z6; fin_prefix_kernel: B1, Z7, Z8), which write only a region
+ * of their own.  They run once: with force_accept every job's pass count is known in advance and the call has ONE host wait; otherwise
+ * they follow the read-back that tells whether a job needs the remaining passes, and the call has two.  B2 of the final linearisation is formed on the host from the
+ * read-back, as dsm_linearize_residuals_batch forms it.  A job's results do not depend on the other jobs of the call or on the launch
+ * geometry.  Validation is all or nothing, before anything is enqueued and with no output touched: DSM_ERR_INVALID for everything
+ * dsm_window_optimize_batch refuses, a NULL required array, a last_res outside [-1, n_res) or naming a residual of another point, a
+ * last_state_in other than DSM_RES_IN / _OOB / _OUTLIER, a negative n_good_residuals_in, a non-finite max_rel_baseline_in.  n_res == 0,
+ * n_pts == 0, a job of one frame and a newest frame that hosts nothing are valid. */
+int dsm_window_finish_batch(dsm_context *ctx, int n_jobs, const dsm_finish_job *jobs, const dsm_linearize_params *lp,
+                            const dsm_step_params *sp, const dsm_optimize_params *op);
+/* The same for one job on the host: dsm_window_optimize_host, plain loops over Z1-Z3, dsm_linearize_residuals_host, plain loops over
+ * Z5-Z8.  A checker that needs no device. */
+int dsm_window_finish_host(int w, int h, const dsm_finish_job *job, const float *const *frame_I, const dsm_linearize_params *lp,
+                           const dsm_step_params *sp, const dsm_optimize_params *op);
+
+/* DIAGNOSTIC, not a maintained interface (tools/finish_timing.py's route before): the host form's two halves on their own, for a
+ * run of the loop and of the final linearisation as separate calls: after
+ * dsm_window_optimize_batch (or _host) has filled job->opt's outputs, _prepare_host forms Z1-Z3 into the job's outputs and fills *lin
+ * with the final linearisation's job (fix_linearization = 1; its tables are the job's pre_*_out arrays, its outputs the job's;
+ * frame_energy_th and the scaled depths go to scratch, n + n_pts floats, which must outlive the use of *lin); the caller runs
+ * dsm_linearize_residuals_batch (or _host) on *lin; _book_host then forms Z5-Z8 from the job's filled new_state, keep, rel_bs and
+ * energy.  Plain loops on one core; DSM_ERR_INVALID for what V refuses. */
+int dsm_diag_finish_prepare_host(const dsm_finish_job *job, const dsm_linearize_params *lp, const dsm_step_params *sp, float *scratch,
+                                   dsm_linearize_job *lin);
+int dsm_diag_finish_book_host(const dsm_finish_job *job);
 
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
