@@ -301,6 +301,21 @@ class MarginalizeJob(C.Structure):
     ]
 
 
+class NullspaceParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int), ("scale_xi_trans", C.c_double), ("scale_xi_rot", C.c_double), ("scale_a", C.c_double),
+        ("scale_b", C.c_double), ("solver_mode_delta", C.c_double),
+    ]
+
+
+class NullspaceJob(C.Structure):
+    _fields_ = [
+        ("n_frames", C.c_int), ("world_to_cam_eval", c_double_p), ("state_zero", c_double_p), ("exposure", c_float_p),
+        ("frame_null_in", c_double_p), ("null_basis", c_double_p), ("null_pinv", c_double_p), ("sing", c_double_p),
+        ("rank", c_int_p), ("flags", c_int_p), ("frame_null_out", c_double_p), ("null_x0_pre", c_double_p),
+    ]
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -579,6 +594,9 @@ SYMBOLS = {
     "dsm_window_marginalize_batch": (C.c_int, [_vp, C.c_int, C.POINTER(MarginalizeJob), C.POINTER(LinearizeParams), C.POINTER(MarginalizeParams)]),
     "dsm_window_marginalize_host": (C.c_int, [C.c_int, C.c_int, C.POINTER(MarginalizeJob), C.POINTER(c_float_p), C.POINTER(LinearizeParams),
                                               C.POINTER(MarginalizeParams)]),
+    "dsm_nullspace_params_default": (C.c_int, [C.POINTER(NullspaceParams)]),
+    "dsm_window_nullspace_batch": (C.c_int, [_vp, C.c_int, C.POINTER(NullspaceJob), C.POINTER(NullspaceParams)]),
+    "dsm_window_nullspace_host": (C.c_int, [C.c_int, C.POINTER(NullspaceJob), C.POINTER(NullspaceParams)]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

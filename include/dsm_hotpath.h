@@ -1794,6 +1794,60 @@ int dsm_diag_finish_prepare_host(const dsm_finish_job *job, const dsm_linearize_
                                    dsm_linearize_job *lin);
 int dsm_diag_finish_book_host(const dsm_finish_job *job);
 
+/* ---- The window's nullspaces and their pseudo-inverse ------------------------------------------------------------
+ * replaces what FrontEnd::solveSystem does before every solve (dso_helpers/FrontEndOptimize.cpp:488-494): getNullspaces (:525-574) with
+ * what feeds it and what reads it -- the frames' numeric nullspaces that FrameHessian::setStateZero recomputes whenever a state_zero
+ * moves (setEvalPT of the newest frame, section 22 Z1), and the basis N with its pseudo-inverse that EnergyFunctional::orthogonalize
+ * forms from the pose and scale vectors (SOLVER_ORTHOGONALIZE_X_LATER, rule F7 of section 18).  getNullspaces is under the reference
+ * tree and followed line for line; setStateZero, orthogonalize, Sophus and Eigen are not: parity is unpinned, and the rules G1-G7 and V
+ * of DESIGN.md section 23 are the project's statement.  From the evaluation poses that dsm_window_finish_batch returns, the call
+ * produces the null_basis / null_pinv (n_null = 7) that the next keyframe's dsm_solve_job reads.
+ * NOT here: the H projections of SOLVER_ORTHOGONALIZE_SYSTEM / _POINTMARG / _FULL, upstream's symmetrised projector, a call from
+ * inside dsm_window_finish_batch, flagFramesForMarginalization.
+ * All arithmetic is IEEE double, left to right as written, without contraction. */
+typedef struct dsm_nullspace_params {
+  int struct_size;          /* sizeof(dsm_nullspace_params) */
+  double scale_xi_trans;    /* 0.5   SCALE_XI_TRANS */
+  double scale_xi_rot;      /* 1     SCALE_XI_ROT */
+  double scale_a;           /* 10    SCALE_A */
+  double scale_b;           /* 1000  SCALE_B */
+  double solver_mode_delta; /* 1e-5  setting_solverModeDelta */
+} dsm_nullspace_params;
+
+#define DSM_NULLSPACE_NONFINITE 1    /* flags: an entry of null_basis, null_pinv or sing is not finite */
+#define DSM_NULLSPACE_SWEEP_CAP 2    /* the Jacobi iteration still rotated in its last allowed sweep */
+#define DSM_NULLSPACE_UNNORMALISED 4 /* a column whose sum of squares is not > 0 was left as it is (G5) */
+
+/* One window; n = n_frames, N = 4 + 8 n; poses are {qx,qy,qz,qw,tx,ty,tz}. */
+typedef struct dsm_nullspace_job {
+  int n_frames;                    /* 1 .. DSM_WINDOW_MAX_FRAMES */
+  const double *world_to_cam_eval; /* n * 7: worldToCam_evalPT, unit quaternions (as dsm_step_job) */
+  const double *state_zero;        /* n * 8, unscaled; only entry 6 of a frame is read */
+  const float *exposure;           /* n: ab_exposure, positive */
+  const double *frame_null_in;     /* optional (NULL), n * 42: per frame a 6 x 7 block, row-major; columns 0-5 nullspaces_pose,
+                                      column 6 nullspaces_scale.  Given: G1 and G2 are skipped and the block is used as it is */
+  double *null_basis;              /* N * 7, row-major: what F7 reads */
+  double *null_pinv;               /* 7 * N */
+  double *sing;                    /* 7: the singular values, in column order after G6 */
+  int *rank;                       /* one word: the singular values kept */
+  int *flags;                      /* one word: DSM_NULLSPACE_* */
+  double *frame_null_out;          /* optional (NULL), n * 42: the blocks used */
+  double *null_x0_pre;             /* optional (NULL), N * 9: getNullspaces' return value in its own order (pose 0-5, affA, affB,
+                                      scale), not normalised */
+} dsm_nullspace_job;
+
+/* the defaults listed above, struct_size set */
+int dsm_nullspace_params_default(dsm_nullspace_params *p);
+/* G1-G7 for every job: one staged copy, ONE launch (nsp_kernel, one 256-lane workgroup per job), one read-back.  params NULL: the
+ * defaults.  A job's results do not depend on the other jobs of the call or on the launch geometry.  Validation is all or nothing,
+ * before anything is enqueued and with no output touched: DSM_ERR_INVALID for a NULL required array, n_frames outside
+ * [1, DSM_WINDOW_MAX_FRAMES], a world_to_cam_eval quaternion whose squared norm is further than 1e-9 from 1, a non-finite input or
+ * parameter, a non-positive exposure, a non-positive scale or delta, a struct_size that is not this struct's. */
+int dsm_window_nullspace_batch(dsm_context *ctx, int n_jobs, const dsm_nullspace_job *jobs, const dsm_nullspace_params *params);
+/* The same on the host, job after job: plain loops over the same nullspace_math.hpp.  The CPU baseline of tools/nullspace_timing.py
+ * and a checker that needs no device. */
+int dsm_window_nullspace_host(int n_jobs, const dsm_nullspace_job *jobs, const dsm_nullspace_params *params);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.
