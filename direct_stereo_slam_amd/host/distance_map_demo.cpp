@@ -14,20 +14,11 @@
 #include <vector>
 
 #include "CoarseDistanceMap.hpp"
+#include "window_case.hpp" // fnv1a, rd
 
 using namespace dsm_host;
-
-static uint64_t fnv1a(const void *p, size_t n) {
-  uint64_t hsh = 1469598103934665603ull;
-  for (size_t i = 0; i < n; i++) hsh = (hsh ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
-  return hsh;
-}
-
-template <typename T>
-static bool rd(FILE *f, std::vector<T> &v, size_t n) {
-  v.resize(n);
-  return fread(v.data(), sizeof(T), n, f) == n;
-}
+using window_case::fnv1a;
+using window_case::rd;
 
 int main(int argc, char **argv) {
   if (argc < 2) {

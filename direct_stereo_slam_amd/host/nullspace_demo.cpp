@@ -1,8 +1,8 @@
 // nullspace_demo.cpp -- what FrontEnd::solveSystem does before a solve (dso_helpers/FrontEndOptimize.cpp:488-494: getNullspaces, :525-574)
 // through the C++ adaptor host/WindowNullspace.hpp, on a window read from a file: one window, then two windows (this one and a second
 // set of poses) in one call, then the device's basis fed to host/WindowSolve.hpp as rule F7 reads it, then the host form.
-// Input file (native byte order): the file of solve_demo.cpp (its n_null, nullBasis and nullPinv are read and not used), then n_frames * 7
-// doubles worldToCamEval, n_frames * 8 stateZero, n_frames floats exposure, and the same three arrays of a second window of n_frames.
+// Input file: a nullspace file (window_case.hpp, kind NULLSPACE): a solve file, whose n_null, nullBasis and nullPinv are not used, then
+// the poses of two windows.
 // Usage: nullspace_demo FILE OUT.  Writes to OUT the device's nullBasis (N * 7 doubles), nullPinv (7 * N) and frameNull (n_frames * 42) of
 // the first window.  Prints one JSON line: the rank and flags of both windows, the hash of lastX of the solve with the device's basis,
 // whether the two-window call repeated the one-window call, whether the host form given the device's frameNull repeated the device's
@@ -15,22 +15,11 @@
 #include <vector>
 
 #include "WindowNullspace.hpp"
+#include "window_case_requests.hpp"
 
 using namespace dsm_host;
+using window_case::vhash;
 
-static uint64_t fnv1a(const void *p, size_t n, uint64_t hsh = 1469598103934665603ull) {
-  for (size_t i = 0; i < n; i++) hsh = (hsh ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
-  return hsh;
-}
-template <typename T>
-static uint64_t vhash(const std::vector<T> &v) {
-  return fnv1a(v.data(), sizeof(T) * v.size());
-}
-template <typename T>
-static bool rd(FILE *f, std::vector<T> &v, size_t n) {
-  v.resize(n);
-  return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
 static bool same(const WindowNullspace &a, const WindowNullspace &b) {
   return vhash(a.nullBasis) == vhash(b.nullBasis) && vhash(a.nullPinv) == vhash(b.nullPinv) && a.rank == b.rank && a.flags == b.flags &&
          memcmp(a.singularValues, b.singularValues, sizeof a.singularValues) == 0;
@@ -41,46 +30,15 @@ int main(int argc, char **argv) {
     fprintf(stderr, "usage: nullspace_demo FILE OUT\n");
     return 2;
   }
-  FILE *f = fopen(argv[1], "rb");
-  int wh[2], nff[2] = {0, 0}, n_pts = 0, n_res = 0, shift = 1, n_null = 0;
-  float cal[6];
-  double lambda = 0;
-  std::vector<int> ids;
-  std::vector<float> planes, pre, eth, prec, rrec, pin;
-  std::vector<double> adh, adt, HL, bL, HM, bM, dx, basis, pinv;
-  WindowNullspace ns, ns2;
-  bool good = f && fread(wh, sizeof(int), 2, f) == 2 && fread(cal, sizeof(float), 6, f) == 6 && fread(nff, sizeof(int), 2, f) == 2 &&
-              nff[0] >= 1 && nff[0] <= DSM_WINDOW_MAX_FRAMES && wh[0] > 0 && wh[1] > 0;
-  const size_t nf = good ? nff[0] : 0, npx = good ? (size_t)wh[0] * wh[1] : 0, N = 4 + 8 * nf;
-  good = good && rd(f, ids, nf) && rd(f, planes, nf * npx) && rd(f, pre, nf * nf * 27) && rd(f, eth, nf) && fread(&n_pts, sizeof(int), 1, f) == 1 &&
-         n_pts >= 0 && rd(f, prec, (size_t)n_pts * 21) && fread(&n_res, sizeof(int), 1, f) == 1 && n_res >= 0 && rd(f, rrec, (size_t)n_res * 5) &&
-         rd(f, adh, nf * nf * 64) && rd(f, adt, nf * nf * 64) && rd(f, pin, (size_t)n_pts * 8) && fread(&shift, sizeof(int), 1, f) == 1;
-  good = good && rd(f, HL, N * N) && rd(f, bL, N) && rd(f, HM, N * N) && rd(f, bM, N) && rd(f, dx, N) && fread(&lambda, sizeof(double), 1, f) == 1 &&
-         fread(&n_null, sizeof(int), 1, f) == 1 && n_null >= 0 && n_null <= DSM_SOLVE_MAX_NULL && rd(f, basis, N * n_null) && rd(f, pinv, N * n_null);
-  good = good && rd(f, ns.worldToCamEval, 7 * nf) && rd(f, ns.stateZero, 8 * nf) && rd(f, ns.exposure, nf) && rd(f, ns2.worldToCamEval, 7 * nf) &&
-         rd(f, ns2.stateZero, 8 * nf) && rd(f, ns2.exposure, nf);
-  if (!good) {
+  window_case::Case c;
+  if (!window_case::read_case(argv[1], window_case::NULLSPACE, c)) {
     fprintf(stderr, "nullspace_demo: cannot read %s\n", argv[1]);
     return 2;
   }
-  fclose(f);
-  std::vector<ActivePointData> points(n_pts);
-  for (int i = 0; i < n_pts; i++) {
-    const float *q = &prec[(size_t)21 * i];
-    memcpy(&points[i].host, q, 4);
-    points[i].u = q[1], points[i].v = q[2], points[i].idepth_scaled = q[3], points[i].idepth_zero_scaled = q[4];
-    memcpy(points[i].color, q + 5, 32);
-    memcpy(points[i].weights, q + 13, 32);
-  }
-  std::vector<ActiveResidualData> residuals(n_res);
-  for (int i = 0; i < n_res; i++) {
-    const float *q = &rrec[(size_t)5 * i];
-    int isnew;
-    memcpy(&residuals[i].point, q, 4), memcpy(&residuals[i].target, q + 1, 4), memcpy(&residuals[i].state_state, q + 2, 4);
-    residuals[i].state_energy = q[3];
-    memcpy(&isnew, q + 4, 4);
-    residuals[i].isNew = isnew != 0;
-  }
+  const std::vector<ActivePointData> points = window_case::points(c);
+  const std::vector<ActiveResidualData> residuals = window_case::residuals(c);
+  WindowNullspace ns, ns2;
+  window_case::fill_poses(ns, c, 0), window_case::fill_poses(ns2, c, 1);
 
   dsm_context *ctx = nullptr;
   immature_check(dsm_context_create(0, &ctx), "dsm_context_create");
@@ -98,27 +56,10 @@ int main(int argc, char **argv) {
     windows_equal = same(a, dev) && same(b, ns2) && vhash(a.frameNull) == vhash(dev.frameNull) && vhash(b.nullspacesX0Pre) == vhash(ns2.nullspacesX0Pre);
 
     // the device's basis where rule F7 reads it
-    KeyframeWindow window(ctx, wh[0], wh[1], (int)nf);
-    for (size_t k = 0; k < nf; k++) window.put(ids[k], &planes[k * npx]);
-    LinearizeRequest &lin = req.hes.lin;
-    lin.window = &window;
-    lin.fxl = cal[0], lin.fyl = cal[1], lin.cxl = cal[2], lin.cyl = cal[3], lin.fxli = cal[4], lin.fyli = cal[5];
-    lin.frame_ids = ids, lin.frameEnergyTH = eth, lin.points = &points, lin.residuals = &residuals, lin.fixLinearization = nff[1] != 0;
-    lin.wantJacobians = false;
-    lin.precalc.resize(nf * nf);
-    for (size_t k = 0; k < nf * nf; k++) {
-      const float *q = &pre[27 * k];
-      memcpy(lin.precalc[k].PRE_RTll_0, q, 36), memcpy(lin.precalc[k].PRE_tTll_0, q + 9, 12);
-      memcpy(lin.precalc[k].PRE_KRKiTll, q + 12, 36), memcpy(lin.precalc[k].PRE_KtTll, q + 21, 12);
-      memcpy(lin.precalc[k].PRE_aff_mode, q + 24, 8), lin.precalc[k].PRE_b0_mode = q[26];
-    }
-    req.hes.adHost = adh, req.hes.adTarget = adt, req.hes.shiftPriorToZero = shift != 0;
-    for (int i = 0; i < n_pts; i++) {
-      const float *q = &pin[(size_t)8 * i];
-      req.hes.priorF.push_back(q[0]), req.hes.deltaF.push_back(q[1]), req.hes.Hdd_accLF.push_back(q[2]), req.hes.bd_accLF.push_back(q[3]);
-      req.hes.Hcd_accLF.insert(req.hes.Hcd_accLF.end(), q + 4, q + 8);
-    }
-    req.H_L = HL, req.b_L = bL, req.HM = HM, req.bM = bM, req.deltaX = dx, req.lambda = lambda;
+    KeyframeWindow window(ctx, c.w, c.h, (int)c.nf);
+    window_case::put_planes(c, window);
+    window_case::fill(req, c);
+    req.hes.lin.window = &window, req.hes.lin.points = &points, req.hes.lin.residuals = &residuals;
     dev.applyTo(req);
     solveWindow(ctx, req);
 

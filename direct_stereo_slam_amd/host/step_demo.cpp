@@ -1,7 +1,7 @@
 // step_demo.cpp -- the loop of FrontEnd::optimize (dso_helpers/FrontEndOptimize.cpp:382-453: lambda 0.1, x 0.25 on an accepted step,
 // x 100 on a rejected one, setting_minOptIterations = 1, step size 1) through the C++ adaptor host/WindowStep.hpp, on a window read
 // from a file: one window on the device, the same window twice in one call per iteration, and through the host form.
-// Input file (native byte order): the step file tools/step_host_standalone.cpp reads (tests/_step_ref.py, write_case); the file's
+// Input file: a step file (window_case.hpp, kind STEP; tests/_step_ref.py writes the checker's scenes); the file's
 // state_backup, calib_backup and idepth_backup are the state the loop starts from, its step and factors are not used.
 // Usage: step_demo FILE [MAX_ITERATIONS = 6].  Prints one JSON line: per form the accept / reject pattern, the FNV-1a hashes of the
 // final state, calibration and inverse depths and of the last energy, and that energy; whether the two windows of one call equalled the
@@ -15,23 +15,11 @@
 #include <string>
 #include <vector>
 
-#include "WindowStep.hpp"
+#include "window_case_requests.hpp"
 
 using namespace dsm_host;
-
-static uint64_t fnv1a(const void *p, size_t n, uint64_t hsh = 1469598103934665603ull) {
-  for (size_t i = 0; i < n; i++) hsh = (hsh ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
-  return hsh;
-}
-template <typename T>
-static uint64_t vhash(const std::vector<T> &v) {
-  return fnv1a(v.data(), sizeof(T) * v.size());
-}
-template <typename T>
-static bool rd(FILE *f, std::vector<T> &v, size_t n) {
-  v.resize(n);
-  return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
+using window_case::fnv1a;
+using window_case::vhash;
 
 struct Outcome {
   std::string pattern; // A / R per iteration
@@ -80,80 +68,31 @@ int main(int argc, char **argv) {
     return 2;
   }
   const int max_its = argc > 2 ? atoi(argv[2]) : 6;
-  FILE *f = fopen(argv[1], "rb");
-  int wh[2], nff[2] = {0, 0}, n_pts = 0, n_res = 0, shift = 1, n_null = 0, has_hm = 0, has_prior = 0;
-  float cal[6];
-  double lambda = 0;
-  std::vector<int> ids;
-  std::vector<float> planes, pre, eth, prec, rrec, pin, idb, ids_step, expo, fac;
-  std::vector<double> adh, adt, HL, bL, HM, bM, basis, pinv, ev, zero, backup, fstep, cz, cb, cs, prior, pzero;
-  bool good = f && fread(wh, sizeof(int), 2, f) == 2 && fread(cal, sizeof(float), 6, f) == 6 && fread(nff, sizeof(int), 2, f) == 2 &&
-              nff[0] >= 1 && nff[0] <= DSM_WINDOW_MAX_FRAMES && wh[0] > 0 && wh[1] > 0;
-  const size_t nf = good ? nff[0] : 0, npx = good ? (size_t)wh[0] * wh[1] : 0, N = 4 + 8 * nf;
-  good = good && rd(f, ids, nf) && rd(f, planes, nf * npx) && rd(f, pre, nf * nf * 27) && rd(f, eth, nf) && fread(&n_pts, sizeof(int), 1, f) == 1 &&
-         n_pts >= 0 && rd(f, prec, (size_t)n_pts * 21) && fread(&n_res, sizeof(int), 1, f) == 1 && n_res >= 0 && rd(f, rrec, (size_t)n_res * 5) &&
-         rd(f, adh, nf * nf * 64) && rd(f, adt, nf * nf * 64) && rd(f, pin, (size_t)n_pts * 8) && fread(&shift, sizeof(int), 1, f) == 1;
-  good = good && rd(f, HL, N * N) && rd(f, bL, N) && fread(&has_hm, sizeof(int), 1, f) == 1 && (!has_hm || (rd(f, HM, N * N) && rd(f, bM, N))) &&
-         fread(&lambda, sizeof(double), 1, f) == 1 && fread(&n_null, sizeof(int), 1, f) == 1 && n_null >= 0 && n_null <= DSM_SOLVE_MAX_NULL &&
-         rd(f, basis, N * n_null) && rd(f, pinv, N * n_null);
-  good = good && rd(f, ev, 7 * nf) && rd(f, zero, 8 * nf) && rd(f, backup, 8 * nf) && rd(f, fstep, 8 * nf) && rd(f, cz, 4) && rd(f, cb, 4) && rd(f, cs, 4) &&
-         rd(f, idb, n_pts) && rd(f, ids_step, n_pts) && rd(f, expo, nf) && rd(f, fac, 5) && fread(&has_prior, sizeof(int), 1, f) == 1 &&
-         (!has_prior || (rd(f, prior, N) && rd(f, pzero, N)));
-  if (!good) {
+  window_case::Case c;
+  if (!window_case::read_case(argv[1], window_case::STEP, c)) {
     fprintf(stderr, "step_demo: cannot read %s\n", argv[1]);
     return 2;
   }
-  fclose(f);
-  std::vector<ActivePointData> points(n_pts);
-  for (int i = 0; i < n_pts; i++) {
-    const float *q = &prec[(size_t)21 * i];
-    memcpy(&points[i].host, q, 4);
-    points[i].u = q[1], points[i].v = q[2], points[i].idepth_scaled = 0, points[i].idepth_zero_scaled = 0;
-    memcpy(points[i].color, q + 5, 32);
-    memcpy(points[i].weights, q + 13, 32);
-  }
+  const std::vector<ActivePointData> points = window_case::points(c);
+  const int n_res = (int)c.nr;
   WindowStep proto;
-  proto.residuals.resize(n_res);
-  for (int i = 0; i < n_res; i++) {
-    const float *q = &rrec[(size_t)5 * i];
-    int isnew;
-    ActiveResidualData &r = proto.residuals[i];
-    memcpy(&r.point, q, 4), memcpy(&r.target, q + 1, 4), memcpy(&r.state_state, q + 2, 4);
-    r.state_energy = q[3];
-    memcpy(&isnew, q + 4, 4);
-    r.isNew = isnew != 0;
-  }
-  LinearizeRequest &lin = proto.req.hes.lin;
-  lin.frame_ids = ids, lin.points = &points, lin.fixLinearization = false, lin.wantJacobians = false; // optimize's loop runs linearizeAll(false)
-  proto.frameEnergyTH = eth;
-  proto.req.hes.adHost = adh, proto.req.hes.adTarget = adt, proto.req.hes.shiftPriorToZero = shift != 0;
-  for (int i = 0; i < n_pts; i++) {
-    const float *q = &pin[(size_t)8 * i];
-    proto.req.hes.priorF.push_back(q[0]), proto.req.hes.Hdd_accLF.push_back(q[2]), proto.req.hes.bd_accLF.push_back(q[3]);
-    proto.req.hes.Hcd_accLF.insert(proto.req.hes.Hcd_accLF.end(), q + 4, q + 8);
-  }
-  proto.req.H_L = HL, proto.req.b_L = bL, proto.req.HM = HM, proto.req.bM = bM, proto.req.nullBasis = basis, proto.req.nullPinv = pinv;
-  proto.worldToCamEval = ev, proto.stateZero = zero, proto.exposure = expo, proto.prior = prior, proto.priorZero = pzero;
-  proto.state = backup, proto.idepth = idb;
-  memcpy(proto.calibZero, cz.data(), 32), memcpy(proto.calib, cb.data(), 32);
+  window_case::fill(proto, c);
+  proto.req.hes.lin.points = &points;
 
   dsm_context *ctx = nullptr;
   immature_check(dsm_context_create(0, &ctx), "dsm_context_create");
   Outcome dev, host;
   int windows_equal = 0, stale_refused = 0;
   {
-    KeyframeWindow window(ctx, wh[0], wh[1], (int)nf), window2(ctx, wh[0], wh[1], (int)nf);
-    for (size_t k = 0; k < nf; k++) {
-      window.put(ids[k], &planes[k * npx]);
-      window2.put(ids[nf - 1 - k], &planes[(nf - 1 - k) * npx]); // (the store's order is not the window's)
-    }
+    KeyframeWindow window(ctx, c.w, c.h, (int)c.nf), window2(ctx, c.w, c.h, (int)c.nf);
+    window_case::put_planes(c, window), window_case::put_planes(c, window2, true);
     WindowStep a = proto;
     a.req.hes.lin.window = &window;
     dev = optimize({&a}, max_its, [&](const float *fac5, double lam) { return std::vector<StepResult>(1, a.iterate(ctx, fac5, lam)); })[0];
 
-    WindowStep b = proto, c = proto; // the windows of two sequences in one call per iteration
-    b.req.hes.lin.window = &window, c.req.hes.lin.window = &window2;
-    std::vector<WindowStep *> two = {&b, &c};
+    WindowStep b = proto, b2 = proto; // the windows of two sequences in one call per iteration
+    b.req.hes.lin.window = &window, b2.req.hes.lin.window = &window2;
+    std::vector<WindowStep *> two = {&b, &b2};
     std::vector<Outcome> o2 = optimize(two, max_its, [&](const float *fac5, double lam) { return WindowStep::iterateMany(ctx, two, fac5, lam); });
     windows_equal = o2[0] == dev && o2[1] == dev;
 
@@ -171,10 +110,8 @@ int main(int argc, char **argv) {
 
     WindowStep h = proto; // the host form
     h.req.hes.lin.window = &window;
-    std::vector<const float *> frame_I(nf);
-    for (size_t k = 0; k < nf; k++) frame_I[k] = &planes[k * npx];
     host = optimize({&h}, max_its, [&](const float *fac5, double lam) {
-      return std::vector<StepResult>(1, h.iterateHost(wh[0], wh[1], frame_I.data(), fac5, lam));
+      return std::vector<StepResult>(1, h.iterateHost(c.w, c.h, c.planes, fac5, lam));
     })[0];
   }
   dsm_context_destroy(ctx);

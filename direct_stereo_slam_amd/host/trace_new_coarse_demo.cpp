@@ -14,19 +14,11 @@
 #include <vector>
 
 #include "TraceNewCoarse.hpp"
+#include "window_case.hpp" // fnv1a, rd
 
 using namespace dsm_host;
-
-static uint64_t fnv1a(const void *p, size_t n, uint64_t hsh = 1469598103934665603ull) {
-  for (size_t i = 0; i < n; i++) hsh = (hsh ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
-  return hsh;
-}
-
-template <typename T>
-static bool rd(FILE *f, std::vector<T> &v, size_t n) {
-  v.resize(n);
-  return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
+using window_case::fnv1a;
+using window_case::rd;
 
 // idepth_min, idepth_max, quality, lastTraceUV, lastTracePixelInterval of every point, NaNs made canonical
 static std::vector<float> traced(const std::vector<TracedPointData> &pts) {

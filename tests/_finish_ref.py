@@ -13,6 +13,7 @@ import numpy as np
 import _linearize_ref as R
 import _optimize_ref as O
 import _step_ref as T
+import _window_files as W
 
 f32, f64 = np.float32, np.float64
 IN, OOB, OUTLIER = 0, 1, 2
@@ -407,20 +408,13 @@ def checker_chain(name="scene", max_iterations=6):
 # ---- for tools/finish_host_standalone.cpp ------------------------------------------------------------------------------------------
 
 def write_case(path, w, h, job, frames):
-    """the finish file: _step_ref's step file (the three steps as zeros), then the finish's inputs"""
-    n, m = len(job["frame_ids"]), len(job["host"])
-    T.write_case(path, w, h, dict(job, frame_step=np.zeros((n, 8)), calib_step=np.zeros(4), idepth_step=np.zeros(m, f32),
-                                  stepfac=np.zeros(5, f32), **{"lambda": job.get("lambda", 1e-5)}), frames)
-    with open(path, "ab") as f:
-        f.write(np.ascontiguousarray(job["n_good_residuals_in"], np.int32).tobytes() + np.ascontiguousarray(job["max_rel_baseline_in"], f32).tobytes())
-        f.write(np.ascontiguousarray(job["last_res"], np.int32).tobytes() + np.ascontiguousarray(job["last_state_in"], np.uint8).tobytes())
+    """the finish file (tests/_window_files.py)"""
+    W.write_finish(path, w, h, job, frames)
 
 
 def hashes(loop, fin):
     """what tools/finish_host_standalone.cpp prints, from the checker's results"""
-    from test_linearize_demo import fnv1a
-
-    raw = lambda a: fnv1a(np.ascontiguousarray(a).tobytes())  # noqa: E731
+    raw = lambda a: W.fnv1a(np.ascontiguousarray(a).tobytes())  # noqa: E731
     hx = lambda a: f"{raw(a):016x}"  # noqa: E731
     tables = 0
     for k in T.PRE:

@@ -12,6 +12,7 @@ import numpy as np
 import _hessian_ref as HR
 import _linearize_ref as R
 import _solve_ref as SR
+import _window_files as W
 
 f32, f64 = np.float32, np.float64
 KEEP, MARGINALIZE, DROP = 0, 1, 2
@@ -487,33 +488,13 @@ HASHED = ("verdict", "H_M_out", "b_M_out", "H_M_points", "b_M_points", "res_to_z
 
 
 def write_case(path, w, h, job, frames):
-    """the marginalize file: the window file of host/linearize_demo.cpp, then the Hessian job's ad_host, ad_target, prior and delta,
-    then what a marginalize job holds on top"""
-    import struct
-
-    from test_linearize_demo import write_case as write_window
-
-    n, m = len(job["frame_ids"]), len(job["host"])
-    write_window(path, w, h, job, frames)
-    pin = np.stack([np.asarray(job[k] if job.get(k) is not None else np.zeros(m), f32).reshape(m) for k in ("prior", "delta")], axis=1)
-    d = lambda k: np.ascontiguousarray(job[k], f64).tobytes()  # noqa: E731
-    s = lambda k: np.ascontiguousarray(job[k], f32).tobytes()  # noqa: E731
-    marg = np.asarray(job.get("marg_frames", ()), np.int32).reshape(-1)
-    with open(path, "ab") as f:
-        f.write(d("ad_host") + d("ad_target") + np.ascontiguousarray(pin, f32).tobytes())
-        f.write(np.ascontiguousarray(job["flagged"], np.uint8).tobytes() + np.ascontiguousarray(job["n_good_residuals"], np.int32).tobytes())
-        f.write(np.ascontiguousarray(job["last_state"], np.uint8).tobytes() + s("idepth_hessian") + s("ad_ht_delta") + s("c_delta"))
-        f.write(struct.pack("i", int(job.get("H_M") is not None)))
-        if job.get("H_M") is not None:
-            f.write(d("H_M") + d("b_M"))
-        f.write(struct.pack("i", len(marg)) + marg.tobytes() + d("frame_prior") + d("frame_delta_prior"))
+    """the marginalize file (tests/_window_files.py)"""
+    W.write_marginalize(path, w, h, job, frames)
 
 
 def hashes(exp):
     """what tools/marginalize_host_standalone.cpp prints, from a checker result"""
-    from test_linearize_demo import fnv1a
-
-    hx = lambda a: f"{fnv1a(np.ascontiguousarray(a).tobytes()):016x}"  # noqa: E731
+    hx = lambda a: f"{W.fnv1a(np.ascontiguousarray(a).tobytes()):016x}"  # noqa: E731
     out = {k: hx(exp[k]) for k in HASHED}
     out.update(n_res=len(exp["new_state"]), n_res_marg=int(exp["n_res_marg"]), energy=hx(np.array([exp["energy"]], f64)),
                new_frame_energy_th=hx(np.array([exp["new_frame_energy_th"]], f32)), lean_equal=1)

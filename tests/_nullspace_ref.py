@@ -13,6 +13,7 @@ import math
 import numpy as np
 
 import _step_ref as T
+import _window_files as W
 
 f32, f64 = np.float32, np.float64
 NP = dict(scale_xi_trans=0.5, scale_xi_rot=1.0, scale_a=10.0, scale_b=1000.0, solver_mode_delta=1e-5)
@@ -291,6 +292,20 @@ def expected(name):
 
 POSE_SCENES = tuple(f"frames_{n}" for n in FRAME_COUNTS) + ("origin_one", "origin_first")
 GIVEN_SCENES = tuple(f"given_frames_{n}" for n in FRAME_COUNTS) + ("given_origin_one", "given_origin_first", "equal_columns")
+
+
+# ---- for tools/nullspace_host_standalone.cpp ---------------------------------------------------------------------------------------
+
+def write_case(path, job):
+    """the stand-alone program's file (tests/_window_files.py)"""
+    W.write_nullspace_job(path, job)
+
+
+def hashes(exp):
+    """what tools/nullspace_host_standalone.cpp prints, from a checker result"""
+    out = {k: f"{W.fnv1a(np.ascontiguousarray(exp[k], np.float64).tobytes()):016x}" for k in ("null_basis", "null_pinv", "sing", "frame_null", "null_x0_pre")}
+    out.update(rank=exp["rank"], flags=exp["flags"], forms_equal=1, refusal=1)
+    return out
 
 
 def bits_equal(a, b):

@@ -13,6 +13,7 @@ import numpy as np
 import _hessian_ref as HR
 import _linearize_ref as R
 import _solve_ref as SR
+import _window_files as W
 
 f32, f64 = np.float32, np.float64
 SP = dict(scale_xi_trans=0.5, scale_xi_rot=1.0, scale_a=10.0, scale_b=1000.0, th_opt_iterations=1.2)
@@ -415,42 +416,16 @@ def invalid_jobs(job):
 # ---- for tools/step_host_standalone.cpp ----------------------------------------------------------------------------------------------
 
 def write_case(path, w, h, job, frames):
-    """the step file: the window file of host/solve_demo.cpp with zeros where the call forms the values, then the step's inputs"""
-    import struct
-
-    from test_linearize_demo import write_case as write_window
-
-    n, m = len(job["frame_ids"]), len(job["host"])
-    N = 4 + 8 * n
-    filled = dict(job, cam=(0, 0, 0, 0), cam_inv=(0, 0), idepth_scaled=np.zeros(m, f32), idepth_zero_scaled=np.zeros(m, f32),
-                  **{k: np.zeros((n, n, width), f32) for k, width in R.PRE})
-    write_window(path, w, h, filled, frames)
-    pin = np.concatenate([np.asarray(job[k] if job.get(k) is not None else np.zeros(m * width), f32).reshape(m, width)
-                          for k, width in (("prior", 1), ("delta", 1), ("hdd_lin", 1), ("bd_lin", 1), ("hcd_lin", 4))], axis=1)
-    d = lambda k: np.ascontiguousarray(job[k], f64).tobytes()  # noqa: E731
-    s = lambda k: np.ascontiguousarray(job[k], f32).tobytes()  # noqa: E731
-    nn = int(job.get("n_null", 0))
-    with open(path, "ab") as f:
-        f.write(d("ad_host") + d("ad_target") + pin.tobytes() + struct.pack("i", int(job["shift_prior_to_zero"])))
-        f.write(d("H_L") + d("b_L") + struct.pack("i", int(job.get("H_M") is not None)))
-        if job.get("H_M") is not None:
-            f.write(d("H_M") + d("b_M"))
-        f.write(struct.pack("d", float(job["lambda"])) + struct.pack("i", nn) + (d("null_basis") + d("null_pinv") if nn else b""))
-        f.write(b"".join(d(k) for k in STEP_IN[:7]) + s("idepth_backup") + s("idepth_step") + s("exposure") + s("stepfac"))
-        f.write(struct.pack("i", int(job.get("state_prior") is not None)))
-        if job.get("state_prior") is not None:
-            assert len(job["state_prior"]) == N
-            f.write(d("state_prior") + d("state_prior_zero"))
+    """the step file (tests/_window_files.py)"""
+    W.write_step(path, w, h, job, frames)
 
 
 def hashes(exp):
     """what tools/step_host_standalone.cpp prints, from a checker result"""
-    from test_linearize_demo import fnv1a
-
-    hx = lambda a: f"{fnv1a(np.ascontiguousarray(a).tobytes()):016x}"  # noqa: E731
+    hx = lambda a: f"{W.fnv1a(np.ascontiguousarray(a).tobytes()):016x}"  # noqa: E731
     pre = 0
     for k in PRE:
-        pre ^= fnv1a(np.ascontiguousarray(exp[k]).tobytes())
+        pre ^= W.fnv1a(np.ascontiguousarray(exp[k]).tobytes())
     out = {k: hx(exp[k]) for k in ("state", "calib", "idepth", "world_to_cam", "cam_to_world", "cam", "delta_x", "H_L", "b_L", "x", "step", "new_energy")}
     out.update(pre=f"{pre:016x}", energy_m=hx(np.array([exp["energy_m"]], f64)), can_break=int(exp["can_break"]), flags=int(exp["flags"]),
                n_res=len(exp["new_energy"]), lean_equal=1)

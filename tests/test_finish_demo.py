@@ -11,7 +11,7 @@ import pytest
 
 import _finish_ref as F
 import _linearize_ref as R
-from test_linearize_demo import fnv1a
+from _window_files import fnv1a
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

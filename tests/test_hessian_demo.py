@@ -3,7 +3,6 @@ host/hessian_demo.cpp like a pass of FrontEnd::optimize: the printed states and 
 JpJdF and the per-point results against the checker tests/_hessian_ref.py."""
 import json
 import os
-import struct
 import subprocess
 
 import numpy as np
@@ -11,7 +10,7 @@ import pytest
 
 import _hessian_ref as HR
 import _linearize_ref as R
-from test_linearize_demo import fnv1a, write_case
+from _window_files import fnv1a, write_hessian
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,13 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_adaptor_one_window_many_windows_and_host_form_equal_the_checker(built, ctx, tmp_path):
     job, frames, exp = HR.case("scene")
     path = tmp_path / "window.bin"
-    write_case(path, R.W, R.H, job, frames)
-    n = len(job["host"])
-    pin = np.concatenate([np.asarray(job[k], np.float32).reshape(n, -1) for k in ("prior", "delta", "hdd_lin", "bd_lin", "hcd_lin")], axis=1)
-    assert pin.shape == (n, 8)
-    with open(path, "ab") as f:
-        f.write(np.asarray(job["ad_host"], np.float64).tobytes() + np.asarray(job["ad_target"], np.float64).tobytes())
-        f.write(pin.tobytes() + struct.pack("i", int(job["shift_prior_to_zero"])))
+    write_hessian(path, R.W, R.H, job, frames)
     exe = os.path.join(ROOT, "direct_stereo_slam_amd", "host", "_build", "hessian_demo")
     out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr + out.stdout

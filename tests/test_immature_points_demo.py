@@ -10,16 +10,10 @@ import numpy as np
 import pytest
 
 import _immature_ref as R
+from _window_files import fnv1a
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def fnv1a(b):
-    h = 1469598103934665603
-    for x in b:
-        h = ((h ^ x) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return h
 
 
 def test_adaptor_one_window_many_windows_and_host_form_equal_the_checker(built, ctx, tmp_path):

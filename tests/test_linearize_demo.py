@@ -3,47 +3,22 @@ the passes of FrontEnd::optimize: the printed states, the hashes of the energies
 threshold, the kept list and the per-point updates against the checker tests/_linearize_ref.py."""
 import json
 import os
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
 import _linearize_ref as R
+from _window_files import fnv1a, write_window
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def fnv1a(b, h=1469598103934665603):
-    for x in b:
-        h = ((h ^ x) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return h
-
-
-def write_case(path, w, h, job, frames):
-    nf, n, nr = len(frames), len(job["host"]), len(job["point"])
-    pre = np.concatenate([np.asarray(job[k], np.float32).reshape(nf * nf, m) for k, m in R.PRE], axis=1)
-    prec = np.zeros((n, 21), np.float32)
-    prec[:, 0] = np.asarray(job["host"], np.int32).view(np.float32)
-    for k, name in enumerate(("u", "v", "idepth_scaled", "idepth_zero_scaled")):
-        prec[:, 1 + k] = job[name]
-    prec[:, 5:13], prec[:, 13:21] = job["color"], job["weights"]
-    rrec = np.zeros((nr, 5), np.int32)
-    rrec[:, 0], rrec[:, 1], rrec[:, 2], rrec[:, 4] = job["point"], job["target"], job["state_in"], job["is_new"]
-    rrec[:, 3] = np.asarray(job["energy_in"], np.float32).view(np.int32)
-    with open(path, "wb") as f:
-        f.write(struct.pack("ii", w, h) + np.array(list(job["cam"]) + list(job["cam_inv"]), np.float32).tobytes())
-        f.write(struct.pack("ii", nf, int(job["fix_linearization"])) + np.asarray(job["frame_ids"], np.int32).tobytes())
-        f.write(b"".join(np.ascontiguousarray(fr, np.float32).tobytes() for fr in frames) + pre.tobytes())
-        f.write(np.asarray(job["frame_energy_th"], np.float32).tobytes())
-        f.write(struct.pack("i", n) + prec.tobytes() + struct.pack("i", nr) + rrec.tobytes())
-
-
 def test_adaptor_one_window_many_windows_and_host_form_equal_the_checker(built, ctx, tmp_path):
     job, frames, exp, _ = R.case("scene")
     path = tmp_path / "window.bin"
-    write_case(path, R.W, R.H, job, frames)
+    write_window(path, R.W, R.H, job, frames)
     exe = os.path.join(ROOT, "direct_stereo_slam_amd", "host", "_build", "linearize_demo")
     out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr + out.stdout

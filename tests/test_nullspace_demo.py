@@ -3,7 +3,6 @@ window, two windows in one call, the device's basis fed to host/WindowSolve.hpp,
 tests/_nullspace_ref.py and tests/_solve_ref.py."""
 import json
 import os
-import struct
 import subprocess
 
 import numpy as np
@@ -12,7 +11,7 @@ import pytest
 import _linearize_ref as R
 import _nullspace_ref as NR
 import _solve_ref as SR
-from test_linearize_demo import fnv1a, write_case
+from _window_files import fnv1a, write_nullspace
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,18 +22,7 @@ def test_adaptor_one_window_two_windows_solve_and_host_form(built, ctx, tmp_path
     nf, N = len(job["frame_ids"]), len(exp["x"])
     poses = [NR.make_job(90, nf), NR.make_job(91, nf)]
     path, out_path = tmp_path / "window.bin", tmp_path / "null.bin"
-    write_case(path, R.W, R.H, job, frames)
-    n = len(job["host"])
-    pin = np.concatenate([np.asarray(job[k], np.float32).reshape(n, -1) for k in ("prior", "delta", "hdd_lin", "bd_lin", "hcd_lin")], axis=1)
-    d = lambda k: np.ascontiguousarray(job[k], np.float64).tobytes()  # noqa: E731
-    with open(path, "ab") as f:
-        f.write(d("ad_host") + d("ad_target"))
-        f.write(pin.tobytes() + struct.pack("i", int(job["shift_prior_to_zero"])))
-        f.write(d("H_L") + d("b_L") + d("H_M") + d("b_M") + d("delta_x") + struct.pack("d", float(job["lambda"])))
-        f.write(struct.pack("i", int(job["n_null"])) + d("null_basis") + d("null_pinv"))
-        for p in poses:
-            f.write(np.ascontiguousarray(p["world_to_cam_eval"], np.float64).tobytes() + np.ascontiguousarray(p["state_zero"], np.float64).tobytes()
-                    + np.ascontiguousarray(p["exposure"], np.float32).tobytes())
+    write_nullspace(path, R.W, R.H, job, frames, poses)
     exe = os.path.join(ROOT, "direct_stereo_slam_amd", "host", "_build", "nullspace_demo")
     out = subprocess.run([exe, str(path), str(out_path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr + out.stdout

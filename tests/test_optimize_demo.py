@@ -11,7 +11,7 @@ import pytest
 import _linearize_ref as R
 import _optimize_ref as O
 import _step_ref as T
-from test_linearize_demo import fnv1a
+from _window_files import fnv1a
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

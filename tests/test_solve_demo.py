@@ -3,7 +3,6 @@ trial step of FrontEnd::optimize: the hashes of lastX, the points' steps, lastHS
 tests/_solve_ref.py."""
 import json
 import os
-import struct
 import subprocess
 
 import numpy as np
@@ -11,7 +10,7 @@ import pytest
 
 import _linearize_ref as R
 import _solve_ref as SR
-from test_linearize_demo import fnv1a, write_case
+from _window_files import fnv1a, write_solve
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,15 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_adaptor_one_window_many_windows_and_host_form_equal_the_checker(built, ctx, tmp_path):
     job, frames, exp = SR.case("scene", n_null=7)
     path = tmp_path / "window.bin"
-    write_case(path, R.W, R.H, job, frames)
-    n = len(job["host"])
-    pin = np.concatenate([np.asarray(job[k], np.float32).reshape(n, -1) for k in ("prior", "delta", "hdd_lin", "bd_lin", "hcd_lin")], axis=1)
-    d = lambda k: np.ascontiguousarray(job[k], np.float64).tobytes()  # noqa: E731
-    with open(path, "ab") as f:
-        f.write(d("ad_host") + d("ad_target"))
-        f.write(pin.tobytes() + struct.pack("i", int(job["shift_prior_to_zero"])))
-        f.write(d("H_L") + d("b_L") + d("H_M") + d("b_M") + d("delta_x") + struct.pack("d", float(job["lambda"])))
-        f.write(struct.pack("i", int(job["n_null"])) + d("null_basis") + d("null_pinv"))
+    write_solve(path, R.W, R.H, job, frames)
     exe = os.path.join(ROOT, "direct_stereo_slam_amd", "host", "_build", "solve_demo")
     out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr + out.stdout

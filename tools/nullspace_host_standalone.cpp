@@ -2,45 +2,16 @@
 // (DESIGN.md section 23): reads a case file (int32 n_frames, int32 given, n_frames * 7 doubles world_to_cam_eval, n_frames * 8 state_zero,
 // n_frames floats exposure, and if given n_frames * 42 doubles frame_null_in), puts every array into a heap block of exactly its size,
 // runs the job once with every optional output and once with none, then twice in one call, and prints one JSON line with the FNV-1a
-// hashes of every output, which tools/nullspace_host_standalone_check.py reproduces from the checker.  Build, from the repository root:
+// hashes of every output, which tests/_nullspace_ref.py's hashes reproduces from the checker (tools/host_standalone_check.py).  Build, from the repository root:
 //   hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //       tools/nullspace_host_standalone.cpp direct_stereo_slam_amd/csrc/nullspace_host.cpp -o nullspace_host_standalone
 // The program frees none of its blocks: run it with ASAN_OPTIONS=detect_leaks=0.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
+#define WINDOW_CASE_STANDALONE
+#include "../direct_stereo_slam_amd/host/window_case.hpp" // block, read_block, fnv1a and the dsm::set_error / dsm::invalid stubs
 
-#include "../include/dsm_hotpath.h"
-
-namespace dsm {
-static std::string last_error;
-void set_error(const std::string &msg) { last_error = msg; }
-int invalid(const char *msg) {
-  last_error = msg;
-  return DSM_ERR_INVALID;
-}
-} // namespace dsm
-
-template <typename T>
-static T *block(size_t n) { // exactly n elements, so that the sanitizer sees every access past an end
-  return (T *)malloc(n ? n * sizeof(T) : 1);
-}
-template <typename T>
-static T *read_block(FILE *f, size_t n) {
-  T *p = block<T>(n);
-  if (n && fread(p, sizeof(T), n, f) != n) {
-    fprintf(stderr, "nullspace_host_standalone: short file\n");
-    exit(2);
-  }
-  return p;
-}
-static uint64_t fnv(const void *p, size_t n) {
-  uint64_t h = 1469598103934665603ull;
-  for (size_t i = 0; i < n; i++) h = (h ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
-  return h;
-}
+using window_case::block;
+using window_case::fnv1a;
+static const char *const PROGRAM = "nullspace_host_standalone";
 
 static dsm_nullspace_job make_job(int n, const double *ev, const double *zero, const float *expo, const double *fn, bool optional) {
   const size_t N = 4 + 8 * (size_t)n;
@@ -63,16 +34,16 @@ int main(int argc, char **argv) {
     fprintf(stderr, "usage: nullspace_host_standalone FILE\n");
     return 2;
   }
-  int *head = read_block<int>(f, 2);
+  int *head = window_case::read_block<int>(f, 2, PROGRAM);
   const int n = head[0];
   if (n < 1 || n > DSM_WINDOW_MAX_FRAMES) {
     fprintf(stderr, "nullspace_host_standalone: n_frames\n");
     return 2;
   }
   const size_t N = 4 + 8 * (size_t)n;
-  double *ev = read_block<double>(f, 7 * (size_t)n), *zero = read_block<double>(f, 8 * (size_t)n);
-  float *expo = read_block<float>(f, n);
-  double *fn = head[1] ? read_block<double>(f, 42 * (size_t)n) : nullptr;
+  double *ev = window_case::read_block<double>(f, 7 * (size_t)n, PROGRAM), *zero = window_case::read_block<double>(f, 8 * (size_t)n, PROGRAM);
+  float *expo = window_case::read_block<float>(f, n, PROGRAM);
+  double *fn = head[1] ? window_case::read_block<double>(f, 42 * (size_t)n, PROGRAM) : nullptr;
   fclose(f);
 
   dsm_nullspace_job full = make_job(n, ev, zero, expo, fn, true), bare = make_job(n, ev, zero, expo, fn, false);
@@ -92,8 +63,8 @@ int main(int argc, char **argv) {
   const int refusal = dsm_window_nullspace_host(1, &refused, nullptr) == DSM_ERR_INVALID;
   printf("{\"null_basis\": \"%016llx\", \"null_pinv\": \"%016llx\", \"sing\": \"%016llx\", \"frame_null\": \"%016llx\", \"null_x0_pre\": \"%016llx\", "
          "\"rank\": %d, \"flags\": %d, \"forms_equal\": %d, \"refusal\": %d}\n",
-         (unsigned long long)fnv(full.null_basis, 56 * N), (unsigned long long)fnv(full.null_pinv, 56 * N), (unsigned long long)fnv(full.sing, 56),
-         (unsigned long long)fnv(full.frame_null_out, 336 * (size_t)n), (unsigned long long)fnv(full.null_x0_pre, 72 * N), *full.rank, *full.flags,
+         (unsigned long long)fnv1a(full.null_basis, 56 * N), (unsigned long long)fnv1a(full.null_pinv, 56 * N), (unsigned long long)fnv1a(full.sing, 56),
+         (unsigned long long)fnv1a(full.frame_null_out, 336 * (size_t)n), (unsigned long long)fnv1a(full.null_x0_pre, 72 * N), *full.rank, *full.flags,
          forms_equal, refusal);
   return forms_equal && refusal ? 0 : 1;
 }

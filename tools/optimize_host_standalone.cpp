@@ -1,163 +1,55 @@
 // optimize_host_standalone.cpp -- dsm_window_optimize_host as a stand-alone CPU program, for a sanitizer run of the host form (DESIGN.md
-// section 20): reads a step file (tests/_step_ref.py, write_case; its state_backup, calib_backup and idepth_backup are the state the
-// loop starts from, its step, factors and lambda are not used), puts every plane and every array into a heap block of exactly its size,
-// runs the loop once with the required outputs alone and once with every optional output, and prints one JSON line with the pattern,
-// the passes and the FNV-1a hashes of the outputs, for a comparison with the checker tests/_optimize_ref.py.  Build, from the
-// repository root:
+// section 20): reads a step file (direct_stereo_slam_amd/host/window_case.hpp, which puts every plane and every array into a heap block
+// of exactly its size; its state_backup, calib_backup and idepth_backup are the state the loop starts from, its steps, factors and lambda
+// are not used), runs the loop once with the required outputs alone and once with every optional output, and prints one JSON line with
+// the pattern, the passes and the FNV-1a hashes of the outputs, for a comparison with the checker tests/_optimize_ref.py.  Build, from
+// the repository root:
 //   hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //       tools/optimize_host_standalone.cpp direct_stereo_slam_amd/csrc/points_host.cpp direct_stereo_slam_amd/csrc/solve_host.cpp \
 //       direct_stereo_slam_amd/csrc/step_host.cpp direct_stereo_slam_amd/csrc/optimize_host.cpp -o optimize_host_standalone
 // Usage: optimize_host_standalone FILE [MAX_ITERATIONS = 6] [STEP_MOMENTUM = 0].  The program frees none of its blocks: run it with
 // ASAN_OPTIONS=detect_leaks=0.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
+#define WINDOW_CASE_STANDALONE
+#include "../direct_stereo_slam_amd/host/window_case.hpp"
 
-#include "../include/dsm_hotpath.h"
-
-namespace dsm {
-static std::string last_error;
-void set_error(const std::string &msg) { last_error = msg; }
-} // namespace dsm
-
-template <typename T>
-static T *block(size_t n) { // exactly n elements, so that the sanitizer sees every access past an end
-  return (T *)malloc(n ? n * sizeof(T) : 1);
-}
-template <typename T>
-static T *read_block(FILE *f, size_t n) {
-  T *p = block<T>(n);
-  if (n && fread(p, sizeof(T), n, f) != n) {
-    fprintf(stderr, "optimize_host_standalone: short file\n");
-    exit(2);
-  }
-  return p;
-}
-static uint64_t fnv(const void *p, size_t n) {
-  uint64_t h = 1469598103934665603ull;
-  for (size_t i = 0; i < n; i++) h = (h ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
-  return h;
-}
+using namespace window_case;
 
 int main(int argc, char **argv) {
-  FILE *f = argc > 1 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) {
-    fprintf(stderr, "usage: optimize_host_standalone FILE\n");
-    return 2;
-  }
-  int *wh = read_block<int>(f, 2);
-  read_block<float>(f, 6); // cam, cam_inv: not read by this call
-  int *nff = read_block<int>(f, 2);
-  const size_t nf = nff[0], npx = (size_t)wh[0] * wh[1], N = 4 + 8 * nf, n2 = nf * nf;
+  Case c;
+  open_case("optimize_host_standalone", argc, argv, STEP, c);
   const int max_its = argc > 2 ? atoi(argv[2]) : 6;
   dsm_optimize_job O;
   memset(&O, 0, sizeof O);
   dsm_step_job &T = O.step;
   dsm_solve_job &S = T.sol;
-  dsm_hessian_job &H = S.hes;
-  dsm_linearize_job &J = H.lin;
-  J.n_frames = (int)nf, J.fix_linearization = nff[1], J.frame_ids = read_block<int>(f, nf);
-  const float **planes = block<const float *>(nf);
-  for (size_t k = 0; k < nf; k++) planes[k] = read_block<float>(f, npx);
-  read_block<float>(f, n2 * 27); // the precalc tables: formed by this call
-  J.frame_energy_th = read_block<float>(f, nf);
-  const size_t n = *read_block<int>(f, 1);
-  float *prec = read_block<float>(f, n * 21);
-  const size_t nr = *read_block<int>(f, 1);
-  float *rrec = read_block<float>(f, nr * 5);
-  int *host = block<int>(n), *point = block<int>(nr), *target = block<int>(nr);
-  float *u = block<float>(n), *v = block<float>(n), *color = block<float>(8 * n), *wts = block<float>(8 * n);
-  for (size_t i = 0; i < n; i++) {
-    const float *q = prec + 21 * i;
-    memcpy(host + i, q, 4), u[i] = q[1], v[i] = q[2];
-    memcpy(color + 8 * i, q + 5, 32), memcpy(wts + 8 * i, q + 13, 32);
-  }
-  unsigned char *sin = block<unsigned char>(nr), *isnew = block<unsigned char>(nr);
-  float *ein = block<float>(nr);
-  for (size_t i = 0; i < nr; i++) {
-    const float *q = rrec + 5 * i;
-    int s, w;
-    memcpy(point + i, q, 4), memcpy(target + i, q + 1, 4), memcpy(&s, q + 2, 4), memcpy(&w, q + 4, 4);
-    sin[i] = (unsigned char)s, isnew[i] = (unsigned char)w, ein[i] = q[3];
-  }
-  J.n_pts = (int)n, J.host = host, J.u = u, J.v = v, J.color = color, J.weights = wts;
-  J.n_res = (int)nr, J.point = point, J.target = target, J.state_in = sin, J.energy_in = ein, J.is_new = isnew;
-  J.new_state = block<unsigned char>(nr), J.new_energy = block<float>(nr), J.new_energy_with_outlier = block<float>(nr);
-  double energy;
-  float th;
-  J.energy_out = &energy, J.new_frame_energy_th_out = &th;
-  H.ad_host = read_block<double>(f, n2 * 64), H.ad_target = read_block<double>(f, n2 * 64);
-  float *pin = read_block<float>(f, n * 8);
-  float *per[4], *hcd_lin = block<float>(4 * n);
-  for (int k = 0; k < 4; k++) {
-    per[k] = block<float>(n);
-    for (size_t i = 0; i < n; i++) per[k][i] = pin[8 * i + k];
-  }
-  for (size_t i = 0; i < n; i++) memcpy(hcd_lin + 4 * i, pin + 8 * i + 4, 16);
-  H.prior = per[0], H.hdd_lin = per[2], H.bd_lin = per[3], H.hcd_lin = hcd_lin; // per[1], delta: formed by this call
-  H.shift_prior_to_zero = *read_block<int>(f, 1);
-  S.H_L = read_block<double>(f, N * N), S.b_L = read_block<double>(f, N);
-  if (*read_block<int>(f, 1)) S.H_M = read_block<double>(f, N * N), S.b_M = read_block<double>(f, N);
-  S.lambda = *read_block<double>(f, 1), S.n_null = *read_block<int>(f, 1);
-  S.null_basis = read_block<double>(f, N * S.n_null), S.null_pinv = read_block<double>(f, N * S.n_null);
-  T.world_to_cam_eval = read_block<double>(f, 7 * nf), T.state_zero = read_block<double>(f, 8 * nf), T.state_backup = read_block<double>(f, 8 * nf);
-  read_block<double>(f, 8 * nf); // frame_step: formed by the loop
-  T.calib_zero = read_block<double>(f, 4), T.calib_backup = read_block<double>(f, 4);
-  read_block<double>(f, 4), T.idepth_backup = read_block<float>(f, n), read_block<float>(f, n); // calib_step, idepth_step: formed by the loop
-  T.exposure = read_block<float>(f, nf);
-  memcpy(T.stepfac, read_block<float>(f, 5), 20);
-  if (*read_block<int>(f, 1)) T.prior = read_block<double>(f, N), T.prior_zero = read_block<double>(f, N);
-  fclose(f);
-  int flags = -1, can_break = -1;
-  double energy_m;
-  S.x = block<double>(N), S.step = block<float>(n), S.flags = &flags;
-  T.state_out = block<double>(8 * nf), T.calib_out = block<double>(4), T.idepth_out = block<float>(n), T.world_to_cam_out = block<double>(7 * nf);
-  T.can_break = &can_break, T.step_sums = block<float>(6), T.energy_m = &energy_m;
-  const size_t its = (size_t)(max_its > 0 ? max_its : 0), passes = 1 + 2 * its;
-  int n_iterations = -1, n_passes = -1;
-  double lambda_out;
-  float eth_out;
-  O.max_iterations = max_its, O.n_iterations = &n_iterations, O.n_passes = &n_passes, O.pattern = block<unsigned char>(its);
-  O.pass_energy = block<double>(2 * passes), O.pass_lambda = block<double>(passes), O.iter_stepsize = block<float>(its);
-  O.iter_can_break = block<unsigned char>(its), O.last_energy = block<double>(2), O.lambda_out = &lambda_out, O.frame_energy_th_out = &eth_out;
+  fill(T, c, false);
+  optimize_outputs(O, c, max_its);
   dsm_linearize_params lp;
   dsm_step_params sp;
   dsm_optimize_params op;
   dsm_linearize_params_default(&lp), dsm_step_params_default(&sp), dsm_optimize_params_default(&op);
   op.step_momentum = argc > 3 ? atoi(argv[3]) : 0;
   // the required outputs alone: the host form keeps everything else in room of its own
-  int rc = dsm_window_optimize_host(wh[0], wh[1], &O, planes, &lp, &sp, &op);
-  const uint64_t x_lean = fnv(S.x, 8 * N), state_lean = fnv(T.state_out, 64 * nf);
+  int rc = dsm_window_optimize_host(c.w, c.h, &O, c.planes, &lp, &sp, &op);
+  const size_t nf = c.nf, n = c.n, N = c.N;
+  const uint64_t x_lean = fnv1a(S.x, 8 * N), state_lean = fnv1a(T.state_out, 64 * nf);
   // every optional output
-  T.cam_to_world_out = block<double>(7 * nf), T.cam_out = block<float>(6);
-  T.pre_RTll_0_out = block<float>(9 * n2), T.pre_tTll_0_out = block<float>(3 * n2), T.pre_KRKiTll_out = block<float>(9 * n2);
-  T.pre_KtTll_out = block<float>(3 * n2), T.pre_aff_mode_out = block<float>(2 * n2), T.pre_b0_mode_out = block<float>(n2);
-  T.delta_x_out = block<double>(N), T.H_L_out = block<double>(N * N), T.b_L_out = block<double>(N);
-  J.J_out = block<float>((size_t)DSM_LINEARIZE_J_FLOATS * nr);
-  J.center_projected_to = block<float>(3 * nr), J.projected_to = block<float>(16 * nr), J.keep = block<unsigned char>(nr), J.rel_bs = block<float>(nr);
-  H.H_A = block<double>(N * N), H.b_A = block<double>(N), H.H_sc = block<double>(N * N), H.b_sc = block<double>(N);
-  H.acc_top = block<double>(n2 * 169), H.acc_D = block<double>(n2 * nf * 64), H.acc_E = block<double>(n2 * 32), H.acc_EB = block<double>(n2 * 8);
-  H.acc_Hcc = block<double>(16), H.acc_bc = block<double>(4);
-  H.active = block<unsigned char>(nr), H.JpJdF = block<float>(8 * nr);
-  H.hdd_acc = block<float>(n), H.bd_acc = block<float>(n), H.hcd_acc = block<float>(4 * n), H.hdi = block<float>(n), H.bd_sum = block<float>(n);
-  H.idepth_hessian = block<float>(n);
-  S.last_HS = block<double>(N * N), S.last_bS = block<double>(N);
-  if (!rc) rc = dsm_window_optimize_host(wh[0], wh[1], &O, planes, &lp, &sp, &op);
+  step_optional(T, c), linearize_optional(S.hes.lin, c, true, true), hessian_optional(S.hes, c, true), solve_optional(S, c);
+  if (!rc) rc = dsm_window_optimize_host(c.w, c.h, &O, c.planes, &lp, &sp, &op);
   if (rc) {
     fprintf(stderr, "optimize_host_standalone: %d %s\n", rc, dsm::last_error.c_str());
     return 1;
   }
-  const bool same = x_lean == fnv(S.x, 8 * N) && state_lean == fnv(T.state_out, 64 * nf);
+  const bool same = x_lean == fnv1a(S.x, 8 * N) && state_lean == fnv1a(T.state_out, 64 * nf);
   auto hx = [](uint64_t h) { return (unsigned long long)h; };
-  const std::string pattern((const char *)O.pattern, (size_t)n_iterations);
+  const size_t n_iterations = (size_t)*O.n_iterations, n_passes = (size_t)*O.n_passes;
+  const std::string pattern((const char *)O.pattern, n_iterations);
   const double last = O.last_energy[0] + O.last_energy[1];
   printf("{\"n_res\": %zu, \"pattern\": \"%s\", \"passes\": %d, \"state\": \"%016llx\", \"calib\": \"%016llx\", \"idepth\": \"%016llx\", "
          "\"x\": \"%016llx\", \"step\": \"%016llx\", \"new_energy\": \"%016llx\", \"pass_energy\": \"%016llx\", \"pass_lambda\": \"%016llx\", "
          "\"iter_stepsize\": \"%016llx\", \"last\": \"%016llx\", \"frame_energy_th\": \"%016llx\", \"flags\": %d, \"lean_equal\": %d}\n",
-         nr, pattern.c_str(), n_passes, hx(fnv(T.state_out, 64 * nf)), hx(fnv(T.calib_out, 32)), hx(fnv(T.idepth_out, 4 * n)), hx(fnv(S.x, 8 * N)),
-         hx(fnv(S.step, 4 * n)), hx(fnv(J.new_energy, 4 * nr)), hx(fnv(O.pass_energy, 16 * (size_t)n_passes)), hx(fnv(O.pass_lambda, 8 * (size_t)n_passes)),
-         hx(fnv(O.iter_stepsize, 4 * (size_t)n_iterations)), hx(fnv(&last, 8)), hx(fnv(&eth_out, 4)), flags, (int)same);
+         c.nr, pattern.c_str(), *O.n_passes, hx(fnv1a(T.state_out, 64 * nf)), hx(fnv1a(T.calib_out, 32)), hx(fnv1a(T.idepth_out, 4 * n)), hx(fnv1a(S.x, 8 * N)),
+         hx(fnv1a(S.step, 4 * n)), hx(fnv1a(S.hes.lin.new_energy, 4 * c.nr)), hx(fnv1a(O.pass_energy, 16 * n_passes)), hx(fnv1a(O.pass_lambda, 8 * n_passes)),
+         hx(fnv1a(O.iter_stepsize, 4 * n_iterations)), hx(fnv1a(&last, 8)), hx(fnv1a(O.frame_energy_th_out, 4)), *S.flags, (int)same);
   return same ? 0 : 1;
 }

@@ -12,27 +12,18 @@
 #include <cstring>
 #include <string>
 
-#include "../include/dsm_hotpath.h"
+#define WINDOW_CASE_STANDALONE
+#include "../direct_stereo_slam_amd/host/window_case.hpp" // block, fnv1a and the dsm::set_error stub
 
-namespace dsm {
-static std::string last_error;
-void set_error(const std::string &msg) { last_error = msg; }
-} // namespace dsm
+using window_case::block;
+using window_case::fnv1a;
 
-template <typename T>
-static T *block(size_t n) { // exactly n elements, so that the sanitizer sees every access past an end
-  return (T *)malloc(n ? n * sizeof(T) : 1);
-}
-static uint64_t fnv(uint64_t h, const void *p, size_t n) {
-  for (size_t i = 0; i < n; i++) h = (h ^ ((const unsigned char *)p)[i]) * 1099511628211ull;
-  return h;
-}
-static uint64_t fnv_floats(uint64_t h, const float *x, size_t n) {
+static uint64_t hash_floats(uint64_t h, const float *x, size_t n) {
   for (size_t i = 0; i < n; i++) {
     uint32_t b;
     memcpy(&b, x + i, 4);
     if (x[i] != x[i]) b = 0x7fc00000u;
-    h = fnv(h, &b, 4);
+    h = fnv1a(&b, 4, h);
   }
   return h;
 }
@@ -70,11 +61,11 @@ int main(int argc, char **argv) {
   }
   const size_t n = (size_t)(*n_pts < (int)cap ? *n_pts : (int)cap);
   uint64_t hp = 1469598103934665603ull;
-  hp = fnv_floats(hp, u, n), hp = fnv_floats(hp, v, n), hp = fnv_floats(hp, eth, n), hp = fnv_floats(hp, G, 4 * n), hp = fnv_floats(hp, color, 8 * n);
-  hp = fnv_floats(hp, wt, 8 * n), hp = fnv_floats(hp, dmin, n), hp = fnv_floats(hp, dmax, n), hp = fnv_floats(hp, quality, n), hp = fnv_floats(hp, type, n);
-  hp = fnv(hp, status, n);
+  hp = hash_floats(hp, u, n), hp = hash_floats(hp, v, n), hp = hash_floats(hp, eth, n), hp = hash_floats(hp, G, 4 * n), hp = hash_floats(hp, color, 8 * n);
+  hp = hash_floats(hp, wt, 8 * n), hp = hash_floats(hp, dmin, n), hp = hash_floats(hp, dmax, n), hp = hash_floats(hp, quality, n), hp = hash_floats(hp, type, n);
+  hp = fnv1a(status, n, hp);
   printf("{\"counts\": [%d, %d, %d], \"n_pts\": %d, \"num_total\": %d, \"passes\": %d, \"potential\": %d, \"map_hash\": \"%016llx\", \"points_hash\": \"%016llx\"}\n",
-         counts[0], counts[1], counts[2], *n_pts, *num_total, *passes, *potential, (unsigned long long)fnv(1469598103934665603ull, map, npx),
+         counts[0], counts[1], counts[2], *n_pts, *num_total, *passes, *potential, (unsigned long long)fnv1a(map, npx),
          (unsigned long long)hp);
   for (void *p : {(void *)I0, (void *)I1, (void *)I2, (void *)rp, (void *)map, (void *)u, (void *)v, (void *)eth, (void *)G, (void *)color, (void *)wt,
                   (void *)dmin, (void *)dmax, (void *)quality, (void *)type, (void *)status, (void *)potential, (void *)n_pts, (void *)num_total,
