@@ -316,6 +316,25 @@ class NullspaceJob(C.Structure):
     ]
 
 
+class RescaleJob(C.Structure):
+    _fields_ = (
+        [("n_frames", C.c_int), ("n_pts", C.c_int), ("enabled", C.c_int), ("scale_error", C.c_float), ("new_scale", C.c_float),
+         ("thres", C.c_float), ("trapped", C.c_int), ("fails", C.c_int)]
+        + [(k, c_float_p) for k in ("idepth", "idepth_scaled", "idepth_zero_scaled", "delta")]
+        + [("world_to_cam_eval", c_double_p), ("state", c_double_p), ("state_zero", c_double_p), ("exposure", c_float_p),
+           ("cam_to_tracking_ref", c_double_p), ("ref_cam_to_world", c_double_p), ("cam_to_world", c_double_p), ("aff_g2l", C.c_double * 2),
+           ("calib_value", c_double_p), ("calib_zero", c_double_p), ("ad_host", c_double_p), ("ad_target", c_double_p)]
+        + [(k, c_float_p) for k in ("pre_RTll_0", "pre_tTll_0", "pre_KRKiTll", "pre_KtTll", "pre_aff_mode", "pre_b0_mode", "cam", "c_delta")]
+        + [("delta_x", c_double_p), ("ad_ht_delta", c_float_p), ("world_to_cam", c_double_p), ("cam_to_world_all", c_double_p)]
+        + [(k, c_float_p) for k in ("idepth_out", "idepth_scaled_out", "idepth_zero_scaled_out", "delta_out")]
+        + [(k, c_double_p) for k in ("world_to_cam_eval_out", "state_out", "state_zero_out", "cam_to_tracking_ref_out", "cam_to_world_out")]
+        + [(k, c_float_p) for k in ("pre_RTll_0_out", "pre_tTll_0_out", "pre_KRKiTll_out", "pre_KtTll_out", "pre_aff_mode_out",
+                                    "pre_b0_mode_out", "cam_out", "c_delta_out")]
+        + [("delta_x_out", c_double_p), ("ad_ht_delta_out", c_float_p), ("world_to_cam_out", c_double_p), ("cam_to_world_out_all", c_double_p),
+           ("decision", c_int_p), ("scale_error_out", c_float_p), ("trapped_out", c_int_p), ("fails_out", c_int_p), ("applied_scale", c_float_p)]
+    )
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -597,6 +616,9 @@ SYMBOLS = {
     "dsm_nullspace_params_default": (C.c_int, [C.POINTER(NullspaceParams)]),
     "dsm_window_nullspace_batch": (C.c_int, [_vp, C.c_int, C.POINTER(NullspaceJob), C.POINTER(NullspaceParams)]),
     "dsm_window_nullspace_host": (C.c_int, [C.c_int, C.POINTER(NullspaceJob), C.POINTER(NullspaceParams)]),
+    "dsm_window_rescale_batch": (C.c_int, [_vp, C.c_int, C.POINTER(RescaleJob), C.POINTER(LinearizeParams), C.POINTER(StepParams)]),
+    "dsm_window_rescale_host": (C.c_int, [C.c_int, C.POINTER(RescaleJob), C.POINTER(LinearizeParams), C.POINTER(StepParams)]),
+    "dsm_rescale_geometry": (C.c_int, [c_int_p, c_int_p]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

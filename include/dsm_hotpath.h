@@ -1848,6 +1848,89 @@ int dsm_window_nullspace_batch(dsm_context *ctx, int n_jobs, const dsm_nullspace
  * and a checker that needs no device. */
 int dsm_window_nullspace_host(int n_jobs, const dsm_nullspace_job *jobs, const dsm_nullspace_params *params);
 
+/* ---- Adopting the stereo scale into the window ---------------------------------------------------------------------
+ * replaces what FrontEnd::makeKeyFrame does between removeOutliers and flagPointsForRemoval (FrontEnd.cpp:806): FrontEnd::optimizeScale
+ * behind its scale search (FrontEnd.cpp:1010-1061) -- the accept / reject decision with its trapped and fail-count state (function
+ * statics there, per job here), the division of every active point's inverse depth by the accepted scale, the newest keyframe's
+ * translation to its tracking reference scaled and its pose and evaluation point rebuilt from the reference's pose, and
+ * setPrecalcValues -- as the rules S0-S6 and V of DESIGN.md section 25 state them.  The cited lines are followed literally; setIdepth,
+ * setIdepthZero, setEvalPT_scaled and setStateScaled are UPSTREAM-DSO and not under the reference tree: parity is unpinned.  The
+ * call sits between dsm_window_finish_batch and dsm_window_marginalize_batch / dsm_window_nullspace_batch and returns every array it
+ * changes in the shape those calls and the next keyframe's dsm_step_job take it.
+ * NOT here: the scale search (dsm_optimize_scale_batch, dsm_tracker_optimize_scale_guesses), scaleCoarseDepthL0 (:1032, the tracker's),
+ * setAdjointsF at the rescaled pose, rescaling immature points, H_M / b_M or the other frames (the reference does none of these),
+ * flagFramesForMarginalization.
+ * All arithmetic is IEEE, left to right as written, without contraction. */
+#define DSM_RESCALE_DISABLED 0
+#define DSM_RESCALE_REJECTED 1
+#define DSM_RESCALE_ACCEPTED 2
+
+/* One window as dsm_window_finish_batch left it (after the caller erased what the finish removed); n = n_frames, N = 4 + 8 n; poses are
+ * {qx,qy,qz,qw,tx,ty,tz}; the newest frame is n - 1.  Every array is required unless it says optional. */
+typedef struct dsm_rescale_job {
+  int n_frames;                     /* 1 .. DSM_WINDOW_MAX_FRAMES */
+  int n_pts;                        /* >= 0: the active points of the whole window */
+  int enabled;                      /* 0: scale_opt_thres_ <= 0 or fewer than five keyframes (FrontEnd.cpp:806) */
+  float scale_error;                /* what the scale call returned; -1 when no guess gave a positive error.  NaN is valid and rejects */
+  float new_scale;                  /* finite, not 0 */
+  float thres;                      /* scale_opt_thres_ */
+  int trapped, fails;               /* scale_trapped, scale_opt_fails before the call */
+  const float *idepth;              /* the next four: n_pts each.  ph->idepth */
+  const float *idepth_scaled;
+  const float *idepth_zero_scaled;
+  const float *delta;               /* EFPoint::deltaF */
+  const double *world_to_cam_eval;  /* n * 7: worldToCam_evalPT, unit quaternions */
+  const double *state;              /* n * 8, unscaled */
+  const double *state_zero;         /* n * 8, unscaled */
+  const float *exposure;            /* n: ab_exposure */
+  const double *cam_to_tracking_ref; /* 7: the newest frame's shell->camToTrackingRef, as tracked */
+  const double *ref_cam_to_world;   /* 7: shell->trackingRef->camToWorld */
+  const double *cam_to_world;       /* 7: the newest frame's shell->camToWorld (copied through when not accepted) */
+  double aff_g2l[2];                /* shell->aff_g2l: (state[n-1][6] * scale_a, state[n-1][7] * scale_b) of the finished window */
+  const double *calib_value;        /* 4: h_calib_.value, unscaled */
+  const double *calib_zero;         /* 4: value_zero */
+  const double *ad_host, *ad_target; /* n * n * 8 * 8 each, as dsm_hessian_job reads them: NOT recomputed (S4) */
+  const float *pre_RTll_0, *pre_tTll_0, *pre_KRKiTll, *pre_KtTll, *pre_aff_mode, *pre_b0_mode; /* n * n * (9, 3, 9, 3, 2, 1): the tables given */
+  const float *cam;                 /* 6: cam, cam_inv */
+  const float *c_delta;             /* 4 */
+  const double *delta_x;            /* N */
+  const float *ad_ht_delta;         /* n * n * 8 */
+  const double *world_to_cam;       /* n * 7: PRE_worldToCam */
+  const double *cam_to_world_all;   /* optional (NULL) unless cam_to_world_out_all is given, n * 7: PRE_camToWorld */
+  float *idepth_out, *idepth_scaled_out, *idepth_zero_scaled_out, *delta_out; /* n_pts each (S2) */
+  double *world_to_cam_eval_out;    /* n * 7 (S3) */
+  double *state_out;                /* n * 8 */
+  double *state_zero_out;           /* n * 8 */
+  double *cam_to_tracking_ref_out;  /* 7 */
+  double *cam_to_world_out;         /* 7 */
+  float *pre_RTll_0_out, *pre_tTll_0_out, *pre_KRKiTll_out, *pre_KtTll_out, *pre_aff_mode_out, *pre_b0_mode_out; /* (S4) */
+  float *cam_out;                   /* 6 */
+  float *c_delta_out;               /* 4 */
+  double *delta_x_out;              /* N */
+  float *ad_ht_delta_out;           /* n * n * 8 */
+  double *world_to_cam_out;         /* n * 7 */
+  double *cam_to_world_out_all;     /* optional (NULL), n * 7 */
+  int *decision;                    /* one word each: DSM_RESCALE_* (S1) */
+  float *scale_error_out;           /* what optimizeScale returns: -1 when disabled or after the sixth failure in a row */
+  int *trapped_out, *fails_out;
+  float *applied_scale;             /* new_scale when accepted, otherwise 1 */
+} dsm_rescale_job;
+
+/* S0-S6 for every job: the decisions during staging on the host, ONE staged copy of the accepted jobs, ONE launch (rsc_kernel: per
+ * accepted job one workgroup with a lane per frame and per pair, and up to eight workgroups that stride over the points), one
+ * read-back; a job that is not accepted gets its byte copies on the host and is not staged.  lp and sp NULL: the defaults.  A job's
+ * results do not depend on the other jobs of the call or on the launch geometry.  Validation is all or nothing, before anything is
+ * enqueued and with no output touched: DSM_ERR_INVALID for a NULL required array, n_frames outside [1, DSM_WINDOW_MAX_FRAMES], a
+ * negative n_pts, a non-finite input (scale_error apart), a world_to_cam_eval, cam_to_tracking_ref, ref_cam_to_world or cam_to_world
+ * quaternion whose squared norm is further than 1e-9 from 1, a new_scale that is not finite or 0, a negative fails, cam_to_world_out_all
+ * without cam_to_world_all, parameters that are not finite and positive.  n_pts == 0 and a job of one frame are valid. */
+int dsm_window_rescale_batch(dsm_context *ctx, int n_jobs, const dsm_rescale_job *jobs, const dsm_linearize_params *lp, const dsm_step_params *sp);
+/* The same on the host, job after job: plain loops over the same rescale_math.hpp.  The CPU baseline of tools/rescale_timing.py and a
+ * checker that needs no device. */
+int dsm_window_rescale_host(int n_jobs, const dsm_rescale_job *jobs, const dsm_linearize_params *lp, const dsm_step_params *sp);
+/* The launch geometry of rsc_kernel, for tests that choose point counts at its edges: the workgroup size and the points' grid stride */
+int dsm_rescale_geometry(int *block, int *grid_stride);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """CPU only: runs the sanitizer builds of the stand-alone programs tools/*_host_standalone.cpp (the build line is in each source's head)
-over the scenes of every checker that has a `hashes` function -- step, marginalize, finish and nullspace -- and compares every value a
+over the scenes of every checker that has a `hashes` function -- step, marginalize, finish, nullspace and rescale -- and compares every value a
 program prints with the checker's.  Any text on stderr, a sanitizer report for one, counts as a failure.
 
   python tools/host_standalone_check.py DIRECTORY_OF_THE_BUILT_PROGRAMS [DIRECTORY FOR THE CASE FILES] [PROGRAM ...]
 
-A program that is not in the directory is reported and counts as a failure; name programs (step, marginalize, finish, nullspace) to
+A program that is not in the directory is reported and counts as a failure; name programs (step, marginalize, finish, nullspace, rescale) to
 run those alone.
 """
 import json
@@ -23,6 +23,7 @@ import _linearize_ref as R  # noqa: E402
 import _marginalize_ref as M  # noqa: E402
 import _nullspace_ref as NR  # noqa: E402
 import _optimize_ref as O  # noqa: E402
+import _rescale_ref as RR  # noqa: E402
 import _step_ref as T  # noqa: E402
 
 
@@ -52,7 +53,12 @@ def nullspace_cases():
         yield name, lambda path, job=NR.scene(name): NR.write_case(path, job), (), NR.hashes(NR.expected(name))
 
 
-PROGRAMS = dict(step=step_cases, marginalize=marginalize_cases, finish=finish_cases, nullspace=nullspace_cases)
+def rescale_cases():
+    for name, job in sorted(RR.scenes().items()):
+        yield name, lambda path, job=job: RR.write_case(path, job), (), dict(RR.hashes(RR.rescale(job)), forms_equal=1, refusal=1)
+
+
+PROGRAMS = dict(step=step_cases, marginalize=marginalize_cases, finish=finish_cases, nullspace=nullspace_cases, rescale=rescale_cases)
 
 
 def main():
