@@ -335,6 +335,37 @@ class RescaleJob(C.Structure):
     )
 
 
+class AdmitParams(C.Structure):
+    _fields_ = [("min_frames", C.c_int), ("max_frames", C.c_int), ("min_frame_age", C.c_int), ("min_points_remaining", C.c_float),
+                ("max_log_aff_fac_in_window", C.c_float)]
+
+
+c_ubyte_p = C.POINTER(C.c_ubyte)
+
+
+class AdmitJob(C.Structure):
+    _fields_ = (
+        [("n_frames", C.c_int), ("n_pts", C.c_int), ("n_res", C.c_int), ("new_keyframe_id", C.c_int), ("new_exposure", C.c_float),
+         ("new_frame_energy_th", C.c_float), ("aff_g2l", C.c_double * 2),
+         ("world_to_cam_eval", c_double_p), ("state", c_double_p), ("state_zero", c_double_p), ("exposure", c_float_p), ("frame_energy_th", c_float_p),
+         ("keyframe_id", c_int_p), ("n_points_in", c_int_p), ("n_points_out", c_int_p)]
+        + [(k, c_double_p) for k in ("ref_cam_to_world", "cam_to_tracking_ref", "new_frame_prior", "new_frame_prior_zero", "calib_value", "calib_zero",
+                                     "H_M", "b_M", "H_L", "b_L", "prior", "prior_zero")]
+        + [("host", c_int_p), ("last_res", c_int_p), ("last_state", c_ubyte_p), ("point", c_int_p), ("target", c_int_p), ("state_in", c_ubyte_p),
+           ("energy_in", c_float_p), ("is_new", c_ubyte_p),
+           ("world_to_cam_eval_out", c_double_p), ("state_out", c_double_p), ("state_zero_out", c_double_p), ("exposure_out", c_float_p),
+           ("frame_energy_th_out", c_float_p), ("keyframe_id_out", c_int_p), ("world_to_cam_out", c_double_p), ("flagged_out", c_ubyte_p),
+           ("cam_to_world_out", c_double_p)]
+        + [(k, c_float_p) for k in ("pre_RTll_0_out", "pre_tTll_0_out", "pre_KRKiTll_out", "pre_KtTll_out", "pre_aff_mode_out", "pre_b0_mode_out",
+                                    "distance_ll_out", "cam_out", "c_delta_out")]
+        + [("delta_x_out", c_double_p), ("ad_host_out", c_double_p), ("ad_target_out", c_double_p), ("ad_ht_delta_out", c_float_p)]
+        + [(k, c_double_p) for k in ("H_M_out", "b_M_out", "H_L_out", "b_L_out", "prior_out", "prior_zero_out", "frame_prior_out", "frame_delta_prior_out")]
+        + [("point_out", c_int_p), ("target_out", c_int_p), ("res_state_out", c_ubyte_p), ("energy_out", c_float_p), ("is_new_out", c_ubyte_p),
+           ("res_index_out", c_int_p), ("new_res_index_out", c_int_p), ("last_res_out", c_int_p), ("last_state_out", c_ubyte_p),
+           ("n_res_out", c_int_p), ("n_flagged", c_int_p), ("dist_score_out", c_double_p)]
+    )
+
+
 class LmProposeIn(C.Structure):
     _fields_ = [
         ("H", C.c_double * 64), ("b", C.c_double * 8), ("cur", C.c_double * 7), ("aff_cur", C.c_double * 2),
@@ -619,6 +650,10 @@ SYMBOLS = {
     "dsm_window_rescale_batch": (C.c_int, [_vp, C.c_int, C.POINTER(RescaleJob), C.POINTER(LinearizeParams), C.POINTER(StepParams)]),
     "dsm_window_rescale_host": (C.c_int, [C.c_int, C.POINTER(RescaleJob), C.POINTER(LinearizeParams), C.POINTER(StepParams)]),
     "dsm_rescale_geometry": (C.c_int, [c_int_p, c_int_p]),
+    "dsm_admit_params_default": (None, [C.POINTER(AdmitParams)]),
+    "dsm_window_admit_batch": (C.c_int, [_vp, C.c_int, C.POINTER(AdmitJob), C.POINTER(LinearizeParams), C.POINTER(StepParams), C.POINTER(AdmitParams)]),
+    "dsm_window_admit_host": (C.c_int, [C.c_int, C.POINTER(AdmitJob), C.POINTER(LinearizeParams), C.POINTER(StepParams), C.POINTER(AdmitParams)]),
+    "dsm_admit_geometry": (C.c_int, [c_int_p, c_int_p]),
     "dsm_write_trajectory": (C.c_int, [C.c_char_p, C.c_int, c_int_p, c_double_p]),
     "dsm_make_coarse_depth_l0": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, _pp_f, c_int_p, _pp_f, _pp_f, _pp_f, _pp_f]),
     "dsm_sc_distance": (C.c_float, [c_int_p, c_double_p, C.c_int, c_int_p, c_double_p, C.c_int, C.c_int]),

@@ -3,7 +3,7 @@
 //   device [in | work | out], mirror [in | out], every part at a multiple of 256 bytes; grown by half on demand, never shrunk.
 // Every call ends with the context's stream idle, so the next call finds the arena free: one call at a time per context.
 // Users: the loop chain, the ring-key search of many indexes, ICP, distance map, immature points, trace, pixel selection, residual
-// linearisation, Hessian accumulation, the window solve, the window step, the window's marginalisation, the window's nullspaces, the window's rescale and dsm_set_refs_from_points with all three regions; dsm_tracker_set_ref, _get_template, _upload_frame and _get_frame with `work` alone
+// linearisation, Hessian accumulation, the window solve, the window step, the window's marginalisation, the window's nullspaces, the window's rescale, the window's admission and dsm_set_refs_from_points with all three regions; dsm_tracker_set_ref, _get_template, _upload_frame and _get_frame with `work` alone
 // (their copies go from and to the caller's memory, so `in` and `out` stay empty and only the device buffer grows).
 #pragma once
 #include "dsm_internal.hpp"

@@ -1931,6 +1931,113 @@ int dsm_window_rescale_host(int n_jobs, const dsm_rescale_job *jobs, const dsm_l
 /* The launch geometry of rsc_kernel, for tests that choose point counts at its edges: the workgroup size and the points' grid stride */
 int dsm_rescale_geometry(int *block, int *grid_stride);
 
+/* ---- Admitting the new keyframe into the window -------------------------------------------------------------------
+ * replaces the head of FrontEnd::makeKeyFrame (FrontEnd.cpp:722-762): the new frame's pose and evaluation point (:725-727),
+ * flagFramesForMarginalization (dso_helpers/FrontEndMarginalize.cpp:62-146, called at :735 BEFORE the insertion), ef_->insertFrame
+ * (:742: H_M, b_M grown by eight zero rows and columns, the frame's prior taken, setAdjointsF over all pairs), setPrecalcValues on
+ * n + 1 frames (:744) and one forward residual of every active point against the new frame (:746-762) -- as the rules A1-A6 and V
+ * of DESIGN.md section 26 state them.  The cited lines are followed literally; insertFrame, EFFrame::takeData, getPrior,
+ * FrameFramePrecalc::set's distanceLL, setAdjointsF and setEvalPT_scaled are UPSTREAM-DSO and not under the reference tree: parity
+ * is unpinned.  The call needs no adjoint input: it forms the adjoints of every pair.
+ * NOT here: the first keyframes (initializeFromInitializer), erasing and renumbering after a marginalisation, connectivityMap,
+ * merging the points dsm_activate_points_batch activates into the lists, dso_error, clearing is_new of old residuals.
+ * All arithmetic is IEEE, left to right as written, without contraction. */
+typedef struct dsm_admit_params {
+  int min_frames;                  /* setting_minFrames, 5; >= 0 */
+  int max_frames;                  /* setting_maxFrames, 7; >= 0 */
+  int min_frame_age;               /* setting_minFrameAge, 1 */
+  float min_points_remaining;      /* setting_minPointsRemaining, 0.05f */
+  float max_log_aff_fac_in_window; /* setting_maxLogAffFacInWindow, 0.7f */
+} dsm_admit_params;
+void dsm_admit_params_default(dsm_admit_params *p);
+
+/* One window BEFORE the admission; n = n_frames, N = 4 + 8 n; the new frame becomes frame n of n + 1, and the lists hold
+ * n_res + n_pts residuals afterwards.  Poses are {qx,qy,qz,qw,tx,ty,tz}.  Every array is required unless it says optional; an array of
+ * n_pts or n_res entries may be NULL when that count is 0. */
+typedef struct dsm_admit_job {
+  int n_frames;                     /* 1 .. DSM_WINDOW_MAX_FRAMES - 1 */
+  int n_pts;                        /* >= 0: the active points of the whole window */
+  int n_res;                        /* >= 0: their residuals, grouped by point in ascending point order (makeIDX's order) */
+  int new_keyframe_id;              /* the new frame's frameID (:740) */
+  float new_exposure;               /* its ab_exposure */
+  float new_frame_energy_th;        /* its frameEnergyTH: the constructor's 8*8*8 (:770 assigns the value to itself) */
+  double aff_g2l[2];                /* its shell->aff_g2l, as tracked */
+  const double *world_to_cam_eval;  /* n * 7: worldToCam_evalPT, unit quaternions */
+  const double *state;              /* n * 8, unscaled */
+  const double *state_zero;         /* n * 8, unscaled */
+  const float *exposure;            /* n: ab_exposure */
+  const float *frame_energy_th;     /* n */
+  const int *keyframe_id;           /* n: frameID */
+  const int *n_points_in;           /* n: pointHessians.size() + immaturePoints.size() */
+  const int *n_points_out;          /* n: pointHessiansMarginalized.size() + pointHessiansOut.size() */
+  const double *ref_cam_to_world;   /* 7: shell->trackingRef->camToWorld */
+  const double *cam_to_tracking_ref; /* 7: shell->camToTrackingRef */
+  const double *new_frame_prior;    /* 8: getPrior of the new frame */
+  const double *new_frame_prior_zero; /* 8 */
+  const double *calib_value;        /* 4: h_calib_.value, unscaled */
+  const double *calib_zero;         /* 4: value_zero */
+  const double *H_M, *b_M;          /* optional (NULL: absent), N * N (row-major) and N */
+  const double *H_L, *b_L;          /* optional, N * N and N */
+  const double *prior, *prior_zero; /* optional, both or neither, N each: what dsm_step_job takes as state_prior, state_prior_zero */
+  const int *host;                  /* n_pts */
+  const int *last_res;              /* n_pts * 2: the residual index of lastResiduals[0].first, [1].first; -1: none */
+  const unsigned char *last_state;  /* n_pts * 2: DSM_RES_* */
+  const int *point;                 /* n_res, non-decreasing */
+  const int *target;                /* n_res */
+  const unsigned char *state_in;    /* n_res: DSM_RES_IN / _OOB / _OUTLIER */
+  const float *energy_in;           /* n_res */
+  const unsigned char *is_new;      /* n_res */
+  double *world_to_cam_eval_out;    /* (n + 1) * 7 (A1) */
+  double *state_out;                /* (n + 1) * 8 */
+  double *state_zero_out;           /* (n + 1) * 8 */
+  float *exposure_out;              /* n + 1 */
+  float *frame_energy_th_out;       /* n + 1 */
+  int *keyframe_id_out;             /* n + 1 */
+  double *world_to_cam_out;         /* (n + 1) * 7: PRE_worldToCam (A2) */
+  unsigned char *flagged_out;       /* n + 1: flaggedForMarginalization (A4); the new frame's is 0 */
+  double *cam_to_world_out;         /* 7: the new frame's shell->camToWorld */
+  float *pre_RTll_0_out, *pre_tTll_0_out, *pre_KRKiTll_out, *pre_KtTll_out, *pre_aff_mode_out, *pre_b0_mode_out; /* (n+1)^2 * (9, 3, 9, 3, 2, 1) */
+  float *distance_ll_out;           /* optional (NULL), (n+1)^2 */
+  float *cam_out;                   /* 6 */
+  float *c_delta_out;               /* 4 */
+  double *delta_x_out;              /* N + 8 */
+  double *ad_host_out, *ad_target_out; /* (n+1)^2 * 8 * 8 each (A3) */
+  float *ad_ht_delta_out;           /* (n+1)^2 * 8 */
+  double *H_M_out, *b_M_out;        /* (N+8)^2 and N + 8; required where the input is given, not read otherwise (A5) */
+  double *H_L_out, *b_L_out;        /* likewise */
+  double *prior_out, *prior_zero_out; /* N + 8 each, likewise */
+  double *frame_prior_out;          /* 8: the new EFFrame's prior */
+  double *frame_delta_prior_out;    /* 8: its delta_prior */
+  int *point_out, *target_out;      /* n_res + n_pts each (A6) */
+  unsigned char *res_state_out;     /* n_res + n_pts */
+  float *energy_out;                /* n_res + n_pts */
+  unsigned char *is_new_out;        /* n_res + n_pts */
+  int *res_index_out;               /* n_res: where each old residual stands */
+  int *new_res_index_out;           /* n_pts: where each point's new residual stands */
+  int *last_res_out;                /* n_pts * 2, in the new numbering */
+  unsigned char *last_state_out;    /* n_pts * 2 */
+  int *n_res_out;                   /* one word: n_res + n_pts */
+  int *n_flagged;                   /* one word: the frames flagged */
+  double *dist_score_out;           /* n: F2's score of a candidate, 0 otherwise and where F2 did not run */
+} dsm_admit_job;
+
+/* A1-A6 for every job: ONE staged copy, ONE launch (adm_kernel: per job one workgroup with a lane per frame and per pair, and up to
+ * eight workgroups that stride over the residuals, the points and the grown matrices), one read-back.  lp, sp, ap NULL: the defaults.
+ * A job's results do not depend on the other jobs of the call or on the launch geometry.  Validation is all or nothing, before
+ * anything is enqueued and with no output touched: DSM_ERR_INVALID for a NULL required array, n_frames outside
+ * [1, DSM_WINDOW_MAX_FRAMES - 1], a negative n_pts or n_res, a host, point or target out of range, a target equal to its point's host,
+ * residuals not grouped by ascending point, a last_res that is out of range or names another point's residual, a state byte other than
+ * DSM_RES_IN / _OOB / _OUTLIER, a non-finite input, a quaternion whose squared norm is further than 1e-9 from 1, a negative
+ * n_points_in or n_points_out or a sum of the two that overflows, prior without prior_zero or the reverse, parameters that are not
+ * finite, a negative min_frames or max_frames.  n_pts == 0, n_res == 0 and a window of one frame are valid. */
+int dsm_window_admit_batch(dsm_context *ctx, int n_jobs, const dsm_admit_job *jobs, const dsm_linearize_params *lp, const dsm_step_params *sp,
+                           const dsm_admit_params *ap);
+/* The same on the host, job after job: plain loops over the same admit_math.hpp.  The CPU baseline of tools/admit_timing.py and a
+ * checker that needs no device. */
+int dsm_window_admit_host(int n_jobs, const dsm_admit_job *jobs, const dsm_linearize_params *lp, const dsm_step_params *sp, const dsm_admit_params *ap);
+/* The launch geometry of adm_kernel, for tests that choose counts at its edges: the workgroup size and the lists' grid stride */
+int dsm_admit_geometry(int *block, int *grid_stride);
+
 /* replaces TrackerAndScaler::makeCoarseDepthL0 (TrackerAndScaler.cpp:143-315) for callers that hold
  * the active points as flat arrays: (pu,pv) = centerProjectedTo[0..1], pidepth = centerProjectedTo[2],
  * pweight = sqrtf(1e-3/(HdiF+1e-12)) (:155-158).  ref_dIp[lvl]: the keyframe's (I,dx,dy) pyramid.

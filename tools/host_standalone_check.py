@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """CPU only: runs the sanitizer builds of the stand-alone programs tools/*_host_standalone.cpp (the build line is in each source's head)
-over the scenes of every checker that has a `hashes` function -- step, marginalize, finish, nullspace and rescale -- and compares every value a
+over the scenes of every checker that has a `hashes` function -- step, marginalize, finish, nullspace, rescale and admit -- and compares every value a
 program prints with the checker's.  Any text on stderr, a sanitizer report for one, counts as a failure.
 
   python tools/host_standalone_check.py DIRECTORY_OF_THE_BUILT_PROGRAMS [DIRECTORY FOR THE CASE FILES] [PROGRAM ...]
 
-A program that is not in the directory is reported and counts as a failure; name programs (step, marginalize, finish, nullspace, rescale) to
+A program that is not in the directory is reported and counts as a failure; name programs (step, marginalize, finish, nullspace, rescale, admit) to
 run those alone.
 """
 import json
@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 
+import _admit_ref as AR  # noqa: E402
 import _finish_ref as F  # noqa: E402
 import _linearize_ref as R  # noqa: E402
 import _marginalize_ref as M  # noqa: E402
@@ -58,7 +59,13 @@ def rescale_cases():
         yield name, lambda path, job=job: RR.write_case(path, job), (), dict(RR.hashes(RR.rescale(job)), forms_equal=1, refusal=1)
 
 
-PROGRAMS = dict(step=step_cases, marginalize=marginalize_cases, finish=finish_cases, nullspace=nullspace_cases, rescale=rescale_cases)
+def admit_cases():
+    jobs = dict(AR.scenes(), **{"chain_" + k: AR.chain_scene(k) for k in AR.CHAINS})
+    for name, job in sorted(jobs.items()):
+        yield name, lambda path, job=job: AR.write_case(path, job), (), dict(AR.hashes(AR.admit(job)), forms_equal=1, refusal=1)
+
+
+PROGRAMS = dict(step=step_cases, marginalize=marginalize_cases, finish=finish_cases, nullspace=nullspace_cases, rescale=rescale_cases, admit=admit_cases)
 
 
 def main():
